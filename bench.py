@@ -21,10 +21,18 @@ Rank 0 prints ONE JSON line (contract in the task statement).  ``--workload prep
 reference's canonical preprocessing (R/operations.py:57-97,10-54) and the north_star's filter set per stage, with
 a roofline per stage; their ``value`` is planes/s and they are supplementary lines, not the headline metric.
 
-The default N = 1 run also times, AFTER the headline and inside the same command (so that the driver's clock covers
-them), the supplementary lines ``sublines``: c2, prep, filters, plate48 (the per-GPU share of configs[3]), unique64
-(64 distinct FOVs), api (the reference-level batch_segment + cell_properties calls on host arrays) and a8_exact (the
-same chain with SURVEY A.8's plain -EDT relief and exact tie handling).  ``--no-sublines`` skips them.
+A plain run sets up, warms up, times ``--steps`` steps and prints the line (``metric``, ``value``, ``unit``,
+``ms_per_step``, ``dtype``, ...).  Everything else the benchmark measures or checks runs only with ``--full``: the
+per-stage device times and the ``roofline`` object, the flood tail (``--tail-reps``), the host-fed variant, the
+``cpu_baseline``, the check of the delivered tables, the per-stage / eager / one-call extras of the other workloads,
+and, in the N = 1 c3 run, AFTER the headline and inside the same command, the supplementary lines ``sublines``: c2,
+prep, filters, plate48 (the per-GPU share of configs[3]), unique64 (64 distinct FOVs), api (the reference-level
+batch_segment + cell_properties calls on host arrays) and a8_exact (the same chain with SURVEY A.8's plain -EDT relief
+and exact tie handling).  ``--no-cpu``, ``--no-h2d`` and ``--no-sublines`` leave out parts of a ``--full`` run.
+
+``--dump-outputs DIR`` (c3 / c2) writes what the last timed step computed, as float32 / float64 ``DIR/<name>.npy``
+(at most 64 MB; a fixed, seeded sample of the fields of view): the cell counts of every FOV, the label images and
+the feature-table rows of the sampled ones.  The inputs depend on the arguments only (seeded synthetic FOVs).
 
 Watershed recipe of the headline: the reference defines no marker recipe.  The timed chain floods the
 SEEDED relief (marker pixels are spread first, in raster order: oracle/skops.py:seeded_flood_image, ``seeds_first``),
@@ -213,9 +221,20 @@ def parse_args():
                     help="N = 1: keep the feature tables on the device (by default every step packs its table and "
                          "copies it to page-locked host memory inside the timed region, two steps lagged)")
     ap.add_argument("--tail-reps", type=int, default=0,
-                    help="c3: time the watershed stage of a 32-FOV launch this many times over rotating windows of "
-                         "the distinct FOVs and report p50 / p99 (flood time is set by the largest component)")
-    return ap.parse_args()
+                    help="c3 with --full: time the watershed stage of a 32-FOV launch this many times over rotating "
+                         "windows of the distinct FOVs and report p50 / p99 (flood time is set by the largest component)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: per-stage times and roofline, "
+                         "host-fed variant, CPU baseline, delivered-table check, supplementary lines (N = 1 c3)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c3 / c2: write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: a fixed, seeded sample of the fields of view)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and args.workload not in ("c3", "c2"):
+        ap.error(f"--dump-outputs is implemented for the c3 / c2 chains, not --workload {args.workload}")
+    return args
 
 
 def launch_ranks_if_needed(args):
@@ -430,56 +449,57 @@ def run_ops(args):
         step()
     ctx.synchronize()
     elapsed = time.perf_counter() - t0
-    timers = {name: ctx.timer() for name, _ in stages}
-    acc = {name: [] for name, _ in stages}
-    for _ in range(3):
-        for name, fn in stages:
-            timers[name].start()
-            fn()
-            timers[name].stop()
-        ctx.synchronize()
-        for name in acc:
-            acc[name].append(timers[name].elapsed_ms())
-    stage_avg = {k: float(np.mean(v)) for k, v in acc.items()}
-    log("stage ms: " + ", ".join(f"{k}={v:.3f}" for k, v in stage_avg.items()))
-    npx = B * S * S
-    per_stage = {}
-    for k, ms in stage_avg.items():
-        bpp = STAGE_BYTES_PER_PX[k.split("#")[0]]
-        gbs = bpp * npx / (ms * 1e-3) / 1e9
-        per_stage[k] = {"ms": ms, "bytes_per_px": bpp, "achieved_GBps": gbs, "frac": gbs / HBM_PEAK_GBS}
-    dom = max(stage_avg, key=stage_avg.get)
-    chain_bytes = sum(v["bytes_per_px"] for v in per_stage.values()) * npx
-    chain_ms = sum(stage_avg.values())
-    if "dog" in per_stage:
-        # The DoG is bound by float64 ISSUE, not by HBM: per pixel two passes of the narrow Gaussian
-        # (radius 2: 2 + 3 + 2 operations each), two of the wide one (radius 64: 64 + 65 + 64 each) and the subtraction.
-        # Bit-exactness forbids fused multiply-add, so the vector unit's ceiling is one float64 operation per lane and
-        # clock: 256 CUs x 64 lanes x 2.4 GHz = 39.3 T operations/s (half the 78.6 TFLOP/s that counts an FMA as two;
-        # derived from the CU count and the nominal clock -- the guide quotes no float64 figure)
-        ops = (2 * 7 + 2 * 193 + 1) * npx
-        tops = ops / (stage_avg["dog"] * 1e-3) / 1e12
-        per_stage["dog"]["fp64"] = {"operations_per_px": 401, "achieved_Tops": tops, "peak_Tops_without_fma": 39.3,
-                                    "frac": tops / 39.3}
-    out = {
+    line = {
         "metric": f"planes/sec (2048^2 uint16) through the {args.workload} operator chain", "value": B * args.steps / elapsed,
         "unit": "planes/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f64" if args.workload == "prep" else "u16", "data": "synthetic",
         "config": {"workload": desc, "planes_per_step": B, "plane_shape": [S, S], "resident_in_hbm": True},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": per_stage[dom]["achieved_GBps"], "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": per_stage[dom]["frac"], "traffic": None,
-                     "algorithmic_bytes_per_launch": per_stage[dom]["bytes_per_px"] * npx, "launch_ms": stage_avg[dom],
-                     "chain": {"achieved": chain_bytes / (chain_ms * 1e-3) / 1e9,
-                               "frac": chain_bytes / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": chain_ms},
-                     "stages": per_stage},
-        "host_gen_s": gen_s,
     }
-    if not args.no_cpu:
+    if args.full:
+        timers = {name: ctx.timer() for name, _ in stages}
+        acc = {name: [] for name, _ in stages}
+        for _ in range(3):
+            for name, fn in stages:
+                timers[name].start()
+                fn()
+                timers[name].stop()
+            ctx.synchronize()
+            for name in acc:
+                acc[name].append(timers[name].elapsed_ms())
+        stage_avg = {k: float(np.mean(v)) for k, v in acc.items()}
+        log("stage ms: " + ", ".join(f"{k}={v:.3f}" for k, v in stage_avg.items()))
+        npx = B * S * S
+        per_stage = {}
+        for k, ms in stage_avg.items():
+            bpp = STAGE_BYTES_PER_PX[k.split("#")[0]]
+            gbs = bpp * npx / (ms * 1e-3) / 1e9
+            per_stage[k] = {"ms": ms, "bytes_per_px": bpp, "achieved_GBps": gbs, "frac": gbs / HBM_PEAK_GBS}
+        dom = max(stage_avg, key=stage_avg.get)
+        chain_bytes = sum(v["bytes_per_px"] for v in per_stage.values()) * npx
+        chain_ms = sum(stage_avg.values())
+        if "dog" in per_stage:
+            # The DoG is bound by float64 ISSUE, not by HBM: per pixel two passes of the narrow Gaussian
+            # (radius 2: 2 + 3 + 2 operations each), two of the wide one (radius 64: 64 + 65 + 64 each) and the subtraction.
+            # Bit-exactness forbids fused multiply-add, so the vector unit's ceiling is one float64 operation per lane and
+            # clock: 256 CUs x 64 lanes x 2.4 GHz = 39.3 T operations/s (half the 78.6 TFLOP/s that counts an FMA as two;
+            # derived from the CU count and the nominal clock -- the guide quotes no float64 figure)
+            ops = (2 * 7 + 2 * 193 + 1) * npx
+            tops = ops / (stage_avg["dog"] * 1e-3) / 1e12
+            per_stage["dog"]["fp64"] = {"operations_per_px": 401, "achieved_Tops": tops, "peak_Tops_without_fma": 39.3,
+                                        "frac": tops / 39.3}
+        line["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": per_stage[dom]["achieved_GBps"], "peak": HBM_PEAK_GBS,
+                            "unit": "GB/s", "frac": per_stage[dom]["frac"], "traffic": None,
+                            "algorithmic_bytes_per_launch": per_stage[dom]["bytes_per_px"] * npx, "launch_ms": stage_avg[dom],
+                            "chain": {"achieved": chain_bytes / (chain_ms * 1e-3) / 1e9,
+                                      "frac": chain_bytes / (chain_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "ms": chain_ms},
+                            "stages": per_stage}
+    line["host_gen_s"] = gen_s
+    if args.full and not args.no_cpu:
         fovs = np.stack(uniq)
-        out["cpu_baseline"] = cpu_baseline(fovs, args.workload, min(args.cpu_fovs, 4))
-        out["gpu_over_cpu_1thread"] = out["value"] / out["cpu_baseline"]["value"]
-    return out
+        line["cpu_baseline"] = cpu_baseline(fovs, args.workload, min(args.cpu_fovs, 4))
+        line["gpu_over_cpu_1thread"] = line["value"] / line["cpu_baseline"]["value"]
+    return line
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -523,7 +543,7 @@ def run_c5(args, json_fd):
         x = x.contiguous(memory_format=torch.channels_last)
     else:
         net = net.to(memory_format=torch.contiguous_format)
-    flops = ch.forward_flops(net, x)
+    flops = ch.forward_flops(net, x) if args.full else None
     t0 = time.perf_counter()
     nuniq = max(1, min(args.unique, T, 2))
     syn = [synth.synthetic_flows((S, S), 1200, seed=100 * rank + i) for i in range(nuniq)]
@@ -532,8 +552,9 @@ def run_c5(args, json_fd):
     gen_s = time.perf_counter() - t0
     labels = ctx.empty((T, S, S), np.int32)
     counts = ctx.empty((T,), np.int32)
-    log(f"rank {rank}: stand-in network {sum(p.numel() for p in net.parameters()) / 1e6:.2f} M parameters, "
-        f"{flops / T / 1e9:.1f} GFLOP per tile; {nuniq} synthetic flow fields in {gen_s:.1f}s")
+    log(f"rank {rank}: stand-in network {sum(p.numel() for p in net.parameters()) / 1e6:.2f} M parameters"
+        + (f", {flops / T / 1e9:.1f} GFLOP per tile" if flops is not None else "")
+        + f"; {nuniq} synthetic flow fields in {gen_s:.1f}s")
 
     # the forward with its elementwise glue fused into HIP passes (cellpose_hip.FusedStandIn; AMT_C5_FUSED=0: eager PyTorch)
     fused = None
@@ -570,42 +591,53 @@ def run_c5(args, json_fd):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    # forward pass alone (HIP events on torch's current stream), post-processing alone (HIP events on ctx's stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fwd = []
-    for _ in range(5):
-        e0.record()
-        with torch.no_grad():
-            fused(x) if fused is not None else net(x)  # (the fused forward joins torch's current stream when it returns)
-        e1.record()
-        e1.synchronize()
-        fwd.append(e0.elapsed_time(e1))
-    fwd_ms = float(np.median(fwd))
-    eager_ms = None
-    if fused is not None:  # the eager forward beside it: what the fused glue bought
-        eg = []
-        for _ in range(3):
+    roofline = None
+    if args.full:
+        # forward pass alone (HIP events on torch's current stream), post-processing alone (HIP events on ctx's stream)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        fwd = []
+        for _ in range(5):
             e0.record()
             with torch.no_grad():
-                net(x)
+                fused(x) if fused is not None else net(x)  # (the fused forward joins torch's current stream when it returns)
             e1.record()
             e1.synchronize()
-            eg.append(e0.elapsed_time(e1))
-        eager_ms = float(np.median(eg))
-    tm = ctx.timer()
-    post = []
-    for _ in range(3):
-        tm.start()
-        hipops.cellpose_masks(dP, pr, 0.0, 200, out=labels, count=counts, flow_threshold=0.4, fill_holes=True)
-        tm.stop()
-        ctx.synchronize()
-        post.append(tm.elapsed_ms())
-    post_ms = float(np.median(post))
+            fwd.append(e0.elapsed_time(e1))
+        fwd_ms = float(np.median(fwd))
+        eager_ms = None
+        if fused is not None:  # the eager forward beside it: what the fused glue bought
+            eg = []
+            for _ in range(3):
+                e0.record()
+                with torch.no_grad():
+                    net(x)
+                e1.record()
+                e1.synchronize()
+                eg.append(e0.elapsed_time(e1))
+            eager_ms = float(np.median(eg))
+        tm = ctx.timer()
+        post = []
+        for _ in range(3):
+            tm.start()
+            hipops.cellpose_masks(dP, pr, 0.0, 200, out=labels, count=counts, flow_threshold=0.4, fill_holes=True)
+            tm.stop()
+            ctx.synchronize()
+            post.append(tm.elapsed_ms())
+        post_ms = float(np.median(post))
+        achieved = flops / (fwd_ms * 1e-3) / 1e12
+        roofline = {"bound": "mfma",
+                    "kernel": "network forward (MIOpen convolutions via PyTorch-ROCm" +
+                              ("; batch norm / ReLU / additions / upsampling fused into amt_nn_affine_act_bf16 passes)"
+                               if fused is not None else ", eager)"),
+                    "eager_forward_ms": eager_ms,
+                    "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / MFMA_PEAK_TFLOPS, "traffic": None,
+                    "flops_per_launch": flops, "launch_ms": fwd_ms,
+                    "postprocessing_ms_per_step": post_ms, "postprocessing_ms_per_tile": post_ms / T}
     nmask = counts.numpy()
     if (nmask < 0).any():
         raise RuntimeError("the post-processing ran out of seed capacity")
     if rank == 0:
-        achieved = flops / (fwd_ms * 1e-3) / 1e12
         out = {
             "metric": "tiles/sec (2x1024^2) Cellpose-style forward (bf16) + HIP flow->mask post-processing",
             "value": world * T * args.steps / elapsed, "unit": "tiles/s", "n_gpus": world, "steps": args.steps,
@@ -622,17 +654,10 @@ def run_c5(args, json_fd):
                 "postprocessing_input": "synthetic flow fields (~1,200 disks per tile), resident on the device",
                 "masks_per_tile_mean": float(nmask.mean()),
             },
-            "roofline": {"bound": "mfma",
-                         "kernel": "network forward (MIOpen convolutions via PyTorch-ROCm" +
-                                   ("; batch norm / ReLU / additions / upsampling fused into amt_nn_affine_act_bf16 passes)"
-                                    if fused is not None else ", eager)"),
-                         "eager_forward_ms": eager_ms,
-                         "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / MFMA_PEAK_TFLOPS, "traffic": None,
-                         "flops_per_launch": flops, "launch_ms": fwd_ms,
-                         "postprocessing_ms_per_step": post_ms, "postprocessing_ms_per_tile": post_ms / T},
-            "host_gen_s": gen_s,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
+        out["host_gen_s"] = gen_s
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if world > 1:
         dist.barrier()
@@ -686,60 +711,62 @@ def run_api(args):
         for _ in range(args.steps):
             res = [r for part in ex.map(work, chunks) for r in part]
         elapsed = time.perf_counter() - t0
-    # the batch results equal the per-image calls (segment(), then the same SegmentationMask)
-    equal = True
-    for k in (0, min(B - 1, per_call + 1)):
-        m1 = model.segment(fovs[k][1])
-        p1 = SegmentationMask(m1, {c: fovs[k][i] for i, c in enumerate(chans)}).cell_properties
-        equal = (equal and res[k][1] is not None and np.array_equal(m1, res[k][1])
-                 and all(np.array_equal(p1[c], res[k][2][c], equal_nan=True) for c in p1))
-    if not equal:
-        raise RuntimeError("batch_segment + cell_properties differ from the per-image calls")
-    # ---- the same results through the one-call form (an addition to the reference's interface): every image crosses
-    # the bus once, labels + rows stay on the device, only the rows of the cells that exist come home ----
-    mask_chunk = int(os.environ.get("AMT_API_MASK_CHUNK", "8"))
-    mworkers = int(os.environ.get("AMT_API_MASK_WORKERS", "2"))
-    MB = int(os.environ.get("AMT_API_MASK_FOVS", "192"))  # FOVs per step of this form (a plate's worth per call)
-    mfovs = [uniq[i % nuniq] for i in range(MB)]
-    share = -(-MB // mworkers)
-    shares = [mfovs[i:i + share] for i in range(0, MB, share)]
+    one_call = None
+    if args.full:
+        # the batch results equal the per-image calls (segment(), then the same SegmentationMask)
+        equal = True
+        for k in (0, min(B - 1, per_call + 1)):
+            m1 = model.segment(fovs[k][1])
+            p1 = SegmentationMask(m1, {c: fovs[k][i] for i, c in enumerate(chans)}).cell_properties
+            equal = (equal and res[k][1] is not None and np.array_equal(m1, res[k][1])
+                     and all(np.array_equal(p1[c], res[k][2][c], equal_nan=True) for c in p1))
+        if not equal:
+            raise RuntimeError("batch_segment + cell_properties differ from the per-image calls")
+        # ---- the same results through the one-call form (an addition to the reference's interface): every image crosses
+        # the bus once, labels + rows stay on the device, only the rows of the cells that exist come home ----
+        mask_chunk = int(os.environ.get("AMT_API_MASK_CHUNK", "8"))
+        mworkers = int(os.environ.get("AMT_API_MASK_WORKERS", "2"))
+        MB = int(os.environ.get("AMT_API_MASK_FOVS", "192"))  # FOVs per step of this form (a plate's worth per call)
+        mfovs = [uniq[i % nuniq] for i in range(MB)]
+        share = -(-MB // mworkers)
+        shares = [mfovs[i:i + share] for i in range(0, MB, share)]
 
-    def mwork(part):
-        masks = model.batch_masks(part, chans, nuclear=DAPI, batch_size=mask_chunk)
-        return [(m, m.cell_properties) for m in masks]
+        def mwork(part):
+            masks = model.batch_masks(part, chans, nuclear=DAPI, batch_size=mask_chunk)
+            return [(m, m.cell_properties) for m in masks]
 
-    with ThreadPoolExecutor(max_workers=mworkers) as ex:
-        for _ in range(max(1, args.warmup)):
-            mres = [r for part in ex.map(mwork, shares) for r in part]
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            mres = [r for part in ex.map(mwork, shares) for r in part]
-        m_elapsed = time.perf_counter() - t0
-    for k in (0, min(MB - 1, per_call + 1)):
-        m1 = model.segment(mfovs[k][1])
-        sm = SegmentationMask(m1, {c: mfovs[k][i] for i, c in enumerate(chans)})
-        p1 = sm.cell_properties
-        if not (np.array_equal(sm.label_image, mres[k][0].label_image)
-                and list(p1) == list(mres[k][1])
-                and all(np.array_equal(p1[c], mres[k][1][c], equal_nan=True) for c in p1)):
-            raise RuntimeError("batch_masks differs from segment + SegmentationMask")
-    one_call = {
-        "value": MB * args.steps / m_elapsed, "unit": "FOV/s", "ms_per_step": m_elapsed / args.steps * 1e3,
-        "fovs_per_step": MB,
-        "workload": "host numpy FOVs -> SegmentationModel(backend='classical').batch_masks(images, channels, "
-                    "nuclear=DAPI) -> SegmentationMask objects (labels on the device, downloaded on access) -> "
-                    ".cell_properties of every mask on the host",
-        "worker_threads": mworkers, "images_per_chunk": mask_chunk,
-        "pcie_bound_fov_per_s": bus_rate / (S * S * 8), "h2d_bytes_per_fov": S * S * 8,
-        "results_equal_two_calls": True,
-    }
-    del mres
+        with ThreadPoolExecutor(max_workers=mworkers) as ex:
+            for _ in range(max(1, args.warmup)):
+                mres = [r for part in ex.map(mwork, shares) for r in part]
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                mres = [r for part in ex.map(mwork, shares) for r in part]
+            m_elapsed = time.perf_counter() - t0
+        for k in (0, min(MB - 1, per_call + 1)):
+            m1 = model.segment(mfovs[k][1])
+            sm = SegmentationMask(m1, {c: mfovs[k][i] for i, c in enumerate(chans)})
+            p1 = sm.cell_properties
+            if not (np.array_equal(sm.label_image, mres[k][0].label_image)
+                    and list(p1) == list(mres[k][1])
+                    and all(np.array_equal(p1[c], mres[k][1][c], equal_nan=True) for c in p1)):
+                raise RuntimeError("batch_masks differs from segment + SegmentationMask")
+        one_call = {
+            "value": MB * args.steps / m_elapsed, "unit": "FOV/s", "ms_per_step": m_elapsed / args.steps * 1e3,
+            "fovs_per_step": MB,
+            "workload": "host numpy FOVs -> SegmentationModel(backend='classical').batch_masks(images, channels, "
+                        "nuclear=DAPI) -> SegmentationMask objects (labels on the device, downloaded on access) -> "
+                        ".cell_properties of every mask on the host",
+            "worker_threads": mworkers, "images_per_chunk": mask_chunk,
+            "pcie_bound_fov_per_s": bus_rate / (S * S * 8), "h2d_bytes_per_fov": S * S * 8,
+            "results_equal_two_calls": True,
+        }
+        del mres
     # bytes that must cross the bus per FOV on this API: DAPI plane up, int64 labels down, labels (narrowed to int32 on
     # their way into the staging buffer) + four uint16 planes up
     h2d = S * S * (2 + 4 + 4 * 2)
     d2h = S * S * 8
     bus = bus_rate
-    return {
+    out = {
         "metric": "fields-of-view/sec through the reference-level API on host arrays (batch_segment + cell_properties)",
         "value": B * args.steps / elapsed, "unit": "FOV/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -757,9 +784,12 @@ def run_api(args):
         # traffic included): DAPI staging 25 MB, label image landing 33.5, its validation pass 33.5, its narrowing upload
         # 67, four planes staged and sent 100 -- the worker threads saturate host memory before they saturate the bus
         "host_memory_traffic_bytes_per_fov": S * S * (6 + 8 + 8 + 16 + 24),
-        "results_equal_per_image_calls": True, "host_gen_s": gen_s,
-        "one_call": one_call,
+        "host_gen_s": gen_s,
     }
+    if args.full:
+        out["results_equal_per_image_calls"] = True
+        out["one_call"] = one_call
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -790,11 +820,7 @@ def run_a8(args):
     ctx.synchronize()
     elapsed = time.perf_counter() - t0
     tied = seg.tied.numpy()
-    prof = FovSegmenter(B, 4, S, S, ctx=ctx, max_cells=args.max_cells, relief="plain", ties="exact", profile=True)
-    prof.run_c3(d)
-    ctx.synchronize()
-    stage_ms = prof.times.ms()
-    return {
+    out = {
         "metric": "fields-of-view/sec (4x2048^2 uint16), config 3 with SURVEY A.8's plain -EDT relief, ties exact",
         "value": B * args.steps / elapsed, "unit": "FOV/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -803,12 +829,19 @@ def run_a8(args):
                                "ties='exact'): tied planes take the sequential single-heap emulation",
                    "fovs_per_step": B, "fov_shape": [4, S, S]},
         "tied_plane_fraction": float((tied != 0).mean()),
-        "roofline": {"kernel": "watershed", "stage_ms": stage_ms,
-                     "launch_ms": stage_ms.get("watershed"), "unit": "GB/s", "peak": HBM_PEAK_GBS,
-                     "achieved": STAGE_BYTES_PER_PX["watershed"] * B * S * S / (stage_ms["watershed"] * 1e-3) / 1e9,
-                     "frac": STAGE_BYTES_PER_PX["watershed"] * B * S * S / (stage_ms["watershed"] * 1e-3) / 1e9 / HBM_PEAK_GBS},
-        "note": "the CPU (scikit-image's own watershed) floods one such plane in 0.3-0.5 s (BASELINE.md section 2)",
     }
+    if args.full:
+        prof = FovSegmenter(B, 4, S, S, ctx=ctx, max_cells=args.max_cells, relief="plain", ties="exact", profile=True)
+        prof.run_c3(d)
+        ctx.synchronize()
+        stage_ms = prof.times.ms()
+        out["roofline"] = {"kernel": "watershed", "stage_ms": stage_ms,
+                           "launch_ms": stage_ms.get("watershed"), "unit": "GB/s", "peak": HBM_PEAK_GBS,
+                           "achieved": STAGE_BYTES_PER_PX["watershed"] * B * S * S / (stage_ms["watershed"] * 1e-3) / 1e9,
+                           "frac": STAGE_BYTES_PER_PX["watershed"] * B * S * S / (stage_ms["watershed"] * 1e-3) / 1e9
+                           / HBM_PEAK_GBS}
+    out["note"] = "the CPU (scikit-image's own watershed) floods one such plane in 0.3-0.5 s (BASELINE.md section 2)"
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -831,7 +864,7 @@ def main():
     if args.workload == "c5":
         return run_c5(args, json_fd)
     out = run_chain(args)
-    default_run = (world == 1 and args.workload == "c3" and args.plate == 0 and not args.no_sublines
+    default_run = (args.full and world == 1 and args.workload == "c3" and args.plate == 0 and not args.no_sublines
                    and os.environ.get("AMT_BENCH_FORCE_DIST") != "1")
     if out is not None and default_run:
         out["sublines"] = run_sublines(args)
@@ -860,7 +893,7 @@ def _brief(line: dict) -> dict:
 
 
 def run_sublines(args) -> dict:
-    """The supplementary lines of the default N = 1 run, a few steps each, timed inside this same command."""
+    """The supplementary lines of the N = 1 ``--full`` run, a few steps each, timed inside this same command."""
     import gc
 
     subs = {}
@@ -878,12 +911,13 @@ def run_sublines(args) -> dict:
             log(f"subline {name} FAILED: {subs[name]['error']}")
         gc.collect()
 
-    quick = dict(no_cpu=True, no_h2d=True, no_sublines=True, tail_reps=0)
+    quick = dict(no_cpu=True, no_h2d=True, no_sublines=True, tail_reps=0, dump_outputs=None)
     attempt("c2", lambda: run_chain(_sub_args(args, workload="c2", steps=10, warmup=2, **quick)))
     def in_child(*argv):
         # a fresh process, as a user's script would be: no heap this command has churned for a minute, no idle contexts
         # and streams of the lines before (measured: the 48-FOV plate 9.8 k FOV/s in here, 10.6-11.1 k on its own)
-        cmd = [sys.executable, os.path.abspath(__file__), *argv, "--size", str(args.size), "--unique", str(min(args.unique, 8))]
+        cmd = [sys.executable, os.path.abspath(__file__), *argv, "--full", "--size", str(args.size),
+               "--unique", str(min(args.unique, 8))]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
         lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
         if r.returncode != 0 or not lines:
@@ -899,6 +933,58 @@ def run_sublines(args) -> dict:
     attempt("api", lambda: in_child("--workload", "api", "--steps", "5", "--warmup", "2"))
     attempt("a8_exact", lambda: run_a8(_sub_args(args, steps=1, warmup=1)))
     return subs
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: everything one command writes
+
+
+def dump_chain_outputs(out_dir, segs, bounds, workload, fov0, suffix="", budget=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last step of the timed region left in the segmenters, as a caller of the chain would
+    receive it (labels, cell counts, feature tables).  Every field of view's count is written; label images and
+    table rows only for a seeded sample of the batch, sized to stay inside ``budget`` bytes.  Names carry ``suffix``
+    (one rank of several)."""
+    os.makedirs(out_dir, exist_ok=True)
+    B = bounds[-1]
+    S = segs[0].H
+    where = [(i, g - bounds[i]) for i in range(len(segs)) for g in range(bounds[i], bounds[i + 1])]
+    rng = np.random.default_rng(0)
+    arrays = {}
+
+    def sample(nbytes_each, share):
+        k = int(max(1, min(B, share // nbytes_each)))
+        return np.sort(rng.choice(B, size=k, replace=False))
+
+    label_fovs = sample(S * S * 4, budget * 5 // 8)
+    pix = None
+    if S * S * 4 > budget * 5 // 8:  # one label image alone is over its share: a seeded pixel sample of it
+        pix = np.sort(rng.choice(S * S, size=budget * 5 // 8 // 4, replace=False))
+    labels = []
+    for g in label_fovs:
+        i, b = where[g]
+        lab = (segs[i].labels if workload == "c3" else segs[i].labels8)[b].numpy().astype(np.float32)
+        labels.append(lab.reshape(-1)[pix] if pix is not None else lab)
+    arrays["labels"] = np.stack(labels)
+    arrays["label_fovs"] = (fov0 + label_fovs).astype(np.float64)
+    counts = [(sg.ncells if workload == "c3" else sg.count8).numpy() for sg in segs]
+    arrays["ncells"] = np.concatenate(counts).astype(np.float64)
+    if workload == "c3":
+        # one row per cell: fov index, the RP_NCOLS morphology columns, C x {mean, max, min, std} intensity columns
+        K, C = segs[0].max_cells, segs[0].C
+        ncols = 1 + segs[0].table.shape[-1] + 4 * C
+        rows = []
+        for g in sample(K * ncols * 8, budget * 2 // 8):
+            i, b = where[g]
+            n = int(counts[i][b])
+            t = segs[i].table[b].numpy()[:n]
+            it = segs[i].itable[b].numpy()[:n].reshape(n, 4 * C)
+            rows.append(np.concatenate([np.full((n, 1), float(fov0 + g)), t, it], axis=1))
+        arrays["features"] = np.concatenate(rows).astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, above the {budget}-byte limit")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    log(f"outputs of the last step: {', '.join(f'{k}{suffix} {v.shape}' for k, v in arrays.items())} -> {out_dir}")
 
 
 def run_chain(args):
@@ -1042,6 +1128,15 @@ def run_chain(args):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.workload == "c3":  # a run whose tables overflowed would have skipped work: refuse to report it
+        for sg in segs:
+            nm = sg.nmarkers.numpy()
+            if (nm < 0).any() or (nm > args.max_cells).any():
+                raise RuntimeError(f"a field of view produced {int(nm.max())} markers, above --max-cells {args.max_cells}")
+    ncells = np.concatenate([(sg.ncells if args.workload == "c3" else sg.count8).numpy() for sg in segs])
+    if args.dump_outputs is not None:
+        dump_chain_outputs(args.dump_outputs, segs, bounds, args.workload, fov0,
+                           suffix=f"_rank{rank}" if world > 1 else "", budget=DUMP_LIMIT_BYTES // world)
 
     exchange_info = None
     if gather:  # outside the timed region: what arrived is what was written
@@ -1071,7 +1166,7 @@ def run_chain(args):
         log(f"plate tables exchanged: {rows_last.shape} rows in the last plate, counts {counts_last}")
 
     delivered = None
-    if deliver:  # outside the timed region: what arrived on the host is what the segmenters computed
+    if deliver and args.full:  # outside the timed region: what arrived on the host is what the segmenters computed
         last = args.warmup + args.steps - 1
         rows = host_tables.rows_of(last)
         ncells_all = np.concatenate([sg.ncells.numpy() for sg in segs])
@@ -1090,31 +1185,31 @@ def run_chain(args):
     # ---- per-stage device times (HIP events on the kernels' own stream), outside the timed region ----
     # one launch of the timed region covers the FOVs of ONE stream: profile that launch size
     PB = bounds[1] - bounds[0]
-    prof = FovSegmenter(PB, 4, S, S, ctx=ctx, profile=True, max_cells=args.max_cells,
-                        bin_plane=os.environ.get("AMT_BENCH_NO_BINS") != "1",
-                        low_traffic=os.environ.get("AMT_BENCH_LOW_TRAFFIC") == "1")
-    d_prof = d_fovs[:PB]
-    stage_ms: dict[str, list[float]] = {}
-    reps = 3
-    for rep in range(reps + 1):
-        (prof.run_c3 if args.workload == "c3" else prof.run_c2)(d_prof)
-        if rep == 0:  # warm-up: this segmenter's arena grows once
-            ctx.synchronize()
-            continue
-        for k, v in prof.times.ms().items():
-            stage_ms.setdefault(k, []).append(v)
-    stage_avg = {k: float(np.mean(v)) for k, v in stage_ms.items()}
-    ncells = prof.ncells.numpy() if args.workload == "c3" else prof.count8.numpy()
-    if args.workload == "c3":  # a run whose tables overflowed would have skipped work: refuse to report it
-        for sg in segs + [prof]:
-            nm = sg.nmarkers.numpy()
+    stage_avg = None
+    if args.full:
+        prof = FovSegmenter(PB, 4, S, S, ctx=ctx, profile=True, max_cells=args.max_cells,
+                            bin_plane=os.environ.get("AMT_BENCH_NO_BINS") != "1",
+                            low_traffic=os.environ.get("AMT_BENCH_LOW_TRAFFIC") == "1")
+        d_prof = d_fovs[:PB]
+        stage_ms: dict[str, list[float]] = {}
+        reps = 3
+        for rep in range(reps + 1):
+            (prof.run_c3 if args.workload == "c3" else prof.run_c2)(d_prof)
+            if rep == 0:  # warm-up: this segmenter's arena grows once
+                ctx.synchronize()
+                continue
+            for k, v in prof.times.ms().items():
+                stage_ms.setdefault(k, []).append(v)
+        stage_avg = {k: float(np.mean(v)) for k, v in stage_ms.items()}
+        if args.workload == "c3":  # the profiled pass must not have overflowed either (the timed ones: checked above)
+            nm = prof.nmarkers.numpy()
             if (nm < 0).any() or (nm > args.max_cells).any():
                 raise RuntimeError(f"a field of view produced {int(nm.max())} markers, above --max-cells {args.max_cells}")
-    log("stage ms: " + ", ".join(f"{k}={v:.3f}" for k, v in stage_avg.items()))
+        log("stage ms: " + ", ".join(f"{k}={v:.3f}" for k, v in stage_avg.items()))
 
     # ---- flood tail: the watershed stage over rotating windows of the distinct FOVs (c3 only) ----
     tail = None
-    if args.workload == "c3" and args.tail_reps > 0 and rank == 0:
+    if args.full and args.workload == "c3" and args.tail_reps > 0 and rank == 0:
         ws_ms = []
         for rep in range(args.tail_reps):
             start = (rep * max(1, PB // 4)) % B
@@ -1134,7 +1229,7 @@ def run_chain(args):
     # ---- host-fed variant (never `value`): the same steps with every batch arriving from pinned host memory over
     # PCIe, double-buffered on a copy stream so that the transfer of batch i + 1 overlaps the segmentation of i ----
     pcie = None
-    if not distributed and not args.no_h2d and args.workload == "c3":
+    if args.full and not distributed and not args.no_h2d and args.workload == "c3":
         from arcadia_microscopy_tools_amd.feeder import FovFeeder
 
         feeder = FovFeeder(fovs.shape, device)
@@ -1171,10 +1266,12 @@ def run_chain(args):
 
     out = None
     if rank == 0:
-        npx = PB * S * S  # pixels per launch (one stream's share of the batch)
-        roofline = stage_roofline(stage_avg, npx, PB)
-        if tail is not None:
-            roofline["watershed_tail"] = tail
+        roofline = None
+        if stage_avg is not None:
+            npx = PB * S * S  # pixels per launch (one stream's share of the batch)
+            roofline = stage_roofline(stage_avg, npx, PB)
+            if tail is not None:
+                roofline["watershed_tail"] = tail
         fovs_per_step = args.plate if args.plate > 0 else world * B
         total_fovs = fovs_per_step * args.steps
         out = {
@@ -1206,10 +1303,11 @@ def run_chain(args):
                 "cells_per_fov_mean": float(np.mean(ncells)),
                 "feature_table_exchange": exchange_info,
             },
-            "roofline": roofline,
-            "host_gen_s": gen_s,
         }
-        if args.workload == "c3":
+        if roofline is not None:
+            out["roofline"] = roofline
+        out["host_gen_s"] = gen_s
+        if args.workload == "c3" and roofline is not None:
             # the whole job against the chain's roofline (448.8 MB algorithmic per FOV -> 17.8 k FOV/s at
             # 8 TB/s), and against the bytes the kernels really move (committed PMC passes, per FOV)
             alg_mb = 107 * S * S / 1e6  # C2's 40 B/px + 67 B/px for EDT ... intensity props
@@ -1228,7 +1326,7 @@ def run_chain(args):
             out["delivered_to_host"] = delivered
         if pcie is not None:
             out["pcie_inclusive"] = pcie
-        if not args.no_cpu and world == 1:  # the CPU baseline is a rank-0, N = 1 measurement
+        if args.full and not args.no_cpu and world == 1:  # the CPU baseline is a rank-0, N = 1 measurement
             out["cpu_baseline"] = cpu_baseline(np.stack(uniq), args.workload, args.cpu_fovs)
             out["gpu_over_cpu_1thread"] = out["value"] / out["cpu_baseline"]["value"]
             out["gpu_over_cpu_all_cores"] = out["value"] / out["cpu_baseline"]["all_cores"]["value"]

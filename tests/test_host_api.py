@@ -527,17 +527,19 @@ def test_nd2_timelapse_without_a_period_still_loads(tmp_path):
     assert meta.channel_metadata_list[0].resolution.xy_step_um == 0.65
 
 
-def test_nd2lite_on_the_reference_fixtures_when_present():
-    """Plumbing check against the files the reference's own tests read (RT/data, known-metadata.yml sizes); skipped on
-    machines without /root/reference (the pixels of config 1 are pinned in tests/golden/nd2_multichannel.npz)."""
-    import pathlib
-
+def test_nd2lite_on_the_reference_fixtures_when_present(golden, tmp_path):
+    """Plumbing check against the files the reference's own tests read (RT/data, known-metadata.yml sizes).  The five
+    ND2 files are stored in tests/golden/nd2_fixture_files.npz (tools/make_golden_nd2.py: byte for byte, pixel payloads
+    zeroed) and written back to disk here, so that the parser reads real files."""
     from arcadia_microscopy_tools_amd import nd2lite
     from arcadia_microscopy_tools_amd.metadata_structures import DimensionFlags
 
-    data = pathlib.Path("/root/reference/src/arcadia_microscopy_tools/tests/data")
-    if not (data / "example-zstack.nd2").exists():
-        pytest.skip("reference fixtures are not on this machine")
+    files = golden("nd2_fixture_files")
+    data = tmp_path
+    blob = files["data"].tobytes()
+    ends = np.cumsum(files["sizes"])
+    for name, start, end in zip(files["names"], ends - files["sizes"], ends):
+        (data / str(name)).write_bytes(blob[start:end])
     want = {"example-multichannel.nd2": ({"C": 4, "Y": 256, "X": 256}, DimensionFlags(0)),
             "example-pbmc.nd2": ({"C": 4, "Y": 256, "X": 256}, DimensionFlags(0)),
             "example-cerevisiae.nd2": ({"C": 2, "Y": 256, "X": 256}, DimensionFlags(0)),

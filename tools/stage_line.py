@@ -1,4 +1,4 @@
-"""Print the per-stage device times and the throughput of a bench.py JSON line (stdin)."""
+"""Print the per-stage device times and the throughput of a `bench.py --full` JSON line (stdin)."""
 import json, sys
 j = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = j["roofline"]
