@@ -215,11 +215,11 @@ def load_library():
         _share_hip_runtime_with_torch()
         try:
             lib = ctypes.CDLL(LIB_PATH)
-            quick = ctypes.PyDLL(LIB_PATH) if os.environ.get("AMT_GIL", "keep") == "keep" else lib
+            quick = ctypes.PyDLL(LIB_PATH)
         except OSError as e:  # missing ROCm runtime etc.
             raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in _SIGS.items():
-            for handle in {id(lib): lib, id(quick): quick}.values():
+            for handle in (lib, quick):
                 fn = getattr(handle, name)  # AttributeError = header / library mismatch: fail loudly
                 fn.restype = res
                 fn.argtypes = args

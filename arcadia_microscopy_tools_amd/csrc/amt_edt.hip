@@ -2,13 +2,13 @@
 //
 // scipy.ndimage.distance_transform_edt(mask) == sqrt(float64(d2)) bitwise, with d2 the exact integer
 // squared distance to the nearest zero pixel.  d2 is computed separably:
-//   pass 1 (rows)   : g(y,x) = distance to the nearest zero pixel in row y (G_INF if none).  The row is
-//                     turned into 64-pixel bit words of "zero" flags (one ballot each); the nearest zero on
-//                     either side of a pixel is a clz / ffs on its own word, walking to further words only
-//                     across solid 64-pixel stretches.  g is stored as uint16 (sides are <= 32768).
-//   pass 2 (columns): d2(y,x) = min_k (k^2 + g(y+-k,x)^2), scanning k outward while k^2 < best.  A block
-//                     stages 64 columns x (64 + 2*16) or (32 + 2*24) rows of g in LDS; only searches deeper than the halo
-//                     continue in HBM (coalesced: a wave reads 64 consecutive x of row y+-k).
+//   rows   : g(y,x) = distance to the nearest zero pixel in row y (G_INF if none).  The mask is packed into
+//            64-pixel bit words of "zero" flags; the nearest zero on either side of a pixel is a clz / ffs on its
+//            own word, walking to further words only across solid 64-pixel stretches.  g fits uint16 (sides are
+//            <= 32768).
+//   columns: d2(y,x) = min_k (k^2 + g(y+-k,x)^2), scanning k outward while k^2 < best.  A block computes the g
+//            of 64 columns x (64 + 2*16) or (32 + 2*24) rows into LDS; only searches deeper than the halo continue,
+//            with g evaluated from the words.
 // Both searches are exact and cost O(distance) per pixel, which is what nuclei-sized objects need; they
 // degrade (never fail) on very large solid regions.
 #include "amt_internal.h"
@@ -17,174 +17,14 @@ constexpr unsigned G_INF = 0xFFFFu;  // no zero pixel in this row
 // column tiles: 64 rows + 2 x 16 halo rows for batches (least staging per output row), 32 + 2 x 24 when a call
 // has too few tiles to fill the chip (single planes)
 
-__global__ void __launch_bounds__(256) edt_rows_kernel(const uint8_t* __restrict__ mask, unsigned short* __restrict__ g,
-                                                       int H, int W) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    unsigned long long* zw = reinterpret_cast<unsigned long long*>(smem_raw);  // zero flags, 64 pixels per word
-    const size_t base = ((size_t)blockIdx.y * H + blockIdx.x) * W;
-    const int nw = (W + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    for (int x0 = (threadIdx.x >> 6) * 64; x0 < W; x0 += 256) {
-        const int x = x0 + lane;
-        const unsigned long long z = __ballot(x < W && mask[base + x] == 0);  // beyond W: "not zero"
-        if (lane == 0) zw[x0 >> 6] = z;
-    }
-    __syncthreads();
-    for (int x = threadIdx.x; x < W; x += 256) {
-        const int wi = x >> 6, bit = x & 63;
-        const unsigned long long own = zw[wi];
-        unsigned d = 0;
-        if (!((own >> bit) & 1ull)) {
-            // nearest zero to the left
-            unsigned dl = G_INF, dr = G_INF;
-            unsigned long long m = own & ((1ull << bit) - 1ull);
-            int w = wi;
-            while (m == 0 && w > 0) m = zw[--w];
-            if (m) dl = (unsigned)(x - (w * 64 + 63 - __clzll((long long)m)));
-            // nearest zero to the right
-            m = bit == 63 ? 0ull : (own >> (bit + 1)) << (bit + 1);
-            w = wi;
-            while (m == 0 && w + 1 < nw) m = zw[++w];
-            if (m) dr = (unsigned)(w * 64 + __ffsll((long long)m) - 1 - x);
-            d = dl < dr ? dl : dr;
-        }
-        g[base + x] = (unsigned short)d;
-    }
-}
-
-// Rows whose width is a multiple of 8 (and 16-byte aligned planes): a thread owns 8 consecutive pixels -- one
-// 8-byte load, the "is zero" flags of its bytes by carry arithmetic, one byte of the row's flag words in LDS; the
-// nearest zero left of the group (clz) and right of it (ffs) seed a forward and a backward sweep over the 8
-// pixels, and the 8 distances leave in one 16-byte store.
-__global__ void __launch_bounds__(256) edt_rows8_kernel(const uint8_t* __restrict__ mask, unsigned short* __restrict__ g,
-                                                        int H, int W) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    unsigned long long* zw = reinterpret_cast<unsigned long long*>(smem_raw);  // zero flags, 64 pixels per word
-    uint8_t* zb = reinterpret_cast<uint8_t*>(smem_raw);
-    const size_t base = ((size_t)blockIdx.y * H + blockIdx.x) * W;
-    const int nw = (W + 63) / 64, nb = W >> 3;
-    for (int b = nb + threadIdx.x; b < nw * 8; b += 256) zb[b] = 0;  // beyond W: "not zero"
-    for (int b = threadIdx.x; b < nb; b += 256) {
-        const unsigned long long v = *reinterpret_cast<const unsigned long long*>(mask + base + (size_t)b * 8);
-        unsigned long long t = (v & 0x7f7f7f7f7f7f7f7full) + 0x7f7f7f7f7f7f7f7full;
-        t = ~(t | v | 0x7f7f7f7f7f7f7f7full);                          // 0x80 in every zero byte
-        zb[b] = (uint8_t)(((t >> 7) * 0x0102040810204080ull) >> 56);   // bit i = byte i is zero
-    }
-    __syncthreads();
-    constexpr unsigned BIG = 0x20000u;  // > any distance inside a row (sides are <= 32768)
-    for (int b = threadIdx.x; b < nb; b += 256) {
-        const int x0 = b * 8, wi = x0 >> 6, bit0 = x0 & 63;
-        const unsigned long long own = zw[wi];
-        const unsigned z8 = (unsigned)(own >> bit0) & 0xffu;
-        uint4 out = make_uint4(0u, 0u, 0u, 0u);
-        if (z8 != 0xffu) {
-            unsigned dl = BIG, dr = BIG;  // distance of pixel x0 to the nearest zero left of the group / of x0+7 right
-            unsigned long long m = own & ((1ull << bit0) - 1ull);
-            int w = wi;
-            while (m == 0 && w > 0) m = zw[--w];
-            if (m) dl = (unsigned)(x0 - (w * 64 + 63 - __clzll((long long)m)));
-            const int sh = bit0 + 8;
-            m = sh == 64 ? 0ull : (own >> sh) << sh;
-            w = wi;
-            while (m == 0 && w + 1 < nw) m = zw[++w];
-            if (m) dr = (unsigned)(w * 64 + __ffsll((long long)m) - 1 - (x0 + 7));
-            unsigned L[8], R[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const unsigned prev = i == 0 ? dl : L[i - 1] + 1u;
-                L[i] = ((z8 >> i) & 1u) ? 0u : (prev < BIG ? prev : BIG);
-            }
-#pragma unroll
-            for (int i = 7; i >= 0; --i) {
-                const unsigned nxt = i == 7 ? dr : R[i + 1] + 1u;
-                R[i] = ((z8 >> i) & 1u) ? 0u : (nxt < BIG ? nxt : BIG);
-            }
-            unsigned d[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const unsigned mn = L[i] < R[i] ? L[i] : R[i];
-                d[i] = mn >= G_INF ? G_INF : mn;
-            }
-            out.x = d[0] | (d[1] << 16);
-            out.y = d[2] | (d[3] << 16);
-            out.z = d[4] | (d[5] << 16);
-            out.w = d[6] | (d[7] << 16);
-        }
-        *reinterpret_cast<uint4*>(g + base + x0) = out;
-    }
-}
-
-template <int EC_ROWS, int EC_HALO>
-__global__ void __launch_bounds__(256) edt_cols_kernel(const unsigned short* __restrict__ g, int* __restrict__ d2_out,
-                                                       double* __restrict__ edt_out, int H, int W) {
-    constexpr int EC_TROWS = EC_ROWS + 2 * EC_HALO;
-    __shared__ unsigned short tile[EC_TROWS][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int x = blockIdx.x * 64 + lane;
-    const int y0 = blockIdx.y * EC_ROWS;
-    const size_t plane = (size_t)blockIdx.z * H * W;
-    const unsigned short* gp = g + plane;
-    const int xc = x < W ? x : W - 1;
-    // all loads of a wave are issued before the first LDS store
-    unsigned short gv[EC_TROWS / 4];
-#pragma unroll
-    for (int j = 0; j < EC_TROWS / 4; ++j) {
-        const int y = y0 - EC_HALO + wave + 4 * j;
-        gv[j] = (y >= 0 && y < H && x < W) ? gp[(size_t)y * W + xc] : (unsigned short)G_INF;
-    }
-#pragma unroll
-    for (int j = 0; j < EC_TROWS / 4; ++j) tile[wave + 4 * j][lane] = gv[j];
-    __syncthreads();
-    if (x >= W) return;
-#pragma unroll 1
-    for (int j = 0; j < EC_ROWS / 4; ++j) {
-        const int ly = EC_HALO + wave * (EC_ROWS / 4) + j;
-        const int y = y0 - EC_HALO + ly;
-        if (y >= H) break;
-        const unsigned g0 = tile[ly][lane];
-        unsigned best = 0;
-        if (g0 != 0) {
-            best = g0 == G_INF ? 0xFFFFFFFFu : g0 * g0;
-            unsigned k = 1;
-            for (; k <= (unsigned)EC_HALO && k * k < best; ++k) {
-                const unsigned gu = tile[ly - (int)k][lane], gd = tile[ly + (int)k][lane];
-                const unsigned gm = gu < gd ? gu : gd;
-                if (gm != G_INF) {
-                    const unsigned c = k * k + gm * gm;
-                    best = c < best ? c : best;
-                }
-            }
-            for (; k < 65536u && (unsigned long long)k * k < best; ++k) {  // beyond the LDS halo
-                const int yu = y - (int)k, yd = y + (int)k;
-                if (yu < 0 && yd >= H) break;
-                unsigned gm = G_INF;
-                if (yu >= 0) gm = gp[(size_t)yu * W + x];
-                if (yd < H) {
-                    const unsigned gd = gp[(size_t)yd * W + x];
-                    gm = gd < gm ? gd : gm;
-                }
-                if (gm != G_INF) {
-                    const unsigned c = k * k + gm * gm;  // < 2^31: both terms < 2^30
-                    best = c < best ? c : best;
-                }
-            }
-            // no zero pixel in the whole plane (a column sees none only then): scipy's feature transform then
-            // measures from index (-1, 0) -- distance_transform_edt(np.ones((2, 2))) == [[1, sqrt 2], [2, sqrt 5]]
-            if (best > 0x7fffffffu) best = (unsigned)(y + 1) * (unsigned)(y + 1) + (unsigned)x * (unsigned)x;
-        }
-        const size_t i = plane + (size_t)y * W + x;
-        if (d2_out) d2_out[i] = (int)best;
-        if (edt_out) edt_out[i] = sqrt((double)best);
-    }
-}
-
 // ---- both passes in one kernel, from a packed plane of zero flags (round 3) -------------------------------------------
-// The row pass wrote g as uint16 (2 bytes per pixel) and the column pass read it back with its halo (3): more traffic
-// than the mask (1) and the result (4) together.  g is a function of the row's ZERO FLAGS alone, and those are one bit per
-// pixel: edt_zero_words_kernel packs them (64 pixels per word, 1/8 byte per pixel), and a column tile computes the g of
-// its 64 x (ROWS + 2 HALO) window itself -- three words per row (its own segment and the ones left / right of it) sit
-// in LDS, a thread owns 8 pixels of a row exactly as edt_rows8_kernel does, and only a row without a zero pixel within 64
-// columns walks further words in global memory.  Searches deeper than the halo evaluate g(y +- k, x) from the words too.
+// A separate row pass would write g as uint16 (2 bytes per pixel) and the column pass read it back with its halo (3): more
+// traffic than the mask (1) and the result (4) together; that two-pass variant was measured and removed.  g is a function
+// of the row's ZERO FLAGS alone, and those are one bit per pixel: edt_zero_words_kernel packs them (64 pixels per word,
+// 1/8 byte per pixel), and a column tile computes the g of its 64 x (ROWS + 2 HALO) window itself -- three words per row
+// (its own segment and the ones left / right of it) sit in LDS, a thread owns 8 consecutive pixels of a row, and only a
+// row without a zero pixel within 64 columns walks further words in global memory.  Searches deeper than the halo
+// evaluate g(y +- k, x) from the words too.
 __global__ void __launch_bounds__(256) edt_zero_words_kernel(const uint8_t* __restrict__ mask, unsigned long long* __restrict__ zw,
                                                              int H, int W, int WW, size_t nwords, int fast) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -251,12 +91,10 @@ __global__ void __launch_bounds__(256) edt_bits_kernel(const unsigned long long*
         zs[r][c] = (y >= 0 && y < H && w >= 0 && w < WW) ? zp[(size_t)y * WW + w] : 0ull;
     }
     __syncthreads();
-    // ---- g of the window: a thread owns 8 consecutive pixels of a row (edt_rows8_kernel's arithmetic) ----
+    // ---- g of the window: a thread owns 8 consecutive pixels of a row.  The nearest zero left of the group (clz) and
+    // right of it (ffs) seed a forward and a backward sweep over the 8 pixels, and the 8 distances leave in one 16-byte
+    // store ----
     constexpr unsigned BIG = 0x20000u;  // > any distance inside a row (sides are <= 32768)
-#if defined(EDT_EXP) && EDT_EXP == 2
-    for (int task = threadIdx.x; task < EC_TROWS * 8; task += 256) *reinterpret_cast<uint4*>(&tile[task >> 3][(task & 7) * 8]) = make_uint4(0, 0, 0, 0);
-    if (false)
-#endif
     for (int task = threadIdx.x; task < EC_TROWS * 8; task += 256) {
         const int r = task >> 3, b = task & 7;
         const int y = y0 - EC_HALO + r;
@@ -313,7 +151,7 @@ __global__ void __launch_bounds__(256) edt_bits_kernel(const unsigned long long*
         *reinterpret_cast<uint4*>(&tile[r][b * 8]) = out;
     }
     __syncthreads();
-    // ---- the column search (edt_cols_kernel's, with g beyond the halo evaluated from the words).  A lane owns FOUR
+    // ---- the column search (g beyond the halo evaluated from the words).  A lane owns FOUR
     // consecutive pixels of a row: one 8-byte LDS read brings the four g of a row above / below, the four searches are
     // independent chains that share every LDS wait, and the results leave in one 16-byte store (a wave writes 4 rows x
     // 256 bytes; with a pixel per lane the stores alone took 223 us per 48 planes, 3.6 TB/s) ----
@@ -334,9 +172,6 @@ __global__ void __launch_bounds__(256) edt_bits_kernel(const unsigned long long*
 #pragma unroll
             for (int i = 0; i < 4; ++i) best[i] = g0[i] == G_INF ? 0xFFFFFFFFu : g0[i] * g0[i];
         }
-#if defined(EDT_EXP) && EDT_EXP == 1
-        if (false)
-#endif
         for (unsigned k = 1; k <= (unsigned)EC_HALO; ++k) {
             const unsigned kk = k * k;
             if (!(kk < best[0] || kk < best[1] || kk < best[2] || kk < best[3])) break;
@@ -371,7 +206,8 @@ __global__ void __launch_bounds__(256) edt_bits_kernel(const unsigned long long*
                         bq = c < bq ? c : bq;
                     }
                 }
-                // no zero pixel in the whole plane: scipy's feature transform then measures from index (-1, 0)
+                // no zero pixel in the whole plane (a column sees none only then): scipy's feature transform then
+                // measures from index (-1, 0) -- distance_transform_edt(np.ones((2, 2))) == [[1, sqrt 2], [2, sqrt 5]]
                 if (bq > 0x7fffffffu) bq = (unsigned)(y + 1) * (unsigned)(y + 1) + (unsigned)x * (unsigned)x;
             }
             best[i] = bq;
@@ -392,57 +228,27 @@ __global__ void __launch_bounds__(256) edt_bits_kernel(const unsigned long long*
     }
 }
 
-// AMT_EDT_FUSED=0: the two-pass transform through a uint16 plane of row distances (A/B switch; identical results)
-static bool edt_fused_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_EDT_FUSED");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
 extern "C" int amt_edt(amt_ctx* ctx, const uint8_t* mask, int32_t* d2_out, double* edt_out, int nplanes, int H,
                        int W) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(mask && (d2_out || edt_out) && nplanes >= 0 && H > 0 && W > 0, "edt: bad arguments");
     AMT_REQUIRE(H <= 32768 && W <= 32768, "edt: image larger than 32768 pixels per side");
     if (nplanes == 0) return AMT_OK;
-    const size_t n = (size_t)H * W;
     const size_t tiles64 = (size_t)((W + 63) / 64) * ((H + 63) / 64) * nplanes;
-    if (edt_fused_enabled()) {
-        const int WW = (W + 63) / 64;
-        const size_t nwords = (size_t)nplanes * H * WW;
-        AMT_TRY(amt_arena_begin(ctx, amt_align(nwords * 8)));
-        unsigned long long* zw = arena_take_t<unsigned long long>(ctx, nwords);
-        const int fast = W % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0;
-        hipLaunchKernelGGL(edt_zero_words_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, ctx->stream, mask, zw, H,
-                           W, WW, nwords, fast);
-        AMT_LAUNCH_CHECK();
-        if (tiles64 >= 4096 && !edt_out)
-            hipLaunchKernelGGL((edt_bits_kernel<64, 16>), dim3(WW, (H + 63) / 64, nplanes), dim3(256), 0, ctx->stream, zw, d2_out,
-                               edt_out, H, W, WW);
-        else
-            hipLaunchKernelGGL((edt_bits_kernel<32, 24>), dim3(WW, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, zw, d2_out,
-                               edt_out, H, W, WW);
-        AMT_LAUNCH_CHECK();
-        return AMT_OK;
-    }
-    AMT_TRY(amt_arena_begin(ctx, amt_align((size_t)nplanes * n * 2)));
-    unsigned short* g = arena_take_t<unsigned short>(ctx, (size_t)nplanes * n);
-    if ((W & 7) == 0 && (reinterpret_cast<uintptr_t>(mask) & 7) == 0)  // g comes from the arena: 256-byte aligned
-        hipLaunchKernelGGL(edt_rows8_kernel, dim3(H, nplanes), dim3(256), (size_t)((W + 63) / 64) * 8, ctx->stream, mask,
-                           g, H, W);
-    else
-        hipLaunchKernelGGL(edt_rows_kernel, dim3(H, nplanes), dim3(256), (size_t)((W + 63) / 64) * 8, ctx->stream, mask,
-                           g, H, W);
+    const int WW = (W + 63) / 64;
+    const size_t nwords = (size_t)nplanes * H * WW;
+    AMT_TRY(amt_arena_begin(ctx, amt_align(nwords * 8)));
+    unsigned long long* zw = arena_take_t<unsigned long long>(ctx, nwords);
+    const int fast = W % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0;
+    hipLaunchKernelGGL(edt_zero_words_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, ctx->stream, mask, zw, H,
+                       W, WW, nwords, fast);
     AMT_LAUNCH_CHECK();
     if (tiles64 >= 4096 && !edt_out)  // with the float64 output (sqrt + 8-byte stores) the shorter tiles measured faster
-        hipLaunchKernelGGL((edt_cols_kernel<64, 16>), dim3((W + 63) / 64, (H + 63) / 64, nplanes), dim3(256), 0,
-                           ctx->stream, g, d2_out, edt_out, H, W);
+        hipLaunchKernelGGL((edt_bits_kernel<64, 16>), dim3(WW, (H + 63) / 64, nplanes), dim3(256), 0, ctx->stream, zw, d2_out,
+                           edt_out, H, W, WW);
     else
-        hipLaunchKernelGGL((edt_cols_kernel<32, 24>), dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0,
-                           ctx->stream, g, d2_out, edt_out, H, W);
+        hipLaunchKernelGGL((edt_bits_kernel<32, 24>), dim3(WW, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, zw, d2_out,
+                           edt_out, H, W, WW);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }

@@ -727,8 +727,7 @@ static int launch_fused(amt_ctx* ctx, const TIn* in, double scale, double* out, 
         const bool aligned = (W % 8 == 0) && W >= 256 && (in_stride % 8 == 0) && ((reinterpret_cast<uintptr_t>(in) & 15) == 0) &&
                              ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
         const bool modeok = mode == AMT_MODE_NEAREST || mode == AMT_MODE_REFLECT || mode == AMT_MODE_MIRROR;
-        const char* off = getenv("AMT_GAUSS_LDS");
-        if (aligned && modeok && H > 2 * R && !(off && off[0] == '0')) {
+        if (aligned && modeok && H > 2 * R) {
             constexpr int RP = (R + 7) & ~7;
             constexpr int OUTW2 = 256 - 2 * RP;
             const int gx2 = (W + OUTW2 - 1) / OUTW2;
@@ -944,15 +943,14 @@ static int gaussian_typed(amt_ctx* ctx, const TIn* in, double scale, double* out
     }
     // register-blocked two-pass path
     const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(tmp) & 15) == 0 &&
-                         (in_stride * sizeof(TIn)) % 16 == 0 && getenv("AMT_GAUSS_NO_GLDS") == nullptr;
+                         (in_stride * sizeof(TIn)) % 16 == 0;
     bool v_done = false, h_done = false;
-    const bool no_rc = getenv("AMT_GAUSS_NO_RC") != nullptr;  // A/B: the runtime-radius instances for r = 64 too
     if (aligned && W % 64 == 0 && H > 2 * r) {  // vertical pass, LDS-DMA staging
         int TH = sizeof(TIn) == 2 ? 128 : 64;
         const int rows_pad = (TH + 2 * r + 7) & ~7;
         const size_t smem0 = (size_t)rows_pad * 64 * sizeof(TIn) + (size_t)(2 * r + 1) * 8 + (size_t)(TH + 2 * r);
         dim3 g0(W / 64, (H + TH - 1) / TH, nplanes);
-        if (r == 64 && !no_rc)
+        if (r == 64)
             hipLaunchKernelGGL((conv_v8g_kernel<TIn, 64>), g0, dim3(256), smem0, ctx->stream, in, scale, tmp, H, W, wdev, r,
                                mode, cval, TH, in_stride);
         else
@@ -982,7 +980,7 @@ static int gaussian_typed(amt_ctx* ctx, const TIn* in, double scale, double* out
         const size_t smem1 = (size_t)ROWS * H8G_PITCH * sizeof(double) + (size_t)(2 * r + 1) * 8;
         dim3 g1((W + TW - 1) / TW, (H + ROWS - 1) / ROWS, nplanes);
         const int remap = (g1.x * g1.y) % 8 == 0;
-        if (r == 64 && !no_rc)
+        if (r == 64)
             hipLaunchKernelGGL((conv_h8g_kernel<ROWS, 64>), g1, dim3(256), smem1, ctx->stream, tmp, out, H, W, wdev, r, mode,
                                cval, TW, minuend, remap);
         else

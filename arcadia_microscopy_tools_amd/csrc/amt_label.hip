@@ -898,26 +898,6 @@ int amt_i_ccl_roots(amt_ctx* ctx, const void* in, int in_dtype, int* L, int* blk
 int amt_i_tile_rows(int H) { return (H + TILE_R - 1) / TILE_R; }
 size_t amt_i_rootlist_cap(int W) { return (size_t)TILE_R * W; }
 
-// AMT_CCL_RUNS=0: amt_label keeps the parent plane for masks too (A/B switch; identical results)
-static bool ccl_runs_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_CCL_RUNS");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
-// AMT_CCL_BITS=0: the pixel-per-lane tile kernel for masks too (A/B switch; identical results)
-static bool ccl_bits_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_CCL_BITS");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
 // ints of scratch behind `multi`: the flag (16 ints) + two 64-bit column words per tile
 size_t amt_i_ccl_scratch_ints(int nplanes, int H, int W) {
     return 16 + (size_t)nplanes * ((W + 63) / 64) * ((H + TILE_R - 1) / TILE_R) * 4;
@@ -936,7 +916,7 @@ static int ccl_tileroots(amt_ctx* ctx, const T* in, int* L, int* rootlist, int* 
     const int ncol_blocks = (ncol_jobs + 256 * segs - 1) / (256 * segs);
     dim3 gb(segs, nrow_blocks + ncol_blocks, nplanes);
     bool done = false;
-    if (std::is_same<T, uint8_t>::value && multi && ccl_bits_enabled() && W % 16 == 0 &&
+    if (std::is_same<T, uint8_t>::value && multi && W % 16 == 0 &&
         (reinterpret_cast<uintptr_t>(in) & 15) == 0 && ((size_t)H * W) % 16 == 0) {
         // masks: the bit-parallel tile kernel; a plane batch that turns out to hold other byte values is redone below
         AMT_HIP_CHECK(hipMemsetAsync(multi, 0, sizeof(int), ctx->stream));
@@ -974,7 +954,7 @@ static int ccl_tileroots(amt_ctx* ctx, const T* in, int* L, int* rootlist, int* 
 
 // the watershed's labelling of its mask from run tables (amt_internal.h)
 bool amt_i_ccl_runs_ok(const void* in, int H, int W, int nplanes) {
-    return ccl_runs_enabled() && W % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && ((size_t)H * W) % 16 == 0 &&
+    return W % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && ((size_t)H * W) % 16 == 0 &&
            (size_t)nplanes * amt_i_tile_rows(H) * ((W + 63) / 64) * RT_CAP < 0x7fffffffull;  // run indices are ints
 }
 
@@ -1161,7 +1141,7 @@ static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, 
     // tile-local union-find + seams; only the listed tile roots are compressed, pixels resolve in two hops
     const int segs = (W + 63) / 64;
     const int ntiles = nplanes * trows * segs;
-    const bool runs = in_dtype == AMT_U8 && ccl_runs_enabled() && W % 16 == 0 &&
+    const bool runs = in_dtype == AMT_U8 && W % 16 == 0 &&
                       (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                       n % 16 == 0 && (size_t)ntiles * 64 < 0x7fffffffull;
     if (runs) {

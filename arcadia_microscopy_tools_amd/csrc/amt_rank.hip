@@ -832,7 +832,6 @@ static int medr_try(amt_ctx* ctx, const uint16_t* in, uint16_t* out, int nplanes
                     int fh, int fw, int mode, uint16_t cval) {
     if ((W & 7) || W < 16 || H < 16 || fh > 5 || fw > 5) return 0;
     if (!(mode == AMT_MODE_REFLECT || mode == AMT_MODE_NEAREST || mode == AMT_MODE_CONSTANT)) return 0;
-    if (getenv("AMT_MM_TILE") != nullptr) return 0;
     const int ry = fh / 2, rx = fw / 2;
     int hw[3] = {-1, -1, -1};
     for (int y = 0; y < fh; ++y) {
@@ -985,8 +984,7 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
                 }
             // register kernel (no LDS, rows loaded 2 ry + 1 steps ahead): aligned widths and boundary modes whose
             // out-of-image columns mirror the edge group (wrap / mirror keep the tile kernel)
-            if ((W & 7) == 0 && W >= 16 && H >= 16 && (mode == AMT_MODE_REFLECT || mode == AMT_MODE_NEAREST || mode == AMT_MODE_CONSTANT) &&
-                getenv("AMT_MM_TILE") == nullptr) {
+            if ((W & 7) == 0 && W >= 16 && H >= 16 && (mode == AMT_MODE_REFLECT || mode == AMT_MODE_NEAREST || mode == AMT_MODE_CONSTANT)) {
                 // disks get compile-time half-widths, rectangles one run-time half-width; anything else (crosses,
                 // diamonds, gapped disks) the run-time table, up to 7 rows
                 int shape = 0;

@@ -372,8 +372,7 @@ static int hist_f64_launch(amt_ctx* ctx, const double* in, const double* minmax,
     AMT_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)nplanes * nbins * sizeof(uint32_t), ctx->stream));
     if (n == 0) return AMT_OK;
     size_t smem = (size_t)(nbins + 1) * sizeof(double) + (size_t)4 * nbins * sizeof(uint32_t);
-    static const int hg = getenv("AMT_HIST_GRID") ? atoi(getenv("AMT_HIST_GRID")) : 512;  // A/B: blocks per plane
-    dim3 grid(amt_grid_for(n, 256 * 16, hg), nplanes);
+    dim3 grid(amt_grid_for(n, 256 * 16, 512), nplanes);  // at most 512 blocks per plane
     hipLaunchKernelGGL(hist_f64_kernel, grid, dim3(256), smem, ctx->stream, in, minmax, hist, nbins, n, bins);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
@@ -1593,9 +1592,8 @@ extern "C" int amt_percentile_f64(amt_ctx* ctx, const double* in, const double* 
     const size_t nbr = (size_t)nplanes * nq;
     // blocks per plane of the classify pass: enough of them to fill the chip over all planes, few enough that their list
     // cursors do not queue on the bracket's cache line
-    static const int pq_grid_env = getenv("AMT_PQ_GRID") ? atoi(getenv("AMT_PQ_GRID")) : 0;  // A/B
-    int want = pq_grid_env > 0 ? pq_grid_env : 4096 / nplanes;
-    want = want < 64 ? 64 : (want > 256 && pq_grid_env <= 0 ? 256 : want);
+    int want = 4096 / nplanes;
+    want = want < 64 ? 64 : (want > 256 ? 256 : want);
     const unsigned gparts = amt_grid_for(n, 256 * PQ_VPT, (unsigned)want);
     AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(rank_req) * 8) + amt_align(sizeof(pq_bracket) * nbr) +
                                      amt_align(nbr * cap * 8) + amt_align(sizeof(sel_state) * 2 * nbr) +

@@ -34,40 +34,23 @@
 #include "amt_internal.h"
 #include <hip/hip_ext.h>
 
-// component classes
-// LB = an L component too large for a persistent flood workgroup that owns only half a CU's LDS (ws_flood_persist_kernel)
-enum { CLS_NONE = 0, CLS_UNIFORM = 1, CLS_XS = 2, CLS_S = 3, CLS_M = 4, CLS_M2 = 5, CLS_L = 6, CLS_X = 7, CLS_LB = 8, CLS_G = 9 };
-constexpr int WS_NLISTS = 7;  // worklists XS, S, M, M2, L, X, LB
-constexpr int WS_CTR = 24;    // ints per plane: work counters [0..7), HBM flood [7], has_g [8], list sizes [9..16), ncomp [16]
-// LDS tile classes: max pixels of the bounding box, max d2 (bucket count - 1).  XS / S / M / M2 / L are flooded by
-// ws_flood_batch_kernel (6 bytes of LDS per pixel + 8 per bucket), X -- the few boxes between L and the 15-bit
-// index limit -- by the one-pop-at-a-time ws_flood_lds_kernel (4 bytes per pixel).
+// component classes (the values of the LDS classes S .. X are consecutive: worklist k holds class CLS_S + k)
+enum { CLS_NONE = 0, CLS_UNIFORM = 1, CLS_S = 3, CLS_M = 4, CLS_M2 = 5, CLS_L = 6, CLS_X = 7, CLS_G = 9 };
+constexpr int WS_NLISTS = CLS_X - CLS_S + 1;  // worklists S, M, M2, L, X
+constexpr int WS_CTR = 24;  // ints per plane of the counters block (layout: watershed_common)
+// LDS tile classes: max pixels of the bounding box, max d2 (bucket count - 1).  S / M / M2 / L are flooded by
+// ws_flood_persist_kernel (LDS reserved per component: 4 bytes per cell, 2 per queue entry, 6 per bucket), X -- the few
+// boxes between L and the 15-bit index limit -- by the one-pop-at-a-time ws_flood_lds_kernel (4 bytes per pixel).
 // Round 3: a class XS (1,280 px / 256 buckets, 9.2 KB: 17 workgroups per CU) for the 46 % of the synthetic plate's flooded
-// components that fit it was measured and is switched OFF (AMT_WS_XS_PX 0): occupancy does bound the small classes
-// (padding S: 10 workgroups per CU 468 us, 5 per CU 711 us), but every class launch has a floor of ~250 us -- its
-// longest component chain -- so splitting S (468 us) gave XS 255 + S 310 us, the stage stayed at 2.51 ms per 48 FOVs and
-// the 48-FOV plate's went from 1.07 to 1.16 ms.
-#ifndef AMT_WS_XS_PX
-#define AMT_WS_XS_PX 0
-#define AMT_WS_XS_NB 256
-#endif
-#ifndef AMT_WS_S_PX
-#define AMT_WS_S_PX 2048
-#define AMT_WS_S_NB 512
-#endif
-#ifndef AMT_WS_M_PX
-// 4,096 px (27 KB with the bucket words: five workgroups per CU).  Measured against 8,192 px / 1,024 buckets (two per
+// components that fit it was measured and removed: occupancy does bound the small classes (padding S: 10 workgroups per
+// CU 468 us, 5 per CU 711 us), but every class launch has a floor of ~250 us -- its longest component chain -- so
+// splitting S (468 us) gave XS 255 + S 310 us, the stage stayed at 2.51 ms per 48 FOVs and the 48-FOV plate's went from
+// 1.07 to 1.16 ms.
+constexpr int S_PX = 2048, S_NB = 512;
+// M: 4,096 px (27 KB with the bucket words: five workgroups per CU).  Measured against 8,192 px / 1,024 buckets (two per
 // CU): watershed stage 1.86 -> 1.73 ms per 32 FOVs, 0.95 -> 0.79 ms per 12 FOVs; boxes above 4,096 px join class M2 / L
-#define AMT_WS_M_PX 4096
-#define AMT_WS_M_NB 512
-#endif
-constexpr int XS_PX = AMT_WS_XS_PX, XS_NB = AMT_WS_XS_NB;
-constexpr int S_PX = AMT_WS_S_PX, S_NB = AMT_WS_S_NB;
-constexpr int M_PX = AMT_WS_M_PX, M_NB = AMT_WS_M_NB;
-#ifndef AMT_WS_M2_PX
-#define AMT_WS_M2_PX 8192
-#endif
-constexpr int M2_PX = AMT_WS_M2_PX, M2_NB = 1024;  // 54 KB: two workgroups per CU (0 = class unused)
+constexpr int M_PX = 4096, M_NB = 512;
+constexpr int M2_PX = 8192, M2_NB = 1024;
 constexpr int L_PX = 24576, L_NB = 2048;
 constexpr int X_PX = 32512, X_NB = 2048;  // pixel indices must fit the 15-bit link field
 
@@ -474,7 +457,7 @@ __global__ void __launch_bounds__(256) ws_classify_kernel(comp_row* __restrict__
                                                           int* __restrict__ moff, int* __restrict__ boff,
                                                           int* __restrict__ has_g, int* __restrict__ wl,
                                                           int* __restrict__ wl_count, int* __restrict__ Fall, size_t n,
-                                                          int nplanes, size_t row_stride, int use_d2, int pf_slots) {
+                                                          int nplanes, size_t row_stride, int use_d2) {
     comp_row* r = rows + (size_t)blockIdx.y * row_stride;
     int* mo = moff + (size_t)blockIdx.y * row_stride;
     int* bo = boff + (size_t)blockIdx.y * row_stride;
@@ -496,16 +479,10 @@ __global__ void __launch_bounds__(256) ws_classify_kernel(comp_row* __restrict__
         } else {
             const long long area = (long long)(c.x1 - c.x0 + 3) * (c.y1 - c.y0 + 3);  // with the sentinel ring
             if (c.labmax >= 0xFFFF) cls = CLS_G;  // labels are kept as 16-bit values in LDS
-            else if (area <= XS_PX && c.cmax < XS_NB) cls = CLS_XS;
             else if (area <= S_PX && c.cmax < S_NB) cls = CLS_S;
             else if (area <= M_PX && c.cmax < M_NB) cls = CLS_M;
             else if (area <= M2_PX && c.cmax < M2_NB) cls = CLS_M2;
-            else if (area <= L_PX && c.cmax < L_NB) {
-                // bytes the persistent flood would reserve for it (6 per tile cell and per bucket, 2,560-byte slots)
-                const long long qn = c.npix > 0 ? c.npix : area;  // queue entries: one per pixel of the component
-                const long long need = (((area + 1) & ~1ll) * 4 + ((qn + 1) & ~1ll) * 2 + ((c.cmax + 2) & ~1) * 6 + 2559) / 2560;
-                cls = (pf_slots > 0 && need > pf_slots) ? CLS_LB : CLS_L;
-            }
+            else if (area <= L_PX && c.cmax < L_NB) cls = CLS_L;
             else if (area <= X_PX && c.cmax < X_NB) cls = CLS_X;
             else cls = CLS_G;
         }
@@ -521,14 +498,14 @@ __global__ void __launch_bounds__(256) ws_classify_kernel(comp_row* __restrict__
         // per-class worklists of this plane (order is irrelevant: components are independent).  One slot counter per
         // class and plane: a returning atomic per COMPONENT queued hundreds deep on one address (the kernel took 60 us
         // for 50,000 components); a wave now reserves its slots with one atomic per class it holds
-        for (int k = 0; k <= CLS_LB - CLS_XS; ++k) {
-            const unsigned long long m = __ballot(live && cls == CLS_XS + k);
+        for (int k = 0; k < WS_NLISTS; ++k) {
+            const unsigned long long m = __ballot(live && cls == CLS_S + k);
             if (!m) continue;
             const int leader = __ffsll((long long)m) - 1;
             int base = 0;
             if (lane == leader) base = atomicAdd(&wl_count[k * nplanes + blockIdx.y], __popcll(m));
             base = __shfl(base, leader);
-            if (live && cls == CLS_XS + k)
+            if (live && cls == CLS_S + k)
                 wl[((size_t)k * nplanes + blockIdx.y) * row_stride + base + __popcll(m & ((1ull << lane) - 1ull))] = i;
         }
     }
@@ -912,7 +889,7 @@ extern "C" int amt_ws_debug_reset() {
 }
 #endif
 // One component, flooded by one wave in the LDS arrays it is given (cell: npx words, cnt: nb words, offs: nb halves, queue:
-// npx halves).  Shared by the per-class kernels (fixed layout per class) and the persistent kernel (layout per component).
+// npx halves), laid out per component by ws_flood_persist_kernel.
 __device__ __forceinline__ void ws_flood_component(unsigned* cell, unsigned* cnt, unsigned short* offs, unsigned short* queue,
                                                    const int* __restrict__ d2, const int* __restrict__ L,
                                                    const int* __restrict__ T, int* __restrict__ out,
@@ -1165,57 +1142,23 @@ __device__ __forceinline__ void ws_flood_component(unsigned* cell, unsigned* cnt
     __builtin_amdgcn_wave_barrier();
 }
 
-template <int TILE_PX, int NB>
-__global__ void __launch_bounds__(64) ws_flood_batch_kernel(const int* __restrict__ d2all, const int* __restrict__ Lall,
-                                                            const int* __restrict__ Tall, int* __restrict__ outall,
-                                                            const comp_row* __restrict__ rows,
-                                                            const int* __restrict__ wl, const int* __restrict__ wl_count,
-                                                            int* __restrict__ counters, size_t row_stride, int H, int W,
-                                                            int seeds_first, int* __restrict__ ties,
-                                                            const int* __restrict__ mkall, amt_runtabs rt) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    unsigned* cell = reinterpret_cast<unsigned*>(smem_raw);
-    unsigned* cnt = cell + TILE_PX;                                       // NB words: histogram, then {hd | tl << 16}
-    unsigned short* offs = reinterpret_cast<unsigned short*>(cnt + NB);  // NB segment starts
-    unsigned short* queue = offs + NB;                                    // TILE_PX entries
-    const int plane = blockIdx.y;
-    const size_t n = (size_t)H * W;
-    const int* d2 = d2all + (size_t)plane * n;
-    const int* L = Lall + (size_t)plane * n;
-    const int* T = Tall + (size_t)plane * n;
-    int* out = outall + (size_t)plane * n;
-    const int* mk = mkall + (size_t)plane * n;  // marker labels (the membership test keeps them inside the mask)
-    const comp_row* rr = rows + (size_t)plane * row_stride;
-    const int* mylist = wl + (size_t)plane * row_stride;
-    const int nwork = wl_count[plane];
-    const int lane = threadIdx.x;
-    while (true) {
-        int kk = 0;
-        if (lane == 0) kk = atomicAdd(&counters[plane], 1);
-        kk = __builtin_amdgcn_readfirstlane(kk);
-        if (kk >= nwork) break;
-        const int c = mylist[kk];
-        const comp_row cr = rr[c];
-        ws_flood_component(cell, cnt, offs, queue, d2, L, T, out, mk, cr, c, W, seeds_first, ties, plane, lane, rt);
-    }
-}
-
 // ---- one launch for all LDS classes ---------------------------------------------------------------------------------
 // Round 3.  The per-class launches are bound by LDS capacity x time: every workgroup reserves its class's MAXIMUM (15 KB
 // for a component that needs 8), a class cannot finish before its longest component, and the classes compete for the same
 // LDS whichever way they are launched (in order 1.41 ms, overlapped 1.06 ms per 48 planes -- the sum barely moves).
-// Here ONE workgroup of 16 waves owns a CU's whole LDS and hands it out in 2,560-byte slots: a wave takes the next
+// Here ONE workgroup of PF_NWAVES waves owns a CU's whole LDS and hands it out in 2,560-byte slots: a wave takes the next
 // component of a global list (largest classes first), reserves exactly the slots ITS box and buckets need (compare-and-
-// swap on a 64-bit mask of slots), floods with the same code as the class kernels, and returns the slots.
-//   * two lists: "big" (classes L, M2) and "small" (M, S, XS).  Wave 0 of a workgroup serves the big list first and the
+// swap on a 64-bit mask of slots), floods it (ws_flood_component), and returns the slots.
+//   * two lists: "big" (classes L, M2) and "small" (M, S).  Wave 0 of a workgroup serves the big list first and the
 //     other waves wait for its first reservation, so a component that needs most of a CU starts at time zero instead of
-//     behind fifteen small ones; when a list runs dry its waves move to the other one.
+//     behind the small ones; when a list runs dry its waves move to the other one.
 //   * a wave that finds the LDS full sleeps and retries; no wave waits while holding slots, so the workgroup always drains.
 constexpr int PF_SLOT = 2560;
-constexpr int PF_SLOTS_FULL = 63;            // data slots of a workgroup that owns a whole CU (the 64th: control words)
-constexpr int PF_SLOTS_HALF = 31;            // ... that owns half a CU: two such workgroups, or other kernels, share it
-constexpr int PF_WAVES = 16;                 // upper bound (launch bounds); the launch decides
-constexpr int PF_NCLS = 5;                   // XS, S, M, M2, L (worklist slots 0..4)
+constexpr int PF_SLOTS = 63;   // data slots of a workgroup (the 64th: control words); a maximal L box needs 63
+// waves per workgroup, also the launch bounds: they set the register budget (bounds of 16 waves cap the kernel at 128
+// VGPRs, and at that cap it spills to scratch; 10 waves allow 137 and fit three waves per SIMD, all the launch needs)
+constexpr int PF_NWAVES = 10;
+constexpr int PF_NCLS = 4;     // S, M, M2, L (worklist slots 0..3)
 
 // idx[c * (nplanes + 1) + plane] = components of class c in the planes before `plane` (the last entry: all of them);
 // ctl[0] / ctl[1] = cursors of the big / small list (zeroed), ctl[2] / ctl[3] = their lengths
@@ -1236,22 +1179,22 @@ __global__ void __launch_bounds__(64) ws_flood_index_kernel(const int* __restric
     if (threadIdx.x == 0) {
         ctl[0] = 0;
         ctl[1] = 0;
-        ctl[2] = tot[4] + tot[3];           // big: L then M2
-        ctl[3] = tot[2] + tot[1] + tot[0];  // small: M, S, XS
+        ctl[2] = tot[3] + tot[2];  // big: L then M2
+        ctl[3] = tot[1] + tot[0];  // small: M then S
     }
 }
 
-__global__ void __launch_bounds__(PF_WAVES * 64) ws_flood_persist_kernel(
+__global__ void __launch_bounds__(PF_NWAVES * 64) ws_flood_persist_kernel(
     const int* __restrict__ d2all, const int* __restrict__ Lall, const int* __restrict__ Tall, int* __restrict__ outall,
     const comp_row* __restrict__ rows, const int* __restrict__ wl, const int* __restrict__ idx, int* __restrict__ ctl,
     size_t row_stride, int H, int W, int seeds_first, int* __restrict__ ties, const int* __restrict__ mkall, int nplanes,
-    int pf_slots, amt_runtabs rt) {
+    amt_runtabs rt) {
     extern __shared__ __attribute__((aligned(16))) char pf_smem[];
-    unsigned long long* slotmask = reinterpret_cast<unsigned long long*>(pf_smem + (size_t)pf_slots * PF_SLOT);
+    unsigned long long* slotmask = reinterpret_cast<unsigned long long*>(pf_smem + (size_t)PF_SLOTS * PF_SLOT);
     int* first_done = reinterpret_cast<int*>(slotmask + 1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (threadIdx.x == 0) {
-        *slotmask = ~0ull << pf_slots;  // bit s set = slot s taken; the slots from pf_slots on do not exist (control block)
+        *slotmask = ~0ull << PF_SLOTS;  // bit s set = slot s taken; slot PF_SLOTS does not exist (control block)
         *first_done = 0;
     }
     __syncthreads();
@@ -1275,13 +1218,13 @@ __global__ void __launch_bounds__(PF_WAVES * 64) ws_flood_persist_kernel(
         // item g of the list -> class, plane, component
         int cls, within = g;
         if (list == 0) {
-            const int nL = idx[4 * (nplanes + 1) + nplanes];
-            cls = within < nL ? 4 : 3;
-            if (cls == 3) within -= nL;
+            const int nL = idx[3 * (nplanes + 1) + nplanes];
+            cls = within < nL ? 3 : 2;
+            if (cls == 2) within -= nL;
         } else {
-            const int nM = idx[2 * (nplanes + 1) + nplanes], nS = idx[1 * (nplanes + 1) + nplanes];
-            cls = within < nM ? 2 : (within < nM + nS ? 1 : 0);
-            within -= cls == 2 ? 0 : (cls == 1 ? nM : nM + nS);
+            const int nM = idx[1 * (nplanes + 1) + nplanes];
+            cls = within < nM ? 1 : 0;
+            if (cls == 0) within -= nM;
         }
         const int* ci = idx + cls * (nplanes + 1);
         int lo = 0, hi = nplanes - 1;  // the last plane whose offset is <= within
@@ -2034,10 +1977,7 @@ __global__ void __launch_bounds__(256) ws_final_runs_kernel(const unsigned long 
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
     if (xg >= W) return;
-#ifndef AMT_WS_FQ
-#define AMT_WS_FQ 4
-#endif
-    constexpr int FQ = AMT_WS_FQ;  // rows per lane whose loads are in flight together
+    constexpr int FQ = 4;  // rows per lane whose loads are in flight together
     const int* lb = lab_s[wv];
     auto lab = [&](int k) -> int { return fast ? lb[k] : F[ccl_rt_root(rtab, (size_t)t, k, ty, bx, W)]; };
 #pragma unroll
@@ -2085,67 +2025,6 @@ __global__ void __launch_bounds__(256) ws_final_runs_kernel(const unsigned long 
             if (y < H) *reinterpret_cast<int4*>(out + (size_t)y * W + xg) = o[q];
         }
     }
-}
-
-// AMT_WS_ANYORDER=0 keeps the flood classes of a context without auxiliary streams strictly in order (A/B switch)
-static bool ws_anyorder() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_WS_ANYORDER");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
-// AMT_WS_PERSIST: 0 = the per-class flood launches of round 2, 1 = one persistent launch, a workgroup per CU with all
-// its LDS, 2 = two workgroups per CU with half the LDS each (A/B switch; identical results)
-static int ws_persist() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_WS_PERSIST");
-        v = (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
-    }
-    return v;
-}
-// AMT_WS_PF_SLOTS: 2,560-byte LDS slots of a mode-1 workgroup (8..63; fewer leave LDS on the CU for other kernels)
-static int ws_pf_slots() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_WS_PF_SLOTS");
-        v = e ? atoi(e) : PF_SLOTS_FULL;
-        if (v < 8 || v > PF_SLOTS_FULL) v = PF_SLOTS_FULL;
-    }
-    return v;
-}
-static int ws_pf_waves() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_WS_PF_WAVES");
-        v = e ? atoi(e) : 10;
-        if (v < 1 || v > PF_WAVES) v = 10;
-    }
-    return v;
-}
-
-// AMT_WS_RUNS=0: the fused chain reads the parent plane in its statistics and final passes (A/B switch; same results)
-static bool ws_runs_enabled() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_WS_RUNS");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
-
-// AMT_WS_LDS_PAD=bytes: extra dynamic LDS per flood workgroup (occupancy experiments only)
-static size_t ws_lds_pad() {
-    static long v = -1;
-    if (v < 0) {
-        const char* e = getenv("AMT_WS_LDS_PAD");
-        v = e ? atol(e) : 0;
-        if (v < 0) v = 0;
-    }
-    return (size_t)v;
 }
 
 static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const int32_t* markers,
@@ -2203,7 +2082,7 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     const int trows = amt_i_tile_rows(H);
     const size_t lcap = amt_i_rootlist_cap(W);
     const size_t nlist = (size_t)nplanes * trows;
-    size_t need = 5 * amt_align(np * 4) + amt_align(nlist * lcap * 4) + amt_align(nlist * 4) + 10 * amt_align(nr * 4) + amt_align(nr * sizeof(comp_row)) +
+    size_t need = 5 * amt_align(np * 4) + amt_align(nlist * lcap * 4) + amt_align(nlist * 4) + (3 + WS_NLISTS) * amt_align(nr * 4) + amt_align(nr * sizeof(comp_row)) +
                   9 * amt_align(nplanes * 4 * WS_CTR) + amt_align((size_t)nplanes * 4) + amt_align((size_t)PF_NCLS * (nplanes + 1) * 4) +
                   amt_align(64);
     need += use_d2 ? 2 * amt_align((size_t)nplanes * bstride * 4) : amt_align((size_t)nplanes * bstride * sizeof(hp_elem));
@@ -2215,10 +2094,10 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     const size_t ccl_ints = amt_i_ccl_scratch_ints(nplanes, H, W);
     need += amt_align(ccl_ints * 4);
     // the fused chain's path (d2 relief, marker list, clear_border + relabel fused): the mask's run tables serve the
-    // statistics and the final mapping instead of the parent plane (AMT_WS_RUNS=0: the parent plane everywhere)
+    // statistics and the final mapping instead of the parent plane
     const int segs = (W + 63) / 64;
     const int ntiles = nplanes * trows * segs;
-    const bool runs = use_d2 && fused_labels && mk_list && ws_runs_enabled() && amt_i_ccl_runs_ok(mask, H, W, nplanes) &&
+    const bool runs = use_d2 && fused_labels && mk_list && amt_i_ccl_runs_ok(mask, H, W, nplanes) &&
                       (reinterpret_cast<uintptr_t>(fused_labels) & 15) == 0 && (reinterpret_cast<uintptr_t>(relief) & 15) == 0 &&
                       (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     if (runs)
@@ -2238,8 +2117,9 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     comp_row* rows = arena_take_t<comp_row>(ctx, nr);
     int* btot = arena_take_t<int>(ctx, nplanes);
     int* mtot = arena_take_t<int>(ctx, nplanes);
-    // per plane: work counters of the six LDS flood classes XS / S / M / M2 / L / X [0..6) and of the HBM flood [6],
-    // has_g [7], worklist sizes of the six classes [8..14), number of components [14]
+    // WS_CTR ints per plane, each field an array over the planes (field k of plane p: counters[k * nplanes + p]):
+    // [0] work counter of the class-X flood, [7] work counter of the HBM flood, [8] has_g,
+    // [9 .. 9 + WS_NLISTS) worklist sizes of classes S / M / M2 / L / X, [16] number of components
     int* counters = arena_take_t<int>(ctx, (size_t)nplanes * WS_CTR);
     int* wl = arena_take_t<int>(ctx, (size_t)WS_NLISTS * nr);  // worklists of the LDS classes
     int* pf_idx = arena_take_t<int>(ctx, (size_t)PF_NCLS * (nplanes + 1));  // the persistent flood's item index
@@ -2284,8 +2164,6 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     AMT_LAUNCH_CHECK();
     int* has_g = counters + 8 * nplanes;
     int* wl_count = counters + 9 * nplanes;  // [WS_NLISTS][nplanes]
-    const int pf_mode = use_d2 ? ws_persist() : 0;  // 0 = class launches, 1 = a whole CU per workgroup, 2 = half a CU
-    const int pf_slots = pf_mode == 1 ? ws_pf_slots() : (pf_mode == 2 ? PF_SLOTS_HALF : 0);
     if (runs) {
         hipLaunchKernelGGL(ws_stats_runs_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, (const int*)relief, tbits, rtab,
                            nruns, L, T, rows, row_stride, H, W, segs, trows, ntiles, rcomp);
@@ -2307,7 +2185,7 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     }
     AMT_LAUNCH_CHECK();
     hipLaunchKernelGGL(ws_classify_kernel, dim3(64, nplanes), dim3(256), 0, ctx->stream, rows, ncomp, moff, boff, has_g,
-                       wl, wl_count, F, n, nplanes, row_stride, use_d2 ? 1 : 0, pf_slots);
+                       wl, wl_count, F, n, nplanes, row_stride, use_d2 ? 1 : 0);
     AMT_LAUNCH_CHECK();
     AMT_TRY(amt_i_propagate_roots(ctx, F, L, rootlist, nroots, nplanes, H, W));
     const bool gprep = fused_labels && use_d2;  // the fused chain: the HBM flood's whole preparation in one launch
@@ -2335,11 +2213,6 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
         AMT_LAUNCH_CHECK();
     }
     if (use_d2) {
-        const size_t ldsXS = (size_t)XS_PX * 6 + (size_t)XS_NB * 6;
-        const size_t ldsS = (size_t)S_PX * 6 + (size_t)S_NB * 6;
-        const size_t ldsM = (size_t)M_PX * 6 + (size_t)M_NB * 6;
-        const size_t ldsM2 = (size_t)(M2_PX > 0 ? M2_PX : 64) * 6 + (size_t)M2_NB * 6;
-        const size_t ldsL = (size_t)L_PX * 6 + (size_t)L_NB * 6;
         const size_t ldsX = (size_t)X_PX * 4 + (size_t)X_NB * 4;
         // the LDS classes and the HBM path are independent, latency-bound and use few waves each:
         // run them side by side (fork / join on the context's auxiliary streams)
@@ -2348,74 +2221,33 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
             AMT_LAUNCH_CHECK();
         }
         AMT_TRY(amt_fork(ctx));
-        // workgroups per plane and class (a workgroup only takes components of its own plane).  Measured: 2 x / 4 x as
-        // many change nothing at 1, 12 or 32 planes per launch -- the chains per workgroup are not what bounds a class
-        const int gXS = 96, gS = XS_PX > 0 ? 80 : 128, gM = XS_PX > 0 ? 48 : 64, gM2 = XS_PX > 0 ? 16 : 32, gL = 16;
-        // Without auxiliary streams the classes still overlap: the first flood is an ordinary (barrier) launch, the
+        // Without auxiliary streams the floods still overlap: the first flood is an ordinary (barrier) launch, the
         // others carry hipExtAnyOrderLaunch -- their packets have no barrier bit, so the command processor dispatches
         // them while the earlier floods are still running; the next ordinary launch waits for all of them.
-        const bool any = ctx->fork == 0 && ws_anyorder();
-        int nflood = 0;
-        auto flood = [&](const void* fn, int gx, size_t lds, hipStream_t st, int cls_slot) -> int {
+        const int any = ctx->fork == 0 ? (int)hipExtAnyOrderLaunch : 0;
+        // one persistent launch for classes S / M / M2 / L (a workgroup of PF_NWAVES waves per CU with all its LDS),
+        // then X and the HBM flood beside it.  Measured on one box against one launch per class (watershed stage per
+        // 48 FOVs in one context / 48-FOV plate / 192-FOV default, FOV/s): class launches 2.53 ms / 10.4 k / 11.5-11.7 k;
+        // whole CU, 8 waves 2.11 / 10.4 k / 11.3 k; 10 waves 2.02 / 10.4 k / 11.6 k; 16 waves 2.10; 46 slots 2.16 /
+        // 10.2 k / 10.9 k; half a CU x 2 2.26 / 10.4 k / 11.1 k.  The stage gains 0.5 ms; with four contexts side by side
+        // the floods were already hidden behind the other contexts' streaming kernels, so the totals do not move.
+        hipLaunchKernelGGL(ws_flood_index_kernel, dim3(1), dim3(64), 0, ctx->stream, wl_count, pf_idx, pf_ctl, nplanes);
+        AMT_LAUNCH_CHECK();
+        {
             const int* a_d2 = (const int*)relief;
-            const int* a_L = L;
-            const int* a_T = T;
-            int* a_out = out;
-            const comp_row* a_rows = rows;
-            const int* a_wl = wl + (size_t)cls_slot * nplanes * row_stride;
-            const int* a_wlc = wl_count + cls_slot * nplanes;
-            int* a_cnt = counters + cls_slot * nplanes;  // the class's work counter
-            size_t a_rs = row_stride;
-            int a_H = H, a_W = W, a_sf = seeds_first;
-            int* a_ties = ties;
-            const int* a_mk = markers;
-            amt_runtabs a_rt = rt;
-            void* args[] = {&a_d2, &a_L, &a_T, &a_out, &a_rows, &a_wl, &a_wlc, &a_cnt, &a_rs, &a_H, &a_W, &a_sf, &a_ties, &a_mk, &a_rt};
-            AMT_HIP_CHECK(hipExtLaunchKernel(fn, dim3(gx, nplanes), dim3(64), args, lds + (cls_slot <= 2 ? ws_lds_pad() : 0), st, nullptr, nullptr,
-                                             (any && nflood > 0) ? (int)hipExtAnyOrderLaunch : 0));
-            ++nflood;
-            return AMT_OK;
-        };
-        const bool persist = pf_mode != 0;
-        if (persist) {
-            // one persistent launch for the five batch classes, then LB (L boxes beyond a workgroup that owns less than a
-            // whole CU), X and the HBM flood beside it.  Mode 1 (default): a workgroup of 10 waves per CU with all its
-            // LDS; mode 2: two workgroups per CU with half each.  Measured on one box (watershed stage per 48 FOVs in one
-            // context / 48-FOV plate / 192-FOV default, FOV/s): class launches 2.53 ms / 10.4 k / 11.5-11.7 k; whole CU,
-            // 8 waves 2.11 / 10.4 k / 11.3 k; 10 waves 2.02 / 10.4 k / 11.6 k; 16 waves 2.10; 46 slots 2.16 / 10.2 k /
-            // 10.9 k; half a CU x 2 2.26 / 10.4 k / 11.1 k.  The stage gains 0.5 ms; with four contexts side by side the
-            // floods were already hidden behind the other contexts' streaming kernels, so the totals do not move.
-            hipLaunchKernelGGL(ws_flood_index_kernel, dim3(1), dim3(64), 0, ctx->stream, wl_count, pf_idx, pf_ctl, nplanes);
-            AMT_LAUNCH_CHECK();
-            const int* a_d2 = (const int*)relief;
-            const int* a_L = L;
-            const int* a_T = T;
-            int* a_out = out;
-            const comp_row* a_rows = rows;
-            const int* a_wl = wl;
-            const int* a_idx = pf_idx;
-            int* a_ctl = pf_ctl;
-            size_t a_rs = row_stride;
-            int a_H = H, a_W = W, a_sf = seeds_first, a_np = nplanes, a_slots = pf_slots;
-            int* a_ties = ties;
-            const int* a_mk = markers;
-            amt_runtabs a_rt = rt;
-            void* args[] = {&a_d2, &a_L, &a_T, &a_out, &a_rows, &a_wl, &a_idx, &a_ctl, &a_rs, &a_H, &a_W, &a_sf, &a_ties, &a_mk,
-                            &a_np, &a_slots, &a_rt};
-            const int wgs = pf_mode == 1 ? ctx->num_cus : 2 * ctx->num_cus;
-            AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_persist_kernel, dim3(wgs), dim3(ws_pf_waves() * 64), args,
-                                             (size_t)(pf_slots + 1) * PF_SLOT, ctx->stream, nullptr, nullptr, 0));
-            ++nflood;
-            if (pf_slots < PF_SLOTS_FULL) AMT_TRY(flood((const void*)ws_flood_batch_kernel<L_PX, L_NB>, gL, ldsL, ctx->stream, 6));
-        } else {
-            AMT_TRY(flood((const void*)ws_flood_batch_kernel<L_PX, L_NB>, gL, ldsL, ctx->stream, 4));
+            void* args[] = {&a_d2, &L, &T, &out, &rows, &wl, &pf_idx, &pf_ctl, (void*)&row_stride, &H, &W, &seeds_first, &ties,
+                            (void*)&markers, &nplanes, &rt};
+            AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_persist_kernel, dim3(ctx->num_cus), dim3(PF_NWAVES * 64), args,
+                                             (size_t)(PF_SLOTS + 1) * PF_SLOT, ctx->stream, nullptr, nullptr, 0));
         }
-        AMT_TRY(flood((const void*)ws_flood_lds_kernel<X_PX, X_NB, CLS_X>, 8, ldsX, ctx->stream, 5));
-        if (!persist) {
-        AMT_TRY(flood((const void*)ws_flood_batch_kernel<M2_PX, M2_NB>, gM2, ldsM2, ctx->aux[2], 3));
-        AMT_TRY(flood((const void*)ws_flood_batch_kernel<M_PX, M_NB>, gM, ldsM, ctx->aux[0], 2));
-        AMT_TRY(flood((const void*)ws_flood_batch_kernel<S_PX, S_NB>, gS, ldsS, ctx->aux[1], 1));
-        if (XS_PX > 0) AMT_TRY(flood((const void*)ws_flood_batch_kernel<(XS_PX > 0 ? XS_PX : 64), XS_NB>, gXS, ldsXS, ctx->aux[2], 0));
+        {
+            const int* a_d2 = (const int*)relief;
+            const int* a_wl = wl + (size_t)(CLS_X - CLS_S) * nplanes * row_stride;
+            const int* a_wlc = wl_count + (CLS_X - CLS_S) * nplanes;
+            void* args[] = {&a_d2, &L, &T, &out, &rows, &a_wl, &a_wlc, &counters, (void*)&row_stride, &H, &W, &seeds_first, &ties,
+                            (void*)&markers, &rt};
+            AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_lds_kernel<X_PX, X_NB, CLS_X>, dim3(8, nplanes), dim3(64), args,
+                                             ldsX, ctx->stream, nullptr, nullptr, any));
         }
         {
             const int* a_d2 = (const int*)relief;
@@ -2424,7 +2256,7 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
             int* a_cnt = counters + 7 * nplanes;
             args[11] = &a_cnt;
             AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_edt_kernel, dim3(4, nplanes), dim3(64), args, 0, ctx->aux[1],
-                                             nullptr, nullptr, any ? (int)hipExtAnyOrderLaunch : 0));
+                                             nullptr, nullptr, any));
         }
         AMT_TRY(amt_join(ctx));
     } else {

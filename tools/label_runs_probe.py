@@ -1,4 +1,4 @@
-"""amt_label on 0 / 1 masks (run tables, AMT_CCL_RUNS=1, against the parent plane, =0): differential check against the
+"""amt_label on 0 / 1 masks (the run-table path): differential check against the
 oracle on widths that take the path (multiples of 16), then the time per 48 planes of 2048^2.
 usage: python tools/label_runs_probe.py [cases] [seed] [planes]"""
 import os, sys, time
@@ -50,7 +50,7 @@ for case in range(ncases):
                 bad += 1
                 print("MISMATCH case", case, "kind", kind, (H, W), "conn", conn, "plane", b, "count", gc[b], ref.max(),
                       "px", int((got[b] != ref).sum()))
-print("label fuzz:", ncases, "cases,", bad, "mismatches, runs =", os.environ.get("AMT_CCL_RUNS", "1"))
+print("label fuzz:", ncases, "cases,", bad, "mismatches")
 
 fov = synth.synth_fov(0)
 for ch, name in ((1, "DAPI nuclei mask"), (0, "brightfield noise mask")):

@@ -1,4 +1,4 @@
-"""Step statistics of the batch flood (ws_flood_batch_kernel): build the instrumented library first,
+"""Step statistics of the LDS flood (ws_flood_component, run by ws_flood_persist_kernel): build the instrumented library first,
 
     cd arcadia_microscopy_tools_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off \
         -fno-fast-math -DWS_STATS -c amt_watershed.hip -o /tmp/ws_dbg.o && \
