@@ -90,48 +90,33 @@ _SIGS = {
     "amt_copy_rect": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "amt_threshold_value": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_int, c_size_t, _P]),
     "amt_threshold_gt": (c_int, [_P, _P, c_int, _P, _P, c_int, c_size_t]),
-    "amt_window_threshold": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_double]),
-    "amt_window_threshold_yx": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double]),
+    "amt_window_threshold": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double]),
     "amt_window_threshold_nd": (c_int, [_P, _P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double,
                                         c_double]),
     "amt_threshold_gt_image": (c_int, [_P, _P, c_int, _P, _P, c_size_t]),
-    "amt_binary_erode": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int]),
-    "amt_binary_dilate": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int]),
-    "amt_binary_open": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int]),
-    "amt_binary_close": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int]),
-    "amt_threshold_open_close": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, c_int]),
+    "amt_binary_morph": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int]),
+    "amt_threshold_open_close": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, _P, c_int, c_int, _P, _P]),
     "amt_otsu_f64_bins": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_size_t]),
-    "amt_threshold_open_close_bins": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, c_int]),
-    "amt_rank_filter": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_double]),
+    "amt_rank_filter": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_double, _P]),
     "amt_gaussian_otsu_codes_supported": (c_int, [c_int, c_int, c_int, c_int, c_size_t]),
     "amt_gaussian_otsu_codes": (c_int, [_P, _P, c_double, c_int, c_int, c_int, _P, c_int, c_int, c_size_t, _P, _P, _P, _P,
                                         _P]),
-    "amt_rank_filter_sub": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int,
-                                    c_double]),
     "amt_subtract": (c_int, [_P, _P, _P, _P, c_int, c_size_t]),
     "amt_label": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_label_mask": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_nn_affine_act_bf16": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "amt_label_sparse": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int]),
-    "amt_label_sparse_reuse": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "amt_label_sparse": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "amt_clear_border": (c_int, [_P, _P, _P, c_int, c_int, c_int]),
     "amt_relabel_sequential": (c_int, [_P, _P, _P, _P, c_int, c_size_t, c_int]),
     "amt_clear_border_relabel": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "amt_keep_labels": (c_int, [_P, _P, _P, _P, c_int, c_size_t, c_int]),
     "amt_cast_i32_i64": (c_int, [_P, _P, _P, c_size_t]),
     "amt_edt": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int]),
-    "amt_peak_mask": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int]),
-    "amt_peak_mask_reuse": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
-    "amt_watershed_edt": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int]),
-    "amt_watershed_f64": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int]),
-    "amt_watershed_edt_cleared": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    "amt_watershed_edt_cleared_sparse": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P,
-                                                 c_int]),
-    "amt_watershed_edt_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
-    "amt_watershed_f64_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
-    "amt_regionprops": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int]),
-    "amt_regionprops_intensity_u16": (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int]),
-    "amt_regionprops_full_u16": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int]),
+    "amt_peak_mask": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
+    "amt_watershed_edt": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "amt_watershed_f64": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "amt_watershed_edt_cleared": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int]),
+    "amt_regionprops": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_regionprops_intensity_f64": (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int]),
     "amt_convolve_axis0": (c_int, [_P, _P, c_int, c_double, _P, c_int, c_int, c_int, _P, c_int, c_int, c_double]),
     "amt_max_i32": (c_int, [_P, _P, _P, c_int, c_size_t]),
@@ -141,7 +126,6 @@ _SIGS = {
     "amt_contours_emit": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
     "amt_borders_find": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "amt_borders_emit": (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
-    "amt_cellpose_masks": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_int]),
     "amt_cellpose_masks_ex": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_float, c_int,
                                       c_float, c_int]),
     "amt_cellpose_flow_error": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int]),

@@ -1,5 +1,5 @@
 """The Cellpose path on MI355X (BASELINE configs[4]): network forward through PyTorch-ROCm (bf16, MFMA) and the
-flow -> mask post-processing in HIP (``amt_cellpose_masks``).
+flow -> mask post-processing in HIP (``amt_cellpose_masks_ex``).
 
 The reference wraps ``cellpose.models.CellposeModel`` (R/model.py:160-169, :206-215, :270-290), whose weights are
 fetched from the network by name -- unobtainable offline, as is the package itself.  What can be built and measured

@@ -859,9 +859,10 @@ static int cp_finish(amt_ctx* ctx, int32_t* labels_out, const int* nlab1, int32_
                      const int* cnt, const double* err, float flow_threshold, int min_size, int fill_holes, int nplanes,
                      int H, int W, int cap);
 
-static int cellpose_masks_impl(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out,
-                               int32_t* count_dev, int nplanes, int H, int W, float cellprob_threshold, int niter,
-                               int min_size, float max_size_fraction, int max_seeds, float flow_threshold, int fill_holes) {
+extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out,
+                                     int32_t* count_dev, int nplanes, int H, int W, float cellprob_threshold, int niter,
+                                     int min_size, float max_size_fraction, int max_seeds, float flow_threshold,
+                                     int fill_holes) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(dP && cellprob && labels_out && count_dev && nplanes >= 0, "cellpose_masks: bad arguments");
     AMT_REQUIRE(H >= 2 && W >= 2 && H + 2 * CP_RPAD < 65536 && W + 2 * CP_RPAD < 65536,
@@ -1011,21 +1012,6 @@ static int cp_finish(amt_ctx* ctx, int32_t* labels_out, const int* nlab1, int32_
                        nplanes);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
-}
-
-extern "C" int amt_cellpose_masks(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out,
-                                  int32_t* count_dev, int nplanes, int H, int W, float cellprob_threshold, int niter,
-                                  int min_size, float max_size_fraction, int max_seeds) {
-    return cellpose_masks_impl(ctx, dP, cellprob, labels_out, count_dev, nplanes, H, W, cellprob_threshold, niter, min_size,
-                               max_size_fraction, max_seeds, 0.0f, 0);
-}
-
-extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out,
-                                     int32_t* count_dev, int nplanes, int H, int W, float cellprob_threshold, int niter,
-                                     int min_size, float max_size_fraction, int max_seeds, float flow_threshold,
-                                     int fill_holes) {
-    return cellpose_masks_impl(ctx, dP, cellprob, labels_out, count_dev, nplanes, H, W, cellprob_threshold, niter, min_size,
-                               max_size_fraction, max_seeds, flow_threshold, fill_holes);
 }
 
 extern "C" int amt_cellpose_flow_error(amt_ctx* ctx, const int32_t* labels, const float* dP, const int32_t* nlabels_dev,

@@ -355,26 +355,13 @@ __global__ void __launch_bounds__(256) peaks_unwrite_kernel(const int* __restric
     for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) o[lst[k]] = 0;
 }
 
-static int peak_mask_impl(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int nplanes, int H, int W,
-                          int min_distance, const int32_t* prev_list, const int32_t* prev_count, int capacity,
-                          const int32_t* prev_status);
-
+// prev_list / prev_count / prev_status (all or none): the previous run's peak lists and label counts (amt_hip.h)
 extern "C" int amt_peak_mask(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int nplanes, int H,
-                             int W, int min_distance) {
-    return peak_mask_impl(ctx, d2, mask, peaks, nplanes, H, W, min_distance, nullptr, nullptr, 0, nullptr);
-}
-
-extern "C" int amt_peak_mask_reuse(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int nplanes,
-                                   int H, int W, int min_distance, const int32_t* prev_list, const int32_t* prev_count,
-                                   int capacity, const int32_t* prev_status) {
-    AMT_REQUIRE(prev_list && prev_count && prev_status && capacity >= 1,
-                "peak_mask_reuse: the previous run's peak lists, counts and label counts are required");
-    return peak_mask_impl(ctx, d2, mask, peaks, nplanes, H, W, min_distance, prev_list, prev_count, capacity, prev_status);
-}
-
-static int peak_mask_impl(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int nplanes, int H, int W,
-                          int min_distance, const int32_t* prev_list, const int32_t* prev_count, int capacity,
-                          const int32_t* prev_status) {
+                             int W, int min_distance, const int32_t* prev_list, const int32_t* prev_count, int capacity,
+                             const int32_t* prev_status) {
+    AMT_REQUIRE(!prev_list == !prev_count && !prev_list == !prev_status,
+                "peak_mask: the previous run's peak lists, counts and label counts go together");
+    AMT_REQUIRE(!prev_list || capacity >= 1, "peak_mask: the previous run's list capacity must be positive");
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(d2 && mask && peaks && nplanes >= 0 && H > 0 && W > 0, "peak_mask: bad arguments");
     AMT_REQUIRE(min_distance >= 0 && min_distance <= PK_MAXM, "peak_mask: min_distance %d out of range 0..%d",
@@ -382,7 +369,7 @@ static int peak_mask_impl(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, 
     if (nplanes == 0) return AMT_OK;
     const int m = min_distance;
     if (prev_list) {
-        // the plane is zero except at the previous run's peaks, which amt_label_sparse_reuse kept as a list
+        // the plane is zero except at the previous run's peaks, which amt_label_sparse kept as a list
         hipLaunchKernelGGL(peaks_unwrite_kernel, dim3(amt_grid_for((size_t)capacity, 256, 64), nplanes), dim3(256), 0,
                            ctx->stream, prev_list, prev_count, prev_status, peaks, (size_t)H * W, capacity);
         AMT_LAUNCH_CHECK();

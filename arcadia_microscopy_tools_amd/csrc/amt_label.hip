@@ -1712,23 +1712,10 @@ __global__ void __launch_bounds__(256) sp_unwrite_kernel(const int* __restrict__
     for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) o[lst[k]] = 0;
 }
 
-static int label_sparse_impl(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
-                             int connectivity, int capacity, int32_t* keep_list, int32_t* keep_count);
-
+// keep_list / keep_count (both or neither): the pixel lists a previous call on the same `out` left behind (amt_hip.h)
 extern "C" int amt_label_sparse(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H,
-                                int W, int connectivity, int capacity) {
-    return label_sparse_impl(ctx, in, out, count_dev, nplanes, H, W, connectivity, capacity, nullptr, nullptr);
-}
-
-extern "C" int amt_label_sparse_reuse(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes,
-                                      int H, int W, int connectivity, int capacity, int32_t* keep_list,
-                                      int32_t* keep_count) {
-    AMT_REQUIRE(keep_list && keep_count, "label_sparse_reuse: keep_list / keep_count are required");
-    return label_sparse_impl(ctx, in, out, count_dev, nplanes, H, W, connectivity, capacity, keep_list, keep_count);
-}
-
-static int label_sparse_impl(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
-                             int connectivity, int capacity, int32_t* keep_list, int32_t* keep_count) {
+                                int W, int connectivity, int capacity, int32_t* keep_list, int32_t* keep_count) {
+    AMT_REQUIRE(!keep_list == !keep_count, "label_sparse: keep_list and keep_count go together");
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "label_sparse: bad arguments");
     AMT_REQUIRE(connectivity == 1 || connectivity == 2, "label_sparse: connectivity must be 1 or 2");

@@ -202,11 +202,12 @@ static int build_offsets(const uint8_t* fp, int fh, int fw, int2* host, int* n) 
     return AMT_OK;
 }
 
-// which: 0 erode, 1 dilate, 2 open (erode then dilate), 3 close (dilate then erode)
-static int morph_common(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                        const uint8_t* footprint, int fh, int fw, int which, int border_value) {
+// op: AMT_MORPH_ERODE, AMT_MORPH_DILATE, AMT_MORPH_OPEN (erode then dilate), AMT_MORPH_CLOSE (dilate then erode)
+extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
+                                const uint8_t* footprint, int fh, int fw, int op, int border_value) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "binary morphology: bad arguments");
+    AMT_REQUIRE(op >= AMT_MORPH_ERODE && op <= AMT_MORPH_CLOSE, "binary morphology: op must be 0..3, got %d", op);
     static thread_local int2 host[MAX_OFFS];
     int noffs = 0;
     AMT_TRY(build_offsets(footprint, fh, fw, host, &noffs));
@@ -224,23 +225,23 @@ static int morph_common(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplan
     AMT_LAUNCH_CHECK();
     dim3 gp((WW + 63) / 64, (H + 3) / 4, nplanes);
     u64* result = pb;
-    switch (which) {
-        case 0:
+    switch (op) {
+        case AMT_MORPH_ERODE:
             hipLaunchKernelGGL((packed_prim_kernel<true>), gp, dim3(256), 0, ctx->stream, pa, pb, H, W, WW, offs, noffs,
                                border_value);
             break;
-        case 1:
+        case AMT_MORPH_DILATE:
             hipLaunchKernelGGL((packed_prim_kernel<false>), gp, dim3(256), 0, ctx->stream, pa, pb, H, W, WW, offs, noffs,
                                border_value);
             break;
-        case 2:  // skimage: erosion sees outside = 1, dilation sees outside = 0
+        case AMT_MORPH_OPEN:  // skimage: erosion sees outside = 1, dilation sees outside = 0
             hipLaunchKernelGGL((packed_prim_kernel<true>), gp, dim3(256), 0, ctx->stream, pa, pb, H, W, WW, offs, noffs, 1);
             AMT_LAUNCH_CHECK();
             hipLaunchKernelGGL((packed_prim_kernel<false>), gp, dim3(256), 0, ctx->stream, pb, pa, H, W, WW, offs, noffs,
                                0);
             result = pa;
             break;
-        default:
+        default:  // AMT_MORPH_CLOSE
             hipLaunchKernelGGL((packed_prim_kernel<false>), gp, dim3(256), 0, ctx->stream, pa, pb, H, W, WW, offs, noffs,
                                0);
             AMT_LAUNCH_CHECK();
@@ -254,23 +255,6 @@ static int morph_common(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplan
                        H, W, WW);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
-}
-
-extern "C" int amt_binary_erode(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                                const uint8_t* footprint, int fh, int fw, int border_value) {
-    return morph_common(ctx, in, out, nplanes, H, W, footprint, fh, fw, 0, border_value);
-}
-extern "C" int amt_binary_dilate(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                                 const uint8_t* footprint, int fh, int fw, int border_value) {
-    return morph_common(ctx, in, out, nplanes, H, W, footprint, fh, fw, 1, border_value);
-}
-extern "C" int amt_binary_open(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                               const uint8_t* footprint, int fh, int fw) {
-    return morph_common(ctx, in, out, nplanes, H, W, footprint, fh, fw, 2, 0);
-}
-extern "C" int amt_binary_close(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                                const uint8_t* footprint, int fh, int fw) {
-    return morph_common(ctx, in, out, nplanes, H, W, footprint, fh, fw, 3, 0);
 }
 
 // ---- fused threshold -> opening -> closing ---------------------------------------------------------
@@ -440,26 +424,13 @@ __global__ void __launch_bounds__(256) toc_fused_kernel(const u64* __restrict__ 
 
 // `binary_closing(binary_opening(in > thr))` in one packed chain: compare -> 4 word-level primitives ->
 // unpack (the Gaussian -> Otsu -> '>' -> open -> close mask chain of BASELINE configs[1]/[2]).
-static int threshold_open_close_impl(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev, uint8_t* out,
-                                     int nplanes, int H, int W, const uint8_t* footprint, int fh, int fw,
-                                     const uint8_t* bins, const double* thr_code_dev);
-
-extern "C" int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev,
-                                        uint8_t* out, int nplanes, int H, int W, const uint8_t* footprint, int fh,
-                                        int fw) {
-    return threshold_open_close_impl(ctx, in, in_dtype, thr_dev, out, nplanes, H, W, footprint, fh, fw, nullptr, nullptr);
-}
-
-extern "C" int amt_threshold_open_close_bins(amt_ctx* ctx, const double* in, const uint8_t* bins, const double* thr_dev,
-                                             const double* thr_code_dev, uint8_t* out, int nplanes, int H, int W,
-                                             const uint8_t* footprint, int fh, int fw) {
-    AMT_REQUIRE(bins && thr_code_dev, "threshold_open_close_bins: the bin plane and the threshold's bin are required");
-    return threshold_open_close_impl(ctx, in, AMT_F64, thr_dev, out, nplanes, H, W, footprint, fh, fw, bins, thr_code_dev);
-}
-
-static int threshold_open_close_impl(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev, uint8_t* out,
-                                     int nplanes, int H, int W, const uint8_t* footprint, int fh, int fw,
-                                     const uint8_t* bins, const double* thr_code_dev) {
+// bins / thr_code_dev (both or neither, float64 input only): the byte plane of bin indices and the threshold's bin that
+// amt_otsu_f64_bins made -- the comparison reads the float64 value only inside that bin.
+extern "C" int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev, uint8_t* out,
+                                        int nplanes, int H, int W, const uint8_t* footprint, int fh, int fw,
+                                        const uint8_t* bins, const double* thr_code_dev) {
+    AMT_REQUIRE(!bins == !thr_code_dev, "threshold_open_close: the bin plane and the threshold's bin go together");
+    AMT_REQUIRE(!bins || in_dtype == AMT_F64, "threshold_open_close: a bin plane requires AMT_F64 input");
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_dev && out && nplanes >= 0 && H > 0 && W > 0, "threshold_open_close: bad arguments");
     AMT_REQUIRE(in_dtype == AMT_U16 || in_dtype == AMT_F64, "threshold_open_close: dtype must be AMT_U16 or AMT_F64");

@@ -664,9 +664,13 @@ __global__ void __launch_bounds__(256) rp_solidity_kernel(double* __restrict__ t
     }
 }
 
-// want_morph: fill the AMT_RP_* table; itable != NULL: fill {mean, max, min, std} per label and channel
-static int regionprops_common(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C, double* table_dev,
-                              double* itable_dev, int nplanes, int H, int W, int max_label) {
+// table_dev != NULL: fill the AMT_RP_* table; itable_dev != NULL: fill {mean, max, min, std} per label and channel
+extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C, double* table_dev,
+                               double* itable_dev, int nplanes, int H, int W, int max_label) {
+    AMT_REQUIRE(labels && (table_dev || itable_dev) && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0,
+                "regionprops: bad arguments");
+    AMT_REQUIRE(!intensity == !itable_dev && (!itable_dev || C >= 1),
+                "regionprops: the intensity planes (C >= 1) and the intensity table go together");
     AMT_TRY(amt_set_device(ctx));
     const bool want_morph = table_dev != nullptr;
     if (nplanes == 0 || max_label == 0) return AMT_OK;
@@ -725,28 +729,6 @@ static int regionprops_common(amt_ctx* ctx, const int32_t* labels, const uint16_
         AMT_LAUNCH_CHECK();
     }
     return AMT_OK;
-}
-
-extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, double* table_dev, int nplanes, int H, int W,
-                               int max_label) {
-    AMT_REQUIRE(labels && table_dev && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0, "regionprops: bad arguments");
-    return regionprops_common(ctx, labels, nullptr, 0, table_dev, nullptr, nplanes, H, W, max_label);
-}
-
-extern "C" int amt_regionprops_intensity_u16(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C,
-                                             double* table_dev, int nplanes, int H, int W, int max_label) {
-    AMT_REQUIRE(labels && intensity && table_dev && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && C >= 1,
-                "regionprops_intensity: bad arguments");
-    return regionprops_common(ctx, labels, intensity, C, nullptr, table_dev, nplanes, H, W, max_label);
-}
-
-extern "C" int amt_regionprops_full_u16(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C,
-                                        double* table_dev, double* itable_dev, int nplanes, int H, int W,
-                                        int max_label) {
-    AMT_REQUIRE(labels && intensity && table_dev && itable_dev && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 &&
-                    C >= 1,
-                "regionprops_full: bad arguments");
-    return regionprops_common(ctx, labels, intensity, C, table_dev, itable_dev, nplanes, H, W, max_label);
 }
 
 // ---- bounding boxes only (what the outline extractor needs, R/masks.py:99) ---------------------------

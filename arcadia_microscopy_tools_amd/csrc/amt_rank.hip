@@ -921,27 +921,7 @@ static bool mm_plan(const uint8_t* footprint, int fh, int fw, mm_params* P) {
     return P->ns > 0;
 }
 
-// 1 = the register kernel was launched and, if `minuend` was given, stored minuend - result; 0 = not applicable
-static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
-                            const uint8_t* footprint, int fh, int fw, int op, int mode, double cval,
-                            const void* minuend, int* fused);
-
-extern "C" int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
-                               const uint8_t* footprint, int fh, int fw, int op, int mode, double cval) {
-    int fused = 0;
-    return rank_filter_impl(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, nullptr, &fused);
-}
-
-extern "C" int amt_rank_filter_sub(amt_ctx* ctx, const void* in, const void* minuend, void* out, int dtype, int nplanes,
-                                   int H, int W, const uint8_t* footprint, int fh, int fw, int op, int mode,
-                                   double cval) {
-    AMT_REQUIRE(minuend && minuend != out, "rank_filter_sub: minuend must be given and differ from out");
-    int fused = 0;
-    AMT_TRY(rank_filter_impl(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, minuend, &fused));
-    if (fused) return AMT_OK;
-    return amt_subtract(ctx, minuend, out, out, dtype, (size_t)nplanes * H * W);  // elementwise: in place is fine
-}
-
+// *fused = 1: the register kernel was launched and, if `minuend` was given, stored minuend - result
 static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
                             const uint8_t* footprint, int fh, int fw, int op, int mode, double cval,
                             const void* minuend, int* fused) {
@@ -1144,4 +1124,16 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
                            H, W, offs, noffs, ry, rx, op, mode, cval);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
+}
+
+// minuend == NULL: the filter alone; otherwise out = minuend - filter(in), subtracted by the uint16 run kernel as it
+// stores, or on every other path by filtering into `out` and subtracting in place
+extern "C" int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
+                               const uint8_t* footprint, int fh, int fw, int op, int mode, double cval,
+                               const void* minuend) {
+    AMT_REQUIRE(!minuend || minuend != out, "rank_filter: minuend must differ from out");
+    int fused = 0;
+    AMT_TRY(rank_filter_impl(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, minuend, &fused));
+    if (!minuend || fused) return AMT_OK;
+    return amt_subtract(ctx, minuend, out, out, dtype, (size_t)nplanes * H * W);  // elementwise: in place is fine
 }

@@ -273,7 +273,7 @@ __device__ __forceinline__ double linspace_edge(double lo, double hi, double ste
 }
 
 // bins (nullable, nbins <= 256): the bin of every sample as a byte plane -- for a threshold that is the centre of bin k
-// (Otsu), `sample > threshold` is decided by the byte alone except inside bin k (amt_threshold_open_close_bins)
+// (Otsu), `sample > threshold` is decided by the byte alone except inside bin k (amt_threshold_open_close's `bins`)
 __global__ void __launch_bounds__(256) hist_f64_kernel(const double* __restrict__ in,
                                                        const double* __restrict__ minmax,
                                                        uint32_t* __restrict__ hist, int nbins, size_t n,

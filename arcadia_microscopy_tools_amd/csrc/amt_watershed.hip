@@ -419,7 +419,7 @@ __global__ void __launch_bounds__(256) ws_stats_runs_kernel(const int* __restric
         }
 }
 
-// marker statistics from the LIST of marker pixels (amt_label_sparse_reuse keeps it): a few thousand pixels per plane
+// marker statistics from the LIST of marker pixels (amt_label_sparse's keep lists): a few thousand pixels per plane
 // instead of a 4-byte read of every pixel of the marker plane in ws_stats_kernel
 __global__ void __launch_bounds__(256) ws_marker_stats_kernel(const int* __restrict__ mk_list, const int* __restrict__ mk_count,
                                                               int mk_cap, const int* __restrict__ markers,
@@ -2300,48 +2300,30 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     return AMT_OK;
 }
 
+// marker_list / marker_count (both or neither): every marker pixel per plane; NULL = the dense statistics pass
 extern "C" int amt_watershed_edt_cleared(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
                                          int32_t* ws_scratch, int32_t* labels_out, int32_t* count_dev, int nplanes,
-                                         int H, int W, int max_label, const int32_t* nlabels_dev) {
+                                         int H, int W, int max_label, const int32_t* nlabels_dev,
+                                         const int32_t* marker_list, const int32_t* marker_count, int list_capacity) {
     AMT_REQUIRE(ws_scratch && labels_out && count_dev && nlabels_dev && max_label >= 0,
                 "watershed_edt_cleared: bad arguments");
+    AMT_REQUIRE(!marker_list == !marker_count, "watershed_edt_cleared: marker_list and marker_count go together");
+    AMT_REQUIRE(!marker_list || list_capacity > 0, "watershed_edt_cleared: list_capacity must be positive");
     AMT_REQUIRE(ws_scratch != labels_out, "watershed_edt_cleared: scratch and output must not alias");
     return watershed_common(ctx, d2, true, markers, mask, ws_scratch, nplanes, H, W, 1, 1, AMT_WS_TIES_EXACT, nullptr,
-                            labels_out, count_dev, nlabels_dev, max_label);
+                            labels_out, count_dev, nlabels_dev, max_label, marker_list, marker_count,
+                            list_capacity);
 }
 
-extern "C" int amt_watershed_edt_cleared_sparse(amt_ctx* ctx, const int32_t* d2, const int32_t* markers,
-                                                const uint8_t* mask, int32_t* ws_scratch, int32_t* labels_out,
-                                                int32_t* count_dev, int nplanes, int H, int W, int max_label,
-                                                const int32_t* nlabels_dev, const int32_t* marker_list,
-                                                const int32_t* marker_count, int list_capacity) {
-    AMT_REQUIRE(ws_scratch && labels_out && count_dev && nlabels_dev && max_label >= 0 && marker_list && marker_count &&
-                    list_capacity > 0,
-                "watershed_edt_cleared_sparse: bad arguments");
-    AMT_REQUIRE(ws_scratch != labels_out, "watershed_edt_cleared_sparse: scratch and output must not alias");
-    return watershed_common(ctx, d2, true, markers, mask, ws_scratch, nplanes, H, W, 1, 1, AMT_WS_TIES_EXACT, nullptr,
-                            labels_out, count_dev, nlabels_dev, max_label, marker_list, marker_count, list_capacity);
-}
-
-extern "C" int amt_watershed_edt_ex(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
-                                    int32_t* out, int nplanes, int H, int W, int seeds_first, int connectivity,
-                                    int tie_policy, int32_t* ties_dev) {
+extern "C" int amt_watershed_edt(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
+                                 int32_t* out, int nplanes, int H, int W, int seeds_first, int connectivity,
+                                 int tie_policy, int32_t* ties_dev) {
     return watershed_common(ctx, d2, true, markers, mask, out, nplanes, H, W, seeds_first, connectivity, tie_policy,
                             ties_dev);
 }
 
-extern "C" int amt_watershed_f64_ex(amt_ctx* ctx, const double* relief, const int32_t* markers, const uint8_t* mask,
-                                    int32_t* out, int nplanes, int H, int W, int connectivity, int tie_policy,
-                                    int32_t* ties_dev) {
-    return watershed_common(ctx, relief, false, markers, mask, out, nplanes, H, W, 0, connectivity, tie_policy, ties_dev);
-}
-
-extern "C" int amt_watershed_edt(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
-                                 int32_t* out, int nplanes, int H, int W, int seeds_first) {
-    return watershed_common(ctx, d2, true, markers, mask, out, nplanes, H, W, seeds_first, 1, AMT_WS_TIES_EXACT, nullptr);
-}
-
 extern "C" int amt_watershed_f64(amt_ctx* ctx, const double* relief, const int32_t* markers, const uint8_t* mask,
-                                 int32_t* out, int nplanes, int H, int W) {
-    return watershed_common(ctx, relief, false, markers, mask, out, nplanes, H, W, 0, 1, AMT_WS_TIES_EXACT, nullptr);
+                                 int32_t* out, int nplanes, int H, int W, int connectivity, int tie_policy,
+                                 int32_t* ties_dev) {
+    return watershed_common(ctx, relief, false, markers, mask, out, nplanes, H, W, 0, connectivity, tie_policy, ties_dev);
 }

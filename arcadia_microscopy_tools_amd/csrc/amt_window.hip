@@ -182,12 +182,7 @@ __global__ void __launch_bounds__(256) win_finish_kernel(const T* __restrict__ S
 }
 
 extern "C" int amt_window_threshold(amt_ctx* ctx, const void* in, int in_dtype, double* thr_image, int nplanes, int H,
-                                    int W, int window_size, int method, double k, double r) {
-    return amt_window_threshold_yx(ctx, in, in_dtype, thr_image, nplanes, H, W, window_size, window_size, method, k, r);
-}
-
-extern "C" int amt_window_threshold_yx(amt_ctx* ctx, const void* in, int in_dtype, double* thr_image, int nplanes, int H,
-                                       int W, int window_y, int window_x, int method, double k, double r) {
+                                    int W, int window_y, int window_x, int method, double k, double r) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_image && nplanes >= 0 && H > 0 && W > 0, "window_threshold: bad arguments");
     AMT_REQUIRE(in_dtype == AMT_U16 || in_dtype == AMT_F64, "window_threshold: dtype must be AMT_U16 or AMT_F64");

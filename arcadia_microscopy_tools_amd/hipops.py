@@ -414,8 +414,8 @@ def window_threshold(a: DeviceArray, window_size=15, method: str = "niblack", k:
         _hip.check(_lib().amt_window_threshold_nd(ctx.handle, a.ptr, _in_code(a), o.ptr, nlead, shp, win, H, W, wy, wx,
                                                   meth, float(k), float(r)), "amt_window_threshold")
     else:  # windows of one sample along the leading axes: every plane on its own
-        _hip.check(_lib().amt_window_threshold_yx(ctx.handle, a.ptr, _in_code(a), o.ptr, n, H, W, wy, wx, meth, float(k),
-                                                  float(r)), "amt_window_threshold")
+        _hip.check(_lib().amt_window_threshold(ctx.handle, a.ptr, _in_code(a), o.ptr, n, H, W, wy, wx, meth, float(k),
+                                               float(r)), "amt_window_threshold")
     return o
 
 
@@ -464,6 +464,9 @@ def _fp(footprint, even: str = "scipy"):
     return np.ascontiguousarray(fp)
 
 
+_MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}  # AMT_MORPH_*
+
+
 def _binary(which: str, a: DeviceArray, footprint, out, border_value=None):
     ctx = a.ctx
     if a.dtype != np.uint8:
@@ -471,19 +474,11 @@ def _binary(which: str, a: DeviceArray, footprint, out, border_value=None):
     n, H, W = _planes(a)
     fp = _fp(footprint)
     o = _out(ctx, out, a.shape, np.uint8)
-    fpp = fp.ctypes.data_as(ctypes.c_void_p)
-    lib = _lib()
-    if which == "erode":
-        rc = lib.amt_binary_erode(ctx.handle, a.ptr, o.ptr, n, H, W, fpp, fp.shape[0], fp.shape[1],
-                                  1 if border_value is None else int(border_value))
-    elif which == "dilate":
-        rc = lib.amt_binary_dilate(ctx.handle, a.ptr, o.ptr, n, H, W, fpp, fp.shape[0], fp.shape[1],
-                                   0 if border_value is None else int(border_value))
-    elif which == "open":
-        rc = lib.amt_binary_open(ctx.handle, a.ptr, o.ptr, n, H, W, fpp, fp.shape[0], fp.shape[1])
-    else:
-        rc = lib.amt_binary_close(ctx.handle, a.ptr, o.ptr, n, H, W, fpp, fp.shape[0], fp.shape[1])
-    _hip.check(rc, "amt_binary_" + which)
+    op = _MORPH_OPS[which]
+    if border_value is None or op >= _MORPH_OPS["open"]:  # open / close apply skimage's border rules themselves
+        border_value = 1 if which == "erode" else 0
+    _hip.check(_lib().amt_binary_morph(ctx.handle, a.ptr, o.ptr, n, H, W, fp.ctypes.data_as(ctypes.c_void_p),
+                                       fp.shape[0], fp.shape[1], op, int(border_value)), "amt_binary_morph")
     o.is_bool = True
     return o
 
@@ -532,27 +527,25 @@ def threshold_open_close(a: DeviceArray, thr: DeviceArray, footprint=None, out=N
     n, H, W = _planes(a)
     fp = _fp(footprint)
     o = _out(ctx, out, a.shape, np.uint8)
-    if bins is not None:
-        _hip.check(_lib().amt_threshold_open_close_bins(ctx.handle, a.ptr, bins.ptr, thr.ptr, thr_code.ptr, o.ptr, n, H, W,
-                                                        fp.ctypes.data_as(ctypes.c_void_p), fp.shape[0], fp.shape[1]),
-                   "amt_threshold_open_close_bins")
-        o.is_bool = True
-        return o
     _hip.check(_lib().amt_threshold_open_close(ctx.handle, a.ptr, _in_code(a), thr.ptr, o.ptr, n, H, W,
-                                               fp.ctypes.data_as(ctypes.c_void_p), fp.shape[0], fp.shape[1]),
+                                               fp.ctypes.data_as(ctypes.c_void_p), fp.shape[0], fp.shape[1],
+                                               None if bins is None else bins.ptr,
+                                               None if thr_code is None else thr_code.ptr),
                "amt_threshold_open_close")
     o.is_bool = True
     return o
 
 
-def _rank(a: DeviceArray, footprint, op: int, mode: str, cval: float, out):
+def _rank(a: DeviceArray, footprint, op: int, mode: str, cval: float, out, minuend: DeviceArray | None = None):
+    """The rank filter of ``a``, or ``minuend - filter(a)`` in the same pass when ``minuend`` is given."""
     ctx = a.ctx
     n, H, W = _planes(a)
     fp = _fp(footprint)  # callers that follow scikit-image's even-size rule pass an odd footprint already
     o = _out(ctx, out, a.shape, a.dtype)
     _hip.check(_lib().amt_rank_filter(ctx.handle, a.ptr, o.ptr, _in_code(a), n, H, W,
                                       fp.ctypes.data_as(ctypes.c_void_p), fp.shape[0], fp.shape[1], op,
-                                      _hip.MODES[mode], float(cval)), "amt_rank_filter")
+                                      _hip.MODES[mode], float(cval), None if minuend is None else minuend.ptr),
+               "amt_rank_filter")
     return o
 
 
@@ -598,13 +591,8 @@ def white_tophat(a, footprint=None, out=None):
     opening (grey_erosion then grey_dilation, both with the footprint as given; SK/morphology/grey.py:425)."""
     fp = _fp(footprint)
     er = _rank(a, fp, 0, "reflect", 0.0, None)
-    n, H, W = _planes(a)
-    o = _out(a.ctx, out, a.shape, a.dtype)
-    # the dilation stores image - dilation(erosion) directly (amt_rank_filter_sub)
-    _hip.check(_lib().amt_rank_filter_sub(a.ctx.handle, er.ptr, a.ptr, o.ptr, _in_code(a), n, H, W,
-                                          fp.ctypes.data_as(ctypes.c_void_p), fp.shape[0], fp.shape[1], 1,
-                                          _hip.MODES["reflect"], 0.0), "amt_rank_filter_sub")
-    return o
+    # the dilation stores image - dilation(erosion) directly
+    return _rank(er, fp, 1, "reflect", 0.0, out, minuend=a)
 
 
 def median(a, footprint=None, mode: str = "nearest", cval: float = 0.0, out=None):
@@ -647,8 +635,8 @@ def label_sparse(a: DeviceArray, connectivity: int = 2, capacity: int | None = N
     plane size / 16)); a plane that overflows reports count -1.
 
     ``keep`` = (int32 (n, capacity) list, int32 (n,) counts), both owned by the caller, turns the full-plane clear of
-    ``out`` into a clear of the pixels the previous call wrote (``amt_label_sparse_reuse``): ``out`` must then be the
-    same array every time, zeroed once together with the counts."""
+    ``out`` into a clear of the pixels the previous call wrote: ``out`` must then be the same array every time, zeroed
+    once together with the counts."""
     ctx = a.ctx
     n, H, W = _planes(a)
     if a.dtype != np.uint8:
@@ -657,17 +645,16 @@ def label_sparse(a: DeviceArray, connectivity: int = 2, capacity: int | None = N
         capacity = label_sparse_capacity(H, W)
     o = _out(ctx, out, a.shape, np.int32)
     c = _out(ctx, count, (n,), np.int32)
+    klist_ptr = kcount_ptr = None
     if keep is not None:
         klist, kcount = keep
         if out is None:
             raise ValueError("keep= needs the caller's persistent out= plane")
         if klist.dtype != np.int32 or klist.size != n * int(capacity) or kcount.dtype != np.int32 or kcount.size != n:
             raise ValueError("keep must be (int32 (n, capacity), int32 (n,))")
-        _hip.check(_lib().amt_label_sparse_reuse(ctx.handle, a.ptr, o.ptr, c.ptr, n, H, W, int(connectivity),
-                                                 int(capacity), klist.ptr, kcount.ptr), "amt_label_sparse_reuse")
-        return o, c
-    _hip.check(_lib().amt_label_sparse(ctx.handle, a.ptr, o.ptr, c.ptr, n, H, W, int(connectivity), int(capacity)),
-               "amt_label_sparse")
+        klist_ptr, kcount_ptr = klist.ptr, kcount.ptr
+    _hip.check(_lib().amt_label_sparse(ctx.handle, a.ptr, o.ptr, c.ptr, n, H, W, int(connectivity), int(capacity),
+                                       klist_ptr, kcount_ptr), "amt_label_sparse")
     return o, c
 
 
@@ -750,19 +737,18 @@ def edt(mask: DeviceArray, want_d2: bool = True, want_edt: bool = True, d2_out=N
 def peak_mask(d2: DeviceArray, mask: DeviceArray, min_distance: int = 5, out=None, keep=None, status=None) -> DeviceArray:
     """Peaks of the EDT per the config-3 marker recipe.  ``keep`` (the lists ``label_sparse(keep=)``
     maintains) + ``status`` (that call's counts) turn the clear of the persistent ``out`` plane into a clear of the
-    previous run's peaks (``amt_peak_mask_reuse``)."""
+    previous run's peaks."""
     ctx = d2.ctx
     n, H, W = _planes(d2)
     o = _out(ctx, out, d2.shape, np.uint8)
+    prev = (None, None, 0, None)  # list, counts, capacity, status
     if keep is not None:
         if out is None or status is None:
             raise ValueError("keep= needs the caller's persistent out= plane and the previous counts (status=)")
         klist, kcount = keep
-        _hip.check(_lib().amt_peak_mask_reuse(ctx.handle, d2.ptr, mask.ptr, o.ptr, n, H, W, int(min_distance), klist.ptr,
-                                              kcount.ptr, klist.size // n, status.ptr), "amt_peak_mask_reuse")
-        o.is_bool = True
-        return o
-    _hip.check(_lib().amt_peak_mask(ctx.handle, d2.ptr, mask.ptr, o.ptr, n, H, W, int(min_distance)), "amt_peak_mask")
+        prev = (klist.ptr, kcount.ptr, klist.size // n, status.ptr)
+    _hip.check(_lib().amt_peak_mask(ctx.handle, d2.ptr, mask.ptr, o.ptr, n, H, W, int(min_distance), *prev),
+               "amt_peak_mask")
     o.is_bool = True
     return o
 
@@ -798,9 +784,9 @@ def watershed_edt(d2: DeviceArray, markers: DeviceArray, mask: DeviceArray, seed
     n, H, W = _planes(d2)
     o = _out(ctx, out, d2.shape, np.int32)
     t = _ws_ties(ctx, n, ties, ties_out)
-    _hip.check(_lib().amt_watershed_edt_ex(ctx.handle, d2.ptr, markers.ptr, mask.ptr, o.ptr, n, H, W,
-                                           1 if seeds_first else 0, int(connectivity), _hip.WS_TIES[ties],
-                                           None if t is None else t.ptr),
+    _hip.check(_lib().amt_watershed_edt(ctx.handle, d2.ptr, markers.ptr, mask.ptr, o.ptr, n, H, W,
+                                        1 if seeds_first else 0, int(connectivity), _hip.WS_TIES[ties],
+                                        None if t is None else t.ptr),
                "amt_watershed_edt")
     _ws_finish(ctx, ties, t, "watershed_edt")
     return o
@@ -818,19 +804,16 @@ def watershed_edt_cleared(d2: DeviceArray, markers: DeviceArray, mask: DeviceArr
     c = _out(ctx, count, (n,), np.int32)
     if scratch.dtype != np.int32 or scratch.size != d2.size or scratch.ctx is not ctx:
         raise ValueError("scratch must be an int32 array of the batch's size on the same context")
+    mk = (None, None, 0)  # list, counts, capacity
     if marker_list is not None:
         # (list, counts) as label_sparse(keep=) leaves them: every non-zero pixel of `markers`; the component statistics
         # then skip the marker plane
         klist, kcount = marker_list
         if klist.dtype != np.int32 or kcount.dtype != np.int32 or kcount.size != n or klist.size % n:
             raise ValueError("marker_list must be (int32 (n, capacity), int32 (n,))")
-        _hip.check(_lib().amt_watershed_edt_cleared_sparse(ctx.handle, d2.ptr, markers.ptr, mask.ptr, scratch.ptr, o.ptr,
-                                                           c.ptr, n, H, W, int(max_label), nlabels.ptr, klist.ptr,
-                                                           kcount.ptr, klist.size // n),
-                   "amt_watershed_edt_cleared_sparse")
-        return o, c
+        mk = (klist.ptr, kcount.ptr, klist.size // n)
     _hip.check(_lib().amt_watershed_edt_cleared(ctx.handle, d2.ptr, markers.ptr, mask.ptr, scratch.ptr, o.ptr, c.ptr, n, H,
-                                                W, int(max_label), nlabels.ptr), "amt_watershed_edt_cleared")
+                                                W, int(max_label), nlabels.ptr, *mk), "amt_watershed_edt_cleared")
     return o, c
 
 
@@ -842,8 +825,8 @@ def watershed(relief: DeviceArray, markers: DeviceArray, mask: DeviceArray, out=
     n, H, W = _planes(relief)
     o = _out(ctx, out, relief.shape, np.int32)
     t = _ws_ties(ctx, n, ties, ties_out)
-    _hip.check(_lib().amt_watershed_f64_ex(ctx.handle, relief.ptr, markers.ptr, mask.ptr, o.ptr, n, H, W,
-                                           int(connectivity), _hip.WS_TIES[ties], None if t is None else t.ptr),
+    _hip.check(_lib().amt_watershed_f64(ctx.handle, relief.ptr, markers.ptr, mask.ptr, o.ptr, n, H, W,
+                                        int(connectivity), _hip.WS_TIES[ties], None if t is None else t.ptr),
                "amt_watershed_f64")
     _ws_finish(ctx, ties, t, "watershed")
     return o
@@ -857,7 +840,8 @@ def regionprops(labels: DeviceArray, max_label: int, out=None) -> DeviceArray:
     ctx = labels.ctx
     n, H, W = _planes(labels)
     o = _out(ctx, out, (n, max_label, _hip.RP_NCOLS), np.float64)
-    _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, o.ptr, n, H, W, int(max_label)), "amt_regionprops")
+    _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, None, 0, o.ptr, None, n, H, W, int(max_label)),
+               "amt_regionprops")
     return o
 
 
@@ -874,8 +858,8 @@ def regionprops_full(labels: DeviceArray, intensity: DeviceArray, max_label: int
         raise ValueError("intensity / labels plane count mismatch")
     o = _out(ctx, out, (n, max_label, _hip.RP_NCOLS), np.float64)
     io = _out(ctx, iout, (n, max_label, C, 4), np.float64)
-    _hip.check(_lib().amt_regionprops_full_u16(ctx.handle, labels.ptr, intensity.ptr, C, o.ptr, io.ptr, n, H, W,
-                                               int(max_label)), "amt_regionprops_full_u16")
+    _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, intensity.ptr, C, o.ptr, io.ptr, n, H, W, int(max_label)),
+               "amt_regionprops")
     return o, io
 
 
@@ -924,8 +908,8 @@ def regionprops_intensity(labels: DeviceArray, intensity: DeviceArray, max_label
         raise ValueError("intensity / labels plane count mismatch")
     o = _out(ctx, out, (n, max_label, C, 4), np.float64)
     if intensity.dtype == np.uint16:  # exact integer accumulation
-        _hip.check(_lib().amt_regionprops_intensity_u16(ctx.handle, labels.ptr, intensity.ptr, C, o.ptr, n, H, W,
-                                                        int(max_label)), "amt_regionprops_intensity_u16")
+        _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, intensity.ptr, C, None, o.ptr, n, H, W,
+                                          int(max_label)), "amt_regionprops")
     else:  # float64 images: two-sweep mean / std as numpy computes them
         _hip.check(_lib().amt_regionprops_intensity_f64(ctx.handle, labels.ptr, intensity.ptr, C, o.ptr, n, H, W,
                                                         int(max_label)), "amt_regionprops_intensity_f64")
@@ -938,8 +922,8 @@ def cellpose_masks(dP: DeviceArray, cellprob: DeviceArray, cellprob_threshold: f
     """Cellpose's flow -> mask post-processing on the device (include/amt_hip.h ``amt_cellpose_masks_ex``; parity
     unpinned): ``dP`` (..., 2, Y, X) float32 flows (dY, dX), ``cellprob`` (..., Y, X) float32 -> (int32 labels, counts).
     ``flow_threshold`` > 0 adds the flow-error filter (``remove_bad_flow_masks``), ``fill_holes`` the hole filling of
-    ``fill_holes_and_remove_small_masks``; with neither, the rounds-1/2 entry point.  A plane that produces more than
-    ``max_seeds`` seeds reports count -1."""
+    ``fill_holes_and_remove_small_masks``; with neither, only the dynamics and the size filters run.  A plane that
+    produces more than ``max_seeds`` seeds reports count -1."""
     ctx = dP.ctx
     if dP.dtype != np.float32 or cellprob.dtype != np.float32:
         raise TypeError("cellpose_masks expects float32 flows and cell probabilities")

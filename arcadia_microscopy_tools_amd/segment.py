@@ -47,7 +47,7 @@ class FovSegmenter:
     def __init__(self, batch: int, C: int, H: int, W: int, *, sigma: float = 2.0, radius: int = 2,
                  min_distance: int = 5, max_cells: int = 4096, dapi_index: int = 1, ctx: Context | None = None,
                  props: bool = True, profile: bool = False, fused: bool = True, low_traffic: bool = False, bin_plane: bool = True,
-                 relief: str = "seeded", ties: str = "exact", marker_list: bool = True):
+                 relief: str = "seeded", ties: str = "exact"):
         self.ctx = ctx or get_context()
         self.B, self.C, self.H, self.W = int(batch), int(C), int(H), int(W)
         self.sigma, self.radius, self.min_distance = float(sigma), int(radius), int(min_distance)
@@ -64,16 +64,13 @@ class FovSegmenter:
         if relief == "plain":
             self.fused = False
         self.tied = None  # per-plane tie flags of the last plain-relief run
-        # marker_list: hand the watershed the list of marker pixels label_sparse keeps (its statistics pass then skips
-        # the marker plane); False = the round-2 call (A/B, identical labels)
-        self.marker_list = bool(marker_list)
         # low_traffic = Gaussian -> Otsu -> '>' through amt_gaussian_otsu_codes: the float64 smoothed planes are never
         # made (8 instead of 26 bytes of HBM traffic per pixel, 25 MB less memory per field of view; same masks, same
         # thresholds).  Off by default: the Gaussian is fp64-issue bound, so computing it twice costs more time than
         # the two reads of the float64 plane it saves (rocprofv3, 32 FOVs: 1.13 ms against 0.93 ms)
         self.low_traffic = bool(low_traffic)
         # bin_plane: the Otsu histogram pass leaves every sample's bin as a byte plane and '>' reads that plane
-        # (amt_otsu_f64_bins / amt_threshold_open_close_bins); False = compare the float64 plane (same masks)
+        # (amt_otsu_f64_bins / amt_threshold_open_close); False = compare the float64 plane (same masks)
         self.bin_plane = bool(bin_plane)
         self.footprint = hipops.disk(self.radius)
         c, B = self.ctx, self.B
@@ -195,11 +192,11 @@ class FovSegmenter:
         hipops.label_sparse(self.peaks, 1, out=self.markers, count=self.nmarkers, keep=self._marker_keep)  # sparse
         if self.fused:
             # watershed + clear_border + relabel_sequential in one call: the watershed image is never written out
-            # (self.ws only receives the pixels of flooded components)
+            # (self.ws only receives the pixels of flooded components); the list of marker pixels label_sparse keeps
+            # spares its statistics pass the marker plane
             self._stage("watershed_clear_relabel")
             hipops.watershed_edt_cleared(self.d2, self.markers, mask, self.nmarkers, self.max_cells, scratch=self.ws,
-                                         out=self.labels, count=self.ncells,
-                                         marker_list=self._marker_keep if self.marker_list else None)
+                                         out=self.labels, count=self.ncells, marker_list=self._marker_keep)
         else:
             self._stage("watershed")
             if self.relief == "plain":

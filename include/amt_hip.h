@@ -202,13 +202,11 @@ int amt_threshold_value(amt_ctx* ctx, const void* in, int in_dtype, int method, 
 int amt_threshold_gt(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev, uint8_t* out, int nplanes,
                      size_t n);
 /* Niblack (method 0: m - k*s) / Sauvola (method 1: m*(1 + k*(s/r - 1))) threshold image from the mean m and
- * standard deviation s of the window_size^2 square around each pixel, mirror padding
+ * standard deviation s of the window of window_y rows x window_x columns around each pixel (scikit-image's
+ * `window_size`, an odd int or a per-axis tuple), mirror padding
  * (SK/filters/thresholding.py:910-964,1026-1027,1083-1087).  uint16 window sums are exact integers. */
 int amt_window_threshold(amt_ctx* ctx, const void* in, int in_dtype, double* thr_image, int nplanes, int H, int W,
-                         int window_size, int method, double k, double r);
-/* The same with a window of window_y rows x window_x columns (scikit-image's per-axis `window_size` tuple). */
-int amt_window_threshold_yx(amt_ctx* ctx, const void* in, int in_dtype, double* thr_image, int nplanes, int H, int W,
-                            int window_y, int window_x, int method, double k, double r);
+                         int window_y, int window_x, int method, double k, double r);
 /* The same for ONE n-D image whose window spans every axis, as scikit-image's _mean_std does for stacks
  * (SK/filters/thresholding.py:910-964): nlead axes of lead_shape[] in front of (H, W), one odd window per axis. */
 int amt_window_threshold_nd(amt_ctx* ctx, const void* in, int in_dtype, double* thr_image, int nlead,
@@ -219,37 +217,36 @@ int amt_threshold_gt_image(amt_ctx* ctx, const void* in, int in_dtype, const dou
                            size_t n);
 
 /* ---- morphology: SK/morphology/binary.py, grey.py (ImageOperation callables, north_star) ----- */
-/* Footprint = HOST uint8 (fh, fw), odd sizes, anchor at the centre.
- * binary erosion: outside the image counts as `border_value` (skimage: 1); dilation: 0. */
-int amt_binary_erode(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                     const uint8_t* footprint, int fh, int fw, int border_value);
-int amt_binary_dilate(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                      const uint8_t* footprint, int fh, int fw, int border_value);
-/* fused opening = dilate(erode(x)) and closing = erode(dilate(x)) with skimage's border rules */
-int amt_binary_open(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                    const uint8_t* footprint, int fh, int fw);
-int amt_binary_close(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
-                     const uint8_t* footprint, int fh, int fw);
-/* out = binary_closing(binary_opening(in > thr[plane])) in one packed chain (the mask chain of BASELINE
- * configs[1]/[2]: R/operations.py:216 followed by SK/morphology/binary.py:82-147). */
-int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev, uint8_t* out,
-                             int nplanes, int H, int W, const uint8_t* footprint, int fh, int fw);
-/* The same chain for a float64 image whose Otsu threshold came from amt_otsu_f64_bins: the comparison reads the byte
- * plane of bin indices (1 B/px) and the float64 value only inside the threshold's own bin -- identical masks. */
+/* Footprint = HOST uint8 (fh, fw), odd sizes, anchor at the centre.  op:
+ *   AMT_MORPH_ERODE   outside the image counts as `border_value` (skimage: 1);
+ *   AMT_MORPH_DILATE  outside the image counts as `border_value` (skimage: 0);
+ *   AMT_MORPH_OPEN    fused opening = dilate(erode(x)), AMT_MORPH_CLOSE fused closing = erode(dilate(x)), both with
+ *                     skimage's border rules (erosion sees 1, dilation 0): border_value is ignored. */
+#define AMT_MORPH_ERODE 0
+#define AMT_MORPH_DILATE 1
+#define AMT_MORPH_OPEN 2
+#define AMT_MORPH_CLOSE 3
+int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
+                     const uint8_t* footprint, int fh, int fw, int op, int border_value);
+/* Otsu threshold of a float64 image (as amt_threshold_value) that also leaves the byte plane of its 256-bin indices
+ * and the threshold's bin, for amt_threshold_open_close. */
 int amt_otsu_f64_bins(amt_ctx* ctx, const double* in, const double* minmax_dev, double* thr_dev, double* thr_code_dev,
                       uint8_t* bins, int nplanes, size_t n);
-int amt_threshold_open_close_bins(amt_ctx* ctx, const double* in, const uint8_t* bins, const double* thr_dev,
-                                  const double* thr_code_dev, uint8_t* out, int nplanes, int H, int W,
-                                  const uint8_t* footprint, int fh, int fw);
+/* out = binary_closing(binary_opening(in > thr[plane])) in one packed chain (the mask chain of BASELINE
+ * configs[1]/[2]: R/operations.py:216 followed by SK/morphology/binary.py:82-147).
+ * bins, thr_code_dev (both NULL or both given; given requires in_dtype AMT_F64): the outputs of amt_otsu_f64_bins for
+ * this image -- the comparison then reads the byte plane of bin indices (1 B/px) and the float64 value only inside
+ * the threshold's own bin -- identical masks. */
+int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev, uint8_t* out,
+                             int nplanes, int H, int W, const uint8_t* footprint, int fh, int fw, const uint8_t* bins,
+                             const double* thr_code_dev);
 /* grey erosion / dilation / median over a footprint (uint16 or float64 images), scipy boundary `mode`.
- * op: 0 = erosion (min), 1 = dilation (max, footprint already mirrored by the caller), 2 = median */
-int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
-                    const uint8_t* footprint, int fh, int fw, int op, int mode, double cval);
-/* out = minuend - rank_filter(in): the last step of ndi.white_tophat (R/ callers reach it through
- * skimage.morphology.white_tophat, SK/morphology/grey.py:425) without a separate subtraction pass; uint16 run
+ * op: 0 = erosion (min), 1 = dilation (max, footprint already mirrored by the caller), 2 = median
+ * minuend (nullable, != out): out = minuend - rank_filter(in), the last step of ndi.white_tophat (R/ callers reach it
+ * through skimage.morphology.white_tophat, SK/morphology/grey.py:425) without a separate subtraction pass; uint16 run
  * footprints subtract inside the filter kernel, everything else filters into `out` and subtracts in place. */
-int amt_rank_filter_sub(amt_ctx* ctx, const void* in, const void* minuend, void* out, int dtype, int nplanes, int H,
-                        int W, const uint8_t* footprint, int fh, int fw, int op, int mode, double cval);
+int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
+                    const uint8_t* footprint, int fh, int fw, int op, int mode, double cval, const void* minuend);
 /* out = a - b (same dtype; white_tophat = image - opening) */
 int amt_subtract(amt_ctx* ctx, const void* a, const void* b, void* out, int dtype, size_t n);
 
@@ -266,15 +263,14 @@ int amt_label_mask(amt_ctx* ctx, const uint8_t* mask, int32_t* out, int32_t* cou
                    int connectivity);
 /* Same result as amt_label for uint8 masks with at most `capacity` foreground pixels per plane (e.g. the EDT
  * peak markers): foreground is compacted in raster order and labelled on the compact list.  If a plane has
- * more foreground pixels than `capacity`, count_dev[plane] = -1 and that plane's labels are invalid. */
-/* The same, for callers that label into the SAME plane batch again and again (a batch driver's marker planes): `out` must
- * be zero except at the pixels listed in keep_list[plane * capacity ...][0 .. keep_count[plane]) -- the state this
- * function leaves behind; start from a zeroed `out` and zeroed keep_count.  Only those pixels are cleared (no
- * full-plane memset), and the lists are replaced by this call's foreground pixels. */
-int amt_label_sparse_reuse(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
-                           int connectivity, int capacity, int32_t* keep_list, int32_t* keep_count);
+ * more foreground pixels than `capacity`, count_dev[plane] = -1 and that plane's labels are invalid.
+ * keep_list, keep_count (both NULL or both given) serve callers that label into the SAME plane batch again and again (a
+ * batch driver's marker planes): `out` must be zero except at the pixels listed in
+ * keep_list[plane * capacity ...][0 .. keep_count[plane]) -- the state this function leaves behind; start from a
+ * zeroed `out` and zeroed keep_count.  Only those pixels are cleared (no full-plane memset), and the lists are replaced
+ * by this call's foreground pixels.  Without them `out` is cleared whole. */
 int amt_label_sparse(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
-                     int connectivity, int capacity);
+                     int connectivity, int capacity, int32_t* keep_list, int32_t* keep_count);
 /* skimage.segmentation.clear_border(labels) with buffer_size=0: zero every 8-connected component of
  * equal-valued pixels that touches the 1-px frame; other pixels keep their value. */
 int amt_clear_border(amt_ctx* ctx, const int32_t* in, int32_t* out, int nplanes, int H, int W);
@@ -298,21 +294,20 @@ int amt_cast_i32_i64(amt_ctx* ctx, const int32_t* in, int64_t* out, size_t n);
 /* Exact squared Euclidean distance to the nearest zero pixel (int32), and its correctly rounded
  * float64 square root = scipy.ndimage.distance_transform_edt.  Either output may be NULL. */
 int amt_edt(amt_ctx* ctx, const uint8_t* mask, int32_t* d2_out, double* edt_out, int nplanes, int H, int W);
-/* peaks = (d2 == maximum_filter(d2, (2m+1)^2, constant 0)) & mask & (d2 > 0), border of width m cleared */
-/* The same into a plane batch that is zero except at the pixels listed in prev_list / prev_count (the lists
- * amt_label_sparse_reuse keeps of the previous run's peaks): only those are cleared, no full-plane memset.
- * prev_status = that run's label counts (count_dev of amt_label_sparse_reuse): a plane whose count is -1 overflowed
- * its list and is cleared whole.  Start from zeroed planes, zeroed counts and zeroed status. */
-int amt_peak_mask_reuse(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int nplanes, int H, int W,
-                        int min_distance, const int32_t* prev_list, const int32_t* prev_count, int capacity,
-                        const int32_t* prev_status);
+/* peaks = (d2 == maximum_filter(d2, (2m+1)^2, constant 0)) & mask & (d2 > 0), border of width m cleared.
+ * prev_list, prev_count, prev_status (all NULL, or all given with capacity >= 1; capacity is ignored otherwise):
+ * `peaks` is zero except at the pixels listed in prev_list / prev_count (the keep lists amt_label_sparse holds of the
+ * previous run's peaks), and only those are cleared -- no full-plane memset.  prev_status = that run's label counts
+ * (count_dev of amt_label_sparse): a plane whose count is -1 overflowed its list and is cleared whole.  Start from
+ * zeroed planes, zeroed counts and zeroed status. */
 int amt_peak_mask(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int nplanes, int H, int W,
-                  int min_distance);
+                  int min_distance, const int32_t* prev_list, const int32_t* prev_count, int capacity,
+                  const int32_t* prev_status);
 /* Priority flood restricted to `mask` (skimage.segmentation.watershed, no compactness, no watershed line;
  * SURVEY.md A.1).  Priority = (value, insertion age); labels are assigned at push time.
  * `mask` holds 0 / 1 bytes (what a bool array is on the device): scikit-image takes the mask as a truth value, and only
- * amt_watershed_edt_cleared_sparse on widths that are a multiple of 16 reads other non-zero bytes that way -- elsewhere
- * differing non-zero byte values would split a region.
+ * amt_watershed_edt_cleared with a marker list, on widths that are a multiple of 16, reads other non-zero bytes that
+ * way -- elsewhere differing non-zero byte values would split a region.
  *   amt_watershed_edt : relief = -sqrt(d2) given as the exact integer d2 (bucket queue).  seeds_first = 1 is the
  *                       config-3 recipe (oracle/skops.py:seeded_flood_image): marker pixels are spread first, in
  *                       raster order -- i.e. the relief with every marker pixel lowered to a distinct lowest value;
@@ -325,37 +320,30 @@ int amt_peak_mask(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t*
  *   AMT_WS_TIES_RASTER  ties are broken in raster order (fast; differs from scikit-image in tied planes).
  *   AMT_WS_TIES_REPORT  as RASTER, and ties_dev[plane] = 1 marks every plane whose result may differ.
  * ties_dev (nullable, nplanes ints) receives the per-plane tie flags under every policy.
- * connectivity 2 (8 neighbours, visited N, E, W, S, NW, NE, SW, SE as scikit-image 0.18.3 does) runs
- * the sequential emulation for every plane and requires AMT_WS_TIES_EXACT.  The two-argument-less entry points are
- * connectivity 1 with AMT_WS_TIES_EXACT. */
+ * connectivity 1 (4 neighbours) or 2 (8 neighbours, visited N, E, W, S, NW, NE, SW, SE as scikit-image 0.18.3 does;
+ * SURVEY.md A.9); connectivity 2 runs the sequential emulation for every plane and requires AMT_WS_TIES_EXACT. */
 #define AMT_WS_TIES_EXACT 0
 #define AMT_WS_TIES_RASTER 1
 #define AMT_WS_TIES_REPORT 2
 int amt_watershed_edt(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask, int32_t* out,
-                      int nplanes, int H, int W, int seeds_first);
+                      int nplanes, int H, int W, int seeds_first, int connectivity, int tie_policy, int32_t* ties_dev);
 int amt_watershed_f64(amt_ctx* ctx, const double* relief, const int32_t* markers, const uint8_t* mask, int32_t* out,
-                      int nplanes, int H, int W);
-int amt_watershed_edt_ex(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask, int32_t* out,
-                         int nplanes, int H, int W, int seeds_first, int connectivity, int tie_policy, int32_t* ties_dev);
-int amt_watershed_f64_ex(amt_ctx* ctx, const double* relief, const int32_t* markers, const uint8_t* mask, int32_t* out,
-                         int nplanes, int H, int W, int connectivity, int tie_policy, int32_t* ties_dev);
-/* The config-3 tail in one call: amt_watershed_edt(seeds_first = 1) followed by amt_clear_border_relabel
- * (R/masks.py:56 + :65 on the watershed of a mask from markers numbered 1..nlabels_dev[plane]; labels that touch the
- * frame are dropped, the rest renumbered 1..count_dev[plane] in ascending order).  Same labels as the two calls, one
- * full-plane write less: the watershed image itself is never materialised -- ws_scratch (nplanes x H x W ints) only
- * receives the pixels of flooded components. */
+                      int nplanes, int H, int W, int connectivity, int tie_policy, int32_t* ties_dev);
+/* The config-3 tail in one call: amt_watershed_edt(seeds_first = 1, connectivity 1, AMT_WS_TIES_EXACT) followed by
+ * amt_clear_border_relabel (R/masks.py:56 + :65 on the watershed of a mask from markers numbered
+ * 1..nlabels_dev[plane]; labels that touch the frame are dropped, the rest renumbered 1..count_dev[plane] in ascending
+ * order).  Same labels as the two calls, one full-plane write less: the watershed image itself is never materialised --
+ * ws_scratch (nplanes x H x W ints) only receives the pixels of flooded components.
+ * marker_list, marker_count (both NULL or both given with list_capacity >= 1; list_capacity is ignored otherwise) serve
+ * callers that hold the LIST of marker pixels (the keep_list / keep_count amt_label_sparse leaves behind:
+ * marker_list[plane * list_capacity ...][0 .. marker_count[plane]) = flat indices of every non-zero pixel of the marker
+ * plane): the per-component marker statistics come from the list and the dense statistics pass does not read the
+ * marker plane (4 of its 12 bytes per pixel).  A plane whose list is incomplete (count above the capacity) gives
+ * undefined labels -- amt_label_sparse reports that plane with count -1. */
 int amt_watershed_edt_cleared(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
                               int32_t* ws_scratch, int32_t* labels_out, int32_t* count_dev, int nplanes, int H, int W,
-                              int max_label, const int32_t* nlabels_dev);
-/* The same for callers that hold the LIST of marker pixels (the keep_list / keep_count amt_label_sparse_reuse leaves
- * behind: marker_list[plane * list_capacity ...][0 .. marker_count[plane]) = flat indices of every non-zero pixel of the
- * marker plane): the per-component marker statistics come from the list and the dense statistics pass does not read the
- * marker plane (4 of its 12 bytes per pixel).  A plane whose list is incomplete (count above the capacity) gives
- * undefined labels -- amt_label_sparse_reuse reports that plane with count -1. */
-int amt_watershed_edt_cleared_sparse(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
-                                     int32_t* ws_scratch, int32_t* labels_out, int32_t* count_dev, int nplanes, int H,
-                                     int W, int max_label, const int32_t* nlabels_dev, const int32_t* marker_list,
-                                     const int32_t* marker_count, int list_capacity);
+                              int max_label, const int32_t* nlabels_dev, const int32_t* marker_list,
+                              const int32_t* marker_count, int list_capacity);
 
 /* ---- region properties: R/masks.py:286-326 (regionprops_table) ------------------------------- */
 /* Morphology columns per label 1..max_label (row = label-1), float64, column order: */
@@ -374,17 +362,14 @@ int amt_watershed_edt_cleared_sparse(amt_ctx* ctx, const int32_t* d2, const int3
 #define AMT_RP_AREA_CONVEX 12
 #define AMT_RP_SOLIDITY 13
 #define AMT_RP_NCOLS 14
-/* table_dev = nplanes x max_label x AMT_RP_NCOLS doubles.  Labels absent from a plane give area 0. */
-int amt_regionprops(amt_ctx* ctx, const int32_t* labels, double* table_dev, int nplanes, int H, int W, int max_label);
-/* Intensity columns per label and channel: {mean, max, min, std} (population std).
- * intensity = nplanes x C planes of uint16 (one (C,Y,X) FOV per label plane);
- * table_dev = nplanes x max_label x C x 4 doubles. */
-int amt_regionprops_intensity_u16(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C,
-                                  double* table_dev, int nplanes, int H, int W, int max_label);
-/* Both tables in one call (the bounding-box pass and the per-label scan are shared): what
- * SegmentationMask.cell_properties needs for a (C,Y,X) field of view (R/masks.py:286-326). */
-int amt_regionprops_full_u16(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C, double* table_dev,
-                             double* itable_dev, int nplanes, int H, int W, int max_label);
+/* table_dev (nullable) = nplanes x max_label x AMT_RP_NCOLS doubles.  Labels absent from a plane give area 0.
+ * itable_dev (nullable) = intensity columns per label and channel: {mean, max, min, std} (population std, SURVEY.md
+ * A.9), nplanes x max_label x C x 4 doubles, from intensity = nplanes x C planes of uint16 (one (C,Y,X) FOV per label
+ * plane).  intensity and C >= 1 are given exactly when itable_dev is; at least one table is.  Both tables in one
+ * call share the bounding-box pass and the per-label scan: what SegmentationMask.cell_properties needs for a (C,Y,X)
+ * field of view (R/masks.py:286-326). */
+int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C, double* table_dev,
+                    double* itable_dev, int nplanes, int H, int W, int max_label);
 /* The same {mean, max, min, std} for float64 intensity images (R/masks.py:178-190, :319-323 accept any 2-D ndarray):
  * two sweeps per label as np.mean / np.std make them; float64 sums, so agreement with numpy is ~1e-15 relative. */
 int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const double* intensity, int C, double* table_dev,
@@ -438,22 +423,18 @@ int amt_borders_emit(amt_ctx* ctx, const int32_t* labels, int H, int W, int nlab
  * through CellposeModel.eval, R/model.py:206-215, :270-290).  Restated from the published algorithm (cellpose
  * dynamics: follow the flow for niter Euler steps with bilinear sampling, histogram the end points, seeds = 5 x 5
  * maxima with more than 10 pixels, five rounds of 3 x 3 growth over bins with more than 2 pixels, labels by end point,
- * masks above max_size_fraction of the image or below min_size dropped, renumbered in raster order); the flow-error
- * filter and hole filling: amt_cellpose_masks_ex.  PARITY UNPINNED: cellpose is not available offline and the
- * reference holds no vector for it (oracle: oracle/cellpose_dynamics.py).
- *   dP = nplanes x 2 x H x W float32 (dY, dX), cellprob = nplanes x H x W float32, labels_out = nplanes x H x W int32,
- *   count_dev[plane] = number of masks, or -1 if the plane produced more than max_seeds seeds. */
-int amt_cellpose_masks(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out, int32_t* count_dev,
-                       int nplanes, int H, int W, float cellprob_threshold, int niter, int min_size,
-                       float max_size_fraction, int max_seeds);
-/* The same with the rest of cellpose's compute_masks, as CellposeModel.eval runs it with the parameters the reference
- * hands over (R/model.py:206-215: flow_threshold, default 0.4):
+ * masks above max_size_fraction of the image or below min_size dropped, renumbered in raster order), then the rest of
+ * cellpose's compute_masks, as CellposeModel.eval runs it with the parameters the reference hands over
+ * (R/model.py:206-215: flow_threshold, default 0.4):
  *   flow_threshold > 0: remove_bad_flow_masks -- the flows are re-derived from the masks (float64 heat diffusion from
  *       each mask's centre, 2 * max(height + width + 2) steps) and a mask whose mean squared difference to dP / 5
  *       exceeds the threshold is dropped;
  *   then fill_holes_and_remove_small_masks: masks below min_size dropped, (fill_holes != 0) the others hole-filled
  *       inside their bounding box, renumbered 1..K in ascending order.
- * flow_threshold == 0 and fill_holes == 0 is amt_cellpose_masks.  PARITY UNPINNED like the above. */
+ * flow_threshold == 0 and fill_holes == 0 stops after the first stage.  PARITY UNPINNED: cellpose is not available
+ * offline and the reference holds no vector for it (oracle: oracle/cellpose_dynamics.py).
+ *   dP = nplanes x 2 x H x W float32 (dY, dX), cellprob = nplanes x H x W float32, labels_out = nplanes x H x W int32,
+ *   count_dev[plane] = number of masks, or -1 if the plane produced more than max_seeds seeds. */
 int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out, int32_t* count_dev,
                           int nplanes, int H, int W, float cellprob_threshold, int niter, int min_size,
                           float max_size_fraction, int max_seeds, float flow_threshold, int fill_holes);

@@ -342,9 +342,10 @@ def test_c3_small_and_non_tile_sizes(ctx):
 
 
 def test_fused_watershed_tail_equals_separate_calls(ctx):
-    """amt_watershed_edt_cleared (watershed + clear_border + relabel in one call, no watershed image) against the three
-    separate calls and the oracle, on windows cut out of larger fields of view so that nuclei DO touch the frame (the
-    synthetic generator keeps them away from it), plus a plane without any marker, at odd sizes."""
+    """amt_watershed_edt_cleared with the marker list (watershed + clear_border + relabel in one call, no watershed
+    image) against the three separate calls and the oracle, on windows cut out of larger fields of view so that nuclei
+    DO touch the frame (the synthetic generator keeps them away from it), plus a plane without any marker, at odd
+    sizes."""
     from arcadia_microscopy_tools_amd import synth
     from arcadia_microscopy_tools_amd.segment import FovSegmenter
     from oracle import chains

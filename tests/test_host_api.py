@@ -42,6 +42,62 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.amt_version()
 
 
+def test_ctypes_signatures_match_the_header():
+    """Every _hip._SIGS row has the return type and the parameter kinds of its prototype in include/amt_hip.h: a row
+    that drifts would pass wrong values into a launch.  Needs neither the library nor a GPU."""
+    import ctypes
+
+    header = open(os.path.join(ROOT, "include", "amt_hip.h")).read()
+    header = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
+    scalar = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "size_t": ctypes.c_size_t, "int64_t": ctypes.c_int64,
+              "float": ctypes.c_float, "double": ctypes.c_double}
+
+    def kind(t):  # the ctypes side: every pointer type is one kind, scalars keep their type
+        pointer = t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer)
+        return "pointer" if pointer else t
+
+    decls = re.findall(r"^(int|const char\s*\*)\s*(amt_\w+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
+    assert {name for _, name, _ in decls} == set(_hip._SIGS)
+    for ret, name, params in decls:
+        restype, argtypes = _hip._SIGS[name]
+        assert restype is (ctypes.c_int if ret == "int" else ctypes.c_char_p), name
+        want = []
+        for p in params.split(","):
+            p = p.strip()
+            if p in ("", "void"):
+                continue
+            want.append("pointer" if "*" in p else scalar[p.rsplit(None, 1)[0]])
+        assert [kind(t) for t in argtypes] == want, name
+
+
+def test_optional_pointer_groups_are_all_or_none():
+    """An entry point whose optional pointers come as a group refuses a partial group before it touches the context
+    (so this runs without a GPU: a complete group gets as far as the null-context check)."""
+    lib = _hip.load_library()
+    buf = np.zeros(64, np.int32)
+    p, q = buf.ctypes.data, buf[32:].ctypes.data
+    fp = np.ones((3, 3), np.uint8).ctypes.data
+    calls = {  # name: (arguments with a partial group, the same with the group complete)
+        "amt_threshold_open_close": ([None, p, _hip.F64, p, p, 1, 4, 4, fp, 3, 3, p, None],
+                                     [None, p, _hip.F64, p, p, 1, 4, 4, fp, 3, 3, p, p]),
+        "amt_label_sparse": ([None, p, p, p, 1, 4, 4, 1, 4, None, p], [None, p, p, p, 1, 4, 4, 1, 4, p, p]),
+        "amt_peak_mask": ([None, p, p, p, 1, 4, 4, 1, p, p, 4, None], [None, p, p, p, 1, 4, 4, 1, p, p, 4, p]),
+        "amt_watershed_edt_cleared": ([None, p, p, p, p, q, p, 1, 4, 4, 8, p, p, None, 4],
+                                      [None, p, p, p, p, q, p, 1, 4, 4, 8, p, p, p, 4]),
+        "amt_regionprops": ([None, p, None, 1, p, p, 1, 4, 4, 8], [None, p, p, 1, p, p, 1, 4, 4, 8]),
+    }
+    for name, (partial, complete) in calls.items():
+        assert getattr(lib, name)(*partial) == -1, name
+        assert b"go together" in lib.amt_last_error(), name
+        assert getattr(lib, name)(*complete) == -1, name
+        assert lib.amt_last_error() == b"null context", name
+    # a bin plane only with a float64 image; a minuend must not be the output
+    assert lib.amt_threshold_open_close(None, p, _hip.U16, p, p, 1, 4, 4, fp, 3, 3, p, p) == -1
+    assert b"AMT_F64" in lib.amt_last_error()
+    assert lib.amt_rank_filter(None, p, p, _hip.U16, 1, 4, 4, fp, 3, 3, 0, 0, 0.0, p) == -1
+    assert b"differ from out" in lib.amt_last_error()
+
+
 def test_no_gpu_fails_loudly():
     lib = _hip.load_library()
     if lib.amt_device_count() > 0:
