@@ -26,6 +26,21 @@ RP_COLS = (
     "axis_major_length", "axis_minor_length", "eccentricity", "orientation", "area_convex", "solidity",
 )
 RP_NCOLS = len(RP_COLS)
+# amt_regionprops_ext: column bits (AMT_RPX_*) by scikit-image 0.25.2 property name, the morphology table's split
+# columns (AMT_RPX_COL_*) and the four weighted-centroid columns per channel
+RPX_BITS = {
+    "euler_number": 1 << 0, "perimeter_crofton": 1 << 1, "area_filled": 1 << 2, "feret_diameter_max": 1 << 3,
+    "centroid_local": 1 << 4, "inertia_tensor": 1 << 5, "inertia_tensor_eigvals": 1 << 6,
+    "centroid_weighted": 1 << 7, "centroid_weighted_local": 1 << 7,
+}
+RPX_WEIGHTED = 1 << 7
+RPX_COLS = (
+    "euler_number", "perimeter_crofton", "area_filled", "feret_diameter_max", "centroid_local-0", "centroid_local-1",
+    "inertia_tensor-0-0", "inertia_tensor-0-1", "inertia_tensor-1-0", "inertia_tensor-1-1", "inertia_tensor_eigvals-0",
+    "inertia_tensor_eigvals-1",
+)
+RPX_NCOLS = len(RPX_COLS)
+RPX_WCOLS = ("centroid_weighted-0", "centroid_weighted-1", "centroid_weighted_local-0", "centroid_weighted_local-1")
 
 
 class HipUnavailableError(RuntimeError):
@@ -118,6 +133,7 @@ _SIGS = {
     "amt_watershed_edt_cleared": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int]),
     "amt_regionprops": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_regionprops_intensity_f64": (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int]),
+    "amt_regionprops_ext": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_convolve_axis0": (c_int, [_P, _P, c_int, c_double, _P, c_int, c_int, c_int, _P, c_int, c_int, c_double]),
     "amt_max_i32": (c_int, [_P, _P, _P, c_int, c_size_t]),
     "amt_pack_plate_rows": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),

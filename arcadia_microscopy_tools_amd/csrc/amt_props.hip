@@ -383,25 +383,29 @@ __device__ __forceinline__ long long ceil_div(long long a, long long b) {  // b 
 // (2y-1, 2b), (2y+1, 2b), (2y, 2b+1) on the right (the inner diamond points can never be extreme).
 // Left chain = lower-left convex boundary of {(Y, minX(Y))}, right chain of {(Y, maxX(Y))}, built by a
 // monotone scan in Y; then pixel centres (2y, 2x) with XL(2y) <= 2x <= XR(2y) are counted exactly.
+// CROWS (amt_regionprops_ext): instead of the count, every row's {min x, max x} of the convex image goes to
+// crows[plane][off(label) + (y - miny)] (the layout of `rows`); `table` is not touched.
+template <bool CROWS>
 __global__ void __launch_bounds__(64) rp_hull_kernel(const int* __restrict__ bbox, const int* __restrict__ hoff,
                                                      const int* __restrict__ htot, const int2* __restrict__ rows,
                                                      int2* __restrict__ chainL, int2* __restrict__ chainR, size_t cap,
-                                                     double* __restrict__ table, int max_label, int skip_h) {
+                                                     double* __restrict__ table, int max_label, int skip_h,
+                                                     int2* __restrict__ crows) {
     const int plane = blockIdx.y;
     const int l = blockIdx.x * 64 + threadIdx.x;
     if (l >= max_label) return;
     const size_t li = (size_t)plane * max_label + l;
-    double* trow = table + li * AMT_RP_NCOLS;
+    double* trow = CROWS ? nullptr : table + li * AMT_RP_NCOLS;
     const int miny = bbox[li * 4 + 0], maxy = bbox[li * 4 + 2];
     if (maxy < miny) {
-        if (skip_h == 0) trow[AMT_RP_AREA_CONVEX] = 0.0;
+        if (!CROWS && skip_h == 0) trow[AMT_RP_AREA_CONVEX] = 0.0;
         return;
     }
     const int h = maxy - miny + 1;
     if (h <= skip_h && bbox[li * 4 + 3] - bbox[li * 4 + 1] + 1 <= HULL_WMAX) return;  // done by rp_hull_lds_kernel
     const size_t off = (size_t)hoff[li];
     if ((size_t)htot[plane] > cap || off + (size_t)h > cap) {  // capacity exceeded (fragmented labels)
-        trow[AMT_RP_AREA_CONVEX] = __longlong_as_double(0x7ff8000000000000ll);
+        if (!CROWS) trow[AMT_RP_AREA_CONVEX] = __longlong_as_double(0x7ff8000000000000ll);
         return;
     }
     const int2* r = rows + (size_t)plane * cap + off;
@@ -487,9 +491,10 @@ __global__ void __launch_bounds__(64) rp_hull_kernel(const int* __restrict__ bbo
                 xmax = floor_div(num, 2 * dY);
             }
         }
-        if (xmax >= xmin) count += xmax - xmin + 1;
+        if (CROWS) crows[(size_t)plane * cap + off + (y - miny)] = make_int2((int)xmin, (int)xmax);
+        else if (xmax >= xmin) count += xmax - xmin + 1;
     }
-    trow[AMT_RP_AREA_CONVEX] = (double)count;
+    if (!CROWS) trow[AMT_RP_AREA_CONVEX] = (double)count;
 }
 
 // The same hull for labels that fit a small box (at most HULL_HMAX rows and HULL_WMAX columns: every nucleus-sized
@@ -511,9 +516,11 @@ __device__ __forceinline__ int ceil_div32(int a, int b) {  // b > 0
     const int q = a / b;
     return (a % b != 0 && a > 0) ? q + 1 : q;
 }
+template <bool CROWS>  // as rp_hull_kernel
 __global__ void __launch_bounds__(64) rp_hull_lds_kernel(const int* __restrict__ bbox, const int* __restrict__ hoff,
                                                          const int* __restrict__ htot, const int2* __restrict__ rows,
-                                                         size_t cap, double* __restrict__ table, int max_label) {
+                                                         size_t cap, double* __restrict__ table, int max_label,
+                                                         int2* __restrict__ crows) {
     __shared__ unsigned short s_rows[HULL_HMAX * 32];
     __shared__ unsigned short s_ch[HULL_CH * 64];
     const int plane = blockIdx.y;
@@ -521,17 +528,17 @@ __global__ void __launch_bounds__(64) rp_hull_lds_kernel(const int* __restrict__
     const int l = blockIdx.x * 32 + pr;
     if (l >= max_label) return;
     const size_t li = (size_t)plane * max_label + l;
-    double* trow = table + li * AMT_RP_NCOLS;
+    double* trow = CROWS ? nullptr : table + li * AMT_RP_NCOLS;
     const int miny = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], maxy = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
     if (maxy < miny) {
-        if (side == 0) trow[AMT_RP_AREA_CONVEX] = 0.0;
+        if (!CROWS && side == 0) trow[AMT_RP_AREA_CONVEX] = 0.0;
         return;
     }
     const int h = maxy - miny + 1;
     if (h > HULL_HMAX || x1 - x0 + 1 > HULL_WMAX) return;  // rp_hull_kernel takes it
     const size_t off = (size_t)hoff[li];
     if ((size_t)htot[plane] > cap || off + (size_t)h > cap) {  // capacity exceeded (fragmented labels)
-        if (side == 0) trow[AMT_RP_AREA_CONVEX] = __longlong_as_double(0x7ff8000000000000ll);
+        if (!CROWS && side == 0) trow[AMT_RP_AREA_CONVEX] = __longlong_as_double(0x7ff8000000000000ll);
         return;
     }
     const int2* r = rows + (size_t)plane * cap + off;
@@ -602,9 +609,13 @@ __global__ void __launch_bounds__(64) rp_hull_lds_kernel(const int* __restrict__
         }
         const int other = __shfl_xor(b, 1);
         const int xmin = side ? other : b, xmax = side ? b : other;
-        if (xmax >= xmin) count += xmax - xmin + 1;
+        if (CROWS) {
+            if (side == 0) crows[(size_t)plane * cap + off + k] = make_int2(xmin + x0, xmax + x0);
+        } else if (xmax >= xmin) {
+            count += xmax - xmin + 1;
+        }
     }
-    if (side == 0) trow[AMT_RP_AREA_CONVEX] = (double)count;
+    if (!CROWS && side == 0) trow[AMT_RP_AREA_CONVEX] = (double)count;
 }
 
 // ---- final per-label columns ------------------------------------------------------------------------
@@ -717,12 +728,12 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
                            table_dev, nlab);
         AMT_LAUNCH_CHECK();
         const int skip_h = HULL_HMAX;
-        hipLaunchKernelGGL(rp_hull_lds_kernel, dim3((max_label + 31) / 32, nplanes), dim3(64), 0, ctx->stream, bbox, hoff, htot,
-                           rows, cap, table_dev, max_label);
+        hipLaunchKernelGGL(rp_hull_lds_kernel<false>, dim3((max_label + 31) / 32, nplanes), dim3(64), 0, ctx->stream, bbox,
+                           hoff, htot, rows, cap, table_dev, max_label, (int2*)nullptr);
         AMT_LAUNCH_CHECK();
         // labels taller than HULL_HMAX rows or wider than HULL_WMAX columns: chains in HBM scratch
-        hipLaunchKernelGGL(rp_hull_kernel, dim3((max_label + 63) / 64, nplanes), dim3(64), 0, ctx->stream, bbox, hoff,
-                           htot, rows, chainL, chainR, cap, table_dev, max_label, skip_h);
+        hipLaunchKernelGGL(rp_hull_kernel<false>, dim3((max_label + 63) / 64, nplanes), dim3(64), 0, ctx->stream, bbox,
+                           hoff, htot, rows, chainL, chainR, cap, table_dev, max_label, skip_h, (int2*)nullptr);
         AMT_LAUNCH_CHECK();
         hipLaunchKernelGGL(rp_solidity_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream,
                            table_dev, nlab);
@@ -832,5 +843,480 @@ extern "C" int amt_label_bboxes(amt_ctx* ctx, const int32_t* labels, int32_t* bb
     hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels,
                        bbox_dev, H, W, max_label);
     AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// ---- extended region properties (amt_regionprops_ext) ---------------------------------------------------------------
+// SK/measure/_regionprops_utils.py:58-184 (euler_number), :252-328 (perimeter_crofton), SK/measure/_regionprops.py
+// filled_image (ndi.binary_fill_holes with a 3x3 structure), feret_diameter_max (find_contours of the padded convex
+// image), local_centroid / weighted_*centroid, SK/measure/_moments.py inertia_tensor(_eigvals).
+
+// 2x2 configurations: window (y, x) over the zero-padded box holds the pixels (y-1, x-1) (8), (y-1, x) (2), (y, x-1) (4)
+// and (y, x) (1) -- the codes ndi.convolve(image, [[0,0,0],[0,1,4],[0,2,8]]) gives.  Windows cover y in [y0, y1 + 1],
+// x in [x0, x1 + 1]: the (h+1) x (w+1) grid including the padding (the other windows are code 0).  One wave per
+// label; a lane keeps its column's previous row in registers.  Codes 0 and 15 (every window outside and inside the
+// label) have coefficient 0 for both properties and are not counted; the rest go to an LDS histogram with integer
+// atomics (exact, so run-to-run identical).
+__global__ void __launch_bounds__(64) rpx_quad_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                      double* __restrict__ table, int H, int W, int max_label,
+                                                      int want_euler, int want_crofton) {
+    __shared__ unsigned hist[16];
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    if (lane < 16) hist[lane] = 0;
+    __syncthreads();
+    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    const int* L = labels + (size_t)plane * H * W;
+    const int want = l + 1;
+    if (y1 >= y0) {
+        for (int xb = x0; xb <= x1 + 1; xb += 64) {
+            const int x = xb + lane;
+            const bool col = x <= x1 + 1;
+            // p(y, x) and p(y, x - 1) of the previous row
+            unsigned up = 0, upl = 0;
+            for (int y = y0; y <= y1 + 1; ++y) {
+                unsigned c = 0, cl = 0;
+                if (col && y <= y1) {
+                    if (x <= x1) c = L[(size_t)y * W + x] == want;
+                    if (x - 1 >= x0) cl = L[(size_t)y * W + x - 1] == want;
+                }
+                const unsigned code = c | (up << 1) | (cl << 2) | (upl << 3);
+                if (col && code != 0 && code != 15) atomicAdd(&hist[code], 1u);
+                up = c;
+                upl = cl;
+            }
+        }
+    }
+    __syncthreads();
+    if (lane == 0) {
+        double* t = table + li * AMT_RPX_NCOLS;
+        long long h[16];
+        for (int k = 0; k < 16; ++k) h[k] = hist[k];
+        if (want_euler) t[AMT_RPX_COL_EULER_NUMBER] = (double)(h[8] - h[6] - h[14]);  // EULER_COEFS2D_8
+        if (want_crofton) {
+            const double pi = 3.141592653589793, s2 = sqrt(2.0);
+            const double coefs[16] = {0, pi / 4 * (1 + 1 / s2), pi / (4 * s2), pi / (2 * s2), 0, pi / 4 * (1 + 1 / s2),
+                                      0, pi / (4 * s2), pi / 4, pi / 2, pi / (4 * s2), pi / (4 * s2), pi / 4, pi / 2, 0, 0};
+            double p = 0.0;
+            for (int k = 0; k < 16; ++k) p += coefs[k] * (double)h[k];
+            t[AMT_RPX_COL_PERIMETER_CROFTON] = y1 >= y0 ? p : 0.0;
+        }
+    }
+}
+
+// ---- area_filled ------------------------------------------------------------------------------------------------------
+// Background = "not this label" inside the box; what is reachable from the box edge through 8-connected background
+// is outside, the rest of the background is holes.  Boxes of at most 64 x 64: one wave per label, lane k holds row k as
+// one 64-bit word (bit j = column x0 + j) in a register; rows above / below come from lane shifts.
+constexpr int HOLE_SMALL = 64;
+__device__ __forceinline__ u64 row_fill(u64 r, u64 b) {  // grow r along the row inside b until it stops
+    for (;;) {
+        const u64 t = (r | (r << 1) | (r >> 1)) & b;
+        if (t == r) return r;
+        r = t;
+    }
+}
+__global__ void __launch_bounds__(64) rpx_holes_small_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                             const u64* __restrict__ acc, double* __restrict__ table,
+                                                             int H, int W, int max_label) {
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    double* t = table + li * AMT_RPX_NCOLS;
+    if (y1 < y0) {
+        if (lane == 0) t[AMT_RPX_COL_AREA_FILLED] = 0.0;
+        return;
+    }
+    const int h = y1 - y0 + 1, w = x1 - x0 + 1;
+    if (h > HOLE_SMALL || w > HOLE_SMALL) return;  // rpx_holes_large_kernel
+    const int* L = labels + (size_t)plane * H * W;
+    const u64 wmask = w == 64 ? ~0ull : (1ull << w) - 1ull;
+    u64 fg = 0;
+    for (int k = 0; k < h; ++k) {  // row k: lane j reads column x0 + j, the ballot is the row's word
+        const bool m = lane < w && L[(size_t)(y0 + k) * W + x0 + lane] == l + 1;
+        const u64 word = __ballot(m);
+        if (lane == k) fg = word;
+    }
+    const u64 b = lane < h ? ~fg & wmask : 0ull;
+    u64 r = (lane == 0 || lane == h - 1) ? b : b & (1ull | (1ull << (w - 1)));
+    for (;;) {
+        r = row_fill(r, b);
+        u64 up = __shfl_up(r, 1), dn = __shfl_down(r, 1);
+        up = lane > 0 ? up : 0ull;
+        dn = lane < 63 ? dn : 0ull;
+        const u64 v = up | dn;
+        const u64 rn = r | ((v | (v << 1) | (v >> 1)) & b);
+        const u64 changed = __ballot(rn != r);
+        r = rn;
+        if (!changed) break;
+    }
+    u64 holes = (u64)__popcll(b & ~r);
+    holes = wave_sum_u64(holes);
+    if (lane == 0) t[AMT_RPX_COL_AREA_FILLED] = (double)(acc[li * A_NACC + A_N] + holes);
+}
+
+// Larger boxes: one workgroup per plane takes its large labels one after the other, with the box's background and
+// reached bits in global scratch (rows of wpr 64-bit words); the fill sweeps the words in place until a sweep changes
+// nothing.  Bits only ever get set and never leave the background, so words read while a neighbour updates them are
+// still a subset of the final set, and a sweep without a change means the fill is complete.
+__global__ void __launch_bounds__(256) rpx_holes_large_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                              const u64* __restrict__ acc, double* __restrict__ table,
+                                                              u64* __restrict__ scratch, size_t scratch_words, int H,
+                                                              int W, int max_label) {
+    __shared__ u64 red[4];
+    __shared__ int list[256];
+    __shared__ int nlist;
+    const int plane = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int* L = labels + (size_t)plane * H * W;
+    u64* Bw = scratch + (size_t)plane * 2 * scratch_words;
+    u64* Rw = Bw + scratch_words;
+    for (int base = 0; base < max_label; base += 256) {
+        // the large labels of the next 256, found in parallel (their order in the list does not matter)
+        if (tid == 0) nlist = 0;
+        __syncthreads();
+        {
+            const int l = base + tid;
+            if (l < max_label) {
+                const int* B = bbox + ((size_t)plane * max_label + l) * 4;
+                if (B[2] >= B[0] && (B[2] - B[0] + 1 > HOLE_SMALL || B[3] - B[1] + 1 > HOLE_SMALL))
+                    list[atomicAdd(&nlist, 1)] = l;
+            }
+        }
+        __syncthreads();
+        const int nl = nlist;
+        for (int il = 0; il < nl; ++il) {
+            const int l = list[il];
+            const size_t li = (size_t)plane * max_label + l;
+            const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+            const int h = y1 - y0 + 1, w = x1 - x0 + 1;
+            const int wpr = (w + 63) / 64;
+            const int nw = h * wpr;
+            const int lastbits = w - (wpr - 1) * 64;
+            const u64 lastmask = lastbits == 64 ? ~0ull : (1ull << lastbits) - 1ull;
+            // background words (one wave per word: lane j reads column 64 q + j) and the seeds on the box edge
+            for (int i = wv; i < nw; i += 4) {
+                const int k = i / wpr, q = i - k * wpr;
+                const int x = x0 + 64 * q + lane;
+                const bool m = x <= x1 && L[(size_t)(y0 + k) * W + x] == l + 1;
+                const u64 fg = __ballot(m);
+                const u64 b = ~fg & (q == wpr - 1 ? lastmask : ~0ull);
+                u64 seed = (k == 0 || k == h - 1) ? b : 0ull;
+                if (q == 0) seed |= b & 1ull;
+                if (q == wpr - 1) seed |= b & (1ull << (lastbits - 1));
+                if (lane == 0) {
+                    Bw[i] = b;
+                    Rw[i] = seed;
+                }
+            }
+            __syncthreads();
+            for (;;) {
+                int changed = 0;
+                for (int i = tid; i < nw; i += 256) {
+                    const int k = i / wpr, q = i - k * wpr;
+                    const u64 b = Bw[i], r = Rw[i];
+                    if (b == r) continue;  // nothing left to reach in this word
+                    // the 3 x 3 neighbourhood: words of the rows above / below and the edge bits of the words beside
+                    u64 v = 0, side = 0;
+                    for (int dk = -1; dk <= 1; ++dk) {
+                        const int kk = k + dk;
+                        if (kk < 0 || kk >= h) continue;
+                        const u64* row = Rw + (size_t)kk * wpr;
+                        if (dk != 0) v |= row[q];
+                        if (q > 0) side |= row[q - 1] >> 63;
+                        if (q + 1 < wpr) side |= (row[q + 1] & 1ull) << 63;
+                    }
+                    u64 rn = r | ((v | (v << 1) | (v >> 1) | side) & b);
+                    rn = row_fill(rn, b);
+                    if (rn != r) {
+                        Rw[i] = rn;
+                        changed = 1;
+                    }
+                }
+                if (!__syncthreads_or(changed)) break;
+            }
+            u64 holes = 0;
+            for (int i = tid; i < nw; i += 256) holes += (u64)__popcll(Bw[i] & ~Rw[i]);
+            holes = wave_sum_u64(holes);
+            if (lane == 0) red[wv] = holes;
+            __syncthreads();
+            if (tid == 0)
+                table[li * AMT_RPX_NCOLS + AMT_RPX_COL_AREA_FILLED] =
+                    (double)(acc[li * A_NACC + A_N] + red[0] + red[1] + red[2] + red[3]);
+            __syncthreads();
+        }
+        __syncthreads();  // every thread has read nlist and the list before they are rewritten
+    }
+}
+
+// ---- feret_diameter_max ---------------------------------------------------------------------------------------------
+// The contour of the convex image at level 0.5 passes through the midpoint of every edge between a pixel of the image
+// and one outside it; the farthest pair of those midpoints is the diameter.  In doubled coordinates the midpoints of
+// row y with convex extent [a, b] are (2y, 2a - 1) and (2y, 2b + 1), and the columns of the row that have no pixel
+// above (below) give midpoints on the line 2y - 1 (2y + 1).  Those lie on at most two segments per side, and the
+// farthest point of a segment from any point is one of its ends: up to 10 candidates per row, all exact integers.
+struct FeretRow {
+    int Y[10], X[10];
+};
+__device__ __forceinline__ int2 crow_at(const int2* cr, int k, int h) {
+    return (k < 0 || k >= h) ? make_int2(1, 0) : cr[k];  // outside the box: empty
+}
+__device__ __forceinline__ void feret_row(const int2* cr, int k, int h, int y0, int2 fallback, FeretRow& p) {
+    const int2 e = crow_at(cr, k, h);
+    const int Y = 2 * (y0 + k);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        p.Y[i] = fallback.x;
+        p.X[i] = fallback.y;
+    }
+    if (e.y < e.x) return;
+    p.Y[0] = Y, p.X[0] = 2 * e.x - 1;
+    p.Y[1] = Y, p.X[1] = 2 * e.y + 1;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {  // s = 0: the neighbour above (edge line Y - 1), s = 1: below (Y + 1)
+        const int2 o = crow_at(cr, s ? k + 1 : k - 1, h);
+        const int Ye = s ? Y + 1 : Y - 1;
+        int a0 = e.x, b0 = e.y, a1 = 1, b1 = 0;  // [a, b] minus [o.x, o.y]: up to two intervals
+        if (o.y >= o.x && o.x <= e.y && o.y >= e.x) {
+            a0 = e.x, b0 = min(e.y, o.x - 1);
+            a1 = max(e.x, o.y + 1), b1 = e.y;
+        }
+        const int base = 2 + 4 * s;
+        if (b0 >= a0) {
+            p.Y[base] = Ye, p.X[base] = 2 * a0;
+            p.Y[base + 1] = Ye, p.X[base + 1] = 2 * b0;
+        } else {
+            p.Y[base] = p.Y[0], p.X[base] = p.X[0];
+            p.Y[base + 1] = p.Y[0], p.X[base + 1] = p.X[0];
+        }
+        if (b1 >= a1) {
+            p.Y[base + 2] = Ye, p.X[base + 2] = 2 * a1;
+            p.Y[base + 3] = Ye, p.X[base + 3] = 2 * b1;
+        } else {
+            p.Y[base + 2] = p.Y[0], p.X[base + 2] = p.X[0];
+            p.Y[base + 3] = p.Y[0], p.X[base + 3] = p.X[0];
+        }
+    }
+}
+__global__ void __launch_bounds__(64) rpx_feret_kernel(const int* __restrict__ bbox, const int* __restrict__ hoff,
+                                                       const int* __restrict__ htot, const int2* __restrict__ crows,
+                                                       size_t cap, double* __restrict__ table, int max_label) {
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    double* t = table + li * AMT_RPX_NCOLS;
+    const int y0 = bbox[li * 4 + 0], y1 = bbox[li * 4 + 2];
+    if (y1 < y0) {
+        if (lane == 0) t[AMT_RPX_COL_FERET_DIAMETER_MAX] = 0.0;
+        return;
+    }
+    const int h = y1 - y0 + 1;
+    const size_t off = (size_t)hoff[li];
+    if ((size_t)htot[plane] > cap || off + (size_t)h > cap) {  // the hull kernels skipped it too
+        if (lane == 0) t[AMT_RPX_COL_FERET_DIAMETER_MAX] = __longlong_as_double(0x7ff8000000000000ll);
+        return;
+    }
+    const int2* cr = crows + (size_t)plane * cap + off;
+    const int2 e0 = cr[0];  // the top row holds a pixel of the label, so its convex extent is not empty
+    const int2 fallback = make_int2(2 * y0, 2 * e0.x - 1);
+    // the lanes share the row pairs (ka <= kb) of the box evenly, not one row each
+    long long best = 0;
+    for (int p = lane; p < h * h; p += 64) {
+        const int ka = p / h, kb = p - ka * h;
+        if (kb < ka) continue;
+        FeretRow a, b;
+        feret_row(cr, ka, h, y0, fallback, a);
+        feret_row(cr, kb, h, y0, fallback, b);
+#pragma unroll
+        for (int i = 0; i < 10; ++i)
+#pragma unroll
+            for (int j = 0; j < 10; ++j) {
+                const long long dy = a.Y[i] - b.Y[j], dx = a.X[i] - b.X[j];
+                const long long d = dy * dy + dx * dx;
+                best = d > best ? d : best;
+            }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const long long v = __shfl_xor(best, o);
+        best = v > best ? v : best;
+    }
+    if (lane == 0) t[AMT_RPX_COL_FERET_DIAMETER_MAX] = sqrt((double)best) * 0.5;  // = sqrt(best / 4), exactly
+}
+
+// ---- centroid_local, inertia_tensor, inertia_tensor_eigvals from the exact moment sums of rp_label_kernel -------------
+__global__ void __launch_bounds__(256) rpx_moments_kernel(const u64* __restrict__ acc, const int* __restrict__ bbox,
+                                                          double* __restrict__ table, size_t nlab, int columns) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nlab; i += (size_t)gridDim.x * 256) {
+        const u64* A = acc + i * A_NACC;
+        double* t = table + i * AMT_RPX_NCOLS;
+        const u64 n = A[A_N];
+        double cy = 0, cx = 0, a = 0, b = 0, c = 0, l1 = 0, l2 = 0;
+        if (n != 0) {
+            const double dn = (double)n;
+            // sum of (y - y0): exact integers, so M10 / M00 rounds once, as the float64 moments of the box do
+            cy = (double)(A[A_SY] - n * (u64)bbox[i * 4 + 0]) / dn;
+            cx = (double)(A[A_SX] - n * (u64)bbox[i * 4 + 1]) / dn;
+            const double Nyy = diff_of_products(n, A[A_SYY], A[A_SY], A[A_SY]);  // n * mu20
+            const double Nxx = diff_of_products(n, A[A_SXX], A[A_SX], A[A_SX]);  // n * mu02
+            const double Nxy = diff_of_products(n, A[A_SXY], A[A_SX], A[A_SY]);  // n * mu11
+            const double n2 = dn * dn;
+            a = Nxx / n2;   // T[0,0] = mu02 / mu00
+            c = Nyy / n2;   // T[1,1] = mu20 / mu00
+            b = -Nxy / n2;  // T[0,1] = T[1,0] = -mu11 / mu00
+            const double tr = (a + c) * 0.5, hd = (a - c) * 0.5;
+            const double rad = sqrt(hd * hd + b * b);
+            l1 = tr + rad;
+            l2 = tr - rad;
+            l1 = l1 < 0.0 ? 0.0 : l1;
+            l2 = l2 < 0.0 ? 0.0 : l2;
+        }
+        if (columns & AMT_RPX_CENTROID_LOCAL) {
+            t[AMT_RPX_COL_CENTROID_LOCAL_Y] = cy;
+            t[AMT_RPX_COL_CENTROID_LOCAL_X] = cx;
+        }
+        if (columns & AMT_RPX_INERTIA_TENSOR) {
+            t[AMT_RPX_COL_INERTIA_00] = a;
+            t[AMT_RPX_COL_INERTIA_01] = b;
+            t[AMT_RPX_COL_INERTIA_10] = b;
+            t[AMT_RPX_COL_INERTIA_11] = c;
+        }
+        if (columns & AMT_RPX_INERTIA_EIGVALS) {
+            t[AMT_RPX_COL_EIGVAL_0] = l1;
+            t[AMT_RPX_COL_EIGVAL_1] = l2;
+        }
+    }
+}
+
+// ---- centroid_weighted(_local) --------------------------------------------------------------------------------------
+// One wave per label over its box: sum I, sum I (y - y0), sum I (x - x0) per channel.  uint16 images sum in 64-bit
+// integers (exact: the float64 moments of the box are exact integers too); float64 images sum in float64.
+template <typename T, typename S>
+__global__ void __launch_bounds__(64) rpx_weighted_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                          const T* __restrict__ inten, int C, double* __restrict__ wtable,
+                                                          int H, int W, int max_label) {
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    double* out = wtable + li * (size_t)C * 4;
+    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    if (y1 < y0) {
+        for (int i = lane; i < C * 4; i += 64) out[i] = 0.0;
+        return;
+    }
+    const size_t n = (size_t)H * W;
+    const int* lab = labels + (size_t)plane * n;
+    for (int c = 0; c < C; ++c) {
+        const T* img = inten + ((size_t)plane * C + c) * n;
+        S s = 0, sy = 0, sx = 0;
+        for (int y = y0; y <= y1; ++y)
+            for (int x = x0 + lane; x <= x1; x += 64)
+                if (lab[(size_t)y * W + x] == l + 1) {
+                    const S v = (S)img[(size_t)y * W + x];
+                    s += v;
+                    sy += v * (S)(y - y0);
+                    sx += v * (S)(x - x0);
+                }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            s += __shfl_xor(s, o);
+            sy += __shfl_xor(sy, o);
+            sx += __shfl_xor(sx, o);
+        }
+        if (lane == 0) {
+            const double ly = (double)sy / (double)s, lx = (double)sx / (double)s;  // 0 / 0 = NaN, as scikit-image
+            out[c * 4 + 0] = ly + (double)y0;
+            out[c * 4 + 1] = lx + (double)x0;
+            out[c * 4 + 2] = ly;
+            out[c * 4 + 3] = lx;
+        }
+    }
+}
+
+extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C,
+                                   int columns, double* table_dev, double* wtable_dev, int nplanes, int H, int W,
+                                   int max_label) {
+    const unsigned cols = (unsigned)columns;
+    const bool want_w = (cols & AMT_RPX_CENTROID_WEIGHTED) != 0;
+    const bool want_m = (cols & ~AMT_RPX_CENTROID_WEIGHTED) != 0;
+    AMT_REQUIRE(labels && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && cols != 0 && (cols & ~AMT_RPX_ALL) == 0,
+                "regionprops_ext: bad arguments");
+    AMT_REQUIRE(!table_dev == !want_m, "regionprops_ext: the morphology table and its column bits go together");
+    AMT_REQUIRE(want_w == !!intensity && want_w == !!wtable_dev && (!want_w || C >= 1),
+                "regionprops_ext: the intensity planes (C >= 1), the weighted table and AMT_RPX_CENTROID_WEIGHTED go "
+                "together");
+    AMT_REQUIRE(!want_w || in_code == AMT_U16 || in_code == AMT_F64, "regionprops_ext: intensity must be AMT_U16 or AMT_F64");
+    AMT_TRY(amt_set_device(ctx));
+    if (nplanes == 0 || max_label == 0) return AMT_OK;
+    const bool euler = cols & (AMT_RPX_EULER_NUMBER | AMT_RPX_PERIMETER_CROFTON);
+    const bool filled = cols & AMT_RPX_AREA_FILLED, feret = cols & AMT_RPX_FERET_DIAMETER_MAX;
+    const bool moments = cols & (AMT_RPX_CENTROID_LOCAL | AMT_RPX_INERTIA_TENSOR | AMT_RPX_INERTIA_EIGVALS);
+    const bool scan = filled || feret || moments;  // rp_label_kernel: pixel counts, moment sums, row extents
+    const size_t n = (size_t)H * W;
+    const size_t nlab = (size_t)nplanes * max_label;
+    const size_t cap = feret ? n : 1;
+    const size_t hwords = filled ? (size_t)H * ((W + 63) / 64) : 0;
+    size_t need = amt_align(nlab * A_NACC * 8) + amt_align(nlab * 16) + amt_align(nlab * 4) + amt_align(nplanes * 4) +
+                  amt_align((size_t)nplanes * cap * 8) + amt_align((size_t)nplanes * cap * 8) +
+                  2 * amt_align((size_t)nplanes * 3 * cap * 8) + amt_align((size_t)nplanes * 2 * hwords * 8);
+    AMT_TRY(amt_arena_begin(ctx, need));
+    u64* acc = arena_take_t<u64>(ctx, nlab * A_NACC);
+    int* bbox = arena_take_t<int>(ctx, nlab * 4);
+    int* hoff = arena_take_t<int>(ctx, nlab);
+    int* htot = arena_take_t<int>(ctx, nplanes);
+    int2* rows = arena_take_t<int2>(ctx, (size_t)nplanes * cap);
+    int2* crows = arena_take_t<int2>(ctx, (size_t)nplanes * cap);
+    int2* chainL = arena_take_t<int2>(ctx, (size_t)nplanes * 3 * cap);
+    int2* chainR = arena_take_t<int2>(ctx, (size_t)nplanes * 3 * cap);
+    u64* hscratch = arena_take_t<u64>(ctx, (size_t)nplanes * 2 * hwords);
+    hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
+    AMT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels,
+                       bbox, H, W, max_label);
+    AMT_LAUNCH_CHECK();
+    if (scan) {
+        hipLaunchKernelGGL(rp_heights_kernel, dim3(amt_grid_for(max_label, 256, 256), nplanes), dim3(256), 0, ctx->stream,
+                           bbox, hoff, max_label);
+        AMT_LAUNCH_CHECK();
+        AMT_TRY(amt_scan_excl(ctx, hoff, max_label, (size_t)max_label, htot, nplanes));
+        hipLaunchKernelGGL(rp_label_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox, hoff, htot,
+                           rows, cap, acc, (const uint16_t*)nullptr, 1, 0, 0, (double*)nullptr, H, W, max_label, 1);
+        AMT_LAUNCH_CHECK();
+    }
+    if (euler) {
+        hipLaunchKernelGGL(rpx_quad_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox, table_dev, H,
+                           W, max_label, (cols & AMT_RPX_EULER_NUMBER) ? 1 : 0, (cols & AMT_RPX_PERIMETER_CROFTON) ? 1 : 0);
+        AMT_LAUNCH_CHECK();
+    }
+    if (filled) {
+        hipLaunchKernelGGL(rpx_holes_small_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox, acc,
+                           table_dev, H, W, max_label);
+        AMT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(rpx_holes_large_kernel, dim3(nplanes), dim3(256), 0, ctx->stream, labels, bbox, acc, table_dev,
+                           hscratch, hwords, H, W, max_label);
+        AMT_LAUNCH_CHECK();
+    }
+    if (feret) {
+        hipLaunchKernelGGL(rp_hull_lds_kernel<true>, dim3((max_label + 31) / 32, nplanes), dim3(64), 0, ctx->stream, bbox,
+                           hoff, htot, rows, cap, (double*)nullptr, max_label, crows);
+        AMT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(rp_hull_kernel<true>, dim3((max_label + 63) / 64, nplanes), dim3(64), 0, ctx->stream, bbox, hoff,
+                           htot, rows, chainL, chainR, cap, (double*)nullptr, max_label, HULL_HMAX, crows);
+        AMT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(rpx_feret_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, bbox, hoff, htot, crows,
+                           cap, table_dev, max_label);
+        AMT_LAUNCH_CHECK();
+    }
+    if (moments) {
+        hipLaunchKernelGGL(rpx_moments_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox,
+                           table_dev, nlab, columns);
+        AMT_LAUNCH_CHECK();
+    }
+    if (want_w) {
+        if (in_code == AMT_U16)
+            hipLaunchKernelGGL((rpx_weighted_kernel<uint16_t, u64>), dim3(max_label, nplanes), dim3(64), 0, ctx->stream,
+                               labels, bbox, (const uint16_t*)intensity, C, wtable_dev, H, W, max_label);
+        else
+            hipLaunchKernelGGL((rpx_weighted_kernel<double, double>), dim3(max_label, nplanes), dim3(64), 0, ctx->stream,
+                               labels, bbox, (const double*)intensity, C, wtable_dev, H, W, max_label);
+        AMT_LAUNCH_CHECK();
+    }
     return AMT_OK;
 }

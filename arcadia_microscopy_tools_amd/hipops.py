@@ -916,6 +916,48 @@ def regionprops_intensity(labels: DeviceArray, intensity: DeviceArray, max_label
     return o
 
 
+def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: DeviceArray | None = None, out=None,
+                    wout=None):
+    """Extended region properties (include/amt_hip.h ``amt_regionprops_ext``) of every label plane in one call.
+
+    ``columns`` is an iterable of scikit-image 0.25.2 names from ``_hip.RPX_BITS`` (or the OR of their bits).
+    Returns (table, wtable): table (nplanes, max_label, RPX_NCOLS) float64 in ``_hip.RPX_COLS`` order, None when only
+    weighted centroids are asked for; wtable (nplanes, max_label, C, 4) float64 in ``_hip.RPX_WCOLS`` order, from
+    ``intensity`` (..., C, Y, X) uint16 or float64 with one (C, Y, X) stack per label plane, None without it.
+    Columns that were not asked for are left unwritten."""
+    ctx = labels.ctx
+    n, H, W = _planes(labels)
+    if labels.dtype != np.int32:
+        raise TypeError("regionprops_ext expects int32 labels")
+    if isinstance(columns, (int, np.integer)):
+        bits = int(columns)
+    else:
+        bits = 0
+        for name in columns:
+            if name not in _hip.RPX_BITS:
+                raise ValueError(f"unknown extended region property {name!r}")
+            bits |= _hip.RPX_BITS[name]
+    want_w = bool(bits & _hip.RPX_WEIGHTED)
+    if want_w != (intensity is not None):
+        raise ValueError("weighted centroids need intensity images, and intensity images are only used for them")
+    code, C = 0, 0
+    if intensity is not None:
+        if intensity.dtype not in (np.uint16, np.float64):
+            raise TypeError("intensity images must be uint16 or float64 on the device path")
+        if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
+            raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
+        C = int(intensity.shape[-3])
+        if intensity.size != n * C * H * W:
+            raise ValueError("intensity / labels plane count mismatch")
+        code = _hip.U16 if intensity.dtype == np.uint16 else _hip.F64
+    o = _out(ctx, out, (n, max_label, _hip.RPX_NCOLS), np.float64) if bits & ~_hip.RPX_WEIGHTED else None
+    wo = _out(ctx, wout, (n, max_label, C, 4), np.float64) if want_w else None
+    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, None if intensity is None else intensity.ptr, code, C,
+                                          bits, None if o is None else o.ptr, None if wo is None else wo.ptr, n, H, W,
+                                          int(max_label)), "amt_regionprops_ext")
+    return o, wo
+
+
 def cellpose_masks(dP: DeviceArray, cellprob: DeviceArray, cellprob_threshold: float = 0.0, niter: int = 200,
                    min_size: int = 15, max_size_fraction: float = 0.4, max_seeds: int = 16384, out=None, count=None,
                    flow_threshold: float = 0.0, fill_holes: bool = False):

@@ -315,56 +315,77 @@ class SegmentationMask:
             return hipops.cell_outlines_borders(plane, int(k))
         return hipops.cell_outlines(plane, int(k))
 
+    def _intensity_stack(self, shape):
+        """The intensity images as one device (C, Y, X) stack -> (stack, channel names, exact).  uint8 / uint16
+        images are kept as uint16 and accumulated exactly (integer sums); any other dtype the reference accepts
+        (R/masks.py:178-190: "any 2-D ndarray") is measured in float64, as regionprops does.  The planes go to the
+        device one by one into their slot of the stack: no host-side stack."""
+        from .device import get_context
+
+        planes, names = [], []
+        for channel, img in self.intensity_image_dict.items():
+            planes.append(np.asarray(img))
+            names.append(channel.name)
+        exact = all(p.dtype in (np.uint8, np.uint16) for p in planes)
+        ctx = get_context()
+        stack = ctx.empty((len(planes),) + tuple(shape), np.uint16 if exact else np.float64)
+        whole = _as_one_block(planes)
+        if whole is not None:  # the planes are the channels of ONE (C, Y, X) array: one staged transfer
+            ctx.asarray(whole, out=stack)
+        else:
+            for c, p in enumerate(planes):
+                ctx.asarray(p, out=stack[c])  # converted to the stack's dtype on its way through staging
+        return stack, names, exact
+
     @cached_property
     def cell_properties(self) -> dict[str, ScalarArray]:
         """Morphology + per-channel intensity features, one entry per cell ordered by label
-        (R/masks.py:247-328; columns of scikit-image's ``regionprops_table``)."""
+        (R/masks.py:247-328; columns of scikit-image's ``regionprops_table``).  Besides the default columns, the
+        extended names of ``segment.EXT_DEVICE_PROPERTIES`` / ``EXT_HOST_PROPERTIES`` (property_names) and
+        ``WEIGHTED_PROPERTIES`` (intensity_property_names) are measured too."""
         from . import hipops
-        from .device import get_context
-        from .segment import assemble_cell_properties
+        from .segment import WEIGHTED_PROPERTIES, assemble_cell_properties, ext_columns
 
         assert self.property_names is not None
         assert self.intensity_property_names is not None
-        if "_rows" in self.__dict__:  # measured by the chain that made the labels (SegmentationModel.batch_masks)
-            morph, inten = self.__dict__["_rows"]
-            names = [c.name for c in self.intensity_image_dict] if self.intensity_image_dict else []
-            use = inten if (names and self.intensity_property_names) else None
-            return assemble_cell_properties(morph, use, names, list(self.property_names),
-                                            list(self.intensity_property_names))
         lab, k = self._labels_device
         k = int(k)
-        inten = None
-        names: list[str] = []
+        shape = tuple(lab.shape[-2:])
+        want_ext = ext_columns(self.property_names, self.intensity_property_names)
+        want_w = bool(self.intensity_image_dict) and any(p in WEIGHTED_PROPERTIES for p in want_ext)
+        if not want_w:  # weighted centroids without intensity images: the reference makes no intensity columns
+            want_ext = [p for p in want_ext if p not in WEIGHTED_PROPERTIES]
+        stack, names, exact = None, [], True
         if self.intensity_image_dict and self.intensity_property_names:
-            planes = []
-            for channel, img in self.intensity_image_dict.items():
-                planes.append(np.asarray(img))
-                names.append(channel.name)
-            ctx = get_context()
-            # uint8 / uint16 images are accumulated exactly (integer sums); any other dtype the reference accepts
-            # (R/masks.py:178-190: "any 2-D ndarray") is measured in float64, as regionprops does.  The planes go to
-            # the device one by one into their slot of a (C, Y, X) buffer: no host-side stack
-            exact = all(p.dtype in (np.uint8, np.uint16) for p in planes)
-            dt = np.uint16 if exact else np.float64
-            stack = ctx.empty((len(planes),) + tuple(lab.shape[-2:]), dt)
-            whole = _as_one_block(planes)
-            if whole is not None:  # the planes are the channels of ONE (C, Y, X) array: one staged transfer
-                ctx.asarray(whole, out=stack)
-            else:
-                for c, p in enumerate(planes):
-                    ctx.asarray(p, out=stack[c])  # converted to ``dt`` on its way through the staging buffer
-            if exact and lab.size == stack.size // len(planes):
-                # morphology + intensities share the bounding-box pass and the per-label scan
-                m, it = hipops.regionprops_full(lab.reshape((1,) + tuple(lab.shape[-2:])),
-                                                stack.reshape((1,) + stack.shape), max(k, 1))
-                morph, inten = m.numpy()[0][:k], it.numpy()[0][:k]
+            names = [c.name for c in self.intensity_image_dict]
+        if "_rows" in self.__dict__:  # measured by the chain that made the labels (SegmentationModel.batch_masks)
+            morph, inten = self.__dict__["_rows"]
+            inten = inten if (names and self.intensity_property_names) else None
+            if want_w:
+                stack, _, _ = self._intensity_stack(shape)
+        else:
+            inten = None
+            if names:
+                stack, names, exact = self._intensity_stack(shape)
+                if exact and lab.size == stack.size // len(names):
+                    # morphology + intensities share the bounding-box pass and the per-label scan
+                    m, it = hipops.regionprops_full(lab.reshape((1,) + shape), stack.reshape((1,) + stack.shape),
+                                                    max(k, 1))
+                    morph, inten = m.numpy()[0][:k], it.numpy()[0][:k]
+                else:
+                    morph = hipops.regionprops(lab, max(k, 1)).numpy()[0][:k]
+                    inten = hipops.regionprops_intensity(lab, stack, max(k, 1)).numpy()[0][:k]
             else:
                 morph = hipops.regionprops(lab, max(k, 1)).numpy()[0][:k]
-                inten = hipops.regionprops_intensity(lab, stack, max(k, 1)).numpy()[0][:k]
-        else:
-            morph = hipops.regionprops(lab, max(k, 1)).numpy()[0][:k]
+        ext = wext = None
+        if want_ext:
+            planes = lab.reshape((1,) + shape)
+            t, w = hipops.regionprops_ext(planes, max(k, 1), want_ext,
+                                          intensity=stack.reshape((1,) + stack.shape) if want_w else None)
+            ext = None if t is None else t.numpy()[0][:k]
+            wext = None if w is None else w.numpy()[0][:k]
         return assemble_cell_properties(morph, inten, names, list(self.property_names),
-                                        list(self.intensity_property_names))
+                                        list(self.intensity_property_names), ext=ext, wext=wext)
 
     @cached_property
     def centroids_yx(self) -> Float64Array:

@@ -260,16 +260,37 @@ class SegmentationResult:
         return out
 
 
+# extended columns (scikit-image 0.25.2 names): from the device table of amt_regionprops_ext, or on the host from the
+# area and the bounding box (area_bbox, extent, equivalent_diameter_area, as regionprops defines them)
+EXT_DEVICE_PROPERTIES = ("euler_number", "perimeter_crofton", "area_filled", "feret_diameter_max", "centroid_local",
+                         "inertia_tensor", "inertia_tensor_eigvals")
+EXT_HOST_PROPERTIES = ("area_bbox", "extent", "equivalent_diameter_area")
+WEIGHTED_PROPERTIES = ("centroid_weighted", "centroid_weighted_local")
+_INTENSITY_STATS = {"intensity_mean": 0, "intensity_max": 1, "intensity_min": 2, "intensity_std": 3}
+
+
+def ext_columns(property_names, intensity_property_names) -> list[str]:
+    """The names ``hipops.regionprops_ext`` has to compute for these property lists (weighted centroids only count
+    from the intensity list: in ``property_names`` they raise, as regionprops does without an intensity image)."""
+    want = [p for p in property_names if p in EXT_DEVICE_PROPERTIES]
+    want += [p for p in intensity_property_names if p in WEIGHTED_PROPERTIES]
+    return list(dict.fromkeys(want))
+
+
 def assemble_cell_properties(morph: np.ndarray, inten: np.ndarray | None, channel_names,
-                             property_names=None, intensity_property_names=None) -> dict[str, np.ndarray]:
+                             property_names=None, intensity_property_names=None, ext: np.ndarray | None = None,
+                             wext: np.ndarray | None = None) -> dict[str, np.ndarray]:
     """Device tables -> the dict R/masks.py:247-328 builds (same keys, same order, derived columns on the
-    host exactly as the reference derives them: circularity :292-297, volume :302-305, renames :311-314)."""
+    host exactly as the reference derives them: circularity :292-297, volume :302-305, renames :311-314).
+    ``ext`` (k, RPX_NCOLS) / ``wext`` (k, C, 4) are the tables of ``hipops.regionprops_ext`` for the extended names;
+    array-valued properties are split with ``-`` as regionprops_table splits them."""
     from .masks import DEFAULT_CELL_PROPERTY_NAMES, DEFAULT_INTENSITY_PROPERTY_NAMES
 
     property_names = list(DEFAULT_CELL_PROPERTY_NAMES if property_names is None else property_names)
     if intensity_property_names is None:
         intensity_property_names = list(DEFAULT_INTENSITY_PROPERTY_NAMES) if inten is not None else []
     col = {c: morph[:, i] for i, c in enumerate(_hip.RP_COLS)}
+    xcol = {} if ext is None else {c: ext[:, i] for i, c in enumerate(_hip.RPX_COLS)}
     k = morph.shape[0]
     needs_circ = "circularity" in property_names
     needs_vol = "volume" in property_names
@@ -295,6 +316,23 @@ def assemble_cell_properties(morph: np.ndarray, inten: np.ndarray | None, channe
                 props[f"bbox-{i}"] = col[f"bbox-{i}"].astype(np.int64)
         elif p in col:
             props[p] = col[p].copy()
+        elif p in EXT_HOST_PROPERTIES:
+            area_bbox = (col["bbox-2"] - col["bbox-0"]) * (col["bbox-3"] - col["bbox-1"])
+            if p == "area_bbox":
+                props[p] = area_bbox
+            elif p == "extent":
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    props[p] = col["area"] / area_bbox
+            else:
+                props[p] = (2 * 2 * col["area"] / np.pi) ** (1 / 2)
+        elif p in EXT_DEVICE_PROPERTIES:
+            if ext is None:
+                raise ValueError(f"property '{p}' needs the extended region-property table")
+            keys = [c for c in _hip.RPX_COLS if c == p or c.startswith(p + "-")]
+            for c in keys:
+                props[c] = xcol[c].astype(np.int64) if p == "euler_number" else xcol[c].copy()
+        elif p in WEIGHTED_PROPERTIES:
+            raise AttributeError(f"property '{p}' needs an intensity image (list it in intensity_property_names)")
         else:
             raise AttributeError(f"property '{p}' is not available on the device path")
     if needs_circ:
@@ -312,13 +350,28 @@ def assemble_cell_properties(morph: np.ndarray, inten: np.ndarray | None, channe
     if "centroid-1" in props:
         props["centroid_x"] = props.pop("centroid-1")
     if inten is not None and intensity_property_names:
-        order = {"intensity_mean": 0, "intensity_max": 1, "intensity_min": 2, "intensity_std": 3}
         for ci, name in enumerate(channel_names):
+            suffix = str(name).lower()
             for p in intensity_property_names:
-                if p not in order:
+                if p in _INTENSITY_STATS:
+                    props[f"{p}_{suffix}"] = inten[:, ci, _INTENSITY_STATS[p]].copy()
+                elif p in WEIGHTED_PROPERTIES:
+                    if wext is None:
+                        raise ValueError(f"intensity property '{p}' needs the weighted-centroid table")
+                    for i, c in enumerate(_hip.RPX_WCOLS):
+                        if c.rsplit("-", 1)[0] == p:
+                            props[f"{c}_{suffix}"] = wext[:, ci, i].copy()
+                else:
                     raise AttributeError(f"intensity property '{p}' is not available on the device path")
-                props[f"{p}_{str(name).lower()}"] = inten[:, ci, order[p]].copy()
     return props
+
+
+def cell_property_keys(channel_names, property_names=None, intensity_property_names=None) -> list[str]:
+    """The keys ``assemble_cell_properties`` gives for these lists, in order (no device needed)."""
+    C = len(channel_names)
+    return list(assemble_cell_properties(np.zeros((0, _hip.RP_NCOLS)), np.zeros((0, C, 4)) if C else None,
+                                         channel_names, property_names, intensity_property_names,
+                                         ext=np.zeros((0, _hip.RPX_NCOLS)), wext=np.zeros((0, C, 4))))
 
 
 def segment_fovs(fovs, *, ctx: Context | None = None, channel_names=DEFAULT_CHANNELS, **kw) -> SegmentationResult:

@@ -374,6 +374,49 @@ int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensi
  * two sweeps per label as np.mean / np.std make them; float64 sums, so agreement with numpy is ~1e-15 relative. */
 int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const double* intensity, int C, double* table_dev,
                                   int nplanes, int H, int W, int max_label);
+/* Extended region properties (scikit-image 0.25.2 names).  `columns` is an OR of the AMT_RPX_* bits; each bit fills
+ * its own columns of the tables below and leaves every other column as it was.
+ *   AMT_RPX_EULER_NUMBER       euler_number (8-connected objects, 2x2 configuration counts, Ohser's coefficients)
+ *   AMT_RPX_PERIMETER_CROFTON  perimeter_crofton (4 directions; same configuration counts)
+ *   AMT_RPX_AREA_FILLED        area_filled (holes = 8-connected components of "not this label" in the bounding box
+ *                              that do not touch its edge; other labels inside a hole count)
+ *   AMT_RPX_FERET_DIAMETER_MAX feret_diameter_max (from the row extents of the convex image; NaN when the row scratch
+ *                              of a plane is exceeded, as for area_convex)
+ *   AMT_RPX_CENTROID_LOCAL     centroid_local-0 / -1
+ *   AMT_RPX_INERTIA_TENSOR     inertia_tensor-0-0, -0-1, -1-0, -1-1
+ *   AMT_RPX_INERTIA_EIGVALS    inertia_tensor_eigvals-0 / -1 (descending)
+ *   AMT_RPX_CENTROID_WEIGHTED  centroid_weighted-0 / -1 and centroid_weighted_local-0 / -1 per channel
+ * table_dev = nplanes x max_label x AMT_RPX_NCOLS doubles (column order AMT_RPX_COL_*); given exactly when a bit
+ * other than AMT_RPX_CENTROID_WEIGHTED is set.  wtable_dev = nplanes x max_label x C x 4 doubles {weighted y, weighted
+ * x, weighted local y, weighted local x}, from intensity = nplanes x C planes of element type in_code (AMT_U16:
+ * integer sums, exact; AMT_F64: float64 sums); intensity, C >= 1 and wtable_dev are given exactly when
+ * AMT_RPX_CENTROID_WEIGHTED is set.  A label with zero total intensity gets NaN weighted centroids; labels absent
+ * from a plane get 0 in every column. */
+#define AMT_RPX_EULER_NUMBER (1u << 0)
+#define AMT_RPX_PERIMETER_CROFTON (1u << 1)
+#define AMT_RPX_AREA_FILLED (1u << 2)
+#define AMT_RPX_FERET_DIAMETER_MAX (1u << 3)
+#define AMT_RPX_CENTROID_LOCAL (1u << 4)
+#define AMT_RPX_INERTIA_TENSOR (1u << 5)
+#define AMT_RPX_INERTIA_EIGVALS (1u << 6)
+#define AMT_RPX_CENTROID_WEIGHTED (1u << 7)
+#define AMT_RPX_ALL 0xffu
+#define AMT_RPX_COL_EULER_NUMBER 0
+#define AMT_RPX_COL_PERIMETER_CROFTON 1
+#define AMT_RPX_COL_AREA_FILLED 2
+#define AMT_RPX_COL_FERET_DIAMETER_MAX 3
+#define AMT_RPX_COL_CENTROID_LOCAL_Y 4
+#define AMT_RPX_COL_CENTROID_LOCAL_X 5
+#define AMT_RPX_COL_INERTIA_00 6
+#define AMT_RPX_COL_INERTIA_01 7
+#define AMT_RPX_COL_INERTIA_10 8
+#define AMT_RPX_COL_INERTIA_11 9
+#define AMT_RPX_COL_EIGVAL_0 10
+#define AMT_RPX_COL_EIGVAL_1 11
+#define AMT_RPX_NCOLS 12
+int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C,
+                        int columns, double* table_dev, double* wtable_dev, int nplanes, int H, int W,
+                        int max_label);
 int amt_max_i32(amt_ctx* ctx, const int32_t* in, int32_t* max_dev, int nplanes, size_t n);
 
 /* ---- per-plate feature rows (the reference's analogue is the list of cell_properties dicts a
