@@ -77,6 +77,49 @@ def _process_mask_device(mask_image, remove_edge_cells: bool, mx=None):
     return lab, int(cnt.numpy()[0])
 
 
+def _hull_columns_of_fragmented_labels(lab, k: int, shape, morph, ext, want_feret: bool):
+    """area_convex, solidity and feret_diameter_max of a label image whose labels' bounding-box heights add up to
+    more than H * W -> (morph, ext).
+
+    The hull kernels keep one row-extent entry per bounding-box row of every label in H * W entries per plane, which
+    connected labels never exceed; the labels of an arbitrary integer image may have many pieces, and past that
+    capacity the kernels give NaN for every label of the plane.  Such images are measured again in groups of labels
+    whose heights fit, each group on a plane of its own (``hipops.keep_labels`` keeps the label values), and the
+    columns are written back.  When the heights fit, nothing is done."""
+    from . import _hip, hipops
+    from .device import get_context
+
+    c = {n: i for i, n in enumerate(_hip.RP_COLS)}
+    H, W = shape
+    heights = (morph[:, c["bbox-2"]] - morph[:, c["bbox-0"]]).astype(np.int64)
+    if k == 0 or int(heights.sum()) <= H * W:
+        return morph, ext
+    morph = morph.copy()
+    ext = None if ext is None else ext.copy()
+    groups, cur, used = [], [], 0
+    for i, h in enumerate(heights.tolist()):
+        if used + h > H * W:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += h
+    groups.append(cur)
+    ctx = get_context()
+    ac, feret = c["area_convex"], _hip.RPX_COLS.index("feret_diameter_max")
+    for g in groups:
+        keep = np.zeros((1, k + 1), np.uint8)
+        keep[0, np.asarray(g) + 1] = 1
+        plane = hipops.keep_labels(lab.reshape((1,) + tuple(shape)), ctx.asarray(keep), k)
+        morph[g, ac] = hipops.regionprops(plane, k).numpy()[0][g, ac]
+        if want_feret and ext is not None:
+            t, _ = hipops.regionprops_ext(plane, k, ["feret_diameter_max"])
+            ext[g, feret] = t.numpy()[0][g, feret]
+    area = morph[:, c["area"]]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        morph[:, c["solidity"]] = np.where(area > 0, area / morph[:, ac], 0.0)
+    return morph, ext
+
+
 def _process_mask(mask_image, remove_edge_cells: bool):
     """The reference's module-level helper (R/masks.py:38-65): host array in, int64 label image out."""
     return _process_mask_device(np.asarray(mask_image), remove_edge_cells)[0].numpy_int64()
@@ -342,7 +385,9 @@ class SegmentationMask:
         """Morphology + per-channel intensity features, one entry per cell ordered by label
         (R/masks.py:247-328; columns of scikit-image's ``regionprops_table``).  Besides the default columns, the
         extended names of ``segment.EXT_DEVICE_PROPERTIES`` / ``EXT_HOST_PROPERTIES`` (property_names) and
-        ``WEIGHTED_PROPERTIES`` (intensity_property_names) are measured too."""
+        ``WEIGHTED_PROPERTIES`` (intensity_property_names) are measured too.  Labels of several pieces whose
+        bounding-box heights add up to more than the image's pixel count get area_convex, solidity and
+        feret_diameter_max from a second pass in groups (``_hull_columns_of_fragmented_labels``), not NaN."""
         from . import hipops
         from .segment import WEIGHTED_PROPERTIES, assemble_cell_properties, ext_columns
 
@@ -384,6 +429,8 @@ class SegmentationMask:
                                           intensity=stack.reshape((1,) + stack.shape) if want_w else None)
             ext = None if t is None else t.numpy()[0][:k]
             wext = None if w is None else w.numpy()[0][:k]
+        morph, ext = _hull_columns_of_fragmented_labels(lab, k, shape, morph, ext,
+                                                        "feret_diameter_max" in want_ext)
         return assemble_cell_properties(morph, inten, names, list(self.property_names),
                                         list(self.intensity_property_names), ext=ext, wext=wext)
 

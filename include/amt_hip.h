@@ -381,7 +381,9 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
  *   AMT_RPX_AREA_FILLED        area_filled (holes = 8-connected components of "not this label" in the bounding box
  *                              that do not touch its edge; other labels inside a hole count)
  *   AMT_RPX_FERET_DIAMETER_MAX feret_diameter_max (from the row extents of the convex image; NaN when the row scratch
- *                              of a plane is exceeded, as for area_convex)
+ *                              of a plane is exceeded, as for area_convex: the labels' bounding-box heights add up to
+ *                              more than H * W, which only labels of several pieces reach.  SegmentationMask measures
+ *                              such planes again in groups of labels whose heights fit)
  *   AMT_RPX_CENTROID_LOCAL     centroid_local-0 / -1
  *   AMT_RPX_INERTIA_TENSOR     inertia_tensor-0-0, -0-1, -1-0, -1-1
  *   AMT_RPX_INERTIA_EIGVALS    inertia_tensor_eigvals-0 / -1 (descending)

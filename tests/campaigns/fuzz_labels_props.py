@@ -1,7 +1,9 @@
 """Randomised differential test of labelling (4 / 8-connected, masks and integer images), clear_border, relabel_sequential
 and the region-property tables (morphology + intensities) against the oracle, on random images whose components range
 from single pixels to blobs spanning many 64 x 64 tiles, thin diagonal structures, rings with holes, labels that touch
-the frame.   usage: python tests/campaigns/fuzz_labels_props.py [cases] [seed]"""
+the frame.  Every case also measures the extended columns (amt_regionprops_ext), and a fragmented integer label image
+(labels of scattered pieces, bounding-box heights past H * W) goes through SegmentationMask.cell_properties with every
+extended and weighted name.   usage: python tests/campaigns/fuzz_labels_props.py [cases] [seed]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
@@ -10,6 +12,11 @@ from arcadia_microscopy_tools_amd import _hip, hipops
 from arcadia_microscopy_tools_amd.device import get_context
 from oracle import regionprops as orp
 from oracle import skops
+from arcadia_microscopy_tools_amd.channels import DAPI
+from arcadia_microscopy_tools_amd.masks import SegmentationMask
+
+EXT = ("euler_number", "perimeter_crofton", "area_filled", "feret_diameter_max", "centroid_local", "inertia_tensor",
+       "inertia_tensor_eigvals")
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -73,6 +80,38 @@ for case in range(ncases):
             ok &= np.allclose(it[:, c, 0], ri["intensity_mean"], rtol=1e-12)
             ok &= np.array_equal(it[:, c, 1], ri["intensity_max"]) and np.array_equal(it[:, c, 2], ri["intensity_min"])
             ok &= np.allclose(it[:, c, 3], ri["intensity_std"], rtol=1e-9, atol=1e-9)
+        # extended columns of the same labels
+        names = list(_hip.RPX_BITS)
+        tx, wx = hipops.regionprops_ext(ctx.asarray(lab8[None]), K, names, intensity=ctx.asarray(chans[None, :1]))
+        tx, wx = tx.numpy()[0], wx.numpy()[0]
+        rx = orp.regionprops_table(lab8, chans[0], ("label",) + EXT + orp.WEIGHTED_PROPS)
+        for i, c in enumerate(_hip.RPX_COLS):
+            if c.startswith(("euler", "area_filled", "feret", "centroid_local")):
+                ok &= np.array_equal(tx[:, i], rx[c])
+            else:
+                ok &= np.allclose(tx[:, i], rx[c], rtol=1e-12, atol=1e-12 * max(1.0, np.abs(rx[c]).max()))
+        for i, c in enumerate(_hip.RPX_WCOLS):
+            ok &= np.allclose(wx[:, 0, i], rx[c], rtol=1e-15, equal_nan=True)
+    # fragmented integer labels: scattered pieces whose bounding-box heights add up to more than H * W
+    h, w = int(rng.integers(16, 80)), int(rng.integers(16, 80))
+    k = int(rng.integers(w + 1, 3 * w))
+    frag = rng.integers(0, k + 1, (h, w))
+    frag[rng.random((h, w)) < rng.uniform(0.0, 0.5)] = 0
+    if frag.max() > 0:
+        inten = rng.integers(0, 65536, (h, w)).astype(np.uint16)
+        props = ["label", "area", "area_convex", "solidity"] + list(EXT)
+        sm = SegmentationMask(frag, {DAPI: inten}, remove_edge_cells=False, property_names=props,
+                              intensity_property_names=list(orp.WEIGHTED_PROPS))
+        fl = skops.relabel_sequential(frag)
+        rf = orp.cell_properties(fl, {"DAPI": inten}, props, list(orp.WEIGHTED_PROPS))
+        got = sm.cell_properties
+        ok &= list(got) == list(rf)
+        for c in rf:
+            if c.startswith(("label", "area", "euler", "feret", "centroid_local", "solidity", "extent")):
+                ok &= np.array_equal(got[c], rf[c], equal_nan=True)
+            else:
+                ok &= np.allclose(got[c], rf[c], rtol=1e-12, atol=1e-12 * max(1.0, np.nanmax(np.abs(rf[c]))),
+                                  equal_nan=True)
     print(case, (H, W), "kind", kind, "labels", K, "ok", bool(ok), flush=True)
     bad += not ok
 print("BAD", bad)
