@@ -147,6 +147,8 @@ _SIGS = {
     "amt_cellpose_flow_error": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_fill_holes_remove_small": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int]),
     "amt_overlay": (c_int, [_P, _P, _P, c_int, _P, _P, _P, _P, c_int, c_int]),
+    "amt_normalize_planes_f32": (c_int, [_P, _P, c_int, _P, c_int, c_int, _P, c_int, c_size_t]),
+    "amt_convert_f32_f64": (c_int, [_P, _P, _P, c_size_t]),
 }
 
 _lib = None

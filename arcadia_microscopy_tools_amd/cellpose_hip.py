@@ -13,6 +13,8 @@ PyTorch is plumbing here (device memory, the conv stack on MFMA); the post-proce
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 from . import _hip, hipops
@@ -217,15 +219,140 @@ def tiled_forward(net, x, batch_size: int = 8, bsize: int = 256, tile_overlap: f
     return out / navg
 
 
-_EVAL_KWARGS = ("min_size", "max_size_fraction", "bsize", "tile_overlap", "fill_holes", "max_seeds")
+_EVAL_KWARGS = ("min_size", "max_size_fraction", "bsize", "tile_overlap", "fill_holes", "max_seeds", "normalize",
+                "invert")
+
+# the keys of CellposeModel.eval's ``normalize=`` dict with cellpose 4.0.x's defaults (models.normalize_default;
+# ``percentile`` None = (1.0, 99.0))
+_NORMALIZE_DEFAULTS = {"normalize": True, "lowhigh": None, "percentile": None, "invert": False, "norm3D": True,
+                       "sharpen_radius": 0, "smooth_radius": 0, "tile_norm_blocksize": 0, "tile_norm_smooth3D": 1}
+_NORMALIZE_REFUSED = ("sharpen_radius", "smooth_radius", "tile_norm_blocksize")  # implemented nowhere on this route
+NORMALIZE_MIN_RANGE = np.float32(1e-3)  # normalize99 leaves a channel at zero unless hi - lo exceeds this
+
+
+class NormalizePlan(NamedTuple):
+    """What ``resolve_normalize`` makes of ``normalize=`` / ``invert=``: exactly one of ``percentile`` (lower, upper)
+    and ``lowhigh`` ((channels, 2) float32) is set."""
+
+    percentile: tuple[float, float] | None
+    lowhigh: np.ndarray | None
+    invert: bool
+
+
+def resolve_normalize(normalize, invert, channels: int) -> NormalizePlan | None:
+    """The ``normalize=`` / ``invert=`` options of ``CellposeModel.eval`` for an image of ``channels`` channels -> a
+    ``NormalizePlan``, or None when the image goes to the network as it is (pure host code).
+
+    Restated from cellpose 4.0.x (``models.CellposeModel.eval`` / ``transforms.normalize_img``; the package is not
+    importable here: **parity unpinned**).  ``normalize`` is False / None, True (= the defaults) or a dict with the keys
+    ``normalize``, ``lowhigh``, ``percentile``, ``invert``, ``norm3D``, ``sharpen_radius``, ``smooth_radius``,
+    ``tile_norm_blocksize``, ``tile_norm_smooth3D``; ``invert`` is ORed with the dict's.  An option is implemented or
+    refused, never ignored: an unknown key raises ``ValueError``, a non-zero ``sharpen_radius`` / ``smooth_radius`` /
+    ``tile_norm_blocksize`` ``TypeError``; ``norm3D`` and ``tile_norm_smooth3D`` have no effect on a 2-D image."""
+    inv = bool(invert)
+    if normalize is None:
+        normalize = False
+    if isinstance(normalize, (bool, np.bool_)):
+        params = dict(_NORMALIZE_DEFAULTS, normalize=bool(normalize))
+    elif isinstance(normalize, dict):
+        unknown = sorted(set(normalize) - set(_NORMALIZE_DEFAULTS), key=str)
+        if unknown:
+            raise ValueError(f"normalize: unknown key(s) {unknown}; recognised: {list(_NORMALIZE_DEFAULTS)}")
+        params = {**_NORMALIZE_DEFAULTS, **normalize}
+    else:
+        raise ValueError(f"normalize must be a bool or a dict, got {type(normalize).__name__}")
+    for key in _NORMALIZE_REFUSED:
+        if params[key]:
+            raise TypeError(f"normalize: '{key}' = {params[key]!r} is not implemented on the network + HIP route "
+                            "(only 0 is accepted)")
+    inv = inv or bool(params["invert"])
+    if not params["normalize"]:
+        if inv:
+            raise ValueError("invert needs normalize: 1 - x of un-normalised intensities is meaningless")
+        return None
+    lowhigh, percentile = params["lowhigh"], params["percentile"]
+    if lowhigh is not None and percentile is not None:
+        raise ValueError("normalize: 'lowhigh' and 'percentile' exclude each other")
+    if lowhigh is not None:
+        try:
+            lh = np.asarray(lowhigh, dtype=np.float32)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"normalize: 'lowhigh' must hold numbers ({e})") from e
+        if lh.shape == (2,):
+            lh = np.broadcast_to(lh, (int(channels), 2))
+        if lh.shape != (int(channels), 2):
+            raise ValueError(f"normalize: 'lowhigh' must be one (low, high) pair or one pair per channel, shape "
+                             f"({channels}, 2); got shape {np.shape(lowhigh)}")
+        lh = np.ascontiguousarray(lh)
+        if not np.all(lh[:, 1] - lh[:, 0] > NORMALIZE_MIN_RANGE):
+            raise ValueError(f"normalize: 'lowhigh' needs high - low > 1e-3 for every channel, got {lh.tolist()}")
+        return NormalizePlan(None, lh, inv)
+    if percentile is None:
+        percentile = (1.0, 99.0)
+    try:
+        lower, upper = (float(v) for v in percentile)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"normalize: 'percentile' must be a (lower, upper) pair, got {percentile!r}") from e
+    if not (0 <= lower < upper <= 100):
+        raise ValueError(f"normalize: 'percentile' must satisfy 0 <= lower < upper <= 100, got {percentile!r}")
+    return NormalizePlan((lower, upper), None, inv)
+
+
+def normalize_image(image: np.ndarray, plan: NormalizePlan, ctx: Context | None = None, device=None):
+    """``([C], H, W)`` image -> the float32 ``(C, H, W)`` CUDA tensor ``CellposeModel.eval`` would hand its network
+    (cellpose 4.0.x ``normalize_img`` / ``normalize99``, restated; **parity unpinned**), computed on the device from the
+    image in the dtype the caller holds.  Per channel, independently:
+
+    1. ``x32`` = the samples as float32 (uint8 / uint16 / float32 exact; float64 and other integers rounded once);
+    2. ``lo, hi`` = the plan's ``lowhigh`` pair, or ``np.percentile(x32.astype(np.float64), p)`` for the plan's two
+       percentiles (exact order statistics, linear interpolation in float64), each rounded once to float32;
+    3. ``y = (x32 - lo) / (hi - lo)`` (float32: a subtraction, then a division by the float32 difference) if
+       ``hi - lo > 1e-3``, else 0 for the whole channel;
+    4. ``invert``: ``y = 1 - y``.
+
+    The image is uploaded once (uint16 travels as 2 bytes per sample; uint8 is widened to it on the host, float64 and
+    other integers are rounded to float32 there), the percentiles of all channels come from one launch of the
+    order-statistics kernels and stay on the device, ``hipops.normalize_planes`` rounds them and writes the tensor.
+    Everything runs on ``ctx``'s stream, which is ordered behind torch's current stream before the tensor is written
+    and in front of it afterwards (the stream rule); the host waits only for its own upload."""
+    torch = _torch()
+    ctx = ctx or get_context()
+    a = np.asarray(image)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError(f"expected an image of shape ([channel], height, width), got {np.shape(image)}")
+    if a.dtype == np.uint8:
+        a = a.astype(np.uint16)  # exact; the order-statistics kernels take uint16
+    elif a.dtype not in (np.uint16, np.float32):
+        a = a.astype(np.float32)
+    C, H, W = a.shape
+    if plan.lowhigh is not None and plan.lowhigh.shape != (C, 2):
+        raise ValueError(f"the plan holds {len(plan.lowhigh)} (low, high) pairs, the image has {C} channel(s)")
+    device = torch.device("cuda", ctx.device) if device is None else torch.device(device)
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    if device.type != "cuda" or index != ctx.device:
+        raise ValueError(f"the context runs on GPU {ctx.device}, the tensor was asked for on {device}")
+    d = ctx.asarray(np.ascontiguousarray(a))
+    if plan.lowhigh is not None:
+        lohi = ctx.asarray(plan.lowhigh)
+    else:
+        lohi = hipops.percentile(d if d.dtype == np.uint16 else hipops.to_float64(d), plan.percentile)
+    y = torch.empty((C, H, W), dtype=torch.float32, device=device)
+    cur = torch.cuda.current_stream(y.device)
+    side = torch.cuda.ExternalStream(ctx.stream_ptr, device=y.device)
+    side.wait_stream(cur)  # torch may have handed out a block that work queued on its stream still uses
+    hipops.normalize_planes(d, lohi, invert=plan.invert, out=tensor_as_device_array(y, ctx))
+    cur.wait_stream(side)  # the network reads y on torch's stream
+    return y
 
 
 def segment_image(net, image: np.ndarray, device, compute_dtype, *, cellprob_threshold=0.0, niter=None, batch_size=8,
                   flow_threshold=0.4, diameter=30.0, ctx: Context | None = None, min_size: int = 15,
                   max_size_fraction: float = 0.4, bsize: int = 256, tile_overlap: float = 0.1, fill_holes: bool = True,
-                  max_seeds: int = 16384) -> np.ndarray:
-    """One ``([C], H, W)`` image -> int64 labels through ``net`` + the HIP post-processing, with the parameters
-    ``CellposeModel.eval`` takes from the reference (R/model.py:206-215) doing what they do there:
+                  max_seeds: int = 16384, normalize=False, invert: bool = False) -> np.ndarray:
+    """One ``([C], H, W)`` image -> int64 labels through ``net`` + the HIP post-processing.  The parameters the
+    reference hands to ``CellposeModel.eval`` (R/model.py:206-215) act as they do there:
 
     * ``diameter``: the image is resized by 30 / diameter (bilinear) before the network and the flows are resized back
       to the image's size before the masks are computed (30 = no resizing);
@@ -233,16 +360,31 @@ def segment_image(net, image: np.ndarray, device, compute_dtype, *, cellprob_thr
     * ``flow_threshold``: the flow-error filter (0 / None switches it off), ``cellprob_threshold``, ``niter`` (None / 0 =
       200), ``min_size`` (with the hole filling of ``fill_holes_and_remove_small_masks``), ``max_size_fraction``.
 
+    **One difference from ``eval``: the image is NOT normalised unless asked.**  ``eval`` defaults to
+    ``normalize=True`` (every channel mapped so that its 1st percentile is 0 and its 99th is 1); this route defaults to
+    ``normalize=False`` and gives the network the caller's intensities as float32, because callers and tests of the
+    route's earlier versions feed it networks that decode raw values.  A network trained by Cellpose expects
+    normalised input: pass ``normalize=True`` with such a checkpoint.  ``normalize=`` (True, or eval's dict:
+    ``lowhigh``, ``percentile``, ``invert``, ...) and ``invert=`` are resolved by ``resolve_normalize`` and computed on
+    the device by ``normalize_image``, at full resolution before the resize, as Cellpose does; tile normalisation,
+    sharpening and smoothing are refused, as is every ``eval`` option not named in ``_EVAL_KWARGS`` (restated from
+    cellpose 4.0.x, parity unpinned).
+
     Tiles smaller than 16 pixels per side cannot pass the four poolings of a U-Net; the (resized) image is padded to a
     multiple of 16 by edge replication and the flows cropped back."""
     torch = _torch()
-    a = np.asarray(image, dtype=np.float32)
-    if a.ndim == 2:
-        a = a[None]
-    if a.ndim != 3:
-        raise ValueError(f"expected an image of shape ([channel], height, width), got {np.shape(image)}")
-    C, H, W = a.shape
-    x = torch.from_numpy(np.ascontiguousarray(a)).to(device=device)
+    shape = np.shape(image)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"expected an image of shape ([channel], height, width), got {shape}")
+    plan = resolve_normalize(normalize, invert, 1 if len(shape) == 2 else shape[0])
+    if plan is None:
+        a = np.asarray(image, dtype=np.float32)
+        if a.ndim == 2:
+            a = a[None]
+        x = torch.from_numpy(np.ascontiguousarray(a)).to(device=device)
+    else:
+        x = normalize_image(image, plan, ctx, device)
+    C, H, W = x.shape
     rescale = 30.0 / float(diameter)
     Hr, Wr = (H, W) if rescale == 1.0 else (max(1, int(H * rescale)), max(1, int(W * rescale)))
     F = torch.nn.functional

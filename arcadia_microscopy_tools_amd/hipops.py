@@ -238,11 +238,43 @@ def uniform_filter(a: DeviceArray, size: int, mode: str = "reflect", cval: float
 
 
 def to_float64(a: DeviceArray, scale: float = 1.0, out=None) -> DeviceArray:
-    """uint16 -> float64 (``x * scale``; ``img_as_float`` uses 1/65535, SK/util/dtype.py:319)."""
+    """uint16 -> float64 (``x * scale``; ``img_as_float`` uses 1/65535, SK/util/dtype.py:319), or float32 -> float64
+    (exact; no scale)."""
+    if a.dtype == np.float32:
+        if scale != 1.0:
+            raise ValueError("to_float64 of a float32 array takes no scale")
+        o = _out(a.ctx, out, a.shape, np.float64)
+        _hip.check(_lib().amt_convert_f32_f64(a.ctx.handle, a.ptr, o.ptr, a.size), "amt_convert_f32_f64")
+        return o
     if a.dtype != np.uint16:
-        raise TypeError("to_float64 expects uint16")
+        raise TypeError("to_float64 expects uint16 or float32")
     o = _out(a.ctx, out, a.shape, np.float64)
     _hip.check(_lib().amt_convert_u16_f64(a.ctx.handle, a.ptr, float(scale), o.ptr, a.size), "amt_convert_u16_f64")
+    return o
+
+
+def normalize_planes(planes: DeviceArray, lohi: DeviceArray, invert: bool = False,
+                     out: DeviceArray | None = None) -> DeviceArray:
+    """``CellposeModel.eval``'s image normalisation per plane (R/model.py:206-215; cellpose 4.0.x ``normalize99``,
+    restated, parity unpinned): with ``lo, hi = float32(lohi[plane])`` and ``d = hi - lo``, ``(x - lo) / d`` in float32
+    (one subtraction, one correctly rounded division) where ``d > 1e-3`` and 0 for the whole plane otherwise;
+    ``invert``: 1 minus that.  ``planes``: uint16, float32 or float64 (rounded once to float32), last two axes (Y, X);
+    ``lohi``: one (lo, hi) pair per plane on the device, float64 (``percentile``'s output as it is) or float32.
+    Returns float32 of ``planes``' shape."""
+    ctx = planes.ctx
+    n, H, W = _planes(planes)
+    if planes.dtype not in (np.uint16, np.float32, np.float64):
+        raise TypeError(f"normalize_planes accepts uint16, float32 or float64 planes, got {planes.dtype}")
+    if lohi.dtype not in (np.float32, np.float64):
+        raise TypeError(f"normalize_planes: lohi must be float32 or float64, got {lohi.dtype}")
+    if lohi.size != 2 * n:
+        raise ValueError(f"normalize_planes: lohi has shape {lohi.shape}, need one (lo, hi) pair for each of {n} planes")
+    if lohi.ctx is not ctx:
+        raise ValueError("lohi belongs to another context than the planes; bind it with DeviceArray.on(ctx)")
+    o = _out(ctx, out, planes.shape, np.float32)
+    codes = {np.dtype(np.uint16): _hip.U16, np.dtype(np.float32): _hip.F32, np.dtype(np.float64): _hip.F64}
+    _hip.check(_lib().amt_normalize_planes_f32(ctx.handle, planes.ptr, codes[planes.dtype], lohi.ptr, codes[lohi.dtype],
+                                               1 if invert else 0, o.ptr, n, H * W), "amt_normalize_planes_f32")
     return o
 
 

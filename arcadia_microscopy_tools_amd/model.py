@@ -21,7 +21,9 @@ cellpose package it fails loudly (``RuntimeError: Failed to load Cellpose model`
       through PyTorch-ROCm and its output goes through the HIP flow -> mask post-processing
       (``cellpose_hip.segment_image``: diameter rescaling, tiled forward in batches of ``batch_size``, flow following,
       flow-error filter at ``flow_threshold``, size filters and hole filling; restated from the published algorithm,
-      parity unpinned); with neither, ``RuntimeError`` as before.
+      parity unpinned); with neither, ``RuntimeError`` as before.  Unlike ``CellposeModel.eval``, this route does NOT
+      normalise the image by default: ``segment(img, normalize=True)`` (or eval's ``normalize=`` dict, ``invert=``)
+      asks for it, computed on the GPU -- a checkpoint trained by Cellpose needs it.
   backend="cellpose-hip": always the ``network=`` + HIP post-processing route (``network="standin"`` builds the
       random-weight architectural stand-in of ``cellpose_hip.make_standin`` -- for throughput measurements only,
       its masks mean nothing).
@@ -169,8 +171,13 @@ class SegmentationModel:
     def _segment_network(self, intensities: np.ndarray, params: CellposeParams, cellpose_kwargs=None) -> Int64Array:
         """Every parameter of R/model.py:171-215 reaches the route and acts there (``cellpose_hip.segment_image``):
         ``diameter`` resizes around the network, ``batch_size`` is the tile batch, ``flow_threshold`` the flow-error
-        filter.  Extra ``**cellpose_kwargs`` are the post-processing / tiling options of ``CellposeModel.eval`` this
-        route implements; any other name is refused (never ignored)."""
+        filter.  Extra ``**cellpose_kwargs`` are the options of ``CellposeModel.eval`` this route implements
+        (``cellpose_hip._EVAL_KWARGS``): post-processing and tiling, and ``normalize=`` / ``invert=``, eval's image
+        normalisation (1st / 99th percentile of every channel to 0 / 1, or ``lowhigh`` / ``percentile`` of its dict form;
+        tile normalisation, sharpening and smoothing are refused).  The one deliberate difference from ``eval``:
+        normalisation is OFF unless asked for -- a call that names neither option hands the network the raw
+        intensities as float32, as this route always did, and a Cellpose-trained checkpoint needs ``normalize=True``.
+        Any other option name is refused (never ignored)."""
         from . import cellpose_hip
 
         kw = dict(cellpose_kwargs or {})

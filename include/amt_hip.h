@@ -515,6 +515,21 @@ int amt_nn_affine_act_bf16(amt_ctx* ctx, const void* x, const void* y, const flo
                            const float* scale, const float* shift, void* out, void* sum_out, int N, int H, int W, int C,
                            int relu, int upsample);
 
+/* ---- image normalisation of CellposeModel.eval (R/model.py:206-215 calls eval, whose `normalize=` / `invert=` options
+ * map every channel of the image before the network sees it; restated from cellpose 4.0.x transforms.normalize_img /
+ * normalize99, PARITY UNPINNED; caller: cellpose_hip.normalize_image) ----
+ * Per plane, float32 arithmetic, one correctly rounded operation each:
+ *   lo, hi = lohi_dev[plane] = {lo, hi} rounded to float32;  d = hi - lo;
+ *   out = d > 1e-3f ? (x - lo) / d : 0;   invert != 0: out = 1 - out
+ * in = nplanes x n samples, AMT_U16 / AMT_F32 (exact as float32) or AMT_F64 (rounded once to float32); lohi_dev =
+ * nplanes x 2 values on the device, AMT_F64 (the percentiles as amt_percentile_u16 / amt_percentile_f64 leave them: no
+ * host round trip between them and this call) or AMT_F32; out = nplanes x n float32, not aliasing in.  At most 65,535
+ * planes per call.  16-byte loads and stores when in and out are 16-byte aligned (any n). */
+int amt_normalize_planes_f32(amt_ctx* ctx, const void* in, int in_dtype, const void* lohi_dev, int lohi_dtype, int invert,
+                             float* out, int nplanes, size_t n);
+/* float32 -> float64 (exact): the way of a float32 image into amt_percentile_f64 (cellpose_hip.normalize_image). */
+int amt_convert_f32_f64(amt_ctx* ctx, const float* in, double* out, size_t n);
+
 #ifdef __cplusplus
 }
 #endif
