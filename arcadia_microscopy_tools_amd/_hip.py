@@ -115,7 +115,7 @@ _SIGS = {
     "amt_rank_filter": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_double, _P]),
     "amt_gaussian_otsu_codes_supported": (c_int, [c_int, c_int, c_int, c_int, c_size_t]),
     "amt_gaussian_otsu_codes": (c_int, [_P, _P, c_double, c_int, c_int, c_int, _P, c_int, c_int, c_size_t, _P, _P, _P, _P,
-                                        _P]),
+                                        _P, _P]),
     "amt_subtract": (c_int, [_P, _P, _P, _P, c_int, c_size_t]),
     "amt_label": (c_int, [_P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_label_mask": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int]),

@@ -180,3 +180,23 @@ def li_from_hist(counts, values, tolerance=None, initial_guess=None, wrap_dtype=
             mean_fore = np.float64(total_sum - s_le) / np.float64(total_cnt - c_le)
             t_next = (mean_back - mean_fore) / (np.log(mean_back) - np.log(mean_fore))
     return t_next + image_min
+
+
+def prefix_rule(v: np.ndarray, vmin: float, vmax: float, nbins: int = 256):
+    """Host model of the rule by which the device derives np.histogram bins and codes from the UPPER 32 BITS of
+    non-negative float64 samples (csrc/amt_filters.hip, prefix_codes_kernel): with vlo / vhi the smallest / largest
+    double that shares a sample's upper half, the bin is that of vlo unless vhi reaches the next edge, and
+    ``v > centre`` is ``vlo > centre`` unless only vhi is above the centre.  Returns ``(bins, above, undecided)``:
+    the bin of vlo, ``vlo > centre of that bin`` and the mask of samples the 32 bits leave open (the device
+    recomputes those exactly)."""
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if (v < 0).any():
+        raise ValueError("the prefix order holds for non-negative samples only")
+    hi32 = v.view(np.uint64) >> np.uint64(32) << np.uint64(32)
+    vlo, vhi = hi32.view(np.float64), (hi32 | np.uint64(0xFFFFFFFF)).view(np.float64)
+    edges = np.linspace(vmin, vmax, nbins + 1)
+    bins = np.clip(np.searchsorted(edges, vlo, side="right") - 1, 0, nbins - 1)
+    centres = (edges[:-1] + edges[1:]) / 2.0
+    above = vlo > centres[bins]
+    undecided = ((bins < nbins - 1) & (vhi >= edges[bins + 1])) | (~above & (vhi > centres[bins]))
+    return bins, above, undecided

@@ -484,6 +484,29 @@ __global__ void __launch_bounds__(256) gauss_fused_kernel(const TIn* __restrict_
     }
 }
 
+// One output of scipy's correlate1d with a symmetric kernel: x[c] w[c] + sum_{j = r..1} (x[c-j] + x[c+j]) w[c-j].  `x`
+// points at the CENTRE sample, w[j] is the weight at distance j.  gauss_lds_kernel (both axes of the tile) and
+// prefix_fixup_kernel (one sample recomputed on its own) share this source, so they round alike.
+template <int R>
+__device__ __forceinline__ double gauss_taps(const double* x, const double (&w)[R + 1]) {
+    double acc = x[0] * w[0];
+#pragma unroll
+    for (int j = R; j >= 1; --j) acc += (x[-j] + x[j]) * w[j];
+    return acc;
+}
+
+// The axis-0 result at (y, column xc) of one uint16 plane, bit for bit what gauss_lds_kernel hands to its horizontal
+// pass: the same conversion and the same boundary mapping of rows and columns (modes nearest / reflect / mirror).
+template <int R>
+__device__ __forceinline__ double gauss_column(const uint16_t* __restrict__ src, double scale, int H, int W, int mode,
+                                               int y, int xc, const double (&w)[R + 1]) {
+    const int xm = amt_map_index(xc, W, mode);
+    double win[2 * R + 1];
+#pragma unroll
+    for (int k = 0; k <= 2 * R; ++k) win[k] = (double)src[(size_t)amt_map_index(y - R + k, H, mode) * W + xm] * scale;
+    return gauss_taps<R>(&win[R], w);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The same fused Gaussian for uint16 input with the INPUT side decoupled from the waves' registers: the raw
 // uint16 rows of the block's 256 columns go straight from HBM into an LDS ring with `global_load_lds_dwordx4`
@@ -503,18 +526,27 @@ __global__ void __launch_bounds__(256) gauss_fused_kernel(const TIn* __restrict_
 //      2 b + (sample > centre of bin b) stored: for the Otsu threshold t = centre of bin k,
 //      sample > t  <=>  code > 2 k  (a sample of a bin above k is >= its lower edge > centre_k, one of a bin below is
 //      < centre_k, and inside bin k the low bit IS the comparison), so the mask chain continues from 2 bytes per pixel.
+//      `redo` (nullable): per-plane counts of prefix_codes_kernel -- only planes whose count exceeds PFX_CAP are done;
+//   3  fold min / max into `keys` and store the UPPER 32 BITS of every sample (`prefix`, one 16-byte store per lane):
+//      the single Gaussian pass of amt_gaussian_otsu_codes with a prefix plane (prefix_codes_kernel continues).
 constexpr int GL_NBINS = 256;
+constexpr uint32_t PFX_CAP = 8192;  // undecided samples listed per plane (see prefix_codes_kernel)
+constexpr int PFX_CNT_STRIDE = 32;   // words between the planes' counters: one 128-byte line each, so that the appends
+                                     // of different planes do not meet in one memory channel
 template <int R, int EPI>
 __global__ void __launch_bounds__(256) gauss_lds_kernel(const uint16_t* __restrict__ in, double scale,
                                                         double* __restrict__ out, int H, int W,
                                                         const double* __restrict__ wts, int mode, size_t in_stride,
                                                         int TH, unsigned long long* __restrict__ keys,
                                                         const double* __restrict__ minmax, uint32_t* __restrict__ hist,
-                                                        uint16_t* __restrict__ codes) {
+                                                        uint16_t* __restrict__ codes, uint32_t* __restrict__ prefix,
+                                                        const uint32_t* __restrict__ redo) {
+    if (EPI == 2 && redo && redo[(size_t)blockIdx.z * PFX_CNT_STRIDE] <= PFX_CAP) return;  // this plane's codes are already exact
     constexpr int K = 2 * R + 1;
     constexpr int RP = (R + 7) & ~7;
     constexpr int OUTW = 256 - 2 * RP;
     constexpr int NSEG = OUTW / 4;
+    constexpr int NST = EPI == 0 ? 2 : (EPI == 1 ? 0 : 1);  // store instructions of a wave per row group
     constexpr int RING = 16;  // raw rows: four groups of four
     // ONE LDS object, carved by hand: with several __shared__ arrays the compiler cannot tell the LDS-DMA writes into
     // the ring from reads of the other arrays and drains the ring (vmcnt(0)) in front of every LDS read
@@ -584,23 +616,19 @@ __global__ void __launch_bounds__(256) gauss_lds_kernel(const uint16_t* __restri
         for (int i = 0; i < 4; ++i) win[K - 1 + i] = (double)raw[(rg + i) & (RING - 1)][ti] * scale;
         const int buf = g & 1;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            double acc = win[R + i] * w[0];
-#pragma unroll
-            for (int j = R; j >= 1; --j) acc += (win[R + i - j] + win[R + i + j]) * w[j];
-            rowbuf[buf][i][t] = acc;
-        }
+        for (int i = 0; i < 4; ++i) rowbuf[buf][i][t] = gauss_taps<R>(&win[R + i], w);
         // Group g + 1 must have landed before the barrier that publishes it.  The vector-memory counter retires in
         // order, so a loader wave may leave outstanding exactly what it issued AFTER that load: the loads of groups
-        // g+2 and g+3 and the two 16-byte stores of each of the groups g-2 and g-1 (waves 0 and 1 always own a row of a
-        // full group).  Near the end of the block, where fewer loads are issued, it simply drains.
+        // g+2 and g+3 and the NST stores of each of the groups g-2 and g-1 (two 16-byte stores of doubles, one store of
+        // prefixes or codes, none when only min / max are folded; waves 0 and 1 always own a row of a full group).
+        // Near the end of the block, where fewer loads are issued, it simply drains.
         if (wave < 2) {
             if (g + 3 >= ngroups)
                 __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
             else if (g >= 2)
-                __builtin_amdgcn_s_waitcnt(0x0F76);  // vmcnt(6)
+                __builtin_amdgcn_s_waitcnt(0x0F70 | (2 + 2 * NST));  // vmcnt(6) when the doubles are stored
             else if (g == 1)
-                __builtin_amdgcn_s_waitcnt(0x0F74);  // vmcnt(4)
+                __builtin_amdgcn_s_waitcnt(0x0F70 | (2 + NST));
             else
                 __builtin_amdgcn_s_waitcnt(0x0F72);  // vmcnt(2)
         }
@@ -613,12 +641,7 @@ __global__ void __launch_bounds__(256) gauss_lds_kernel(const uint16_t* __restri
             for (int i = 0; i < 2 * R + 4; ++i) c[i] = c0[i];
             double a[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                double a2 = c[i + R] * w[0];
-#pragma unroll
-                for (int j = R; j >= 1; --j) a2 += (c[i + R - j] + c[i + R + j]) * w[j];
-                a[i] = a2;
-            }
+            for (int i = 0; i < 4; ++i) a[i] = gauss_taps<R>(&c[i + R], w);
             // W and the tile origin are multiples of 8: the four outputs are inside the image together or not at
             // all, and the destination is 16-byte aligned -> exactly two store instructions per row
             if (EPI == 0) {
@@ -628,7 +651,12 @@ __global__ void __launch_bounds__(256) gauss_lds_kernel(const uint16_t* __restri
                     reinterpret_cast<double2*>(dst)[1] = make_double2(a[2], a[3]);
                 }
             }
-            if (EPI <= 1 && keys && xo < W) {
+            if (EPI == 3 && xo < W) {
+                uint32_t* pdst = prefix + plane + (size_t)(y0 + rg + q) * W + xo;
+                *reinterpret_cast<uint4*>(pdst) = make_uint4((unsigned)__double2hiint(a[0]), (unsigned)__double2hiint(a[1]),
+                                                             (unsigned)__double2hiint(a[2]), (unsigned)__double2hiint(a[3]));
+            }
+            if ((EPI <= 1 || EPI == 3) && keys && xo < W) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     vlo = vmin_f64(vlo, a[i]);
@@ -692,7 +720,7 @@ __global__ void __launch_bounds__(256) gauss_lds_kernel(const uint16_t* __restri
 #pragma unroll
         for (int k = 0; k < K - 1; ++k) win[k] = win[k + 4];
     }
-    if (EPI <= 1 && keys) {
+    if ((EPI <= 1 || EPI == 3) && keys) {
         unsigned long long klo = amt_f64_key(vlo), khi = amt_f64_key(vhi);
         if (vlo > vhi) {
             klo = ~0ull;
@@ -736,7 +764,7 @@ static int launch_fused(amt_ctx* ctx, const TIn* in, double scale, double* out, 
             dim3 grid2(gx2, (H + TH2 - 1) / TH2, nplanes);
             hipLaunchKernelGGL((gauss_lds_kernel<R, 0>), grid2, dim3(256), 0, ctx->stream, (const uint16_t*)in, scale, out,
                                H, W, wdev, mode, in_stride, TH2, keys, (const double*)nullptr, (uint32_t*)nullptr,
-                               (uint16_t*)nullptr);
+                               (uint16_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr);
             AMT_LAUNCH_CHECK();
             return AMT_OK;
         }
@@ -1096,14 +1124,190 @@ extern "C" int amt_gaussian(amt_ctx* ctx, const void* in, int in_dtype, double s
 
 // ---- Gaussian -> Otsu without the float64 plane (the mask chain of BASELINE configs[1] / [2]) ------------------------
 // R/ callers: ski.filters.gaussian -> ski.filters.threshold_otsu -> `>` (SURVEY.md A.7/A.8 recipes through
-// R/pipeline.py:25-45).  Two passes of the fused uint16 Gaussian over the input: the first folds min / max, the second
-// recomputes the samples, counts np.histogram's 256 bins and stores 2-byte codes; Otsu runs on the histogram and the
-// threshold comparison continues on the codes (amt_threshold_open_close / amt_threshold_gt on the uint16 code plane
-// with thr_code).  26 bytes of HBM traffic per pixel (write + two reads of a float64 plane, read uint16) become 8.
+// R/pipeline.py:25-45).  Otsu runs on the 256-bin histogram and the threshold comparison continues on 2-byte codes
+// (amt_threshold_open_close / amt_threshold_gt on the uint16 code plane with thr_code).  Two forms, same results:
+//   two passes  of the fused uint16 Gaussian over the input: the first folds min / max, the second recomputes the
+//               samples, counts np.histogram's bins and stores the codes (8 bytes of HBM traffic per pixel);
+//   prefix plane: ONE Gaussian pass that folds min / max and stores the upper 32 bits of every float64 sample, then a
+//               streaming pass over those prefixes (prefix_codes_kernel below) -- 2 + 4 + 4 + 2 bytes per pixel.
+
+__device__ __forceinline__ double gl_edge(double lo, double hi, double step, int i) {
+    return i == GL_NBINS ? hi : (double)i * step + lo;  // np.linspace(lo, hi, 257)[i]
+}
+
+// np.histogram's bin of `v` (edges as above, last bin closed), repaired from the scaled guess
+__device__ __forceinline__ int gl_bin(double v, double lo, double hi, double step, double norm) {
+    int b = (int)((v - lo) * norm);
+    b = b < 0 ? 0 : (b > GL_NBINS - 1 ? GL_NBINS - 1 : b);
+    while (b > 0 && v < gl_edge(lo, hi, step, b)) --b;
+    while (b < GL_NBINS - 1 && v >= gl_edge(lo, hi, step, b + 1)) ++b;
+    return b;
+}
+
+// Histogram and codes from the prefix plane.  A smoothed sample v is a non-negative float64, so its upper 32 bits p
+// order like v itself: with vlo / vhi the smallest / largest double that starts with p, vlo <= v <= vhi, and both the
+// bin and the comparison with the bin's centre are monotone in v.  Where vlo and vhi agree the answer is v's, exactly;
+// where they differ (v within 2^-20 relative of an edge or a centre: ~230 samples of a 2048^2 field) the sample is
+// UNDECIDED: it is not counted, its code is left 0 and its index is appended to the plane's list (one atomic per wave
+// and step), for prefix_fixup_kernel to recompute.  A plane with more than PFX_CAP undecided samples (range of about a
+// grey level) stops being processed -- its count stays above PFX_CAP and gauss_lds_kernel<R, 2> redoes it as a whole.
+__global__ void __launch_bounds__(256) prefix_codes_kernel(const uint32_t* __restrict__ prefix,
+                                                           const double* __restrict__ minmax,
+                                                           uint32_t* __restrict__ hist, uint16_t* __restrict__ codes,
+                                                           size_t n, uint32_t* __restrict__ und_count,
+                                                           uint32_t* __restrict__ und_list) {
+    __shared__ uint32_t lh[4 * GL_NBINS];
+    const int plane = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const double lo = minmax[2 * plane], hi = minmax[2 * plane + 1];
+    const uint32_t* src = prefix + (size_t)plane * n;
+    uint16_t* dst = codes + (size_t)plane * n;
+    const size_t first = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4, stride = (size_t)gridDim.x * 1024;
+    if (!(lo < hi)) {  // constant plane: every code 0, nothing counted (the threshold is the value, its code 0)
+        for (size_t i0 = first; i0 < n; i0 += stride) *reinterpret_cast<uint2*>(dst + i0) = make_uint2(0u, 0u);
+        return;
+    }
+    for (int i = threadIdx.x; i < 4 * GL_NBINS; i += 256) lh[i] = 0;
+    __syncthreads();
+    uint32_t* mine = lh + (threadIdx.x >> 6) * GL_NBINS;
+    const double step = (hi - lo) / (double)GL_NBINS, norm = (double)GL_NBINS / (hi - lo);
+    uint32_t* cnt = und_count + (size_t)plane * PFX_CNT_STRIDE;
+    uint32_t* list = und_list + (size_t)plane * PFX_CAP;
+    // no look at the counter when a block starts: with every wave of the chip reading the one line that the appends keep
+    // dirty the pass took 1.07 ms per 48 planes instead of 0.36 (rocprofv3); a wave of an overflowed plane learns it
+    // from its own first append
+    bool dead = false;
+    for (size_t i0 = first; i0 < n && !dead; i0 += stride) {
+        const uint4 p4 = *reinterpret_cast<const uint4*>(src + i0);
+        const unsigned p[4] = {p4.x, p4.y, p4.z, p4.w};
+        int b4[4];
+        double elo4[4], ehi4[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {  // first guess of the bin of vlo and both of its edges (no dependent chain)
+            const double vlo = __hiloint2double((int)p[u], 0);
+            int b = (int)((vlo - lo) * norm);
+            b = b < 0 ? 0 : (b > GL_NBINS - 1 ? GL_NBINS - 1 : b);
+            b4[u] = b;
+            elo4[u] = (double)b * step + lo;
+            ehi4[u] = gl_edge(lo, hi, step, b + 1);
+        }
+        unsigned cd[4], undm = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const double vlo = __hiloint2double((int)p[u], 0), vhi = __hiloint2double((int)p[u], (int)0xffffffffu);
+            int b = b4[u];
+            if (vlo < elo4[u] || (b < GL_NBINS - 1 && vlo >= ehi4[u])) {  // within rounding distance of an edge
+                b = gl_bin(vlo, lo, hi, step, norm);
+                elo4[u] = gl_edge(lo, hi, step, b);
+                ehi4[u] = gl_edge(lo, hi, step, b + 1);
+            }
+            const double ctr = (elo4[u] + ehi4[u]) / 2.0;
+            const bool gt = vlo > ctr;
+            // bin(v) == bin(vlo) unless vhi reaches the next edge; (v > ctr) == (vlo > ctr) unless only vhi is above
+            const bool und = (b < GL_NBINS - 1 && vhi >= ehi4[u]) || (!gt && vhi > ctr);
+            undm |= (und ? 1u : 0u) << u;
+            cd[u] = und ? 0u : (((unsigned)b << 1) | (gt ? 1u : 0u));
+            const unsigned long long act = __ballot(!und);
+            if (!act) continue;
+            // two rounds of "first lane's bin, counted once for everyone who shares it", then lane by lane
+            // (as hist_f64_kernel: a smoothed background wave straddles at most one bin edge)
+            const int l0 = __ffsll((long long)act) - 1;
+            const int b0 = __shfl(b, l0);
+            const unsigned long long s0 = __ballot(!und && b == b0);
+            if (lane == l0) atomicAdd(&mine[b0], (unsigned)__popcll(s0));
+            unsigned long long rest = act & ~s0;
+            if (rest) {
+                const int l1 = __ffsll((long long)rest) - 1;
+                const int b1 = __shfl(b, l1);
+                const unsigned long long s1 = __ballot(!und && b == b1);
+                if (lane == l1) atomicAdd(&mine[b1], (unsigned)__popcll(s1));
+                rest &= ~s1;
+                if ((rest >> lane) & 1ull) atomicAdd(&mine[b], 1u);
+            }
+        }
+        *reinterpret_cast<uint2*>(dst + i0) = make_uint2(cd[0] | (cd[1] << 16), cd[2] | (cd[3] << 16));
+        const unsigned long long any = __ballot(undm != 0);
+        if (any) {  // rare: append this wave's undecided samples with ONE atomic
+            const unsigned long long m0 = __ballot(undm & 1u), m1 = __ballot(undm & 2u), m2 = __ballot(undm & 4u),
+                                     m3 = __ballot(undm & 8u);
+            const unsigned n0 = __popcll(m0), n1 = __popcll(m1), n2 = __popcll(m2), n3 = __popcll(m3);
+            const int leader = __ffsll((long long)any) - 1;
+            unsigned base = 0;
+            if (lane == leader) base = atomicAdd(cnt, n0 + n1 + n2 + n3);
+            base = __shfl(base, leader);
+            const unsigned long long below = (1ull << lane) - 1ull;
+            const unsigned pos[4] = {base + (unsigned)__popcll(m0 & below), base + n0 + (unsigned)__popcll(m1 & below),
+                                     base + n0 + n1 + (unsigned)__popcll(m2 & below),
+                                     base + n0 + n1 + n2 + (unsigned)__popcll(m3 & below)};
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (((undm >> u) & 1u) && pos[u] < PFX_CAP) list[pos[u]] = (uint32_t)(i0 + u);
+            dead = base + n0 + n1 + n2 + n3 > PFX_CAP;  // wave-uniform: the whole plane will be redone
+        }
+    }
+    __syncthreads();
+    uint32_t* gh = hist + (size_t)plane * GL_NBINS;
+    for (int i = threadIdx.x; i < GL_NBINS; i += 256) {
+        const uint32_t c = lh[i] + lh[GL_NBINS + i] + lh[2 * GL_NBINS + i] + lh[3 * GL_NBINS + i];
+        if (c) atomicAdd(&gh[i], c);
+    }
+}
+
+// The undecided samples of prefix_codes_kernel, one per half wave: recompute the float64 value from the uint16 input with
+// the Gaussian kernel's own arithmetic (lane d: gauss_column of column x - R + d; lane 0: the horizontal gauss_taps over
+// the 2R + 1 column results), count its bin and patch its code.  A plane whose list overflowed gets its histogram
+// cleared instead -- gauss_lds_kernel<R, 2> (launched next with `redo`) recounts it from nothing.
+constexpr int PFX_FIX_BLOCKS = 64;
+template <int R>
+__global__ void __launch_bounds__(64) prefix_fixup_kernel(const uint16_t* __restrict__ in, double scale, int H, int W,
+                                                          const double* __restrict__ wts, int mode, size_t in_stride,
+                                                          const double* __restrict__ minmax,
+                                                          const uint32_t* __restrict__ und_count,
+                                                          const uint32_t* __restrict__ und_list,
+                                                          uint32_t* __restrict__ hist, uint16_t* __restrict__ codes) {
+    constexpr int K = 2 * R + 1;
+    static_assert(K <= 32, "one half wave per sample");
+    __shared__ double cs[2][32];
+    const int plane = blockIdx.y;
+    const uint32_t cnt = und_count[(size_t)plane * PFX_CNT_STRIDE];
+    uint32_t* gh = hist + (size_t)plane * GL_NBINS;
+    if (cnt > PFX_CAP) {
+        if (blockIdx.x == 0)
+            for (int i = threadIdx.x; i < GL_NBINS; i += 64) gh[i] = 0;
+        return;
+    }
+    if (blockIdx.x * 2u >= cnt) return;
+    double w[R + 1];
+#pragma unroll
+    for (int j = 0; j <= R; ++j) w[j] = wts[R - j];
+    const uint16_t* src = in + (size_t)plane * in_stride;
+    const double lo = minmax[2 * plane], hi = minmax[2 * plane + 1];
+    const double step = (hi - lo) / (double)GL_NBINS, norm = (double)GL_NBINS / (hi - lo);
+    const int half = threadIdx.x >> 5, d = threadIdx.x & 31;
+    for (uint32_t e0 = blockIdx.x * 2u; e0 < cnt; e0 += 2u * PFX_FIX_BLOCKS) {  // block-uniform trip count
+        const bool valid = e0 + half < cnt;
+        const uint32_t idx = valid ? und_list[(size_t)plane * PFX_CAP + e0 + half] : 0u;
+        const int y = (int)(idx / (uint32_t)W), x = (int)(idx % (uint32_t)W);
+        if (valid && d < K) cs[half][d] = gauss_column<R>(src, scale, H, W, mode, y, x - R + d, w);
+        __syncthreads();
+        if (valid && d == 0) {
+            double c[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) c[k] = cs[half][k];
+            const double v = gauss_taps<R>(&c[R], w);
+            const int b = gl_bin(v, lo, hi, step, norm);
+            const double ctr = (gl_edge(lo, hi, step, b) + gl_edge(lo, hi, step, b + 1)) / 2.0;
+            atomicAdd(&gh[b], 1u);
+            codes[(size_t)plane * H * W + idx] = (uint16_t)((b << 1) | (v > ctr ? 1 : 0));
+        }
+        __syncthreads();
+    }
+}
+
 template <int R>
 static int launch_codes(amt_ctx* ctx, const uint16_t* in, double scale, int nplanes, int H, int W, const double* wdev,
                         int mode, size_t in_stride, unsigned long long* keys, double* mm, uint32_t* hist,
-                        uint16_t* codes) {
+                        uint16_t* codes, uint32_t* prefix, uint32_t* und_count, uint32_t* und_list) {
     constexpr int RP = (R + 7) & ~7;
     constexpr int OUTW2 = 256 - 2 * RP;
     const int gx2 = (W + OUTW2 - 1) / OUTW2;
@@ -1111,13 +1315,38 @@ static int launch_codes(amt_ctx* ctx, const uint16_t* in, double scale, int npla
     while (TH2 > 32 && (long long)gx2 * ((H + TH2 - 1) / TH2) * nplanes < 4LL * ctx->num_cus) TH2 >>= 1;
     dim3 grid2(gx2, (H + TH2 - 1) / TH2, nplanes);
     AMT_TRY(amt_i_minmax_init(ctx, keys, nplanes));
+    if (prefix) {
+        hipLaunchKernelGGL((gauss_lds_kernel<R, 3>), grid2, dim3(256), 0, ctx->stream, in, scale, (double*)nullptr, H, W,
+                           wdev, mode, in_stride, TH2, keys, (const double*)nullptr, (uint32_t*)nullptr,
+                           (uint16_t*)nullptr, prefix, (const uint32_t*)nullptr);
+        AMT_LAUNCH_CHECK();
+        AMT_TRY(amt_i_minmax_finish(ctx, keys, mm, nplanes));
+        AMT_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)nplanes * GL_NBINS * sizeof(uint32_t), ctx->stream));
+        AMT_HIP_CHECK(hipMemsetAsync(und_count, 0, (size_t)nplanes * PFX_CNT_STRIDE * sizeof(uint32_t), ctx->stream));
+        const size_t n = (size_t)H * W;
+        hipLaunchKernelGGL(prefix_codes_kernel, dim3(amt_grid_for(n, 256 * 16, 512), nplanes), dim3(256), 0, ctx->stream,
+                           (const uint32_t*)prefix, (const double*)mm, hist, codes, n, und_count, und_list);
+        AMT_LAUNCH_CHECK();
+        hipLaunchKernelGGL((prefix_fixup_kernel<R>), dim3(PFX_FIX_BLOCKS, nplanes), dim3(64), 0, ctx->stream, in, scale, H, W,
+                           wdev, mode, in_stride, (const double*)mm, (const uint32_t*)und_count,
+                           (const uint32_t*)und_list, hist, codes);
+        AMT_LAUNCH_CHECK();
+        // planes whose list overflowed: the exact second pass of the two-pass form (every other block returns at once)
+        hipLaunchKernelGGL((gauss_lds_kernel<R, 2>), grid2, dim3(256), 0, ctx->stream, in, scale, (double*)nullptr, H, W,
+                           wdev, mode, in_stride, TH2, (unsigned long long*)nullptr, (const double*)mm, hist, codes,
+                           (uint32_t*)nullptr, (const uint32_t*)und_count);
+        AMT_LAUNCH_CHECK();
+        return AMT_OK;
+    }
     hipLaunchKernelGGL((gauss_lds_kernel<R, 1>), grid2, dim3(256), 0, ctx->stream, in, scale, (double*)nullptr, H, W,
-                       wdev, mode, in_stride, TH2, keys, (const double*)nullptr, (uint32_t*)nullptr, (uint16_t*)nullptr);
+                       wdev, mode, in_stride, TH2, keys, (const double*)nullptr, (uint32_t*)nullptr, (uint16_t*)nullptr,
+                       (uint32_t*)nullptr, (const uint32_t*)nullptr);
     AMT_LAUNCH_CHECK();
     AMT_TRY(amt_i_minmax_finish(ctx, keys, mm, nplanes));
     AMT_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)nplanes * GL_NBINS * sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL((gauss_lds_kernel<R, 2>), grid2, dim3(256), 0, ctx->stream, in, scale, (double*)nullptr, H, W,
-                       wdev, mode, in_stride, TH2, (unsigned long long*)nullptr, (const double*)mm, hist, codes);
+                       wdev, mode, in_stride, TH2, (unsigned long long*)nullptr, (const double*)mm, hist, codes,
+                       (uint32_t*)nullptr, (const uint32_t*)nullptr);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -1131,26 +1360,36 @@ extern "C" int amt_gaussian_otsu_codes_supported(int H, int W, int radius, int m
 extern "C" int amt_gaussian_otsu_codes(amt_ctx* ctx, const uint16_t* in, double scale, int nplanes, int H, int W,
                                        const double* weights, int radius, int mode, size_t in_plane_stride,
                                        double* minmax_dev, uint32_t* hist_dev, double* thr_dev, double* thr_code_dev,
-                                       uint16_t* codes) {
+                                       uint16_t* codes, uint32_t* prefix) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && weights && minmax_dev && hist_dev && thr_dev && thr_code_dev && codes && nplanes >= 0,
                 "gaussian_otsu_codes: bad arguments");
     AMT_REQUIRE(amt_gaussian_otsu_codes_supported(H, W, radius, mode, in_plane_stride) &&
-                    (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(codes) & 15) == 0,
+                    (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(codes) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(prefix) & 15) == 0,
                 "gaussian_otsu_codes: unsupported shape / radius / mode / alignment (ask "
                 "amt_gaussian_otsu_codes_supported; the separate operators handle every case)");
     if (nplanes == 0) return AMT_OK;
     if (in_plane_stride == 0) in_plane_stride = (size_t)H * W;
+    // the prefix order holds for non-negative samples (uint16 input, positive scale and weights) and the list of
+    // undecided samples holds 32-bit pixel indices: anything else takes the two-pass form
+    bool ordered = scale > 0.0 && (size_t)H * W <= 0xffffffffull;
+    for (int i = 0; i <= 2 * radius; ++i) ordered = ordered && weights[i] >= 0.0;
+    if (!ordered) prefix = nullptr;
     const size_t wbytes = amt_align((2 * radius + 1) * sizeof(double)), kbytes = amt_align((size_t)2 * nplanes * 8);
-    AMT_TRY(amt_arena_begin(ctx, wbytes + kbytes));
+    const size_t cbytes = prefix ? amt_align((size_t)nplanes * PFX_CNT_STRIDE * sizeof(uint32_t)) : 0;
+    const size_t lbytes = prefix ? amt_align((size_t)nplanes * PFX_CAP * sizeof(uint32_t)) : 0;
+    AMT_TRY(amt_arena_begin(ctx, wbytes + kbytes + cbytes + lbytes));
     double* wdev = (double*)amt_arena_take(ctx, wbytes);
     unsigned long long* keys = (unsigned long long*)amt_arena_take(ctx, kbytes);
+    uint32_t* und_count = prefix ? (uint32_t*)amt_arena_take(ctx, cbytes) : nullptr;
+    uint32_t* und_list = prefix ? (uint32_t*)amt_arena_take(ctx, lbytes) : nullptr;
     AMT_TRY(amt_param_upload(ctx, wdev, weights, (2 * radius + 1) * sizeof(double)));
     switch (radius) {
 #define AMT_CODES_CASE(RR)                                                                                            \
     case RR:                                                                                                          \
         AMT_TRY(launch_codes<RR>(ctx, in, scale, nplanes, H, W, wdev, mode, in_plane_stride, keys, minmax_dev, hist_dev, \
-                                 codes));                                                                             \
+                                 codes, prefix, und_count, und_list));                                                \
         break;
         AMT_CODES_CASE(1)
         AMT_CODES_CASE(2)

@@ -105,6 +105,30 @@ __global__ void __launch_bounds__(256) pack_bins_kernel(const uint8_t* __restric
     if ((threadIdx.x & 3) == 0) packed[plane * (n / 64) + q / 4] = (u64)m | (m1 << 16) | (m2 << 32) | (m3 << 48);
 }
 
+// `in > thr[plane]` for uint16 planes (the 2-byte codes of amt_gaussian_otsu_codes) in the layout of pack_bins_kernel: a
+// thread owns 16 consecutive pixels (two 16-byte loads), four threads make a 64-pixel word.  W % 64 == 0.  For an integer
+// v the comparison (double)v > t is v > floor(t) (t >= 0), always true for t < 0, never for NaN.
+__global__ void __launch_bounds__(256) pack_gt_u16x16_kernel(const uint16_t* __restrict__ in, const double* __restrict__ thr,
+                                                             u64* __restrict__ packed, size_t n) {
+    const size_t plane = blockIdx.y;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;  // 16-pixel group of the plane
+    if (q * 16 >= n) return;                                  // whole quads leave together (n % 64 == 0)
+    const double t = thr[plane];
+    const int it = t < 0.0 ? -1 : (t < 65535.0 ? (int)t : 65535);  // NaN -> 65535: no uint16 is above it
+    const uint4* src = reinterpret_cast<const uint4*>(in + plane * n + q * 16);
+    const uint4 a = src[0], b = src[1];
+    const unsigned wv[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    unsigned m = 0;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int v = (int)((wv[j >> 1] >> (16 * (j & 1))) & 0xFFFFu);
+        m |= (v > it ? 1u : 0u) << j;
+    }
+    const u64 m1 = (u64)(unsigned)__shfl_down((int)m, 1), m2 = (u64)(unsigned)__shfl_down((int)m, 2),
+              m3 = (u64)(unsigned)__shfl_down((int)m, 3);
+    if ((threadIdx.x & 3) == 0) packed[plane * (n / 64) + q / 4] = (u64)m | (m1 << 16) | (m2 << 32) | (m3 << 48);
+}
+
 __device__ __forceinline__ unsigned spread4(unsigned nib) {
     return (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
 }
@@ -456,6 +480,9 @@ extern "C" int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dty
         else if (in_dtype == AMT_F64)
             hipLaunchKernelGGL((pack_gt_kernel<double>), dim3(gpack, nplanes), dim3(256), 0, ctx->stream,
                                (const double*)in, thr_dev, pa, H, W, WW);
+        else if ((W & 63) == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0)
+            hipLaunchKernelGGL(pack_gt_u16x16_kernel, dim3((unsigned)((npx / 16 + 255) / 256), nplanes), dim3(256), 0,
+                               ctx->stream, (const uint16_t*)in, thr_dev, pa, npx);
         else
             hipLaunchKernelGGL((pack_gt_kernel<uint16_t>), dim3(gpack, nplanes), dim3(256), 0, ctx->stream,
                                (const uint16_t*)in, thr_dev, pa, H, W, WW);

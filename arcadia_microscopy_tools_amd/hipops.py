@@ -140,12 +140,16 @@ def gaussian_otsu_codes_supported(a: DeviceArray, sigma: float, mode: str = "nea
 
 def gaussian_otsu_codes(a: DeviceArray, sigma: float, codes: DeviceArray, thr: DeviceArray, thr_code: DeviceArray,
                         minmax: DeviceArray, hist: DeviceArray, mode: str = "nearest", truncate: float = 4.0,
-                        channel: int | None = None) -> DeviceArray:
+                        channel: int | None = None, prefix: DeviceArray | None = None) -> DeviceArray:
     """``threshold_otsu(gaussian(a, sigma))`` per plane WITHOUT the float64 image: ``thr`` receives the thresholds,
     ``codes`` (uint16, one per pixel) and ``thr_code`` continue the chain -- ``gaussian(a) > thr`` is exactly
     ``codes > thr_code`` (csrc/amt_filters.hip, gauss_lds_kernel EPI 2), so ``threshold_open_close(codes, thr_code)``
     yields the mask of the separate operators.  ``minmax`` (n, 2) and ``hist`` (n, 256) receive np.histogram's range
-    and counts.  All outputs are caller-owned device arrays (nothing is allocated per call)."""
+    and counts.  All outputs are caller-owned device arrays (nothing is allocated per call).
+
+    ``prefix`` (uint32, one word per pixel, scratch): the Gaussian runs ONCE and leaves the upper half of every float64
+    sample there; histogram and codes come from a streaming pass over that plane, and the few samples whose 32 bits do
+    not decide their bin are recomputed exactly.  Without it the Gaussian runs twice.  Same outputs either way."""
     ctx = a.ctx
     n, H, W = _planes(a)
     ptr, stride = a.ptr, 0
@@ -157,7 +161,9 @@ def gaussian_otsu_codes(a: DeviceArray, sigma: float, codes: DeviceArray, thr: D
         raise TypeError("gaussian_otsu_codes takes uint16 images")
     for name, arr, dt, size in (("codes", codes, np.uint16, n * H * W), ("thr", thr, np.float64, n),
                                 ("thr_code", thr_code, np.float64, n), ("minmax", minmax, np.float64, 2 * n),
-                                ("hist", hist, np.uint32, 256 * n)):
+                                ("hist", hist, np.uint32, 256 * n), ("prefix", prefix, np.uint32, n * H * W)):
+        if arr is None and name == "prefix":
+            continue
         if arr.dtype != dt or arr.size != size:
             raise ValueError(f"{name} must be a {np.dtype(dt).name} DeviceArray of {size} elements")
         if arr.ctx is not ctx:
@@ -166,7 +172,8 @@ def gaussian_otsu_codes(a: DeviceArray, sigma: float, codes: DeviceArray, thr: D
     r = (len(w) - 1) // 2
     wa, wp = _host_f64(w)
     _hip.check(_lib().amt_gaussian_otsu_codes(ctx.handle, ptr, 1.0 / 65535, n, H, W, wp, r, _hip.MODES[mode], stride,
-                                              minmax.ptr, hist.ptr, thr.ptr, thr_code.ptr, codes.ptr),
+                                              minmax.ptr, hist.ptr, thr.ptr, thr_code.ptr, codes.ptr,
+                                              prefix.ptr if prefix is not None else None),
                "amt_gaussian_otsu_codes")
     return codes
 

@@ -47,7 +47,7 @@ class FovSegmenter:
     def __init__(self, batch: int, C: int, H: int, W: int, *, sigma: float = 2.0, radius: int = 2,
                  min_distance: int = 5, max_cells: int = 4096, dapi_index: int = 1, ctx: Context | None = None,
                  props: bool = True, profile: bool = False, fused: bool = True, low_traffic: bool = False, bin_plane: bool = True,
-                 relief: str = "seeded", ties: str = "exact"):
+                 prefix_plane: bool = True, relief: str = "seeded", ties: str = "exact"):
         self.ctx = ctx or get_context()
         self.B, self.C, self.H, self.W = int(batch), int(C), int(H), int(W)
         self.sigma, self.radius, self.min_distance = float(sigma), int(radius), int(min_distance)
@@ -72,13 +72,18 @@ class FovSegmenter:
         # bin_plane: the Otsu histogram pass leaves every sample's bin as a byte plane and '>' reads that plane
         # (amt_otsu_f64_bins / amt_threshold_open_close); False = compare the float64 plane (same masks)
         self.bin_plane = bool(bin_plane)
+        # prefix_plane (the default where amt_gaussian_otsu_codes takes the batch and neither of the two switches above
+        # asks for another path): ONE Gaussian pass stores the upper 32 bits of every float64 sample, the histogram pass
+        # reads those and leaves 2-byte codes -- 6 instead of 9 bytes per pixel held and moved, same masks and
+        # thresholds.  False = the float64 plane + byte bins
+        self.prefix_plane = bool(prefix_plane)
         self.footprint = hipops.disk(self.radius)
         c, B = self.ctx, self.B
         shp = (B, self.H, self.W)
         # Gaussian -> Otsu -> '>' without the float64 image when the fused path takes this shape (2-byte codes instead)
-        self.codes_path = None  # decided on the first batch (needs the batch's alignment)
+        self.codes_path = self.prefix_path = None  # decided on the first batch (needs the batch's alignment)
         self._gauss = None
-        self.codes = self.thr_code = self.ghist = None
+        self.codes = self.thr_code = self.ghist = self._prefix = None
         self._bins = self._thr_code = None
         self.thr = c.empty((B,), np.float64)
         self.gmm = c.empty((B, 2), np.float64)  # [min, max] of the smoothed image, folded in by the Gaussian
@@ -124,19 +129,22 @@ class FovSegmenter:
     def mask_chain(self, fovs: DeviceArray) -> DeviceArray:
         """Gaussian -> Otsu -> '>' -> opening -> closing on the DAPI channel of every FOV."""
         if self.codes_path is None:
-            self.codes_path = self.low_traffic and hipops.gaussian_otsu_codes_supported(
-                fovs, self.sigma, channel=self.dapi_index)
-            if self.codes_path:
+            supported = hipops.gaussian_otsu_codes_supported(fovs, self.sigma, channel=self.dapi_index)
+            self.codes_path = self.low_traffic and supported  # the two-pass form
+            self.prefix_path = self.prefix_plane and self.bin_plane and not self.low_traffic and supported
+            if self.codes_path or self.prefix_path:
                 shp = (self.B, self.H, self.W)
                 self.codes = self.ctx.empty(shp, np.uint16)
                 self.thr_code = self.ctx.empty((self.B,), np.float64)
                 self.ghist = self.ctx.empty((self.B, 256), np.uint32)
-        if self.codes_path:
-            # two passes over the uint16 input (min / max, then histogram + 2-byte codes): `gaussian > thr` is exactly
-            # `codes > thr_code`, and the float64 plane (8 B/px written, read twice) is never made
+                if self.prefix_path:
+                    self._prefix = self.ctx.empty(shp, np.uint32)
+        if self.codes_path or self.prefix_path:
+            # `gaussian > thr` is exactly `codes > thr_code`, and the float64 plane (8 B/px written, read twice) is never
+            # made: one Gaussian pass + the prefix plane + a histogram pass, or (low_traffic) two Gaussian passes
             self._stage("gaussian_otsu")
             hipops.gaussian_otsu_codes(fovs, self.sigma, self.codes, self.thr, self.thr_code, self.gmm, self.ghist,
-                                       channel=self.dapi_index)
+                                       channel=self.dapi_index, prefix=self._prefix)
             self._stage("threshold_open_close")
             hipops.threshold_open_close(self.codes, self.thr_code, self.footprint, out=self.mask_a)
             return self.mask_a

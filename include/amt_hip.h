@@ -131,11 +131,17 @@ int amt_gaussian(amt_ctx* ctx, const void* in, int in_dtype, double scale, doubl
  * Outputs (all caller-owned): minmax_dev[2 n] = range of the smoothed plane, hist_dev[256 n] = np.histogram counts,
  * thr_dev[n] = the Otsu threshold (bit-identical to amt_gaussian + amt_threshold_value), codes[n H W] = uint16 code
  * per pixel with   gaussian(in) > thr  <=>  code > thr_code_dev[plane]   exactly, so amt_threshold_gt /
- * amt_threshold_open_close on (codes, AMT_U16, thr_code_dev) produce the mask of the separate operators. */
+ * amt_threshold_open_close on (codes, AMT_U16, thr_code_dev) produce the mask of the separate operators.
+ * prefix (nullable, caller-owned, n H W words, 16-byte aligned): scratch plane for the single-pass form -- ONE Gaussian
+ * pass stores the upper 32 bits of every float64 sample there and a streaming pass derives histogram and codes from
+ * them, recomputing exactly the few samples the 32 bits leave undecided (R/pipeline.py:25-45 batches: fewer bytes and
+ * no second Gaussian).  Null, scale <= 0 or a negative weight: two Gaussian passes over the input.  The outputs are
+ * the same bit for bit either way. */
 int amt_gaussian_otsu_codes_supported(int H, int W, int radius, int mode, size_t in_plane_stride);
 int amt_gaussian_otsu_codes(amt_ctx* ctx, const uint16_t* in, double scale, int nplanes, int H, int W,
                             const double* weights, int radius, int mode, size_t in_plane_stride, double* minmax_dev,
-                            uint32_t* hist_dev, double* thr_dev, double* thr_code_dev, uint16_t* codes);
+                            uint32_t* hist_dev, double* thr_dev, double* thr_code_dev, uint16_t* codes,
+                            uint32_t* prefix);
 /* out = G(w_lo) - G(w_hi) of the same converted input (SK/filters/_gaussian.py:284-290). */
 /* One leading axis of an n-D Gaussian (skimage filters EVERY axis of an n-D image, leading axes first,
  * SP/_filters.py:423-427): the array is nplanes x L x inner, the 1-D filter runs along L; out is float64. */
