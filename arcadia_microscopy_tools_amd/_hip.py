@@ -126,6 +126,8 @@ _SIGS = {
     "amt_clear_border_relabel": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "amt_keep_labels": (c_int, [_P, _P, _P, _P, c_int, c_size_t, c_int]),
     "amt_cast_i32_i64": (c_int, [_P, _P, _P, c_size_t]),
+    "amt_cast_labels": (c_int, [_P, _P, c_int, _P, c_int, c_size_t]),
+    "amt_expand_labels": (c_int, [_P, _P, _P, c_int, c_int, c_int, ctypes.c_int64, c_int]),
     "amt_edt": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int]),
     "amt_peak_mask": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
     "amt_watershed_edt": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -760,6 +760,63 @@ def max_per_plane(labels: DeviceArray, out=None) -> DeviceArray:
     return o
 
 
+def cast_labels(labels: DeviceArray, dtype, out=None) -> DeviceArray:
+    """Label planes between uint8 / uint16 and the int32 the label kernels take (values copied; narrowing is the
+    caller's promise that they fit)."""
+    o = _out(labels.ctx, out, labels.shape, dtype)
+    pair = (labels.dtype, o.dtype)
+    if np.dtype(np.int32) not in pair or not all(d in (np.uint8, np.uint16, np.int32) for d in pair) or pair[0] == pair[1]:
+        raise TypeError(f"cast_labels converts uint8 / uint16 to int32 and back, not {pair[0]} to {pair[1]}")
+    codes = {np.dtype(np.uint8): _hip.U8, np.dtype(np.uint16): _hip.U16, np.dtype(np.int32): _hip.I32}
+    _hip.check(_lib().amt_cast_labels(labels.ctx.handle, labels.ptr, codes[pair[0]], o.ptr, codes[pair[1]], labels.size),
+               "amt_cast_labels")
+    return o
+
+
+def expand_nmax(distance: float) -> int:
+    """The integer bound of ``expand_labels``: the largest n with ``np.sqrt(np.float64(n)) <= distance`` (-1 when there
+    is none, i.e. ``distance < 0`` or NaN), so that ``D2 <= nmax`` on exact integer squared distances is scikit-image's
+    ``distances <= distance`` on their float64 square roots.  ``floor(distance**2)`` is off by at most one."""
+    d = float(distance)
+    if not d >= 0.0:
+        return -1
+    if d >= 2.0 ** 31:  # beyond any squared distance on a plane the device takes (sides <= 32768)
+        return 2 ** 62
+    n = int(np.floor(d * d))
+    while n > 0 and not np.sqrt(np.float64(n)) <= d:
+        n -= 1
+    while np.sqrt(np.float64(n + 1)) <= d:
+        n += 1
+    return n
+
+
+def expand_labels(labels: DeviceArray, distance: float, ring: bool = False, out=None) -> DeviceArray:
+    """``skimage.segmentation.expand_labels(labels, distance)`` per plane (SK/segmentation/_expand_labels.py): every
+    label grows by up to ``distance`` pixels into the background without overlapping its neighbours.  ``labels`` is an
+    int32 (H, W) or (N, H, W) array of non-negative labels; the planes are independent.
+
+    A background pixel is labelled iff the float64 square root of its exact squared distance to the nearest labelled
+    pixel is ``<= distance`` (any float distance: the bound is turned into an integer by ``expand_nmax``), with the
+    label of that nearest pixel.  Where pixels of several labels are equally near, the SMALLEST label is written:
+    scipy's feature transform picks whichever tied pixel its scan meets first, which is an artefact of its algorithm;
+    this rule is deterministic and independent of tiling, plane size and batch position.  The support and every
+    untied pixel equal scikit-image's.  ``distance < 0`` gives zeros, as that expression does.
+
+    ``ring=True`` writes 0 inside the input's labels: the annulus each label gains."""
+    ctx = labels.ctx
+    if labels.ndim not in (2, 3):
+        raise ValueError(f"expand_labels expects an (H, W) or (N, H, W) array, got shape {labels.shape}")
+    if labels.dtype != np.int32:
+        raise TypeError("expand_labels expects int32 labels on the device")
+    n, H, W = _planes(labels)
+    o = _out(ctx, out, labels.shape, np.int32)
+    if o.ptr == labels.ptr:
+        raise ValueError("expand_labels cannot work in place: out must be another buffer than labels")
+    _hip.check(_lib().amt_expand_labels(ctx.handle, labels.ptr, o.ptr, n, H, W, expand_nmax(distance), int(bool(ring))),
+               "amt_expand_labels")
+    return o
+
+
 # --------------------------------------------------------------------------------------------------
 # distance transform, markers, watershed
 # --------------------------------------------------------------------------------------------------

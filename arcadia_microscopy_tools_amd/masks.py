@@ -300,9 +300,34 @@ class SegmentationMask:
         d["_sealed"] = True
         return self
 
+    @classmethod
+    def _derived(cls, parent: "SegmentationMask", labels, num_cells: int, parent_labels: np.ndarray):
+        """A mask whose label plane was computed on the device FROM ``parent``'s (``expanded`` / ``ring``): ``labels``
+        is an int32 (Y, X) plane numbered 1..``num_cells``, ``parent_labels[j]`` the label of ``parent.label_image``
+        that label ``j + 1`` came from.  It shares the parent's intensity images, outline extractor and property
+        lists, records ``remove_edge_cells=False`` (nothing is dropped), downloads ``mask_image`` / ``label_image``
+        only when they are read and measures ``cell_properties`` on first access."""
+        if num_cells <= 0:
+            raise ValueError("mask_image contains no cells (all values are 0)")
+        self = object.__new__(cls)
+        channels = None if parent.intensity_image_dict is None else dict(parent.intensity_image_dict)
+        given = (channels, False, parent.outline_extractor, list(parent.property_names),
+                 list(parent.intensity_property_names))
+        for name, value in zip(cls._CTOR_FIELDS[1:], given):
+            object.__setattr__(self, name, value)
+        d = self.__dict__
+        d["_mask_max"] = int(num_cells)
+        d["_labels_device"] = (labels, int(num_cells))
+        d["parent_labels"] = parent_labels
+        d["_sealed"] = True
+        return self
+
+    # row j of a derived mask (``expanded`` / ``ring``) came from label parent_labels[j] of the mask it was derived from
+    parent_labels = None
+
     def __getattr__(self, name):
         # only reached for attributes that are not set: the lazily downloaded label image of a device-born mask
-        if name == "mask_image" and "_rows" in self.__dict__:
+        if name == "mask_image" and "_labels_device" in self.__dict__:
             image = self.__dict__["_labels_device"][0].numpy_int64()
             self.__dict__["mask_image"] = image
             return image
@@ -484,6 +509,46 @@ class SegmentationMask:
                         property_names=list(self.property_names),
                         intensity_property_names=list(self.intensity_property_names))
         return SegmentationMask(**settings)
+
+    def _label_plane(self):
+        """(int32 (Y, X) device plane of ``label_image``, num_cells)"""
+        lab, k = self._labels_device
+        return lab.reshape(tuple(lab.shape[-2:])), int(k)
+
+    def expanded(self, distance: float) -> "SegmentationMask":
+        """The same cells with the same numbering, each grown by up to ``distance`` pixels into the background without
+        overlapping its neighbours: ``skimage.segmentation.expand_labels(self.label_image, distance)`` as a
+        ``SegmentationMask`` (nuclei -> "cells").  Label ``i`` of the result is cell ``i`` of this mask, so row ``i`` of
+        both ``cell_properties`` tables describes the same cell; ``parent_labels`` is ``arange(1, num_cells + 1)``.
+        A background pixel equally near to several cells goes to the one with the SMALLEST label (scipy's choice
+        among tied pixels is an artefact of its scan order; see ``hipops.expand_labels``).  The label plane is made
+        on the device from this mask's and downloaded only if ``mask_image`` / ``label_image`` are read."""
+        from . import hipops
+
+        if not float(distance) >= 0:
+            raise ValueError(f"distance must be non-negative, got {distance}")
+        plane, k = self._label_plane()
+        grown = hipops.expand_labels(plane, distance)
+        return SegmentationMask._derived(self, grown, k, np.arange(1, k + 1, dtype=np.int64))
+
+    def ring(self, distance: float) -> "SegmentationMask":
+        """The annulus each cell gains by ``expanded(distance)`` -- the grown cell minus the cell itself ("cytoplasm"
+        around a nucleus) -- as a ``SegmentationMask``.  Non-empty rings are numbered 1..K' in ascending order of
+        their parent cell and ``parent_labels[j]`` is the label of this mask that ring ``j + 1`` surrounds; a cell
+        enclosed by its neighbours gains no pixel and has no ring.  Raises the constructor's "contains no cells"
+        ``ValueError`` when no ring pixel exists."""
+        from . import hipops
+
+        if not float(distance) >= 0:
+            raise ValueError(f"distance must be non-negative, got {distance}")
+        plane, k = self._label_plane()
+        annulus = hipops.expand_labels(plane, distance, ring=True)
+        boxes = hipops.label_bboxes(annulus, k)[0]
+        parents = np.flatnonzero(boxes[:, 2] >= boxes[:, 0]).astype(np.int64) + 1
+        if parents.size == 0:
+            raise ValueError("mask_image contains no cells (all values are 0)")
+        lab, _ = hipops.relabel_sequential(annulus, k)
+        return SegmentationMask._derived(self, lab, int(parents.size), parents)
 
     def convert_properties_to_microns(self, pixel_size_um: float) -> dict[str, ScalarArray]:
         """Scale lengths / areas / volumes to microns with ``_um`` / ``_um2`` / ``_um3`` key suffixes

@@ -196,6 +196,45 @@ def crop_to_center(intensities: ScalarArray, output_shape: tuple[int, int]) -> S
     return intensities[..., top: top + crop_height, left: left + crop_width]
 
 
+@device_operator
+def expand_labels(label_image, distance: float = 1):
+    """``skimage.segmentation.expand_labels(label_image, distance)`` on a 2-D label image
+    (SK/segmentation/_expand_labels.py): every label grows by up to ``distance`` pixels into the background without
+    overlapping its neighbours.  bool and integer dtypes; a numpy result has the input's dtype, as scikit-image's
+    ``zeros_like`` gives it.  Labels must be non-negative and below 2**31 - 1.  A ``DeviceArray`` (int32, or the
+    uint16 / uint8 a ``Pipeline`` uploads) stays on the device; its values are the caller's promise.
+
+    Any float distance is exact (``hipops.expand_nmax``); ``distance < 0`` gives zeros.  Where pixels of several
+    labels are equally near, the SMALLEST label is written: scipy's feature transform keeps whichever tied pixel its
+    scan meets first, an artefact of its algorithm, while this rule is deterministic.  The support and every untied
+    pixel equal scikit-image's.  Stacks are refused rather than treated as volumes (scikit-image would run a 3-D
+    distance transform over them): map planes with ``Pipeline(parallel=True)`` or call ``hipops.expand_labels``."""
+    if isinstance(label_image, DeviceArray):
+        d = label_image
+        if d.ndim != 2:
+            raise ValueError("label_image must be a 2D array")
+        if d.dtype == np.int32:
+            return hipops.expand_labels(d, distance)
+        if d.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f"expand_labels: device label images must be int32, uint16 or uint8, got {d.dtype}")
+        grown = hipops.cast_labels(hipops.expand_labels(hipops.cast_labels(d, np.int32), distance), d.dtype)
+        grown.is_bool = d.is_bool
+        return grown
+    a = np.asarray(label_image)
+    if a.ndim != 2:
+        raise ValueError("label_image must be a 2D array")
+    if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"expand_labels: label_image must have a bool or integer dtype, got {a.dtype}")
+    if a.size == 0:
+        return np.zeros_like(a)
+    if a.dtype.kind == "i" and int(a.min()) < 0:
+        raise ValueError("label_image must have non-negative values")
+    if int(a.max()) >= 2**31 - 1:
+        raise ValueError("label values above 2**31 - 2 are not supported on the device path")
+    d = get_context().asarray(a, dtype=np.int32)  # narrowed / widened while it moves into the staging buffer
+    return hipops.expand_labels(d, distance).numpy(dtype=a.dtype)
+
+
 def _global_threshold(d: DeviceArray, method: str, kwargs: dict) -> float:
     """Threshold VALUE for the histogram-based methods: histogram on the device, selection on <= 65,536 counts."""
     nbins = int(kwargs.pop("nbins", 256))

@@ -295,6 +295,24 @@ int amt_clear_border_relabel(amt_ctx* ctx, const int32_t* in, int32_t* out, int3
 int amt_keep_labels(amt_ctx* ctx, const int32_t* in, const uint8_t* keep_dev, int32_t* out, int nplanes, size_t n,
                     int max_label);
 int amt_cast_i32_i64(amt_ctx* ctx, const int32_t* in, int64_t* out, size_t n);
+/* Label planes of other element types: AMT_U8 / AMT_U16 -> AMT_I32 (widened) and AMT_I32 -> AMT_U8 / AMT_U16
+ * (narrowed; the caller vouches that the values fit).  Any other pair is refused. */
+int amt_cast_labels(amt_ctx* ctx, const void* in, int in_dtype, void* out, int out_dtype, size_t n);
+/* skimage.segmentation.expand_labels(label_image, distance) per plane (SK/segmentation/_expand_labels.py:
+ * `out[distances <= distance] = label_image[nearest]` on distance_transform_edt(label_image == 0, return_indices=True)).
+ * labels = nplanes x H x W non-negative int32; out (another buffer than labels) receives
+ *   - the pixel's own label where it has one (0 there when ring != 0, so the annulus comes out of the same pass);
+ *   - for a background pixel p with D2(p) <= nmax the label of the nearest labelled pixel, D2 = exact integer squared
+ *     Euclidean distance to the nearest labelled pixel; 0 otherwise, and 0 everywhere on a plane without labels.
+ * nmax contract: the caller passes nmax = max{n : sqrt(float64(n)) <= distance} (floor(distance^2) corrected by +-1
+ * against that very test), so that the integer comparison equals scikit-image's `distances <= distance` for every
+ * float distance; nmax < 0 (distance < 0) zeroes the planes, labelled pixels included, as that expression does.
+ * Tie rule: when pixels of several labels lie at distance D2(p), the SMALLEST of those labels is written.  scipy's
+ * feature transform keeps whichever tied pixel its scan meets first (undocumented); this rule is deterministic and
+ * independent of tiling, plane size and batch position.  Untied pixels and the support equal scipy's.
+ * Every nmax is exact: searches within 32 rows run from LDS, deeper ones from the packed flags (slower, never wrong). */
+int amt_expand_labels(amt_ctx* ctx, const int32_t* labels, int32_t* out, int nplanes, int H, int W, int64_t nmax,
+                      int ring);
 
 /* ---- distance transform, markers, watershed (north_star) ------------ */
 /* Exact squared Euclidean distance to the nearest zero pixel (int32), and its correctly rounded
