@@ -8,15 +8,15 @@
 #include <cstring>
 
 #include "../../include/amt_hip.h"
+#include "amt_scratch_plan.h"
 
 struct amt_ctx {
     int device;
     hipStream_t stream;
     bool own_stream;
-    // grow-only scratch arena; reset at the start of every public op
+    // grow-only scratch arena; handed out whole by amt_scratch::commit at the start of every public op
     char* arena;
     size_t arena_cap;
-    size_t arena_off;
     // pinned host ring for small parameter tables (weights, footprint offsets, rank requests): the
     // caller's pointer is consumed before the public function returns, the DMA reads the pinned copy.
     char* mailbox;
@@ -69,21 +69,20 @@ void amt_set_error(const char* fmt, ...);
         if (_rc != AMT_OK) return _rc; \
     } while (0)
 
-// ---- arena -----------------------------------------------------------------------------------
-// Ops call arena_begin(ctx, total_bytes) once (may reallocate: synchronises the stream first),
-// then carve with arena_take.  Memory is only valid until the next op on the same context, which
-// is safe because all work of one context is ordered on one stream.
-int amt_arena_begin(amt_ctx* ctx, size_t total_bytes);
+// ---- scratch ----------------------------------------------------------------------------------
+// An op declares its buffers into an amt_scratch (amt_scratch_plan.h: the layout rule), then commits once: commit()
+// reserves exactly the declared total in the context's arena (may reallocate: synchronises the stream first) and only
+// then fills the pointers.  Memory is only valid until the next op on the same context, which is safe because all
+// work of one context is ordered on one stream.
+struct amt_scratch : amt_scratch_plan {
+    amt_ctx* ctx;
+    explicit amt_scratch(amt_ctx* c) : ctx(c) {}
+    int commit();
+};
 // copy `bytes` from caller-owned host memory to device memory via the pinned ring (stream ordered)
 int amt_param_upload(amt_ctx* ctx, void* dev_dst, const void* host_src, size_t bytes);
-void* amt_arena_take(amt_ctx* ctx, size_t bytes);
 
 __host__ __device__ static inline size_t amt_align(size_t n, size_t a = 256) { return (n + a - 1) / a * a; }
-
-template <typename T>
-static inline T* arena_take_t(amt_ctx* ctx, size_t count) {
-    return reinterpret_cast<T*>(amt_arena_take(ctx, amt_align(count * sizeof(T))));
-}
 
 static inline int amt_set_device(amt_ctx* ctx) {
     if (!ctx) {

@@ -48,7 +48,6 @@ static int ctx_create_common(int device, hipStream_t stream, bool own, amt_ctx**
     }
     c->arena = nullptr;
     c->arena_cap = 0;
-    c->arena_off = 0;
     c->mailbox = nullptr;
     c->mailbox_cap = 0;
     c->mailbox_off = 0;
@@ -109,8 +108,9 @@ static bool poison_enabled() {
     return v == 1;
 }
 
-int amt_arena_begin(amt_ctx* ctx, size_t total_bytes) {
-    total_bytes = amt_align(total_bytes) + 4096;
+int amt_scratch::commit() {
+    AMT_REQUIRE(!overflow, "scratch plan: more than %d buffers declared", AMT_SCRATCH_SLOTS);
+    const size_t total_bytes = total + 4096;  // total is a multiple of 256
     if (total_bytes > ctx->arena_cap) {
         // previous users of the arena are ordered before us on the stream; drain it before freeing
         AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -125,8 +125,8 @@ int amt_arena_begin(amt_ctx* ctx, size_t total_bytes) {
         }
         ctx->arena_cap = cap;
     }
-    ctx->arena_off = 0;
     if (poison_enabled()) AMT_HIP_CHECK(hipMemsetAsync(ctx->arena, 0xCD, ctx->arena_cap, ctx->stream));
+    fill(ctx->arena);
     return AMT_OK;
 }
 
@@ -196,13 +196,6 @@ int amt_param_upload(amt_ctx* ctx, void* dev_dst, const void* host_src, size_t b
     memcpy(slot, host_src, bytes);
     AMT_HIP_CHECK(hipMemcpyAsync(dev_dst, slot, bytes, hipMemcpyHostToDevice, ctx->stream));
     return AMT_OK;
-}
-
-void* amt_arena_take(amt_ctx* ctx, size_t bytes) {
-    bytes = amt_align(bytes);
-    void* p = ctx->arena + ctx->arena_off;
-    ctx->arena_off += bytes;
-    return p;
 }
 
 extern "C" int amt_malloc(amt_ctx* ctx, size_t bytes, void** dptr) {

@@ -854,10 +854,18 @@ static int cp_flow_errors(amt_ctx* ctx, const int* labels, const float* dP, cons
     return AMT_OK;
 }
 
-static size_t cp_finish_bytes(int nplanes, size_t n, int cap, int fill_holes);
-static int cp_finish(amt_ctx* ctx, int32_t* labels_out, const int* nlab1, int32_t* count_dev, const cp_box* box,
-                     const int* cnt, const double* err, float flow_threshold, int min_size, int fill_holes, int nplanes,
-                     int H, int W, int cap);
+// cp_finish's scratch, declared into the caller's plan before its commit
+struct cp_finish_scratch {
+    amt_buf<int> keep, keepflow, scan, map2, total, nested, fill, work;
+    amt_buf<unsigned char> bytes;
+    cp_finish_scratch(amt_scratch& s, size_t nl, size_t np, int nplanes, bool wanted, bool fill_holes)
+        : keep(s, nl, wanted), keepflow(s, nl, wanted), scan(s, nl, wanted), map2(s, nl, wanted), total(s, nplanes, wanted),
+          nested(s, nplanes, wanted), fill(s, np, wanted && fill_holes), work(s, np, wanted && fill_holes),
+          bytes(s, np, wanted && fill_holes) {}
+};
+static int cp_finish(amt_ctx* ctx, const cp_finish_scratch& fs, int32_t* labels_out, const int* nlab1, int32_t* count_dev,
+                     const cp_box* box, const int* cnt, const double* err, float flow_threshold, int min_size,
+                     int fill_holes, int nplanes, int H, int W, int cap);
 
 extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out,
                                      int32_t* count_dev, int nplanes, int H, int W, float cellprob_threshold, int niter,
@@ -876,28 +884,32 @@ extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float*
     const size_t hn = (size_t)Hp * Wp;
     const int cap = max_seeds;
     const size_t nl = (size_t)nplanes * (cap + 1);
-    size_t need = amt_align((size_t)nplanes * n * 4) + 2 * amt_align((size_t)nplanes * hn * 4) +
-                  amt_align((size_t)nplanes * cap * 8) + amt_align((size_t)nplanes * cap * 4) + 3 * amt_align(nl * 4) +
-                  amt_align((size_t)nplanes * 4);
-    if (post)
-        need += amt_align(nl * sizeof(cp_box)) + amt_align(nl * 4) + amt_align(nl * 16) + 2 * amt_align(nl * 8) +
-                2 * amt_align((size_t)nplanes * 4) + 2 * amt_align((size_t)nplanes * n * 8) +
-                cp_finish_bytes(nplanes, n, cap, fill_holes);
-    need += amt_align((size_t)nplanes * n * 8) + amt_align((size_t)nplanes * n * 4) + amt_align((size_t)nplanes * 4);
-    AMT_TRY(amt_arena_begin(ctx, need));
-    unsigned* pos = arena_take_t<unsigned>(ctx, (size_t)nplanes * n);
-    float2* fld = arena_take_t<float2>(ctx, (size_t)nplanes * n);  // (cell ? dP : 0) / 5, y and x
-    int* mvlist = arena_take_t<int>(ctx, (size_t)nplanes * n);     // the pixels that move
-    int* nmv = arena_take_t<int>(ctx, nplanes);
+    amt_scratch s(ctx);
+    amt_buf<unsigned> pos(s, (size_t)nplanes * n);
+    amt_buf<float2> fld(s, (size_t)nplanes * n);  // (cell ? dP : 0) / 5, y and x
+    amt_buf<int> mvlist(s, (size_t)nplanes * n);  // the pixels that move
+    amt_buf<int> nmv(s, nplanes);
+    amt_buf<int> hist(s, (size_t)nplanes * hn);
+    amt_buf<int> M(s, (size_t)nplanes * hn);
+    amt_buf<unsigned long long> seeds(s, (size_t)nplanes * cap);
+    amt_buf<unsigned> order(s, (size_t)nplanes * cap);
+    amt_buf<int> count(s, nl);
+    amt_buf<int> first(s, nl);
+    amt_buf<int> map(s, nl);
+    amt_buf<int> nseeds(s, nplanes);
+    // the later stages (post)
+    amt_buf<cp_box> box(s, nl, post);
+    amt_buf<int> cnt(s, nl, post);
+    amt_buf<unsigned long long> sums(s, 2 * nl, post);
+    amt_buf<double> err(s, nl, post);
+    amt_buf<int> center(s, 2 * nl, post);
+    amt_buf<int> nit(s, nplanes, post);
+    amt_buf<int> nlab1(s, nplanes, post);  // number of get_masks labels (count_dev becomes the final count)
+    amt_buf<double> TA(s, (size_t)nplanes * n, post);
+    amt_buf<double> TB(s, (size_t)nplanes * n, post);
+    cp_finish_scratch fs(s, nl, (size_t)nplanes * n, nplanes, post, fill_holes);
+    AMT_TRY(s.commit());
     AMT_HIP_CHECK(hipMemsetAsync(nmv, 0, (size_t)nplanes * 4, ctx->stream));
-    int* hist = arena_take_t<int>(ctx, (size_t)nplanes * hn);
-    int* M = arena_take_t<int>(ctx, (size_t)nplanes * hn);
-    unsigned long long* seeds = arena_take_t<unsigned long long>(ctx, (size_t)nplanes * cap);
-    unsigned* order = arena_take_t<unsigned>(ctx, (size_t)nplanes * cap);
-    int* count = arena_take_t<int>(ctx, nl);
-    int* first = arena_take_t<int>(ctx, nl);
-    int* map = arena_take_t<int>(ctx, nl);
-    int* nseeds = arena_take_t<int>(ctx, nplanes);
     AMT_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)nplanes * hn * 4, ctx->stream));
     AMT_HIP_CHECK(hipMemsetAsync(M, 0, (size_t)nplanes * hn * 4, ctx->stream));
     AMT_HIP_CHECK(hipMemsetAsync(count, 0, nl * 4, ctx->stream));
@@ -936,43 +948,22 @@ extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float*
     hipLaunchKernelGGL(cp_apply_kernel, gpx, dim3(256), 0, ctx->stream, labels_out, map, n, cap);
     AMT_LAUNCH_CHECK();
     if (!post) return AMT_OK;
-    cp_box* box = arena_take_t<cp_box>(ctx, nl);
-    int* cnt = arena_take_t<int>(ctx, nl);
-    unsigned long long* sums = arena_take_t<unsigned long long>(ctx, 2 * nl);
-    double* err = arena_take_t<double>(ctx, nl);
-    int* center = arena_take_t<int>(ctx, 2 * nl);
-    int* nit = arena_take_t<int>(ctx, nplanes);
-    int* nlab1 = arena_take_t<int>(ctx, nplanes);  // number of get_masks labels (count_dev becomes the final count)
-    double* TA = arena_take_t<double>(ctx, (size_t)nplanes * n);
-    double* TB = arena_take_t<double>(ctx, (size_t)nplanes * n);
     AMT_HIP_CHECK(hipMemcpyAsync(nlab1, count_dev, (size_t)nplanes * 4, hipMemcpyDeviceToDevice, ctx->stream));
     const bool want_err = flow_threshold > 0.0f;
     AMT_TRY(cp_flow_errors(ctx, labels_out, dP, nlab1, box, cnt, sums, center, nit, TA, TB, err, nplanes, H, W, cap, want_err));
-    return cp_finish(ctx, labels_out, nlab1, count_dev, box, cnt, err, flow_threshold, min_size, fill_holes, nplanes, H, W,
-                     cap);
+    return cp_finish(ctx, fs, labels_out, nlab1, count_dev, box, cnt, err, flow_threshold, min_size, fill_holes, nplanes, H,
+                     W, cap);
 }
 
 // step 6 (and the flow filter's verdicts): keep flags -> new numbers -> hole filling -> labels_io in place.
 // nlab1[plane] = number of labels in labels_io (1..nlab1), count_dev receives the final number (stays -1 where it was -1).
-// Scratch comes from the caller's arena reservation (cp_finish_bytes).
-static size_t cp_finish_bytes(int nplanes, size_t n, int cap, int fill_holes) {
-    const size_t nl = (size_t)nplanes * (cap + 1);
-    return 4 * amt_align(nl * 4) + 2 * amt_align((size_t)nplanes * 4) +
-           (fill_holes ? 2 * amt_align((size_t)nplanes * n * 4) + amt_align((size_t)nplanes * n) : 0);
-}
-
-static int cp_finish(amt_ctx* ctx, int32_t* labels_out, const int* nlab1, int32_t* count_dev, const cp_box* box,
-                     const int* cnt, const double* err, float flow_threshold, int min_size, int fill_holes, int nplanes,
-                     int H, int W, int cap) {
+static int cp_finish(amt_ctx* ctx, const cp_finish_scratch& fs, int32_t* labels_out, const int* nlab1, int32_t* count_dev,
+                     const cp_box* box, const int* cnt, const double* err, float flow_threshold, int min_size,
+                     int fill_holes, int nplanes, int H, int W, int cap) {
     const size_t n = (size_t)H * W;
     const size_t nl = (size_t)nplanes * (cap + 1);
     dim3 gpx(amt_grid_for(n, 256, 4096), nplanes);
-    int* keep = arena_take_t<int>(ctx, nl);
-    int* keepflow = arena_take_t<int>(ctx, nl);
-    int* scan = arena_take_t<int>(ctx, nl);
-    int* map2 = arena_take_t<int>(ctx, nl);
-    int* total = arena_take_t<int>(ctx, nplanes);
-    int* nested = arena_take_t<int>(ctx, nplanes);
+    int *keep = fs.keep, *keepflow = fs.keepflow, *scan = fs.scan, *map2 = fs.map2, *total = fs.total, *nested = fs.nested;
     dim3 glab(amt_grid_for((size_t)cap + 1, 256, 64), nplanes);
     hipLaunchKernelGGL(cp_keep_kernel, glab, dim3(256), 0, ctx->stream, cnt, err, nlab1, keep, cap, min_size,
                        (double)flow_threshold);
@@ -986,9 +977,8 @@ static int cp_finish(amt_ctx* ctx, int32_t* labels_out, const int* nlab1, int32_
         AMT_LAUNCH_CHECK();
         return AMT_OK;
     }
-    int* fill = arena_take_t<int>(ctx, (size_t)nplanes * n);
-    int* work = arena_take_t<int>(ctx, (size_t)nplanes * n);
-    unsigned char* bytes = arena_take_t<unsigned char>(ctx, (size_t)nplanes * n);
+    int *fill = fs.fill, *work = fs.work;
+    unsigned char* bytes = fs.bytes;
     AMT_HIP_CHECK(hipMemsetAsync(fill, 0, (size_t)nplanes * n * 4, ctx->stream));
     AMT_HIP_CHECK(hipMemsetAsync(nested, 0, (size_t)nplanes * 4, ctx->stream));
     const int gl = cap < 2048 ? cap : 2048;
@@ -1023,16 +1013,16 @@ extern "C" int amt_cellpose_flow_error(amt_ctx* ctx, const int32_t* labels, cons
     const size_t n = (size_t)H * W;
     const int cap = max_label;
     const size_t nl = (size_t)nplanes * (cap + 1);
-    AMT_TRY(amt_arena_begin(ctx, amt_align(nl * sizeof(cp_box)) + amt_align(nl * 4) + amt_align(nl * 16) + amt_align(nl * 8) +
-                                     amt_align(nl * 8) + amt_align((size_t)nplanes * 4) + 2 * amt_align((size_t)nplanes * n * 8)));
-    cp_box* box = arena_take_t<cp_box>(ctx, nl);
-    int* cnt = arena_take_t<int>(ctx, nl);
-    unsigned long long* sums = arena_take_t<unsigned long long>(ctx, 2 * nl);
-    int* center = arena_take_t<int>(ctx, 2 * nl);
-    double* err = arena_take_t<double>(ctx, nl);
-    int* nit = arena_take_t<int>(ctx, nplanes);
-    double* TA = arena_take_t<double>(ctx, (size_t)nplanes * n);
-    double* TB = arena_take_t<double>(ctx, (size_t)nplanes * n);
+    amt_scratch s(ctx);
+    amt_buf<cp_box> box(s, nl);
+    amt_buf<int> cnt(s, nl);
+    amt_buf<unsigned long long> sums(s, 2 * nl);
+    amt_buf<int> center(s, 2 * nl);
+    amt_buf<double> err(s, nl);
+    amt_buf<int> nit(s, nplanes);
+    amt_buf<double> TA(s, (size_t)nplanes * n);
+    amt_buf<double> TB(s, (size_t)nplanes * n);
+    AMT_TRY(s.commit());
     AMT_TRY(cp_flow_errors(ctx, labels, dP, nlabels_dev, box, cnt, sums, center, nit, TA, TB, err, nplanes, H, W, cap, true));
     // err is (cap + 1) per plane with slot 0 unused: hand out slots 1..cap
     for (int p = 0; p < nplanes; ++p)
@@ -1050,13 +1040,14 @@ extern "C" int amt_fill_holes_remove_small(amt_ctx* ctx, int32_t* labels_io, con
     const size_t n = (size_t)H * W;
     const int cap = max_label;
     const size_t nl = (size_t)nplanes * (cap + 1);
-    AMT_TRY(amt_arena_begin(ctx, amt_align(nl * sizeof(cp_box)) + amt_align(nl * 4) + amt_align(nl * 16) +
-                                     cp_finish_bytes(nplanes, n, cap, fill_holes)));
-    cp_box* box = arena_take_t<cp_box>(ctx, nl);
-    int* cnt = arena_take_t<int>(ctx, nl);
-    unsigned long long* sums = arena_take_t<unsigned long long>(ctx, 2 * nl);
+    amt_scratch s(ctx);
+    amt_buf<cp_box> box(s, nl);
+    amt_buf<int> cnt(s, nl);
+    amt_buf<unsigned long long> sums(s, 2 * nl);
+    cp_finish_scratch fs(s, nl, (size_t)nplanes * n, nplanes, true, fill_holes);
+    AMT_TRY(s.commit());
     AMT_TRY(cp_flow_errors(ctx, labels_io, nullptr, nlabels_dev, box, cnt, sums, nullptr, nullptr, nullptr, nullptr, nullptr,
                            nplanes, H, W, cap, false));
     AMT_HIP_CHECK(hipMemcpyAsync(count_dev, nlabels_dev, (size_t)nplanes * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    return cp_finish(ctx, labels_io, nlabels_dev, count_dev, box, cnt, nullptr, 0.0f, min_size, fill_holes, nplanes, H, W, cap);
+    return cp_finish(ctx, fs, labels_io, nlabels_dev, count_dev, box, cnt, nullptr, 0.0f, min_size, fill_holes, nplanes, H, W, cap);
 }

@@ -237,8 +237,9 @@ extern "C" int amt_edt(amt_ctx* ctx, const uint8_t* mask, int32_t* d2_out, doubl
     const size_t tiles64 = (size_t)((W + 63) / 64) * ((H + 63) / 64) * nplanes;
     const int WW = (W + 63) / 64;
     const size_t nwords = (size_t)nplanes * H * WW;
-    AMT_TRY(amt_arena_begin(ctx, amt_align(nwords * 8)));
-    unsigned long long* zw = arena_take_t<unsigned long long>(ctx, nwords);
+    amt_scratch s(ctx);
+    amt_buf<unsigned long long> zw(s, nwords);
+    AMT_TRY(s.commit());
     const int fast = W % 16 == 0 && (reinterpret_cast<uintptr_t>(mask) & 15) == 0;
     hipLaunchKernelGGL(edt_zero_words_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, ctx->stream, mask, zw, H,
                        W, WW, nwords, fast);

@@ -278,8 +278,9 @@ extern "C" int amt_expand_labels(amt_ctx* ctx, const int32_t* labels, int32_t* o
     while ((long long)(r + 1) * (r + 1) <= (long long)nm) ++r;
     const int WW = (W + 63) / 64;
     const size_t nwords = (size_t)nplanes * H * WW;
-    AMT_TRY(amt_arena_begin(ctx, amt_align(nwords * 8)));
-    unsigned long long* lw = arena_take_t<unsigned long long>(ctx, nwords);
+    amt_scratch s(ctx);
+    amt_buf<unsigned long long> lw(s, nwords);
+    AMT_TRY(s.commit());
     const size_t nwaves = (nwords + XL_WORDS_PER_WAVE - 1) / XL_WORDS_PER_WAVE;
     hipLaunchKernelGGL(expand_label_words_kernel, dim3((unsigned)((nwaves + 3) / 4)), dim3(256), 0, ctx->stream, labels, lw, W,
                        WW, nwords);

@@ -1085,7 +1085,6 @@ extern "C" int amt_gaussian(amt_ctx* ctx, const void* in, int in_dtype, double s
                 "gaussian: strided input needs radius >= 1");
     if (nplanes == 0) return AMT_OK;
     size_t n = (size_t)nplanes * H * W;
-    const size_t kbytes = minmax_dev ? amt_align((size_t)2 * nplanes * 8) : 0;
     if (radius == 0) {  // sigma too small: scipy's kernel is the single weight 1.0
         if (in_dtype == AMT_U16) {
             AMT_TRY(amt_convert_u16_f64(ctx, (const uint16_t*)in, scale, out, n));
@@ -1095,18 +1094,18 @@ extern "C" int amt_gaussian(amt_ctx* ctx, const void* in, int in_dtype, double s
             AMT_LAUNCH_CHECK();
         }
         if (minmax_dev) {
-            AMT_TRY(amt_arena_begin(ctx, kbytes));
-            unsigned long long* keys = (unsigned long long*)amt_arena_take(ctx, kbytes);
+            amt_scratch s(ctx);
+            amt_buf<unsigned long long> keys(s, (size_t)2 * nplanes);
+            AMT_TRY(s.commit());
             AMT_TRY(amt_i_minmax_f64(ctx, out, keys, minmax_dev, nplanes, (size_t)H * W));
         }
         return AMT_OK;
     }
-    size_t wbytes = amt_align((2 * radius + 1) * sizeof(double));
-    size_t tmpbytes = radius > FR_MAX ? amt_align(n * sizeof(double)) : 0;
-    AMT_TRY(amt_arena_begin(ctx, wbytes + tmpbytes + kbytes));
-    double* wdev = (double*)amt_arena_take(ctx, wbytes);
-    double* tmp = tmpbytes ? (double*)amt_arena_take(ctx, tmpbytes) : nullptr;
-    unsigned long long* keys = kbytes ? (unsigned long long*)amt_arena_take(ctx, kbytes) : nullptr;
+    amt_scratch s(ctx);
+    amt_buf<double> wdev(s, 2 * radius + 1);
+    amt_buf<double> tmp(s, n, radius > FR_MAX);
+    amt_buf<unsigned long long> keys(s, (size_t)2 * nplanes, minmax_dev != nullptr);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, wdev, weights, (2 * radius + 1) * sizeof(double)));
     if (!minmax_dev)
         return gaussian_dispatch(ctx, in, in_dtype, scale, out, tmp, nplanes, H, W, wdev, radius, mode, cval,
@@ -1376,14 +1375,12 @@ extern "C" int amt_gaussian_otsu_codes(amt_ctx* ctx, const uint16_t* in, double 
     bool ordered = scale > 0.0 && (size_t)H * W <= 0xffffffffull;
     for (int i = 0; i <= 2 * radius; ++i) ordered = ordered && weights[i] >= 0.0;
     if (!ordered) prefix = nullptr;
-    const size_t wbytes = amt_align((2 * radius + 1) * sizeof(double)), kbytes = amt_align((size_t)2 * nplanes * 8);
-    const size_t cbytes = prefix ? amt_align((size_t)nplanes * PFX_CNT_STRIDE * sizeof(uint32_t)) : 0;
-    const size_t lbytes = prefix ? amt_align((size_t)nplanes * PFX_CAP * sizeof(uint32_t)) : 0;
-    AMT_TRY(amt_arena_begin(ctx, wbytes + kbytes + cbytes + lbytes));
-    double* wdev = (double*)amt_arena_take(ctx, wbytes);
-    unsigned long long* keys = (unsigned long long*)amt_arena_take(ctx, kbytes);
-    uint32_t* und_count = prefix ? (uint32_t*)amt_arena_take(ctx, cbytes) : nullptr;
-    uint32_t* und_list = prefix ? (uint32_t*)amt_arena_take(ctx, lbytes) : nullptr;
+    amt_scratch s(ctx);
+    amt_buf<double> wdev(s, 2 * radius + 1);
+    amt_buf<unsigned long long> keys(s, (size_t)2 * nplanes);
+    amt_buf<uint32_t> und_count(s, (size_t)nplanes * PFX_CNT_STRIDE, prefix != nullptr);
+    amt_buf<uint32_t> und_list(s, (size_t)nplanes * PFX_CAP, prefix != nullptr);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, wdev, weights, (2 * radius + 1) * sizeof(double)));
     switch (radius) {
 #define AMT_CODES_CASE(RR)                                                                                            \
@@ -1427,9 +1424,9 @@ extern "C" int amt_convolve_axis0(amt_ctx* ctx, const void* in, int in_dtype, do
     AMT_REQUIRE((const void*)in != (const void*)out, "convolve_axis0: in-place operation is not supported");
     if (nplanes == 0) return AMT_OK;
     const int r = radius;
-    size_t wbytes = amt_align((2 * r + 1) * sizeof(double));
-    AMT_TRY(amt_arena_begin(ctx, wbytes));
-    double* wdev = (double*)amt_arena_take(ctx, wbytes);
+    amt_scratch s(ctx);
+    amt_buf<double> wdev(s, 2 * r + 1);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, wdev, weights, (2 * r + 1) * sizeof(double)));
     const size_t esz = in_dtype == AMT_U16 ? 2 : 8;
     int TH = 128;
@@ -1454,17 +1451,15 @@ extern "C" int amt_dog(amt_ctx* ctx, const void* in, int in_dtype, double scale,
     AMT_REQUIRE(r_lo >= 1 && r_hi >= 1, "dog: radii must be >= 1");
     if (nplanes == 0) return AMT_OK;
     size_t n = (size_t)nplanes * H * W;
-    size_t wl = amt_align((2 * r_lo + 1) * sizeof(double)), wh = amt_align((2 * r_hi + 1) * sizeof(double));
-    size_t nb = amt_align(n * sizeof(double));
     bool need_tmp = (r_lo > FR_MAX) || (r_hi > FR_MAX);
     // a wide second Gaussian (two-pass path) subtracts itself from the first in its horizontal pass: no ghi plane, no
     // subtraction pass (the reference's default sigmas 0.6 / 16 take this route)
     const bool fused_sub = r_hi > FR_MAX;
-    AMT_TRY(amt_arena_begin(ctx, wl + wh + (fused_sub ? 0 : nb) + (need_tmp ? nb : 0)));
-    double* wlo_d = (double*)amt_arena_take(ctx, wl);
-    double* whi_d = (double*)amt_arena_take(ctx, wh);
-    double* ghi = fused_sub ? nullptr : (double*)amt_arena_take(ctx, nb);
-    double* tmp = need_tmp ? (double*)amt_arena_take(ctx, nb) : nullptr;
+    amt_scratch s(ctx);
+    amt_buf<double> wlo_d(s, 2 * r_lo + 1), whi_d(s, 2 * r_hi + 1);
+    amt_buf<double> ghi(s, n, !fused_sub);
+    amt_buf<double> tmp(s, n, need_tmp);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, wlo_d, w_lo, (2 * r_lo + 1) * sizeof(double)));
     AMT_TRY(amt_param_upload(ctx, whi_d, w_hi, (2 * r_hi + 1) * sizeof(double)));
     AMT_TRY(gaussian_dispatch(ctx, in, in_dtype, scale, out, tmp, nplanes, H, W, wlo_d, r_lo, mode, cval));

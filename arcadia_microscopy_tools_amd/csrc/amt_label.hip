@@ -1121,35 +1121,31 @@ static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, 
     const size_t cap = amt_i_rootlist_cap(W);
     const size_t nlist = (size_t)nplanes * trows;
     const size_t nwords = (n + 63) / 64;
-    const size_t ntiles_all = (size_t)nplanes * trows * ((W + 63) / 64);  // run tables of the 0 / 1 mask path
-    AMT_TRY(amt_arena_begin(ctx, 2 * amt_align((size_t)nplanes * n * 4) + amt_align(nlist * cap * 4) +
-                                     amt_align((size_t)nplanes * nblk * 4) + amt_align(nlist * 4) +
-                                     amt_align((size_t)nplanes * nwords * 8) +
-                                     amt_align(amt_i_ccl_scratch_ints(nplanes, H, W) * 4) +
-                                     amt_align(ntiles_all * 64 * 8) + amt_align(ntiles_all * RT_CAP * 2) +
-                                     amt_align(ntiles_all * 4)));
-    int* L = arena_take_t<int>(ctx, (size_t)nplanes * n);
-    // "a byte other than 0 / 1 was seen" + the tiles' column words (ccl_tile_bits_kernel)
-    int* multi = arena_take_t<int>(ctx, amt_i_ccl_scratch_ints(nplanes, H, W));
-    int* T = arena_take_t<int>(ctx, (size_t)nplanes * n);
-    int* rootlist = arena_take_t<int>(ctx, nlist * cap);
-    int* blk = arena_take_t<int>(ctx, (size_t)nplanes * nblk);
-    int* nroots = arena_take_t<int>(ctx, nlist);
-    unsigned long long* bitmap = arena_take_t<unsigned long long>(ctx, (size_t)nplanes * nwords);
-    // chunk counts, list counts and the root bitmap were taken from the arena one after the other: ONE fill clears them
-    AMT_HIP_CHECK(hipMemsetAsync(blk, 0, (size_t)((char*)(bitmap + (size_t)nplanes * nwords) - (char*)blk), ctx->stream));
     // tile-local union-find + seams; only the listed tile roots are compressed, pixels resolve in two hops
     const int segs = (W + 63) / 64;
     const int ntiles = nplanes * trows * segs;
     const bool runs = in_dtype == AMT_U8 && W % 16 == 0 &&
                       (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
                       n % 16 == 0 && (size_t)ntiles * 64 < 0x7fffffffull;
+    amt_scratch s(ctx);
+    amt_buf<int> L(s, (size_t)nplanes * n);
+    // "a byte other than 0 / 1 was seen" + the tiles' column words (ccl_tile_bits_kernel)
+    amt_buf<int> multi(s, amt_i_ccl_scratch_ints(nplanes, H, W));
+    amt_buf<int> T(s, (size_t)nplanes * n);
+    amt_buf<int> rootlist(s, nlist * cap);
+    amt_buf<int> blk(s, (size_t)nplanes * nblk);
+    amt_buf<int> nroots(s, nlist);
+    amt_buf<unsigned long long> bitmap(s, (size_t)nplanes * nwords);
+    // run tables of the 0 / 1 mask path
+    amt_buf<unsigned long long> tbits(s, (size_t)ntiles * 64, runs);
+    amt_buf<unsigned short> rtab(s, (size_t)ntiles * RT_CAP, runs);
+    amt_buf<int> nruns(s, (size_t)ntiles, runs);
+    AMT_TRY(s.commit());
+    // chunk counts, list counts and the root bitmap are declared one after the other: ONE fill clears them
+    AMT_HIP_CHECK(hipMemsetAsync(blk, 0, (size_t)((char*)(bitmap + (size_t)nplanes * nwords) - (char*)blk.p), ctx->stream));
     if (runs) {
         // 0 / 1 masks: run tables instead of a parent plane.  A batch that turns out to hold other byte values raises
         // *multi; every run-table kernel then stands down and the byte kernels -- which otherwise leave at once -- redo it
-        unsigned long long* tbits = arena_take_t<unsigned long long>(ctx, (size_t)ntiles * 64);
-        unsigned short* rtab = arena_take_t<unsigned short>(ctx, (size_t)ntiles * RT_CAP);
-        int* nruns = arena_take_t<int>(ctx, (size_t)ntiles);
         const uint8_t* in8 = (const uint8_t*)in;
         const bool c8 = connectivity == 2;
         dim3 gs(segs, trows, nplanes);
@@ -1305,9 +1301,10 @@ extern "C" int amt_clear_border(amt_ctx* ctx, const int32_t* in, int32_t* out, i
     AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "clear_border: plane too large");
     if (nplanes == 0) return AMT_OK;
     const size_t n = (size_t)H * W;
-    AMT_TRY(amt_arena_begin(ctx, 2 * amt_align((size_t)nplanes * n * 4)));
-    int* L = arena_take_t<int>(ctx, (size_t)nplanes * n);
-    int* T = arena_take_t<int>(ctx, (size_t)nplanes * n);
+    amt_scratch s(ctx);
+    amt_buf<int> L(s, (size_t)nplanes * n);
+    amt_buf<int> T(s, (size_t)nplanes * n);
+    AMT_TRY(s.commit());
     AMT_HIP_CHECK(hipMemsetAsync(T, 0, (size_t)nplanes * n * 4, ctx->stream));
     AMT_TRY(ccl_roots<int32_t>(ctx, in, L, nullptr, nplanes, H, W, 1));
     dim3 gf(amt_grid_for((size_t)2 * W + 2 * H, 256, 64), nplanes);
@@ -1391,8 +1388,9 @@ extern "C" int amt_relabel_sequential(amt_ctx* ctx, const int32_t* in, int32_t* 
     AMT_REQUIRE(in && out && nplanes >= 0 && max_label >= 0, "relabel_sequential: bad arguments");
     if (nplanes == 0) return AMT_OK;
     size_t msz = (size_t)nplanes * ((size_t)max_label + 1);
-    AMT_TRY(amt_arena_begin(ctx, amt_align(msz * 4)));
-    int* P = arena_take_t<int>(ctx, msz);
+    amt_scratch s(ctx);
+    amt_buf<int> P(s, msz);
+    AMT_TRY(s.commit());
     AMT_HIP_CHECK(hipMemsetAsync(P, 0, msz * 4, ctx->stream));
     dim3 g1(amt_grid_for(n, 256, 4096), nplanes);
     if (n) {
@@ -1475,8 +1473,9 @@ extern "C" int amt_clear_border_relabel(amt_ctx* ctx, const int32_t* in, int32_t
     if (nplanes == 0) return AMT_OK;
     const size_t n = (size_t)H * W;
     size_t msz = (size_t)nplanes * ((size_t)max_label + 1);
-    AMT_TRY(amt_arena_begin(ctx, amt_align(msz * 4)));
-    int* P = arena_take_t<int>(ctx, msz);
+    amt_scratch s(ctx);
+    amt_buf<int> P(s, msz);
+    AMT_TRY(s.commit());
     dim3 g1(amt_grid_for(n, 256, 4096), nplanes);
     if (nlabels_dev) {  // labels 1 .. nlabels[plane] are known to be present: no pass over the image
         hipLaunchKernelGGL(presence_fill_kernel, dim3(amt_grid_for((size_t)max_label + 1, 256, 64), nplanes), dim3(256),
@@ -1725,15 +1724,16 @@ extern "C" int amt_label_sparse(amt_ctx* ctx, const uint8_t* in, int32_t* out, i
     const size_t n = (size_t)H * W;
     const int nblk = (int)((n + SP_CHUNK - 1) / SP_CHUNK);
     const size_t capn = (size_t)nplanes * capacity;
-    AMT_TRY(amt_arena_begin(ctx, 3 * amt_align(capn * 4) + amt_align((size_t)nplanes * nblk * 4) +
-                                     3 * amt_align(nplanes * 4)));
-    int* list = arena_take_t<int>(ctx, capn);
-    int* parent = arena_take_t<int>(ctx, capn);
-    int* flags = arena_take_t<int>(ctx, capn);
-    int* blk = arena_take_t<int>(ctx, (size_t)nplanes * nblk);
-    int* total = arena_take_t<int>(ctx, nplanes);
-    int* total_c = arena_take_t<int>(ctx, nplanes);
-    int* nroots = arena_take_t<int>(ctx, nplanes);
+    amt_scratch s(ctx);
+    amt_buf<int> list_own(s, capn);
+    amt_buf<int> parent(s, capn);
+    amt_buf<int> flags(s, capn);
+    amt_buf<int> blk(s, (size_t)nplanes * nblk);
+    amt_buf<int> total(s, nplanes);
+    amt_buf<int> total_c_own(s, nplanes);
+    amt_buf<int> nroots(s, nplanes);
+    AMT_TRY(s.commit());
+    int *list = list_own, *total_c = total_c_own;
     const unsigned gk0 = amt_grid_for((size_t)capacity, 256, 64);
     if (keep_list) {
         // `out` is zero except where the previous call on these buffers wrote: undo exactly those writes (the list of

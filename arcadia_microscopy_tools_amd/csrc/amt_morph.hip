@@ -238,10 +238,11 @@ extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, i
     if (nplanes == 0) return AMT_OK;
     const int WW = (W + 63) / 64;
     const size_t words = (size_t)nplanes * H * WW;
-    AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(int2) * noffs) + 2 * amt_align(words * 8)));
-    int2* offs = arena_take_t<int2>(ctx, noffs);
-    u64* pa = arena_take_t<u64>(ctx, words);
-    u64* pb = arena_take_t<u64>(ctx, words);
+    amt_scratch s(ctx);
+    amt_buf<int2> offs(s, noffs);
+    amt_buf<u64> pa(s, words);
+    amt_buf<u64> pb(s, words);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, offs, host, sizeof(int2) * noffs));
     const size_t nwords = (size_t)H * WW;
     const unsigned gpack = (unsigned)((nwords + 4 * PACK_WORDS_PER_WAVE - 1) / (4 * PACK_WORDS_PER_WAVE));
@@ -467,9 +468,10 @@ extern "C" int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dty
     const int ry = fh / 2, rx = fw / 2;
     if (noffs <= TOC_MAX_OFFS && 4 * ry <= 16 && 4 * rx <= 64) {
         // single fused kernel: halo of 4 * ry rows and one 64-pixel word per side covers the four primitives
-        AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(int2) * noffs) + amt_align(words * 8)));
-        int2* offs = arena_take_t<int2>(ctx, noffs);
-        u64* pa = arena_take_t<u64>(ctx, words);
+        amt_scratch s(ctx);
+        amt_buf<int2> offs(s, noffs);
+        amt_buf<u64> pa(s, words);
+        AMT_TRY(s.commit());
         AMT_TRY(amt_param_upload(ctx, offs, host, sizeof(int2) * noffs));
         const size_t nwords = (size_t)H * WW;
         const unsigned gpack = (unsigned)((nwords + 4 * PACK_WORDS_PER_WAVE - 1) / (4 * PACK_WORDS_PER_WAVE));
@@ -503,10 +505,11 @@ extern "C" int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dty
         AMT_LAUNCH_CHECK();
         return AMT_OK;
     }
-    AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(int2) * noffs) + 2 * amt_align(words * 8)));
-    int2* offs = arena_take_t<int2>(ctx, noffs);
-    u64* pa = arena_take_t<u64>(ctx, words);
-    u64* pb = arena_take_t<u64>(ctx, words);
+    amt_scratch s(ctx);
+    amt_buf<int2> offs(s, noffs);
+    amt_buf<u64> pa(s, words);
+    amt_buf<u64> pb(s, words);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, offs, host, sizeof(int2) * noffs));
     const size_t nwords = (size_t)H * WW;
     const unsigned gpack = (unsigned)((nwords + 4 * PACK_WORDS_PER_WAVE - 1) / (4 * PACK_WORDS_PER_WAVE));

@@ -80,9 +80,10 @@ extern "C" int amt_overlay(amt_ctx* ctx, const double* background, const double*
         hp.mode[l] = mode_host[l];
     }
     const size_t lbytes = (size_t)(nlayers > 0 ? nlayers : 1) * 1024 * sizeof(double);
-    AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(ov_params)) + amt_align(lbytes)));
-    ov_params* dp = (ov_params*)amt_arena_take(ctx, sizeof(ov_params));
-    double* dl = (double*)amt_arena_take(ctx, lbytes);
+    amt_scratch s(ctx);
+    amt_buf<ov_params> dp(s, 1);
+    amt_buf<double> dl(s, lbytes / sizeof(double));
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, dp, &hp, sizeof(hp)));
     if (nlayers) AMT_TRY(amt_param_upload(ctx, dl, luts_host, (size_t)nlayers * 1024 * sizeof(double)));
     const size_t n = (size_t)H * W;

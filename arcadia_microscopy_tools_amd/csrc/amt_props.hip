@@ -688,16 +688,15 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
     const size_t n = (size_t)H * W;
     const size_t nlab = (size_t)nplanes * max_label;
     const size_t cap = want_morph ? n : 1;  // row-extent entries per plane (sum of bbox heights)
-    size_t need = amt_align(nlab * A_NACC * 8) + amt_align(nlab * 16) + amt_align(nlab * 4) + amt_align(nplanes * 4) +
-                  amt_align((size_t)nplanes * cap * 8) + 2 * amt_align((size_t)nplanes * 3 * cap * 8);
-    AMT_TRY(amt_arena_begin(ctx, need));
-    u64* acc = arena_take_t<u64>(ctx, nlab * A_NACC);
-    int* bbox = arena_take_t<int>(ctx, nlab * 4);
-    int* hoff = arena_take_t<int>(ctx, nlab);
-    int* htot = arena_take_t<int>(ctx, nplanes);
-    int2* rows = arena_take_t<int2>(ctx, (size_t)nplanes * cap);
-    int2* chainL = arena_take_t<int2>(ctx, (size_t)nplanes * 3 * cap);
-    int2* chainR = arena_take_t<int2>(ctx, (size_t)nplanes * 3 * cap);
+    amt_scratch s(ctx);
+    amt_buf<u64> acc(s, nlab * A_NACC);
+    amt_buf<int> bbox(s, nlab * 4);
+    amt_buf<int> hoff(s, nlab);
+    amt_buf<int> htot(s, nplanes);
+    amt_buf<int2> rows(s, (size_t)nplanes * cap);
+    amt_buf<int2> chainL(s, (size_t)nplanes * 3 * cap);
+    amt_buf<int2> chainR(s, (size_t)nplanes * 3 * cap);
+    AMT_TRY(s.commit());
     hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
     AMT_LAUNCH_CHECK();
     if (want_morph) {  // the perimeter pass stages every label tile anyway: it folds the bounding boxes too
@@ -819,8 +818,9 @@ extern "C" int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels
                 "regionprops_intensity_f64: bad arguments");
     if (nplanes == 0 || max_label == 0) return AMT_OK;
     const size_t nlab = (size_t)nplanes * max_label;
-    AMT_TRY(amt_arena_begin(ctx, amt_align(nlab * 16)));
-    int* bbox = arena_take_t<int>(ctx, nlab * 4);
+    amt_scratch s(ctx);
+    amt_buf<int> bbox(s, nlab * 4);
+    AMT_TRY(s.commit());
     hipLaunchKernelGGL(bbox_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, bbox, nlab);
     AMT_LAUNCH_CHECK();
     hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels, bbox,
@@ -1253,19 +1253,17 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
     const size_t nlab = (size_t)nplanes * max_label;
     const size_t cap = feret ? n : 1;
     const size_t hwords = filled ? (size_t)H * ((W + 63) / 64) : 0;
-    size_t need = amt_align(nlab * A_NACC * 8) + amt_align(nlab * 16) + amt_align(nlab * 4) + amt_align(nplanes * 4) +
-                  amt_align((size_t)nplanes * cap * 8) + amt_align((size_t)nplanes * cap * 8) +
-                  2 * amt_align((size_t)nplanes * 3 * cap * 8) + amt_align((size_t)nplanes * 2 * hwords * 8);
-    AMT_TRY(amt_arena_begin(ctx, need));
-    u64* acc = arena_take_t<u64>(ctx, nlab * A_NACC);
-    int* bbox = arena_take_t<int>(ctx, nlab * 4);
-    int* hoff = arena_take_t<int>(ctx, nlab);
-    int* htot = arena_take_t<int>(ctx, nplanes);
-    int2* rows = arena_take_t<int2>(ctx, (size_t)nplanes * cap);
-    int2* crows = arena_take_t<int2>(ctx, (size_t)nplanes * cap);
-    int2* chainL = arena_take_t<int2>(ctx, (size_t)nplanes * 3 * cap);
-    int2* chainR = arena_take_t<int2>(ctx, (size_t)nplanes * 3 * cap);
-    u64* hscratch = arena_take_t<u64>(ctx, (size_t)nplanes * 2 * hwords);
+    amt_scratch s(ctx);
+    amt_buf<u64> acc(s, nlab * A_NACC);
+    amt_buf<int> bbox(s, nlab * 4);
+    amt_buf<int> hoff(s, nlab);
+    amt_buf<int> htot(s, nplanes);
+    amt_buf<int2> rows(s, (size_t)nplanes * cap);
+    amt_buf<int2> crows(s, (size_t)nplanes * cap);
+    amt_buf<int2> chainL(s, (size_t)nplanes * 3 * cap);
+    amt_buf<int2> chainR(s, (size_t)nplanes * 3 * cap);
+    amt_buf<u64> hscratch(s, (size_t)nplanes * 2 * hwords);
+    AMT_TRY(s.commit());
     hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
     AMT_LAUNCH_CHECK();
     hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels,

@@ -945,8 +945,9 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
     AMT_REQUIRE(noffs > 0, "rank_filter: empty footprint");
     if (nplanes == 0) return AMT_OK;
     const int ry = fh / 2, rx = fw / 2;
-    AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(int2) * noffs)));
-    int2* offs = (int2*)amt_arena_take(ctx, sizeof(int2) * noffs);
+    amt_scratch s(ctx);
+    amt_buf<int2> offs(s, noffs);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, offs, host, sizeof(int2) * noffs));
     if (op <= 1 && dtype == AMT_U16 && (size_t)H * W >= 16) {  // uint16, small symmetric run footprint: packed kernel
         mm_params P;
@@ -1072,8 +1073,9 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
         const size_t smem2 = amt_align((size_t)(kmax + 1) * tsz * ksz2, 16) +
                              (size_t)(RT_W + 2 * rx + RT_H + 2 * ry) * sizeof(int);
         if (ok && smem2 <= 96 * 1024) {
-            AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(run3) * nruns)));
-            run3* druns = (run3*)amt_arena_take(ctx, sizeof(run3) * nruns);
+            amt_scratch s(ctx);
+            amt_buf<run3> druns(s, nruns);
+            AMT_TRY(s.commit());
             AMT_TRY(amt_param_upload(ctx, druns, hruns, sizeof(run3) * nruns));
             dim3 grid2((W + RT_W - 1) / RT_W, (H + RT_H - 1) / RT_H, nplanes);
             if (dtype == AMT_U16) {

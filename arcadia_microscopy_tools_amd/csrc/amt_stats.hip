@@ -164,11 +164,9 @@ extern "C" int amt_hist_u16(amt_ctx* ctx, const uint16_t* in, uint32_t* hist, in
     AMT_REQUIRE(in && hist && nplanes >= 0, "hist_u16: bad arguments");
     if (nplanes == 0) return AMT_OK;
     const size_t sb = hist_u16_scratch_bytes(nplanes, n);
-    uint32_t* scratch = nullptr;
-    if (sb) {
-        AMT_TRY(amt_arena_begin(ctx, sb));
-        scratch = reinterpret_cast<uint32_t*>(amt_arena_take(ctx, sb));
-    }
+    amt_scratch s(ctx);
+    amt_buf<uint32_t> scratch(s, sb / sizeof(uint32_t), sb > 0);
+    if (sb) AMT_TRY(s.commit());
     return hist_u16_launch(ctx, in, hist, nplanes, n, scratch);
 }
 
@@ -257,8 +255,9 @@ extern "C" int amt_minmax_f64(amt_ctx* ctx, const double* in, double* minmax_dev
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && minmax_dev && nplanes >= 0, "minmax_f64: bad arguments");
     if (nplanes == 0) return AMT_OK;
-    AMT_TRY(amt_arena_begin(ctx, amt_align(2 * nplanes * sizeof(unsigned long long))));
-    unsigned long long* keys = arena_take_t<unsigned long long>(ctx, 2 * nplanes);
+    amt_scratch s(ctx);
+    amt_buf<unsigned long long> keys(s, 2 * nplanes);
+    AMT_TRY(s.commit());
     return minmax_f64_launch(ctx, in, keys, minmax_dev, nplanes, n);
 }
 
@@ -638,23 +637,23 @@ extern "C" int amt_threshold_value(amt_ctx* ctx, const void* in, int in_dtype, i
     if (status_dev) AMT_HIP_CHECK(hipMemsetAsync(status_dev, 0, (size_t)nplanes * sizeof(int32_t), ctx->stream));
     if (in_dtype == AMT_U16) {
         const size_t sb = hist_u16_scratch_bytes(nplanes, n);
-        AMT_TRY(amt_arena_begin(ctx, amt_align((size_t)nplanes * 65536 * sizeof(uint32_t)) + sb));
-        uint32_t* hist = arena_take_t<uint32_t>(ctx, (size_t)nplanes * 65536);
-        uint32_t* scratch = sb ? reinterpret_cast<uint32_t*>(amt_arena_take(ctx, sb)) : nullptr;
+        amt_scratch s(ctx);
+        amt_buf<uint32_t> hist(s, (size_t)nplanes * 65536);
+        amt_buf<uint32_t> scratch(s, sb / sizeof(uint32_t), sb > 0);
+        AMT_TRY(s.commit());
         AMT_TRY(hist_u16_launch(ctx, (const uint16_t*)in, hist, nplanes, n, scratch));
         hipLaunchKernelGGL(otsu_u16_kernel, dim3(nplanes), dim3(1024), 0, ctx->stream, hist, thr_dev);
         AMT_LAUNCH_CHECK();
         return AMT_OK;
     }
     AMT_REQUIRE(nbins >= 2 && nbins <= 4096, "threshold_value: nbins %d out of range", nbins);
-    AMT_TRY(amt_arena_begin(ctx, amt_align(2 * nplanes * 8) * 2 + amt_align((size_t)nplanes * nbins * 4)));
-    unsigned long long* keys = arena_take_t<unsigned long long>(ctx, 2 * nplanes);
-    double* mm = arena_take_t<double>(ctx, 2 * nplanes);
-    uint32_t* hist = arena_take_t<uint32_t>(ctx, (size_t)nplanes * nbins);
-    if (minmax_dev)
-        mm = const_cast<double*>(minmax_dev);
-    else
-        AMT_TRY(minmax_f64_launch(ctx, (const double*)in, keys, mm, nplanes, n));
+    amt_scratch s(ctx);
+    amt_buf<unsigned long long> keys(s, 2 * nplanes);
+    amt_buf<double> mm_own(s, 2 * nplanes);
+    amt_buf<uint32_t> hist(s, (size_t)nplanes * nbins);
+    AMT_TRY(s.commit());
+    const double* mm = minmax_dev ? minmax_dev : mm_own.p;
+    if (!minmax_dev) AMT_TRY(minmax_f64_launch(ctx, (const double*)in, keys, mm_own, nplanes, n));
     AMT_TRY(hist_f64_launch(ctx, (const double*)in, mm, hist, nbins, nplanes, n));
     return amt_i_otsu_from_hist(ctx, hist, mm, nbins, thr_dev, nullptr, nplanes);
 }
@@ -667,8 +666,9 @@ extern "C" int amt_otsu_f64_bins(amt_ctx* ctx, const double* in, const double* m
     AMT_REQUIRE(in && minmax_dev && thr_dev && thr_code_dev && bins && nplanes >= 0, "otsu_f64_bins: bad arguments");
     if (nplanes == 0) return AMT_OK;
     const int nbins = 256;
-    AMT_TRY(amt_arena_begin(ctx, amt_align((size_t)nplanes * nbins * 4)));
-    uint32_t* hist = arena_take_t<uint32_t>(ctx, (size_t)nplanes * nbins);
+    amt_scratch s(ctx);
+    amt_buf<uint32_t> hist(s, (size_t)nplanes * nbins);
+    AMT_TRY(s.commit());
     AMT_TRY(hist_f64_launch(ctx, in, minmax_dev, hist, nbins, nplanes, n, bins));
     return amt_i_otsu_from_hist(ctx, hist, minmax_dev, nbins, thr_dev, thr_code_dev, nplanes);
 }
@@ -836,10 +836,11 @@ extern "C" int amt_percentile_u16(amt_ctx* ctx, const uint16_t* in, const double
     rank_req reqs[64];
     make_rank_reqs(q_host, nq, n, reqs);
     const size_t sb = hist_u16_scratch_bytes(nplanes, n);
-    AMT_TRY(amt_arena_begin(ctx, amt_align((size_t)nplanes * 65536 * 4) + amt_align(sizeof(reqs)) + sb));
-    uint32_t* hist = arena_take_t<uint32_t>(ctx, (size_t)nplanes * 65536);
-    rank_req* rd = arena_take_t<rank_req>(ctx, 64);
-    uint32_t* scratch = sb ? reinterpret_cast<uint32_t*>(amt_arena_take(ctx, sb)) : nullptr;
+    amt_scratch s(ctx);
+    amt_buf<uint32_t> hist(s, (size_t)nplanes * 65536);
+    amt_buf<rank_req> rd(s, 64);
+    amt_buf<uint32_t> scratch(s, sb / sizeof(uint32_t), sb > 0);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, rd, reqs, sizeof(rank_req) * nq));
     AMT_TRY(hist_u16_launch(ctx, in, hist, nplanes, n, scratch));
     hipLaunchKernelGGL(percentile_u16_kernel, dim3(nplanes), dim3(1024), 0, ctx->stream, hist, rd, nq, out_dev);
@@ -1595,14 +1596,13 @@ extern "C" int amt_percentile_f64(amt_ctx* ctx, const double* in, const double* 
     int want = 4096 / nplanes;
     want = want < 64 ? 64 : (want > 256 ? 256 : want);
     const unsigned gparts = amt_grid_for(n, 256 * PQ_VPT, (unsigned)want);
-    AMT_TRY(amt_arena_begin(ctx, amt_align(sizeof(rank_req) * 8) + amt_align(sizeof(pq_bracket) * nbr) +
-                                     amt_align(nbr * cap * 8) + amt_align(sizeof(sel_state) * 2 * nbr) +
-                                     amt_align(sizeof(uint4) * nbr * gparts)));
-    rank_req* rd = arena_take_t<rank_req>(ctx, 8);
-    pq_bracket* br = arena_take_t<pq_bracket>(ctx, nbr);
-    unsigned long long* lists = arena_take_t<unsigned long long>(ctx, nbr * cap);
-    sel_state* res = arena_take_t<sel_state>(ctx, 2 * nbr);
-    uint4* partial = arena_take_t<uint4>(ctx, nbr * gparts);
+    amt_scratch s(ctx);
+    amt_buf<rank_req> rd(s, 8);
+    amt_buf<pq_bracket> br(s, nbr);
+    amt_buf<unsigned long long> lists(s, nbr * cap);
+    amt_buf<sel_state> res(s, 2 * nbr);
+    amt_buf<uint4> partial(s, nbr * gparts);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, rd, reqs, sizeof(rank_req) * nq));
     hipLaunchKernelGGL(pq_sample_kernel, dim3(nplanes), dim3(1024), (size_t)PQ_M * 8, ctx->stream, in, rd, nq, br, n);
     AMT_LAUNCH_CHECK();
@@ -1642,16 +1642,14 @@ static int percentile_f64_radix(amt_ctx* ctx, const double* in, const rank_req* 
     // candidate lists: keys matching the first 24 resolved bits (a 1/4096 slice of the exponent / mantissa space);
     // n / 16 entries per slot cover everything but massive ties, which fall back to full scans
     const size_t cap = n / 16 + 1024;
-    size_t need = amt_align(sizeof(rank_req) * 8) + amt_align(sizeof(sel_state) * 2 * total) +
-                  amt_align((size_t)8 * total * 256 * 4) + amt_align((size_t)total * cap * 8) +
-                  amt_align((size_t)total * 4) + amt_align((size_t)nplanes * 4);
-    AMT_TRY(amt_arena_begin(ctx, need));
-    rank_req* rd = arena_take_t<rank_req>(ctx, 8);
-    sel_state* st = arena_take_t<sel_state>(ctx, 2 * (size_t)total);
-    uint32_t* counts = arena_take_t<uint32_t>(ctx, (size_t)8 * total * 256);
-    unsigned long long* cand = arena_take_t<unsigned long long>(ctx, (size_t)total * cap);
-    unsigned* ncand = arena_take_t<unsigned>(ctx, (size_t)total);
-    int* overflow = arena_take_t<int>(ctx, nplanes);
+    amt_scratch s(ctx);
+    amt_buf<rank_req> rd(s, 8);
+    amt_buf<sel_state> st(s, 2 * (size_t)total);
+    amt_buf<uint32_t> counts(s, (size_t)8 * total * 256);
+    amt_buf<unsigned long long> cand(s, (size_t)total * cap);
+    amt_buf<unsigned> ncand(s, (size_t)total);
+    amt_buf<int> overflow(s, nplanes);
+    AMT_TRY(s.commit());
     AMT_TRY(amt_param_upload(ctx, rd, reqs, sizeof(rank_req) * nq));
     hipLaunchKernelGGL(sel_init_kernel, dim3((total + 255) / 256), dim3(256), 0, ctx->stream, st, rd, nq, nplanes);
     AMT_LAUNCH_CHECK();
@@ -1695,8 +1693,7 @@ static int percentile_f64_radix(amt_ctx* ctx, const double* in, const rank_req* 
     hipLaunchKernelGGL(sel_list_passes_kernel, dim3(nslots, nplanes), dim3(256), 0, ctx->stream, in, cur, nslots, n, cand,
                        ncand, cap, (const int*)overflow);
     AMT_LAUNCH_CHECK();
-    st = cur;
-    hipLaunchKernelGGL(sel_finish_kernel, dim3((nplanes * nq + 63) / 64), dim3(64), 0, ctx->stream, st, rd, nq, nplanes,
+    hipLaunchKernelGGL(sel_finish_kernel, dim3((nplanes * nq + 63) / 64), dim3(64), 0, ctx->stream, cur, rd, nq, nplanes,
                        out_dev);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
@@ -1763,8 +1760,9 @@ extern "C" int amt_masked_sums_f64(amt_ctx* ctx, const double* in, const double*
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_dev && out_dev && nplanes >= 0, "masked_sums_f64: bad arguments");
     if (nplanes == 0) return AMT_OK;
-    AMT_TRY(amt_arena_begin(ctx, amt_align((size_t)nplanes * MS_BLOCKS * 4 * sizeof(double))));
-    double* partial = arena_take_t<double>(ctx, (size_t)nplanes * MS_BLOCKS * 4);
+    amt_scratch s(ctx);
+    amt_buf<double> partial(s, (size_t)nplanes * MS_BLOCKS * 4);
+    AMT_TRY(s.commit());
     hipLaunchKernelGGL(masked_sums_partial_kernel, dim3(MS_BLOCKS, nplanes), dim3(256), 0, ctx->stream, in, thr_dev,
                        partial, n);
     AMT_LAUNCH_CHECK();

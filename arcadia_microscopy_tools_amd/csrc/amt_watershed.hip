@@ -2054,8 +2054,9 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
                 "watershed: exact tie handling / connectivity 2 support planes of at most 2^26 pixels, got %d x %d", H, W);
     if (connectivity == 2) {
         // 8-connected floods: no component decomposition here -- every plane goes through the sequential emulation
-        AMT_TRY(amt_arena_begin(ctx, amt_align(np * sizeof(hp_elem)) + amt_align((size_t)nplanes * 4)));
-        hp_elem* gheap = arena_take_t<hp_elem>(ctx, np);
+        amt_scratch s(ctx);
+        amt_buf<hp_elem> gheap(s, np);
+        AMT_TRY(s.commit());
         if (ties_dev) {
             hipLaunchKernelGGL(ws_set_flags_kernel, dim3((nplanes + 63) / 64), dim3(64), 0, ctx->stream, ties_dev, nplanes, 0);
             AMT_LAUNCH_CHECK();
@@ -2082,17 +2083,7 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     const int trows = amt_i_tile_rows(H);
     const size_t lcap = amt_i_rootlist_cap(W);
     const size_t nlist = (size_t)nplanes * trows;
-    size_t need = 5 * amt_align(np * 4) + amt_align(nlist * lcap * 4) + amt_align(nlist * 4) + (3 + WS_NLISTS) * amt_align(nr * 4) + amt_align(nr * sizeof(comp_row)) +
-                  9 * amt_align(nplanes * 4 * WS_CTR) + amt_align((size_t)nplanes * 4) + amt_align((size_t)PF_NCLS * (nplanes + 1) * 4) +
-                  amt_align(64);
-    need += use_d2 ? 2 * amt_align((size_t)nplanes * bstride * 4) : amt_align((size_t)nplanes * bstride * sizeof(hp_elem));
-    // the sequential emulation's heap (every pixel is pushed at most once): the float64 path reuses its per-component
-    // heap space, the bucket path needs it extra -- and only when ties are to be resolved exactly
-    if (exact && use_d2) need += amt_align(np * sizeof(hp_elem));
     const size_t msz = (size_t)nplanes * ((size_t)max_label + 1);
-    if (fused_labels) need += amt_align(msz * 4);
-    const size_t ccl_ints = amt_i_ccl_scratch_ints(nplanes, H, W);
-    need += amt_align(ccl_ints * 4);
     // the fused chain's path (d2 relief, marker list, clear_border + relabel fused): the mask's run tables serve the
     // statistics and the final mapping instead of the parent plane
     const int segs = (W + 63) / 64;
@@ -2100,51 +2091,48 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     const bool runs = use_d2 && fused_labels && mk_list && amt_i_ccl_runs_ok(mask, H, W, nplanes) &&
                       (reinterpret_cast<uintptr_t>(fused_labels) & 15) == 0 && (reinterpret_cast<uintptr_t>(relief) & 15) == 0 &&
                       (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    if (runs)
-        need += amt_align((size_t)ntiles * 64 * 8) + amt_align((size_t)ntiles * RT_CAP * 2) + amt_align((size_t)ntiles * 4) +
-                amt_align((size_t)ntiles * 64 * 2) + amt_align((size_t)ntiles * RT_CAP * 4);
-    AMT_TRY(amt_arena_begin(ctx, need));
-    int* L = arena_take_t<int>(ctx, np);
-    int* T = arena_take_t<int>(ctx, np);
-    int* moff = arena_take_t<int>(ctx, nr);
-    int* boff = arena_take_t<int>(ctx, nr);
-    int* cursor = arena_take_t<int>(ctx, nr);
-    int* mlist = arena_take_t<int>(ctx, np);
-    int* next = arena_take_t<int>(ctx, np);
-    int* F = arena_take_t<int>(ctx, np);  // per-root fill value (only root positions are used)
-    int* rootlist = arena_take_t<int>(ctx, nlist * lcap);  // tile-local roots, one list per tile row
-    int* nroots = arena_take_t<int>(ctx, nlist);
-    comp_row* rows = arena_take_t<comp_row>(ctx, nr);
-    int* btot = arena_take_t<int>(ctx, nplanes);
-    int* mtot = arena_take_t<int>(ctx, nplanes);
+    amt_scratch s(ctx);
+    amt_buf<int> L(s, np);
+    amt_buf<int> T(s, np);
+    amt_buf<int> moff(s, nr);
+    amt_buf<int> boff(s, nr);
+    amt_buf<int> cursor(s, nr);
+    amt_buf<int> mlist(s, np);
+    amt_buf<int> next(s, np);
+    amt_buf<int> F(s, np);  // per-root fill value (only root positions are used)
+    amt_buf<int> rootlist(s, nlist * lcap);  // tile-local roots, one list per tile row
+    amt_buf<int> nroots(s, nlist);
+    amt_buf<comp_row> rows(s, nr);
+    amt_buf<int> btot(s, nplanes);
+    amt_buf<int> mtot(s, nplanes);
     // WS_CTR ints per plane, each field an array over the planes (field k of plane p: counters[k * nplanes + p]):
     // [0] work counter of the class-X flood, [7] work counter of the HBM flood, [8] has_g,
     // [9 .. 9 + WS_NLISTS) worklist sizes of classes S / M / M2 / L / X, [16] number of components
-    int* counters = arena_take_t<int>(ctx, (size_t)nplanes * WS_CTR);
-    int* wl = arena_take_t<int>(ctx, (size_t)WS_NLISTS * nr);  // worklists of the LDS classes
-    int* pf_idx = arena_take_t<int>(ctx, (size_t)PF_NCLS * (nplanes + 1));  // the persistent flood's item index
-    int* pf_ctl = arena_take_t<int>(ctx, 16);
-    int* ccl_scratch = arena_take_t<int>(ctx, ccl_ints);  // the tile labelling's flag + the tiles' column words
-    int* ties = ties_dev ? ties_dev : arena_take_t<int>(ctx, nplanes);
-    int* P = fused_labels ? arena_take_t<int>(ctx, msz) : nullptr;
-    unsigned long long* tbits = runs ? arena_take_t<unsigned long long>(ctx, (size_t)ntiles * 64) : nullptr;
-    unsigned short* rtab = runs ? arena_take_t<unsigned short>(ctx, (size_t)ntiles * RT_CAP) : nullptr;
-    int* nruns = runs ? arena_take_t<int>(ctx, (size_t)ntiles) : nullptr;
-    unsigned short* roff = runs ? arena_take_t<unsigned short>(ctx, (size_t)ntiles * 64) : nullptr;
-    int* rcomp = runs ? arena_take_t<int>(ctx, (size_t)ntiles * RT_CAP) : nullptr;  // only the runs that exist are touched
+    amt_buf<int> counters(s, (size_t)nplanes * WS_CTR);
+    amt_buf<int> wl(s, (size_t)WS_NLISTS * nr);  // worklists of the LDS classes
+    amt_buf<int> pf_idx(s, (size_t)PF_NCLS * (nplanes + 1));  // the persistent flood's item index
+    amt_buf<int> pf_ctl(s, 16);
+    // the tile labelling's flag + the tiles' column words
+    amt_buf<int> ccl_scratch(s, amt_i_ccl_scratch_ints(nplanes, H, W));
+    amt_buf<int> ties_own(s, nplanes, !ties_dev);
+    amt_buf<int> P(s, msz, fused_labels != nullptr);
+    amt_buf<unsigned long long> tbits(s, (size_t)ntiles * 64, runs);
+    amt_buf<unsigned short> rtab(s, (size_t)ntiles * RT_CAP, runs);
+    amt_buf<int> nruns(s, (size_t)ntiles, runs);
+    amt_buf<unsigned short> roff(s, (size_t)ntiles * 64, runs);
+    amt_buf<int> rcomp(s, (size_t)ntiles * RT_CAP, runs);  // only the runs that exist are touched
+    // the sequential emulation's heap (every pixel is pushed at most once): the float64 path reuses its per-component
+    // heap space (bstride == n: those heaps are dead when the emulation starts), the bucket path needs it extra -- and
+    // only when ties are to be resolved exactly
+    amt_buf<int> head(s, (size_t)nplanes * bstride, use_d2);
+    amt_buf<int> tail(s, (size_t)nplanes * bstride, use_d2);
+    amt_buf<hp_elem> gheap_own(s, np, use_d2 && exact);
+    amt_buf<hp_elem> heap(s, (size_t)nplanes * bstride, !use_d2);
+    AMT_TRY(s.commit());
+    int* ties = ties_dev ? ties_dev : ties_own.p;
+    hp_elem* gheap = use_d2 ? gheap_own.p : heap.p;
     // with run tables the parent plane holds tile roots only; every pixel look-up goes through the tables
     amt_runtabs rt = {tbits, roff, rtab, rcomp, segs, trows};
-    int *head = nullptr, *tail = nullptr;
-    hp_elem* heap = nullptr;
-    hp_elem* gheap = nullptr;
-    if (use_d2) {
-        head = arena_take_t<int>(ctx, (size_t)nplanes * bstride);
-        tail = arena_take_t<int>(ctx, (size_t)nplanes * bstride);
-        if (exact) gheap = arena_take_t<hp_elem>(ctx, np);
-    } else {
-        heap = arena_take_t<hp_elem>(ctx, (size_t)nplanes * bstride);
-        gheap = heap;  // bstride == n: the per-component heaps are dead when the emulation starts
-    }
 
     int* ncomp = counters + 16 * (size_t)nplanes;
     // counters, tie flags and the root lists' counts in ONE launch (three trivial launches cost ~5 us each in a stage
@@ -2235,7 +2223,7 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
         AMT_LAUNCH_CHECK();
         {
             const int* a_d2 = (const int*)relief;
-            void* args[] = {&a_d2, &L, &T, &out, &rows, &wl, &pf_idx, &pf_ctl, (void*)&row_stride, &H, &W, &seeds_first, &ties,
+            void* args[] = {&a_d2, &L.p, &T.p, &out, &rows.p, &wl.p, &pf_idx.p, &pf_ctl.p, (void*)&row_stride, &H, &W, &seeds_first, &ties,
                             (void*)&markers, &nplanes, &rt};
             AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_persist_kernel, dim3(ctx->num_cus), dim3(PF_NWAVES * 64), args,
                                              (size_t)(PF_SLOTS + 1) * PF_SLOT, ctx->stream, nullptr, nullptr, 0));
@@ -2244,14 +2232,14 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
             const int* a_d2 = (const int*)relief;
             const int* a_wl = wl + (size_t)(CLS_X - CLS_S) * nplanes * row_stride;
             const int* a_wlc = wl_count + (CLS_X - CLS_S) * nplanes;
-            void* args[] = {&a_d2, &L, &T, &out, &rows, &a_wl, &a_wlc, &counters, (void*)&row_stride, &H, &W, &seeds_first, &ties,
+            void* args[] = {&a_d2, &L.p, &T.p, &out, &rows.p, &a_wl, &a_wlc, &counters.p, (void*)&row_stride, &H, &W, &seeds_first, &ties,
                             (void*)&markers, &rt};
             AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_lds_kernel<X_PX, X_NB, CLS_X>, dim3(8, nplanes), dim3(64), args,
                                              ldsX, ctx->stream, nullptr, nullptr, any));
         }
         {
             const int* a_d2 = (const int*)relief;
-            void* args[] = {&a_d2, (void*)&mask, &out, &next, &head, &tail, &mlist, (void*)&rows, &moff, &boff, &ncomp, nullptr,
+            void* args[] = {&a_d2, (void*)&mask, &out, &next.p, &head.p, &tail.p, &mlist.p, &rows.p, &moff.p, &boff.p, &ncomp, nullptr,
                             (void*)&row_stride, &H, &W, (void*)&n, (void*)&bstride, &seeds_first, &ties};
             int* a_cnt = counters + 7 * nplanes;
             args[11] = &a_cnt;

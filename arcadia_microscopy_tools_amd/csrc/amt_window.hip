@@ -195,9 +195,10 @@ extern "C" int amt_window_threshold(amt_ctx* ctx, const void* in, int in_dtype, 
     if (nplanes == 0) return AMT_OK;
     const size_t np = (size_t)nplanes * H * W;
     if (in_dtype == AMT_U16) {
-        AMT_TRY(amt_arena_begin(ctx, amt_align(np * 4) + amt_align(np * 8)));
-        unsigned* hs = arena_take_t<unsigned>(ctx, np);
-        u64* hq = arena_take_t<u64>(ctx, np);
+        amt_scratch s(ctx);
+        amt_buf<unsigned> hs(s, np);
+        amt_buf<u64> hq(s, np);
+        AMT_TRY(s.commit());
         size_t smem = (size_t)2 * (W + 2 * hx + 1) * sizeof(u64);
         AMT_REQUIRE(smem <= 150 * 1024, "window_threshold: row too long for the LDS prefix (W = %d)", W);
         hipLaunchKernelGGL(win_rows_u16_kernel, dim3(H, nplanes), dim3(256), smem, ctx->stream, (const uint16_t*)in, hs,
@@ -209,9 +210,10 @@ extern "C" int amt_window_threshold(amt_ctx* ctx, const void* in, int in_dtype, 
         AMT_LAUNCH_CHECK();
         return AMT_OK;
     }
-    AMT_TRY(amt_arena_begin(ctx, 2 * amt_align(np * 8)));
-    double* hs = arena_take_t<double>(ctx, np);
-    double* hq = arena_take_t<double>(ctx, np);
+    amt_scratch s(ctx);
+    amt_buf<double> hs(s, np);
+    amt_buf<double> hq(s, np);
+    AMT_TRY(s.commit());
     dim3 grid((W + 255) / 256, H, nplanes);
     hipLaunchKernelGGL(win_rows_f64_kernel, grid, dim3(256), 0, ctx->stream, (const double*)in, hs, hq, H, W, hx);
     AMT_LAUNCH_CHECK();
@@ -271,11 +273,11 @@ extern "C" int amt_window_threshold_nd(amt_ctx* ctx, const void* in, int in_dtyp
     const int h = window_y / 2, hx = window_x / 2;
     const size_t plane = (size_t)H * W, np = nplanes * plane;
     if (in_dtype == AMT_U16) {
-        AMT_TRY(amt_arena_begin(ctx, amt_align(np * 4) + 5 * amt_align(np * 8)));
-        unsigned* hs = arena_take_t<unsigned>(ctx, np);
-        u64* hq = arena_take_t<u64>(ctx, np);
-        u64 *S = arena_take_t<u64>(ctx, np), *Q = arena_take_t<u64>(ctx, np);
-        u64 *S2 = arena_take_t<u64>(ctx, np), *Q2 = arena_take_t<u64>(ctx, np);
+        amt_scratch s(ctx);
+        amt_buf<unsigned> hs(s, np);
+        amt_buf<u64> hq(s, np);
+        amt_buf<u64> S(s, np), Q(s, np), S2(s, np), Q2(s, np);
+        AMT_TRY(s.commit());
         size_t smem = (size_t)2 * (W + 2 * hx + 1) * sizeof(u64);
         AMT_REQUIRE(smem <= 150 * 1024, "window_threshold: row too long for the LDS prefix (W = %d)", W);
         hipLaunchKernelGGL(win_rows_u16_kernel, dim3(H, (unsigned)nplanes), dim3(256), smem, ctx->stream,
@@ -287,10 +289,9 @@ extern "C" int amt_window_threshold_nd(amt_ctx* ctx, const void* in, int in_dtyp
         AMT_LAUNCH_CHECK();
         return window_nd_tail<u64>(ctx, S, Q, S2, Q2, thr_image, nlead, lead_shape, lead_window, plane, wsz, method, k, r);
     }
-    AMT_TRY(amt_arena_begin(ctx, 6 * amt_align(np * 8)));
-    double *hs = arena_take_t<double>(ctx, np), *hq = arena_take_t<double>(ctx, np);
-    double *S = arena_take_t<double>(ctx, np), *Q = arena_take_t<double>(ctx, np);
-    double *S2 = arena_take_t<double>(ctx, np), *Q2 = arena_take_t<double>(ctx, np);
+    amt_scratch s(ctx);
+    amt_buf<double> hs(s, np), hq(s, np), S(s, np), Q(s, np), S2(s, np), Q2(s, np);
+    AMT_TRY(s.commit());
     dim3 grid((W + 255) / 256, H, (unsigned)nplanes);
     hipLaunchKernelGGL(win_rows_f64_kernel, grid, dim3(256), 0, ctx->stream, (const double*)in, hs, hq, H, W, hx);
     AMT_LAUNCH_CHECK();
