@@ -41,6 +41,9 @@ RPX_COLS = (
 )
 RPX_NCOLS = len(RPX_COLS)
 RPX_WCOLS = ("centroid_weighted-0", "centroid_weighted-1", "centroid_weighted_local-0", "centroid_weighted_local-1")
+# amt_colocalization: the columns of a (label, channel pair) row (AMT_COLOC_*)
+COLOC_COLS = ("pearson", "overlap", "m1", "m2", "intersection1", "intersection2")
+COLOC_NCOLS = len(COLOC_COLS)
 
 
 class HipUnavailableError(RuntimeError):
@@ -136,6 +139,7 @@ _SIGS = {
     "amt_regionprops": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int, c_int, c_int]),
     "amt_regionprops_intensity_f64": (c_int, [_P, _P, _P, c_int, _P, c_int, c_int, c_int, c_int]),
     "amt_regionprops_ext": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_int]),
+    "amt_colocalization": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, c_int, _P, c_int, c_int, c_int, c_int]),
     "amt_convolve_axis0": (c_int, [_P, _P, c_int, c_double, _P, c_int, c_int, c_int, _P, c_int, c_int, c_double]),
     "amt_max_i32": (c_int, [_P, _P, _P, c_int, c_size_t]),
     "amt_pack_plate_rows": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_size_t, _P]),

@@ -11,6 +11,8 @@
 // form (coordinates) or with wave prefix sums (intensities), so each run costs one set of atomics.
 #include "amt_internal.h"
 
+#include <vector>
+
 typedef unsigned long long u64;
 
 // accumulator slots per (plane, label)
@@ -1314,6 +1316,345 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
         else
             hipLaunchKernelGGL((rpx_weighted_kernel<double, double>), dim3(max_label, nplanes), dim3(64), 0, ctx->stream,
                                labels, bbox, (const double*)intensity, C, wtable_dev, H, W, max_label);
+        AMT_LAUNCH_CHECK();
+    }
+    return AMT_OK;
+}
+
+// ---- per-label channel colocalisation (amt_colocalization) ----------------------------------------------------------
+// Pearson, Manders' overlap / M1 / M2 and the intersection coefficients of channel pairs inside every label (the
+// definitions stand in include/amt_hip.h).  Same traffic as the intensity pass of rp_label_kernel: the label's bounding
+// box in the label plane and in the channels of the launch.
+
+// One launch measures up to COLOC_MAXC channels and every pair of them: slot pair k = (a, b), a < b, in the order
+// (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  out[k] = index of the requested pair that slot pair answers, -1 for none;
+// swap[k]: the request names the channels the other way round (m1 / m2 and intersection1 / 2 change places).
+constexpr int COLOC_MAXC = 4, COLOC_MAXP = 6;
+struct coloc_launch {
+    int chan[COLOC_MAXC];
+    int nch;
+    int out[COLOC_MAXP];
+    int swap[COLOC_MAXP];
+};
+__host__ __device__ __forceinline__ int coloc_slot_a(int k) { return k < 3 ? 0 : (k < 5 ? 1 : 2); }
+__host__ __device__ __forceinline__ int coloc_slot_b(int k) { return k < 3 ? k + 1 : (k < 5 ? k - 1 : 3); }
+
+// Sums of 32 values per lane over the wave for the price of ~32 exchanges (64 x 6 as one all-reduce each): every step
+// halves what a lane still carries -- it keeps one half of its values, hands the other half to the lane `off` away and
+// adds what that lane hands over.  On return lane L holds the wave's sum of value L >> 1.  Integer sums: any order
+// gives the same bits.
+template <int HALF>
+__device__ __forceinline__ void wave_scatter_step(u64 (&t)[32], int lane) {
+    const bool up = (lane & (2 * HALF)) != 0;
+#pragma unroll
+    for (int i = 0; i < HALF; ++i) {
+        const u64 keep = up ? t[i + HALF] : t[i];
+        const u64 send = up ? t[i] : t[i + HALF];
+        t[i] = keep + __shfl_xor(send, 2 * HALF);
+    }
+}
+__device__ __forceinline__ u64 wave_reduce_scatter32(u64 (&t)[32], int lane) {
+    wave_scatter_step<16>(t, lane);
+    wave_scatter_step<8>(t, lane);
+    wave_scatter_step<4>(t, lane);
+    wave_scatter_step<2>(t, lane);
+    wave_scatter_step<1>(t, lane);
+    return t[0] + __shfl_xor(t[0], 1);
+}
+
+// layout of the 32 reduced words: per channel slot sum v, sum v^2; per slot pair sum a b, sum a[b > tB], sum b[a > tA];
+// then the counts, two to a word (each stays below 2^32): n, positives per slot, both-positive per pair
+enum { CO_S = 0, CO_Q = 4, CO_AB = 8, CO_AIF = 14, CO_BIF = 20, CO_CNT = 26 };
+__device__ __forceinline__ u64 coloc_count(const u64* red, int i) {
+    return (red[CO_CNT + (i >> 1)] >> (32 * (i & 1))) & 0xffffffffull;
+}
+
+__device__ __forceinline__ void coloc_write_empty(double* t) {
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    t[0] = nan;
+    t[1] = nan;
+    t[2] = t[3] = t[4] = t[5] = 0.0;
+}
+
+// uint16 images: one wave per (label, plane) over the label's bounding box, rows in steps of RPS with the label and the
+// intensity loads of a step issued together from clamped coordinates, lanes own columns (rp_label_kernel's scan).  All
+// sums are exact integers, private per lane, reduced once; lanes 0..5 finalise one slot pair each in float64.
+// "v > t" for an integer v and a float64 t is "v > floor(t)", so the comparison runs on integers.
+__global__ void __launch_bounds__(64) coloc_u16_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                       const uint16_t* __restrict__ inten, int C,
+                                                       const double* __restrict__ thr, const coloc_launch P,
+                                                       double* __restrict__ table, int npairs, int H, int W,
+                                                       int max_label) {
+    __shared__ u64 red[32];
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    double* rows = table + li * (size_t)npairs * AMT_COLOC_NCOLS;
+    if (y1 < y0) {  // label absent from this plane
+        if (lane < COLOC_MAXP && P.out[lane] >= 0) coloc_write_empty(rows + (size_t)P.out[lane] * AMT_COLOC_NCOLS);
+        return;
+    }
+    const size_t n = (size_t)H * W;
+    const int* L = labels + (size_t)plane * n;
+    const uint16_t* I = inten + (size_t)plane * C * n;
+    const int want = l + 1;
+    size_t coff[COLOC_MAXC];
+    int ti[COLOC_MAXC];  // v is positive when v > ti: -1 = every value, 65535 = none (a NaN threshold too)
+#pragma unroll
+    for (int c = 0; c < COLOC_MAXC; ++c) {
+        const int ch = P.chan[c < P.nch ? c : 0];
+        coff[c] = (size_t)ch * n;
+        const double t = thr[(size_t)plane * C + ch];
+        ti[c] = !(t < 65535.0) ? 65535 : (t < 0.0 ? -1 : (int)floor(t));
+    }
+    u64 s[COLOC_MAXC], q[COLOC_MAXC], ab[COLOC_MAXP], aif[COLOC_MAXP], bif[COLOC_MAXP];
+    unsigned cnt = 0, np[COLOC_MAXC], both[COLOC_MAXP];
+#pragma unroll
+    for (int c = 0; c < COLOC_MAXC; ++c) s[c] = q[c] = 0, np[c] = 0;
+#pragma unroll
+    for (int k = 0; k < COLOC_MAXP; ++k) ab[k] = aif[k] = bif[k] = 0, both[k] = 0;
+    constexpr int RPS = 3;
+    for (int yb = y0; yb <= y1; yb += RPS) {
+        for (int xb = x0; xb <= x1; xb += 64) {
+            const int x = xb + lane;
+            const int xc = x <= x1 ? x : x1;
+            int lv[RPS];
+            unsigned iv[RPS][COLOC_MAXC];
+#pragma unroll
+            for (int j = 0; j < RPS; ++j) {
+                const int yc = yb + j <= y1 ? yb + j : y1;
+                lv[j] = L[(size_t)yc * W + xc];
+            }
+#pragma unroll
+            for (int j = 0; j < RPS; ++j) {
+                const int yc = yb + j <= y1 ? yb + j : y1;
+#pragma unroll
+                for (int c = 0; c < COLOC_MAXC; ++c) iv[j][c] = I[coff[c] + (size_t)yc * W + xc];
+            }
+#pragma unroll
+            for (int j = 0; j < RPS; ++j) {
+                const bool m = x <= x1 && yb + j <= y1 && lv[j] == want;
+                unsigned v[COLOC_MAXC];
+                bool pos[COLOC_MAXC];
+                cnt += m ? 1u : 0u;
+#pragma unroll
+                for (int c = 0; c < COLOC_MAXC; ++c) {
+                    v[c] = m ? iv[j][c] : 0u;
+                    pos[c] = m && (int)iv[j][c] > ti[c];
+                    if (c < P.nch) {
+                        s[c] += v[c];
+                        q[c] += (u64)v[c] * v[c];
+                        np[c] += pos[c] ? 1u : 0u;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < COLOC_MAXP; ++k)
+                    if (P.out[k] >= 0) {
+                        const int a = coloc_slot_a(k), b = coloc_slot_b(k);
+                        ab[k] += (u64)v[a] * v[b];
+                        aif[k] += pos[b] ? v[a] : 0u;
+                        bif[k] += pos[a] ? v[b] : 0u;
+                        both[k] += (pos[a] && pos[b]) ? 1u : 0u;
+                    }
+            }
+        }
+    }
+    u64 t[32];
+#pragma unroll
+    for (int c = 0; c < COLOC_MAXC; ++c) t[CO_S + c] = s[c], t[CO_Q + c] = q[c];
+#pragma unroll
+    for (int k = 0; k < COLOC_MAXP; ++k) t[CO_AB + k] = ab[k], t[CO_AIF + k] = aif[k], t[CO_BIF + k] = bif[k];
+    t[CO_CNT + 0] = (u64)cnt | ((u64)np[0] << 32);
+    t[CO_CNT + 1] = (u64)np[1] | ((u64)np[2] << 32);
+    t[CO_CNT + 2] = (u64)np[3] | ((u64)both[0] << 32);
+    t[CO_CNT + 3] = (u64)both[1] | ((u64)both[2] << 32);
+    t[CO_CNT + 4] = (u64)both[3] | ((u64)both[4] << 32);
+    t[CO_CNT + 5] = (u64)both[5];
+    const u64 mine = wave_reduce_scatter32(t, lane);
+    if (!(lane & 1)) red[lane >> 1] = mine;
+    __syncthreads();
+    if (lane < COLOC_MAXP && P.out[lane] >= 0) {
+        const int k = lane, a = coloc_slot_a(k), b = coloc_slot_b(k);
+        const u64 N = coloc_count(red, 0), na = coloc_count(red, 1 + a), nb = coloc_count(red, 1 + b);
+        const u64 nab = coloc_count(red, 5 + k);
+        const u64 Sa = red[CO_S + a], Sb = red[CO_S + b], Qa = red[CO_Q + a], Qb = red[CO_Q + b];
+        const u64 AB = red[CO_AB + k], AIF = red[CO_AIF + k], BIF = red[CO_BIF + k];
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        // exact 128-bit differences, rounded only once they are formed: nothing cancels in float64
+        const double da = diff_of_products(N, Qa, Sa, Sa), db = diff_of_products(N, Qb, Sb, Sb);
+        const double num = diff_of_products(N, AB, Sa, Sb);
+        double m1 = Sa ? (double)AIF / (double)Sa : 0.0, m2 = Sb ? (double)BIF / (double)Sb : 0.0;
+        double i1 = na ? (double)nab / (double)na : 0.0, i2 = nb ? (double)nab / (double)nb : 0.0;
+        if (P.swap[k]) {
+            double tmp = m1;
+            m1 = m2, m2 = tmp;
+            tmp = i1;
+            i1 = i2, i2 = tmp;
+        }
+        double* o = rows + (size_t)P.out[k] * AMT_COLOC_NCOLS;
+        o[AMT_COLOC_PEARSON] = (da == 0.0 || db == 0.0) ? nan : num / sqrt(da * db);  // da == 0: n Saa == Sa^2, exactly
+        o[AMT_COLOC_OVERLAP] = (Qa == 0 || Qb == 0) ? nan : (double)AB / sqrt((double)Qa * (double)Qb);
+        o[AMT_COLOC_M1] = m1;
+        o[AMT_COLOC_M2] = m2;
+        o[AMT_COLOC_INTERSECTION1] = i1;
+        o[AMT_COLOC_INTERSECTION2] = i2;
+    }
+}
+
+// float64 images: one wave per label and requested pair, two sweeps as rp_intensity_f64_kernel makes them -- raw sums,
+// extrema and the thresholded sums first, then the sums centred on the means.  Plain and untuned.
+__global__ void __launch_bounds__(64) coloc_f64_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                       const double* __restrict__ inten, int C,
+                                                       const double* __restrict__ thr, int ca, int cb, int pair,
+                                                       double* __restrict__ table, int npairs, int H, int W,
+                                                       int max_label) {
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    double* o = table + (li * (size_t)npairs + pair) * AMT_COLOC_NCOLS;
+    if (y1 < y0) {
+        if (lane == 0) coloc_write_empty(o);
+        return;
+    }
+    const size_t n = (size_t)H * W;
+    const int* lab = labels + (size_t)plane * n;
+    const double* A = inten + ((size_t)plane * C + ca) * n;
+    const double* B = inten + ((size_t)plane * C + cb) * n;
+    const double ta = thr[(size_t)plane * C + ca], tb = thr[(size_t)plane * C + cb];
+    auto wsum = [&](double v) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        return v;
+    };
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    double cnt = 0, sa = 0, sb = 0, qa = 0, qb = 0, pab = 0, aif = 0, bif = 0, na = 0, nb = 0, nab = 0;
+    double mna = inf, mxa = -inf, mnb = inf, mxb = -inf;
+    for (int y = y0; y <= y1; ++y)
+        for (int x = x0 + lane; x <= x1; x += 64)
+            if (lab[(size_t)y * W + x] == l + 1) {
+                const double a = A[(size_t)y * W + x], b = B[(size_t)y * W + x];
+                const bool pa = a > ta, pb = b > tb;
+                cnt += 1.0;
+                sa += a;
+                sb += b;
+                qa += a * a;
+                qb += b * b;
+                pab += a * b;
+                if (pb) aif += a;
+                if (pa) bif += b;
+                na += pa ? 1.0 : 0.0;
+                nb += pb ? 1.0 : 0.0;
+                nab += (pa && pb) ? 1.0 : 0.0;
+                mna = a < mna ? a : mna;
+                mxa = a > mxa ? a : mxa;
+                mnb = b < mnb ? b : mnb;
+                mxb = b > mxb ? b : mxb;
+            }
+    cnt = wsum(cnt), sa = wsum(sa), sb = wsum(sb), qa = wsum(qa), qb = wsum(qb), pab = wsum(pab);
+    aif = wsum(aif), bif = wsum(bif), na = wsum(na), nb = wsum(nb), nab = wsum(nab);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double a0 = __shfl_xor(mna, off), a1 = __shfl_xor(mxa, off);
+        const double b0 = __shfl_xor(mnb, off), b1 = __shfl_xor(mxb, off);
+        mna = a0 < mna ? a0 : mna;
+        mxa = a1 > mxa ? a1 : mxa;
+        mnb = b0 < mnb ? b0 : mnb;
+        mxb = b1 > mxb ? b1 : mxb;
+    }
+    const double ma = sa / cnt, mb = sb / cnt;
+    double cab = 0, caa = 0, cbb = 0;
+    for (int y = y0; y <= y1; ++y)
+        for (int x = x0 + lane; x <= x1; x += 64)
+            if (lab[(size_t)y * W + x] == l + 1) {
+                const double da = A[(size_t)y * W + x] - ma, db = B[(size_t)y * W + x] - mb;
+                cab += da * db;
+                caa += da * da;
+                cbb += db * db;
+            }
+    cab = wsum(cab), caa = wsum(caa), cbb = wsum(cbb);
+    if (lane == 0) {
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        const bool constant = !(mna < mxa) || !(mnb < mxb);  // min == max over the label (an empty label too)
+        const double den = sqrt(caa * cbb), oden = sqrt(qa * qb);
+        o[AMT_COLOC_PEARSON] = (constant || den == 0.0) ? nan : cab / den;
+        o[AMT_COLOC_OVERLAP] = oden == 0.0 ? nan : pab / oden;
+        o[AMT_COLOC_M1] = sa != 0.0 ? aif / sa : 0.0;
+        o[AMT_COLOC_M2] = sb != 0.0 ? bif / sb : 0.0;
+        o[AMT_COLOC_INTERSECTION1] = na != 0.0 ? nab / na : 0.0;
+        o[AMT_COLOC_INTERSECTION2] = nb != 0.0 ? nab / nb : 0.0;
+    }
+}
+
+extern "C" int amt_colocalization(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C,
+                                  const double* thresholds_dev, const int32_t* pairs_host, int npairs,
+                                  double* table_dev, int nplanes, int H, int W, int max_label) {
+    AMT_REQUIRE(labels && intensity && thresholds_dev && pairs_host && table_dev && nplanes >= 0 && H > 0 && W > 0 &&
+                    max_label >= 0 && C >= 2 && npairs >= 1,
+                "colocalization: bad arguments");
+    AMT_REQUIRE(in_code == AMT_U16 || in_code == AMT_F64, "colocalization: intensity must be AMT_U16 or AMT_F64");
+    AMT_REQUIRE((size_t)H * W <= 0xffffffffull, "colocalization: planes of more than 2^32 - 1 pixels are not supported");
+    for (int p = 0; p < npairs; ++p) {
+        const int i = pairs_host[2 * p], j = pairs_host[2 * p + 1];
+        AMT_REQUIRE(i >= 0 && i < C && j >= 0 && j < C && i != j,
+                    "colocalization: pair %d = (%d, %d) must name two different channels below %d", p, i, j, C);
+    }
+    AMT_TRY(amt_set_device(ctx));
+    if (nplanes == 0 || max_label == 0) return AMT_OK;
+    const size_t nlab = (size_t)nplanes * max_label;
+    amt_scratch s(ctx);
+    amt_buf<int> bbox(s, nlab * 4);
+    AMT_TRY(s.commit());
+    hipLaunchKernelGGL(bbox_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, bbox, nlab);
+    AMT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels, bbox,
+                       H, W, max_label);
+    AMT_LAUNCH_CHECK();
+    if (in_code == AMT_F64) {
+        for (int p = 0; p < npairs; ++p) {
+            hipLaunchKernelGGL(coloc_f64_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,
+                               (const double*)intensity, C, thresholds_dev, pairs_host[2 * p], pairs_host[2 * p + 1], p,
+                               table_dev, npairs, H, W, max_label);
+            AMT_LAUNCH_CHECK();
+        }
+        return AMT_OK;
+    }
+    // Cover the requested pairs with channel lists of at most COLOC_MAXC: a list starts from the first pair that is
+    // still open and takes the channels of further open pairs while they fit; every open pair inside the list whose
+    // slot pair is free is answered by that launch (a pair asked for twice, or both ways round, waits for the next).
+    std::vector<char> done((size_t)npairs, 0);
+    for (int first = 0; first < npairs; ++first) {
+        if (done[first]) continue;
+        coloc_launch P;
+        P.nch = 0;
+        for (int c = 0; c < COLOC_MAXC; ++c) P.chan[c] = 0;
+        for (int k = 0; k < COLOC_MAXP; ++k) P.out[k] = -1, P.swap[k] = 0;
+        auto slot_of = [&](int ch) {
+            for (int c = 0; c < P.nch; ++c)
+                if (P.chan[c] == ch) return c;
+            return -1;
+        };
+        for (int p = first; p < npairs; ++p) {
+            if (done[p]) continue;
+            const int i = pairs_host[2 * p], j = pairs_host[2 * p + 1];
+            const int missing = (slot_of(i) < 0 ? 1 : 0) + (slot_of(j) < 0 ? 1 : 0);
+            if (P.nch + missing > COLOC_MAXC) continue;
+            if (slot_of(i) < 0) P.chan[P.nch++] = i;
+            if (slot_of(j) < 0) P.chan[P.nch++] = j;
+        }
+        for (int p = first; p < npairs; ++p) {
+            if (done[p]) continue;
+            const int si = slot_of(pairs_host[2 * p]), sj = slot_of(pairs_host[2 * p + 1]);
+            if (si < 0 || sj < 0) continue;
+            const int a = si < sj ? si : sj, b = si < sj ? sj : si;
+            int k = 0;
+            while (coloc_slot_a(k) != a || coloc_slot_b(k) != b) ++k;
+            if (P.out[k] >= 0) continue;
+            P.out[k] = p;
+            P.swap[k] = si > sj ? 1 : 0;
+            done[p] = 1;
+        }
+        hipLaunchKernelGGL(coloc_u16_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,
+                           (const uint16_t*)intensity, C, thresholds_dev, P, table_dev, npairs, H, W, max_label);
         AMT_LAUNCH_CHECK();
     }
     return AMT_OK;

@@ -1054,6 +1054,68 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
     return o, wo
 
 
+def colocalization_pairs(C: int, pairs=None) -> np.ndarray:
+    """The (npairs, 2) int32 channel-index pairs ``colocalization`` measures: every i < j in channel order for
+    ``pairs=None``, else the given (i, j) with i != j, both below ``C``, in the given order."""
+    if pairs is None:
+        return np.array([(i, j) for i in range(C) for j in range(i + 1, C)], dtype=np.int32).reshape(-1, 2)
+    listed = [tuple(p) for p in pairs]
+    if not listed:
+        raise ValueError("pairs must name at least one pair of channels")
+    for p in listed:
+        if len(p) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in p):
+            raise TypeError(f"pairs must be (i, j) tuples of channel indices, got {p!r}")
+        i, j = int(p[0]), int(p[1])
+        if not (0 <= i < C and 0 <= j < C):
+            raise ValueError(f"pair {p!r} names a channel outside 0..{C - 1}")
+        if i == j:
+            raise ValueError(f"pair {p!r} names the same channel twice")
+    return np.array(listed, dtype=np.int32).reshape(-1, 2)
+
+
+def colocalization(labels: DeviceArray, intensity: DeviceArray, max_label: int, thresholds=None, pairs=None,
+                   out=None) -> DeviceArray:
+    """Per-label colocalisation of channel pairs (include/amt_hip.h ``amt_colocalization``): table (nplanes, max_label,
+    npairs, COLOC_NCOLS) float64 in ``_hip.COLOC_COLS`` order -- Pearson, Manders' overlap, M1, M2 and the two
+    intersection coefficients, as ``skimage.measure`` (0.20 and later) defines them, of every label 1..max_label.
+
+    ``labels`` is int32 (..., Y, X); ``intensity`` is (..., C, Y, X) uint16 (exact integer sums, reproducible bit for
+    bit) or float64, one (C, Y, X) stack per label plane, C >= 2.  ``thresholds`` (a pixel is positive when its value
+    is > the threshold of its channel): None = 0 for every channel, a number, an array broadcastable to (nplanes, C),
+    or a float64 ``DeviceArray`` of that shape, which is used as it is (no synchronisation).  ``pairs``: None = every
+    i < j in channel order, or a list of (i, j), i != j; for pair (i, j) channel i is A and channel j is B.  A label
+    absent from its plane gives NaN, NaN, 0, 0, 0, 0."""
+    ctx = labels.ctx
+    n, H, W = _planes(labels)
+    if labels.dtype != np.int32:
+        raise TypeError("colocalization expects int32 labels")
+    if intensity.dtype not in (np.uint16, np.float64):
+        raise TypeError("intensity images must be uint16 or float64 on the device path")
+    if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
+        raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
+    C = int(intensity.shape[-3])
+    if C < 2:
+        raise ValueError("colocalization needs at least two channels")
+    if intensity.size != n * C * H * W:
+        raise ValueError("intensity / labels plane count mismatch")
+    if isinstance(thresholds, DeviceArray):
+        if thresholds.dtype != np.float64 or tuple(thresholds.shape) != (n, C):
+            raise ValueError(f"device thresholds must be ({n}, {C}) float64, got {thresholds.shape} {thresholds.dtype}")
+        thr = thresholds
+    else:
+        try:
+            host = np.broadcast_to(np.asarray(0.0 if thresholds is None else thresholds, dtype=np.float64), (n, C))
+        except ValueError:
+            raise ValueError(f"thresholds must be broadcastable to ({n}, {C})") from None
+        thr = ctx.asarray(np.ascontiguousarray(host))
+    pr = colocalization_pairs(C, pairs)
+    o = _out(ctx, out, (n, max_label, len(pr), _hip.COLOC_NCOLS), np.float64)
+    _hip.check(_lib().amt_colocalization(ctx.handle, labels.ptr, intensity.ptr, _hip.U16 if intensity.dtype == np.uint16
+                                         else _hip.F64, C, thr.ptr, pr.ctypes.data_as(ctypes.c_void_p), len(pr), o.ptr,
+                                         n, H, W, int(max_label)), "amt_colocalization")
+    return o
+
+
 def cellpose_masks(dP: DeviceArray, cellprob: DeviceArray, cellprob_threshold: float = 0.0, niter: int = 200,
                    min_size: int = 15, max_size_fraction: float = 0.4, max_seeds: int = 16384, out=None, count=None,
                    flow_threshold: float = 0.0, fill_holes: bool = False):

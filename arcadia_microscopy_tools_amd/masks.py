@@ -459,6 +459,59 @@ class SegmentationMask:
         return assemble_cell_properties(morph, inten, names, list(self.property_names),
                                         list(self.intensity_property_names), ext=ext, wext=wext)
 
+    def cell_colocalization(self, thresholds=None, pairs=None) -> dict[str, Float64Array]:
+        """How pairs of channels relate inside every cell: ``pearson``, ``overlap`` (Manders' overlap coefficient),
+        ``m1`` / ``m2`` (Manders' colocalisation coefficients) and ``intersection1`` / ``intersection2``, as
+        ``skimage.measure`` (0.20 and later) defines them (include/amt_hip.h states the formulas), measured on the
+        device.  Keys are ``f"{measure}_{a}_{b}"`` with the lower-cased channel names of ``intensity_image_dict`` in
+        its order (``segment.colocalization_keys``), e.g. ``pearson_fitc_tritc``; each entry holds one value per cell,
+        ordered by label like ``cell_properties`` (row j of a ring's table belongs to ``parent_labels[j]``).
+
+        ``thresholds`` decides which pixels count as positive (value > threshold) for m1 / m2 and the intersection
+        coefficients: None (0 for every channel), one number for all channels, or a mapping Channel -> number or
+        ``"otsu"`` -- the Otsu threshold of that whole image, the value ``apply_threshold(image, "otsu")`` compares
+        against; channels the mapping leaves out get 0.  ``pairs`` is a list of (Channel, Channel), default every pair
+        in channel order; for (a, b), m1 is the share of a's intensity on b-positive pixels.  uint8 / uint16 images
+        are summed exactly in integers, any other dtype in float64.  A channel that is constant over a cell gives a
+        NaN ``pearson``."""
+        from . import hipops
+        from .device import get_context
+        from .segment import colocalization_keys, colocalization_pairs
+
+        channels = list(self.intensity_image_dict or {})
+        if len(channels) < 2:
+            raise ValueError("cell_colocalization needs at least two intensity images")
+        index_pairs = colocalization_pairs(channels, pairs)
+        values = [0.0] * len(channels)
+        if isinstance(thresholds, Mapping):
+            for channel, t in thresholds.items():
+                if channel not in self.intensity_image_dict:
+                    raise ValueError(f"thresholds names '{getattr(channel, 'name', channel)}', which has no intensity image")
+                if isinstance(t, str):
+                    if t.lower() != "otsu":
+                        raise ValueError(f"threshold '{t}' is not supported: give a number or 'otsu'")
+                elif isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)):
+                    raise TypeError(f"a threshold must be a number or 'otsu', got {t!r}")
+                values[channels.index(channel)] = t
+        elif thresholds is not None:
+            if isinstance(thresholds, (bool, str)) or not isinstance(thresholds, (int, float, np.integer, np.floating)):
+                raise TypeError("thresholds must be None, a number or a mapping of channels to numbers or 'otsu'")
+            values = [float(thresholds)] * len(channels)
+        for c, t in enumerate(values):
+            if isinstance(t, str):
+                from .operations import otsu_threshold_value
+
+                values[c] = otsu_threshold_value(self.intensity_image_dict[channels[c]])
+        lab, k = self._labels_device
+        k = int(k)
+        shape = tuple(lab.shape[-2:])
+        stack, _, _ = self._intensity_stack(shape)
+        table = hipops.colocalization(lab.reshape((1,) + shape), stack.reshape((1,) + stack.shape), max(k, 1),
+                                      thresholds=np.asarray(values, dtype=np.float64)[None, :],
+                                      pairs=index_pairs).numpy()[0][:k]
+        cols = table.reshape(k, -1)
+        return {key: cols[:, i].copy() for i, key in enumerate(colocalization_keys(channels, index_pairs))}
+
     @cached_property
     def centroids_yx(self) -> Float64Array:
         """(num_cells, 2) array of [y, x] centroids (R/masks.py:330-353)."""

@@ -322,6 +322,32 @@ def _local_threshold(d: DeviceArray, block_size, method="gaussian", offset=0, mo
     return t
 
 
+def otsu_threshold_value(intensities, nbins: int = 256) -> float:
+    """The value ``t`` behind ``apply_threshold(intensities, "otsu")``: that mask is ``intensities > t``, in the image's
+    own value space.  The same device code picks it -- per dtype as ``apply_threshold`` does (module docstring):
+    ``hipops.threshold_otsu`` for images that travel as uint16 or float64, the integer histograms for wider integers.
+    A constant image gives its value (nothing lies above it, as ``apply_threshold`` answers all False); an empty one
+    NaN."""
+    if not isinstance(intensities, DeviceArray) and np.asarray(intensities).size == 0:
+        return float("nan")
+    shifted = [0]
+    d, _ = _to_device(intensities, "apply_threshold", integer_histogram=True, shifted=shifted)
+    offset = int(shifted[0])
+    wide_bins = int(shifted[1]) if len(shifted) > 1 else 0
+    d = _flat(d)
+    lo, hi = _min_max(d)
+    if lo == hi:
+        return float(lo) + (0 if wide_bins else offset)
+    if wide_bins:  # x > t on the float64 image
+        counts = hipops.histogram_range(d, offset, wide_bins).numpy()[0].astype(np.int64)
+        return float(_thresholds.otsu(counts, np.arange(offset, offset + wide_bins)))
+    if offset:  # x - min > floor(t) - min  <=>  x > floor(t) for integers
+        counts, centers = _thresholds.counts_centers_u16(hipops.histogram_u16(d).numpy()[0])
+        t = _thresholds.otsu(counts, centers + offset)
+        return float(t) if np.isnan(t) else float(np.floor(t))
+    return float(hipops.threshold_otsu(d, nbins=int(nbins)).numpy()[0])
+
+
 @device_operator
 def apply_threshold(
     intensities: ScalarArray,

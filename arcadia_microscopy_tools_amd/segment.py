@@ -382,6 +382,47 @@ def cell_property_keys(channel_names, property_names=None, intensity_property_na
                                          ext=np.zeros((0, _hip.RPX_NCOLS)), wext=np.zeros((0, C, 4))))
 
 
+def colocalization_pairs(channel_names, pairs=None) -> list[tuple[int, int]]:
+    """Channel-index pairs for ``colocalization_keys`` / ``SegmentationMask.cell_colocalization``: every i < j in
+    channel order for ``pairs=None``; else each (a, b) of ``pairs``, whose members are indices, names (any case) or
+    objects with a ``name`` (a ``Channel``), must be two different channels of ``channel_names``."""
+    names = [str(getattr(c, "name", c)).lower() for c in channel_names]
+    if len(names) < 2:
+        raise ValueError("colocalization needs at least two channels")
+    if pairs is None:
+        return [(i, j) for i in range(len(names)) for j in range(i + 1, len(names))]
+
+    def index(member):
+        if isinstance(member, (int, np.integer)) and not isinstance(member, bool):
+            if not 0 <= int(member) < len(names):
+                raise ValueError(f"pair member {member!r} is not a channel index below {len(names)}")
+            return int(member)
+        name = str(getattr(member, "name", member)).lower()
+        if name not in names:
+            raise ValueError(f"pair member {member!r} is not one of the channels {names}")
+        return names.index(name)
+
+    out = []
+    for pair in pairs:
+        if isinstance(pair, (str, bytes)) or len(pair) != 2:
+            raise TypeError(f"pairs must be (channel, channel) tuples, got {pair!r}")
+        i, j = index(pair[0]), index(pair[1])
+        if i == j:
+            raise ValueError(f"pair {pair!r} names the same channel twice")
+        out.append((i, j))
+    if not out:
+        raise ValueError("pairs must name at least one pair of channels")
+    return out
+
+
+def colocalization_keys(channel_names, pairs=None) -> list[str]:
+    """The keys of ``SegmentationMask.cell_colocalization`` for these channels, in order (no device needed): per pair
+    (a, b), ``f"{measure}_{a}_{b}"`` for the measures of ``_hip.COLOC_COLS`` with the lower-cased channel names,
+    e.g. ``pearson_fitc_tritc``."""
+    names = [str(getattr(c, "name", c)).lower() for c in channel_names]
+    return [f"{m}_{names[i]}_{names[j]}" for i, j in colocalization_pairs(channel_names, pairs) for m in _hip.COLOC_COLS]
+
+
 def segment_fovs(fovs, *, ctx: Context | None = None, channel_names=DEFAULT_CHANNELS, **kw) -> SegmentationResult:
     """Convenience: (B, C, H, W) uint16 (numpy or DeviceArray) -> config-3 ``SegmentationResult``."""
     ctx = ctx or get_context()

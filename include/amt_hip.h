@@ -444,6 +444,36 @@ int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const void* intensi
                         int columns, double* table_dev, double* wtable_dev, int nplanes, int H, int W,
                         int max_label);
 int amt_max_i32(amt_ctx* ctx, const int32_t* in, int32_t* max_dev, int nplanes, size_t n);
+/* ---- per-label colocalisation of channel pairs ----------------------------------------------------------
+ * For one label with pixel set P (n pixels), channels A and B with values a_p, b_p and thresholds tA, tB
+ * ("positive" means value > threshold, the comparison amt_threshold_gt makes), the columns are
+ *   AMT_COLOC_PEARSON        (n Sum ab - Sum a Sum b) / sqrt((n Sum a^2 - (Sum a)^2) (n Sum b^2 - (Sum b)^2));
+ *                            NaN when either channel is constant over P (n = 1 and an absent label included)
+ *   AMT_COLOC_OVERLAP        Sum ab / sqrt(Sum a^2 Sum b^2), Manders' overlap coefficient; NaN when that root is 0
+ *   AMT_COLOC_M1             Sum a_p[b_p > tB] / Sum a; 0 when Sum a = 0
+ *   AMT_COLOC_M2             Sum b_p[a_p > tA] / Sum b; 0 when Sum b = 0
+ *   AMT_COLOC_INTERSECTION1  |{a > tA and b > tB}| / |{a > tA}|; 0 when no pixel has a > tA
+ *   AMT_COLOC_INTERSECTION2  |{a > tA and b > tB}| / |{b > tB}|; 0 when no pixel has b > tB
+ * A label with no pixel in its plane gives NaN, NaN, 0, 0, 0, 0.  These restate the colocalisation functions of
+ * skimage.measure (pearson_corr_coeff, manders_overlap_coeff, manders_coloc_coeff, intersection_coeff, scikit-image
+ * 0.20 and later) per label; parity with that module is unpinned offline.
+ * intensity = nplanes x C planes (C >= 2) of element type in_code, one (C, Y, X) stack per label plane.  AMT_U16: every
+ * sum is an exact 64-bit integer and Pearson's differences are taken in 128 bits, so results do not depend on any
+ * order of summation, the four quotient columns are correctly rounded and pearson / overlap carry a few roundings.
+ * AMT_F64: two sweeps in float64 (means, then centred sums); a channel is constant when its min equals its max over
+ * P; NaN or infinite intensities are not supported.  thresholds_dev = nplanes x C doubles on the device;
+ * pairs_host = npairs x 2 channel indices (i, j), i != j, in HOST memory: A = channel i, B = channel j.
+ * table_dev = nplanes x max_label x npairs x AMT_COLOC_NCOLS doubles.  No atomics: two runs give identical bits. */
+#define AMT_COLOC_PEARSON 0
+#define AMT_COLOC_OVERLAP 1
+#define AMT_COLOC_M1 2
+#define AMT_COLOC_M2 3
+#define AMT_COLOC_INTERSECTION1 4
+#define AMT_COLOC_INTERSECTION2 5
+#define AMT_COLOC_NCOLS 6
+int amt_colocalization(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C,
+                       const double* thresholds_dev, const int32_t* pairs_host, int npairs, double* table_dev,
+                       int nplanes, int H, int W, int max_label);
 
 /* ---- per-plate feature rows (the reference's analogue is the list of cell_properties dicts a
  * user collects per image, R/masks.py:247-328, R/pipeline.py:145-149) ------------------------------------------
