@@ -44,6 +44,8 @@ RPX_WCOLS = ("centroid_weighted-0", "centroid_weighted-1", "centroid_weighted_lo
 # amt_colocalization: the columns of a (label, channel pair) row (AMT_COLOC_*)
 COLOC_COLS = ("pearson", "overlap", "m1", "m2", "intersection1", "intersection2")
 COLOC_NCOLS = len(COLOC_COLS)
+# amt_peak_markers: the longest peak list of a plane that is labelled from LDS (AMT_PEAK_MARKERS_LDS_TIER)
+PEAK_MARKERS_LDS_TIER = 4096
 
 
 class HipUnavailableError(RuntimeError):
@@ -133,6 +135,7 @@ _SIGS = {
     "amt_expand_labels": (c_int, [_P, _P, _P, c_int, c_int, c_int, ctypes.c_int64, c_int]),
     "amt_edt": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int]),
     "amt_peak_mask": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),
+    "amt_peak_markers": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "amt_watershed_edt": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "amt_watershed_f64": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "amt_watershed_edt_cleared": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_int]),

@@ -1,4 +1,5 @@
-// Exact Euclidean distance transform and the peak mask of the config-3 marker recipe.
+// Exact Euclidean distance transform, the peak mask of the config-3 marker recipe, and the markers labelled from the list of
+// the peaks that the search found (amt_peak_markers, at the end of the file).
 //
 // scipy.ndimage.distance_transform_edt(mask) == sqrt(float64(d2)) bitwise, with d2 the exact integer
 // squared distance to the nearest zero pixel.  d2 is computed separably:
@@ -268,9 +269,16 @@ constexpr int PK_MAXM = 16;
 // pixels are written.
 constexpr int PKR_ROWS = 64, PKR_IN = 62, PKR_BATCH = 22, PKR_NBATCH = (PKR_ROWS + 2) / PKR_BATCH;
 static_assert(PKR_BATCH * PKR_NBATCH == PKR_ROWS + 2, "row batches must tile the strip");
+// LIST (amt_peak_markers): every peak is also appended to its plane's "found" list, found[plane * cap ...], a wave's
+// peaks together with one returning atomic on the plane's counter fcount[plane * PKM_CNT_STRIDE]; the order is whatever
+// the waves' timing makes it, and the counter keeps counting past `cap` (the entries beyond are dropped: that plane has
+// overflowed).
+constexpr int PKM_CNT_STRIDE = 32;  // words between the planes' counters: one 128-byte line each (PFX_CNT_STRIDE's reason)
 
+template <bool LIST>
 __global__ void __launch_bounds__(256) peaks_rows_kernel(const int* __restrict__ d2, const uint8_t* __restrict__ mask,
-                                                         uint8_t* __restrict__ peaks, int H, int W, int m) {
+                                                         uint8_t* __restrict__ peaks, int H, int W, int m,
+                                                         int* __restrict__ found, int* __restrict__ fcount, int cap) {
     const int lane = threadIdx.x & 63;
     const int strip = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (strip * PKR_IN >= W) return;  // whole wave; the kernel has no barrier
@@ -289,6 +297,15 @@ __global__ void __launch_bounds__(256) peaks_rows_kernel(const int* __restrict__
     auto load_row = [&](int y) -> int {
         const int yc = y < 0 ? 0 : (y < H ? y : H - 1);
         return D[(size_t)yc * W + xc];
+    };
+    // LIST: the wave collects its peaks in registers and appends them with ONE returning atomic when it ends (or holds 64)
+    int npk = 0, mypk = 0;
+    auto flush = [&]() {
+        int at = 0;
+        if (lane == 0) at = atomicAdd(&fcount[(size_t)blockIdx.z * PKM_CNT_STRIDE], npk);
+        at = __shfl(at, 0) + lane;
+        if (lane < npk && at < cap) found[(size_t)blockIdx.z * cap + at] = mypk;
+        npk = 0;
     };
     int cur[PKR_BATCH], nxt[PKR_BATCH];
 #pragma unroll
@@ -330,8 +347,12 @@ __global__ void __launch_bounds__(256) peaks_rows_kernel(const int* __restrict__
                     const int dy = k / side, dx = k - dy * side;
                     gt |= D[(size_t)(yc - m + dy) * W + (sx - m + dx)] > sv;  // inside the image: the frame is cleared
                 }
-                if (__ballot(gt) == 0ull && lane == sl && mask[base + (size_t)yc * W + sx])
-                    peaks[base + (size_t)yc * W + sx] = 1;
+                const bool hit = __ballot(gt) == 0ull && lane == sl && mask[base + (size_t)yc * W + sx];
+                if (hit) peaks[base + (size_t)yc * W + sx] = 1;
+                if (LIST && __ballot(hit) != 0ull) {  // uniform: the wave's npk-th peak waits in lane npk
+                    if (lane == npk) mypk = yc * W + sx;
+                    if (++npk == 64) flush();
+                }
             }
             h2 = h1, h1 = h0;
             v1 = v0, v1l = v0l, v1r = v0r;
@@ -339,6 +360,7 @@ __global__ void __launch_bounds__(256) peaks_rows_kernel(const int* __restrict__
 #pragma unroll
         for (int j = 0; j < PKR_BATCH; ++j) cur[j] = nxt[j];
     }
+    if (LIST && npk) flush();
 }
 
 // peaks[list[k]] = 0 for the listed pixels of every plane
@@ -379,7 +401,214 @@ extern "C" int amt_peak_mask(amt_ctx* ctx, const int32_t* d2, const uint8_t* mas
     }
     const int nstrips = (W + PKR_IN - 1) / PKR_IN;
     dim3 grid((nstrips + 3) / 4, (H + PKR_ROWS - 1) / PKR_ROWS, nplanes);
-    hipLaunchKernelGGL(peaks_rows_kernel, grid, dim3(256), 0, ctx->stream, d2, mask, peaks, H, W, m);
+    hipLaunchKernelGGL(peaks_rows_kernel<false>, grid, dim3(256), 0, ctx->stream, d2, mask, peaks, H, W, m, (int*)nullptr,
+                       (int*)nullptr, 0);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// ---- peak markers: amt_peak_mask + amt_label_sparse from the list of the peaks the search found ------------------------
+// The search knows every peak when it writes it, so nothing scans a plane for them: peaks_clear_kernel undoes the previous
+// run's writes in both planes, peaks_rows_kernel<true> lists what it finds, and ONE workgroup per plane
+// (sp_markers_kernel) sorts that list into raster order -- which makes it amt_label_sparse's compacted list --, joins
+// neighbours, ranks the roots and scatters the labels.  Same numbering as amt_label_sparse by construction: the root of a
+// component is its smallest list index, roots are numbered in list order.
+constexpr int PKM_TIER = AMT_PEAK_MARKERS_LDS_TIER;  // longer lists are labelled in the arena's global scratch
+constexpr int PKM_THREADS = 1024;
+static_assert(2 * PKM_TIER * sizeof(int) <= 36 * 1024 - 256, "list + parents of the LDS tier stay below 36 KB");
+
+// peaks[p] = 0 and markers[p] = 0 for the pixels the previous run listed (status[plane] < 0: that run overflowed its
+// list and both planes are cleared whole); the plane's counter of found peaks starts at zero
+__global__ void __launch_bounds__(256) peaks_clear_kernel(const int* __restrict__ list, const int* __restrict__ count,
+                                                          const int* __restrict__ status, uint8_t* __restrict__ peaks,
+                                                          int* __restrict__ markers, int* __restrict__ fcount, size_t n,
+                                                          int cap) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) fcount[(size_t)blockIdx.y * PKM_CNT_STRIDE] = 0;
+    uint8_t* pk = peaks + (size_t)blockIdx.y * n;
+    int* mk = markers + (size_t)blockIdx.y * n;
+    if (status[blockIdx.y] < 0) {
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) pk[i] = 0, mk[i] = 0;
+        return;
+    }
+    const int K = count[blockIdx.y] < cap ? count[blockIdx.y] : cap;
+    const int* lst = list + (size_t)blockIdx.y * cap;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < K; k += gridDim.x * 256) {
+        const int p = lst[k];
+        pk[p] = 0;
+        mk[p] = 0;
+    }
+}
+
+// Ascending sort of a[0 .. n) by the whole workgroup, any n: bitonic merges whose first step mirrors its block, so every
+// compare-exchange moves the smaller value to the lower index and the elements past n -- which stand for +infinity --
+// would never move; pairs that reach past n are skipped.  Ends behind a barrier.
+__device__ __forceinline__ void pkm_exchange(int* a, int i, int l, int n) {
+    if (l < n) {
+        const int u = a[i], v = a[l];
+        if (u > v) a[i] = v, a[l] = u;
+    }
+}
+__device__ __forceinline__ void pkm_sort(int* a, int n) {
+    int n2 = 1;
+    while (n2 < n) n2 <<= 1;
+    const int pairs = n2 >> 1;
+    for (int k = 2; k <= n2; k <<= 1) {
+        const int hk = k >> 1;
+        for (int t = threadIdx.x; t < pairs; t += PKM_THREADS) {
+            const int i = ((t & ~(hk - 1)) << 1) | (t & (hk - 1));
+            pkm_exchange(a, i, i ^ (k - 1), n);
+        }
+        __syncthreads();
+        for (int j = hk >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < pairs; t += PKM_THREADS) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                pkm_exchange(a, i, i | j, n);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// The found list lst[0 .. K) of one plane -> sorted (and stored as the keep list kl), labelled, scattered into mk.
+// lst / par live in LDS (LDS) or in global scratch; returns the number of components.  wsum = one int per wave.
+template <bool LDS>
+__device__ __forceinline__ int pkm_label(int* lst, int* par, int K, int W, int conn8, int* __restrict__ mk,
+                                         int* __restrict__ kl, int* wsum) {
+    const int tid = threadIdx.x;
+    pkm_sort(lst, K);
+    for (int k = tid; k < K; k += PKM_THREADS) {
+        par[k] = k;
+        if (kl) kl[k] = lst[k];
+    }
+    __syncthreads();
+    // unions with the west, north and (8-connectivity) north-west / north-east neighbours: the west one is the previous
+    // entry, the others sit around the lower bound of p - W among the entries before k
+    for (int k = tid; k < K; k += PKM_THREADS) {
+        const int p = lst[k];
+        const int y = p / W, x = p - y * W;
+        if (x > 0 && k > 0 && lst[k - 1] == p - 1) {
+            if (LDS) lds_union(par, k, k - 1); else uf_union(par, k, k - 1);
+        }
+        if (y == 0) continue;
+        const int north = p - W;
+        int lo = 0, hi = k;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (lst[mid] < north) lo = mid + 1; else hi = mid;
+        }
+        // lo <= k and lst[lo] >= north (lst[k] = p itself ends the search)
+        const bool up = lst[lo] == north;
+        if (up) {
+            if (LDS) lds_union(par, k, lo); else uf_union(par, k, lo);
+        }
+        if (conn8) {
+            if (x > 0 && lo > 0 && lst[lo - 1] == north - 1) {
+                if (LDS) lds_union(par, k, lo - 1); else uf_union(par, k, lo - 1);
+            }
+            const int ne = lo + (up ? 1 : 0);
+            if (x + 1 < W && ne < k && lst[ne] == north + 1) {
+                if (LDS) lds_union(par, k, ne); else uf_union(par, k, ne);
+            }
+        }
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += PKM_THREADS) par[k] = LDS ? lds_find(par, k) : uf_find_volatile(par, k);
+    __syncthreads();
+    // rank the roots in list order: every thread owns a stretch of consecutive entries
+    const int per = (K + PKM_THREADS - 1) / PKM_THREADS;
+    const int b = tid * per < K ? tid * per : K, e = b + per < K ? b + per : K;
+    int mine = 0;
+    for (int k = b; k < e; ++k) mine += par[k] == k ? 1 : 0;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int incl = ccl_wave_incl_scan(mine, lane);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int rank = incl - mine, total = 0;
+    for (int w = 0; w < PKM_THREADS / 64; ++w) {
+        if (w < wave) rank += wsum[w];
+        total += wsum[w];
+    }
+    for (int k = b; k < e; ++k)
+        if (par[k] == k) par[k] = ~(rank++);  // a root carries its rank, complemented: negative, so no parent index
+    __syncthreads();
+    for (int k = tid; k < K; k += PKM_THREADS) {
+        int v = par[k];
+        if (v >= 0) v = par[v];
+        mk[lst[k]] = -v;  // rank + 1
+    }
+    return total;
+}
+
+__global__ void __launch_bounds__(PKM_THREADS) sp_markers_kernel(int* found, const int* __restrict__ fcount, int* gpar,
+                                                                 int* __restrict__ markers, int* __restrict__ count_dev,
+                                                                 int* __restrict__ keep_list, int* __restrict__ keep_count,
+                                                                 size_t n, int W, int cap, int conn8) {
+    __shared__ int s_lst[PKM_TIER], s_par[PKM_TIER];
+    __shared__ int s_wsum[PKM_THREADS / 64];
+    const int plane = blockIdx.x;
+    const int K = fcount[(size_t)plane * PKM_CNT_STRIDE];
+    if (K > cap) {  // block-uniform: the list does not hold every peak -- no markers, and the next run clears whole planes
+        if (threadIdx.x == 0) {
+            count_dev[plane] = -1;
+            if (keep_count) keep_count[plane] = 0;
+        }
+        return;
+    }
+    int* fl = found + (size_t)plane * cap;
+    int* mk = markers + (size_t)plane * n;
+    int* kl = keep_list ? keep_list + (size_t)plane * cap : nullptr;
+    int nroots;
+    if (K <= PKM_TIER) {
+        for (int k = threadIdx.x; k < K; k += PKM_THREADS) s_lst[k] = fl[k];
+        __syncthreads();
+        nroots = pkm_label<true>(s_lst, s_par, K, W, conn8, mk, kl, s_wsum);
+    } else {
+        nroots = pkm_label<false>(fl, gpar + (size_t)plane * cap, K, W, conn8, mk, kl, s_wsum);
+    }
+    if (threadIdx.x == 0) {
+        count_dev[plane] = nroots;
+        if (keep_count) keep_count[plane] = K;
+    }
+}
+
+extern "C" int amt_peak_markers(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int32_t* markers,
+                                int32_t* count_dev, int nplanes, int H, int W, int min_distance, int connectivity,
+                                int capacity, int32_t* keep_list, int32_t* keep_count) {
+    AMT_REQUIRE(!keep_list == !keep_count, "peak_markers: keep_list and keep_count go together");
+    AMT_REQUIRE(d2 && mask && peaks && markers && count_dev && nplanes >= 0 && H > 0 && W > 0,
+                "peak_markers: bad arguments");
+    AMT_REQUIRE(min_distance >= 0 && min_distance <= PK_MAXM, "peak_markers: min_distance %d out of range 0..%d",
+                min_distance, PK_MAXM);
+    AMT_REQUIRE(connectivity == 1 || connectivity == 2, "peak_markers: connectivity must be 1 or 2");
+    AMT_REQUIRE(capacity >= 1, "peak_markers: capacity must be positive");
+    AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "peak_markers: plane too large");
+    AMT_TRY(amt_set_device(ctx));
+    if (nplanes == 0) return AMT_OK;
+    const size_t n = (size_t)H * W;
+    const size_t capn = (size_t)nplanes * capacity;
+    amt_scratch s(ctx);
+    amt_buf<int> found(s, capn);   // a buffer of its own: the keep list holds the previous run's pixels until the clear has run
+    amt_buf<int> parent(s, capn);  // lists beyond the LDS tier only
+    amt_buf<int> fcount(s, (size_t)nplanes * PKM_CNT_STRIDE);
+    AMT_TRY(s.commit());
+    if (keep_list) {
+        hipLaunchKernelGGL(peaks_clear_kernel, dim3(amt_grid_for((size_t)capacity, 256, 64), nplanes), dim3(256), 0,
+                           ctx->stream, (const int*)keep_list, (const int*)keep_count, (const int*)count_dev, peaks, markers,
+                           (int*)fcount, n, capacity);
+        AMT_LAUNCH_CHECK();
+    } else {
+        AMT_HIP_CHECK(hipMemsetAsync(peaks, 0, (size_t)nplanes * n, ctx->stream));
+        AMT_HIP_CHECK(hipMemsetAsync(markers, 0, (size_t)nplanes * n * sizeof(int32_t), ctx->stream));
+        AMT_HIP_CHECK(hipMemsetAsync(fcount, 0, (size_t)nplanes * PKM_CNT_STRIDE * sizeof(int), ctx->stream));
+    }
+    const int nstrips = (W + PKR_IN - 1) / PKR_IN;
+    dim3 grid((nstrips + 3) / 4, (H + PKR_ROWS - 1) / PKR_ROWS, nplanes);
+    hipLaunchKernelGGL(peaks_rows_kernel<true>, grid, dim3(256), 0, ctx->stream, d2, mask, peaks, H, W, min_distance,
+                       (int*)found, (int*)fcount, capacity);
+    AMT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sp_markers_kernel, dim3(nplanes), dim3(PKM_THREADS), 0, ctx->stream, (int*)found,
+                       (const int*)fcount, (int*)parent, markers, count_dev, keep_list, keep_count, n, W, capacity,
+                       connectivity == 2 ? 1 : 0);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }

@@ -130,6 +130,60 @@ int amt_i_drop_and_scan(amt_ctx* ctx, int* P, int max_label, int* count_dev, int
 // amt_lane_left / lane 63 of amt_lane_right receive 0, every caller masks those lanes itself.  All 64 lanes must be
 // active (call from wave-uniform control flow only).
 #ifdef __HIPCC__
+// Lock-free union-find on an int array of parents (amt_label.hip's labelling, amt_edt.hip's peak markers): uf_* on a
+// plane or list in HBM, lds_* on one in LDS.  The root of a set is its smallest index.
+__device__ __forceinline__ int uf_find_volatile(int* L, int a) {
+    int p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (p != a) {
+        a = p;
+        p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return a;
+}
+
+// union by minimum index (Komura-style): the larger root is redirected to the smaller one.
+__device__ __forceinline__ void uf_union(int* L, int a, int b) {
+    while (true) {
+        a = uf_find_volatile(L, a);
+        b = uf_find_volatile(L, b);
+        if (a == b) return;
+        if (a < b) {
+            int t = a;
+            a = b;
+            b = t;
+        }
+        // a > b: try to hang a below b
+        int old = atomicMin(&L[a], b);
+        if (old == a) return;
+        a = old;  // someone else moved a meanwhile; retry from there
+    }
+}
+
+__device__ __forceinline__ int lds_find(int* S, int a) {
+    int p = __hip_atomic_load(&S[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    while (p != a) {
+        a = p;
+        p = __hip_atomic_load(&S[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    return a;
+}
+
+__device__ __forceinline__ void lds_union(int* S, int a, int b) {
+    while (true) {
+        a = lds_find(S, a);
+        b = lds_find(S, b);
+        if (a == b) return;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = atomicMin(&S[a], b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
 __device__ __forceinline__ int ccl_wave_incl_scan(int v, int lane) {
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {

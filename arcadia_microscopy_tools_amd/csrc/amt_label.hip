@@ -20,33 +20,6 @@ __device__ __forceinline__ int uf_find(const int* __restrict__ L, int a) {
     return a;
 }
 
-__device__ __forceinline__ int uf_find_volatile(int* L, int a) {
-    int p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != a) {
-        a = p;
-        p = __hip_atomic_load(&L[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return a;
-}
-
-// union by minimum index (Komura-style): the larger root is redirected to the smaller one.
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-    while (true) {
-        a = uf_find_volatile(L, a);
-        b = uf_find_volatile(L, b);
-        if (a == b) return;
-        if (a < b) {
-            int t = a;
-            a = b;
-            b = t;
-        }
-        // a > b: try to hang a below b
-        int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;  // someone else moved a meanwhile; retry from there
-    }
-}
-
 // ---- run-based, tile-local union-find -------------------------------------------------------------
 // Runs: maximal horizontal stretches of equal non-zero values inside one 64-pixel wave segment (found with
 // one ballot).  Every pixel initially points at the first pixel of its run, so whole runs are trees of depth 1
@@ -75,31 +48,6 @@ struct ccl_wide<int32_t> {
     typedef long long type;
     static constexpr long long NOVAL = -(1ll << 40);
 };
-
-__device__ __forceinline__ int lds_find(int* S, int a) {
-    int p = __hip_atomic_load(&S[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    while (p != a) {
-        a = p;
-        p = __hip_atomic_load(&S[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return a;
-}
-
-__device__ __forceinline__ void lds_union(int* S, int a, int b) {
-    while (true) {
-        a = lds_find(S, a);
-        b = lds_find(S, b);
-        if (a == b) return;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = atomicMin(&S[a], b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // stitch row y (values v, index p) to row y-1 (values up) inside one 64-lane segment; executed by all lanes.
 // LDS = true: L is the tile's LDS array and `pitch` = 64; otherwise L is the plane in HBM and pitch = W.

@@ -849,6 +849,40 @@ def peak_mask(d2: DeviceArray, mask: DeviceArray, min_distance: int = 5, out=Non
     return o
 
 
+PEAK_MARKERS_LDS_TIER = _hip.PEAK_MARKERS_LDS_TIER  # peak lists up to this length are labelled from LDS
+
+
+def peak_markers(d2: DeviceArray, mask: DeviceArray, min_distance: int = 5, connectivity: int = 1,
+                 capacity: int | None = None, peaks=None, markers=None, count=None, keep=None):
+    """``peak_mask`` followed by ``label_sparse`` in one call (``amt_peak_markers``): the peak search lists the peaks it
+    finds and the markers are labelled from that list, so neither plane is read again.  Returns (peaks, markers, count),
+    bit for bit what the two operators give; a plane with more than ``capacity`` peaks reports count -1 and gets no
+    markers.
+
+    ``keep`` = (int32 (n, capacity) list, int32 (n,) counts) as ``label_sparse(keep=)`` takes it: ``peaks``, ``markers``
+    and ``count`` must then be the caller's persistent arrays, zeroed once together with the counts, and every call clears
+    only the pixels the previous call wrote."""
+    ctx = d2.ctx
+    n, H, W = _planes(d2)
+    if capacity is None:
+        capacity = label_sparse_capacity(H, W)
+    klist_ptr = kcount_ptr = None
+    if keep is not None:
+        klist, kcount = keep
+        if peaks is None or markers is None or count is None:
+            raise ValueError("keep= needs the caller's persistent peaks=, markers= and count= arrays")
+        if klist.dtype != np.int32 or klist.size != n * int(capacity) or kcount.dtype != np.int32 or kcount.size != n:
+            raise ValueError("keep must be (int32 (n, capacity), int32 (n,))")
+        klist_ptr, kcount_ptr = klist.ptr, kcount.ptr
+    pk = _out(ctx, peaks, d2.shape, np.uint8)
+    mk = _out(ctx, markers, d2.shape, np.int32)
+    c = _out(ctx, count, (n,), np.int32)
+    _hip.check(_lib().amt_peak_markers(ctx.handle, d2.ptr, mask.ptr, pk.ptr, mk.ptr, c.ptr, n, H, W, int(min_distance),
+                                       int(connectivity), int(capacity), klist_ptr, kcount_ptr), "amt_peak_markers")
+    pk.is_bool = True
+    return pk, mk, c
+
+
 def _ws_ties(ctx, n: int, ties_policy: str, ties_out):
     """The per-plane tie flags: the caller's array, a fresh one when the policy needs them, else none (the hot path
     allocates nothing)."""

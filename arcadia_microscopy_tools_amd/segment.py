@@ -93,7 +93,7 @@ class FovSegmenter:
         self.count8 = c.empty((B,), np.int32)
         self.d2 = c.empty(shp, np.int32)
         self.peaks = c.zeros(shp, np.uint8)  # zeroed once; see self._marker_keep
-        # marker planes are zeroed ONCE: every run clears only the pixels the previous run wrote (label_sparse keep=)
+        # marker planes are zeroed ONCE: every run clears only the pixels the previous run wrote (peak_markers keep=)
         self.markers = c.zeros(shp, np.int32)
         self._marker_keep = (c.empty((B, hipops.label_sparse_capacity(self.H, self.W)), np.int32), c.zeros((B,), np.int32))
         self.nmarkers = c.zeros((B,), np.int32)
@@ -195,12 +195,12 @@ class FovSegmenter:
         self._stage("edt")
         hipops.edt(mask, want_edt=False, d2_out=self.d2)
         self._stage("peaks")
-        hipops.peak_mask(self.d2, mask, self.min_distance, out=self.peaks, keep=self._marker_keep, status=self.nmarkers)
-        self._stage("markers")
-        hipops.label_sparse(self.peaks, 1, out=self.markers, count=self.nmarkers, keep=self._marker_keep)  # sparse
+        # peak search + sparse labelling of the peaks it lists, one call: neither plane is scanned for its few peaks
+        hipops.peak_markers(self.d2, mask, self.min_distance, 1, peaks=self.peaks, markers=self.markers,
+                            count=self.nmarkers, keep=self._marker_keep)
         if self.fused:
             # watershed + clear_border + relabel_sequential in one call: the watershed image is never written out
-            # (self.ws only receives the pixels of flooded components); the list of marker pixels label_sparse keeps
+            # (self.ws only receives the pixels of flooded components); the list of marker pixels peak_markers keeps
             # spares its statistics pass the marker plane
             self._stage("watershed_clear_relabel")
             hipops.watershed_edt_cleared(self.d2, self.markers, mask, self.nmarkers, self.max_cells, scratch=self.ws,

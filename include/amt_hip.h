@@ -327,6 +327,20 @@ int amt_edt(amt_ctx* ctx, const uint8_t* mask, int32_t* d2_out, double* edt_out,
 int amt_peak_mask(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int nplanes, int H, int W,
                   int min_distance, const int32_t* prev_list, const int32_t* prev_count, int capacity,
                   const int32_t* prev_status);
+/* amt_peak_mask followed by amt_label_sparse in one operation, without reading either plane again: the peak search
+ * lists the peaks it writes, and one workgroup per plane sorts that list into raster order, joins neighbours
+ * (connectivity 1 or 2), numbers the components and writes the markers.  Bit for bit the results of the two calls:
+ * `peaks` as the peak mask, and for every plane with at most `capacity` peaks `markers`, count_dev, keep_count and the
+ * first keep_count entries of keep_list[plane * capacity ...] (raster order) as the sparse labelling leaves them.  A
+ * plane with more peaks reports count_dev = -1 and keep_count = 0 and gets NO markers.
+ * keep_list, keep_count (both NULL or both given): with them `peaks`, `markers`, the lists, keep_count and count_dev are
+ * the caller's persistent buffers, zeroed once -- count_dev is read as the previous run's status (-1: both planes are
+ * cleared whole) before it receives this run's counts, and only the listed pixels are cleared.  Without them both planes
+ * are cleared whole.  Lists of up to AMT_PEAK_MARKERS_LDS_TIER peaks are labelled from LDS, longer ones in scratch. */
+#define AMT_PEAK_MARKERS_LDS_TIER 4096
+int amt_peak_markers(amt_ctx* ctx, const int32_t* d2, const uint8_t* mask, uint8_t* peaks, int32_t* markers,
+                     int32_t* count_dev, int nplanes, int H, int W, int min_distance, int connectivity, int capacity,
+                     int32_t* keep_list, int32_t* keep_count);
 /* Priority flood restricted to `mask` (skimage.segmentation.watershed, no compactness, no watershed line;
  * SURVEY.md A.1).  Priority = (value, insertion age); labels are assigned at push time.
  * `mask` holds 0 / 1 bytes (what a bool array is on the device): scikit-image takes the mask as a truth value, and only
