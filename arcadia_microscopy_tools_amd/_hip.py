@@ -75,6 +75,7 @@ _SIGS = {
     "amt_memcpy_d2d": (c_int, [_P, _P, _P, c_size_t]),
     "amt_memset": (c_int, [_P, _P, c_int, c_size_t]),
     "amt_sync": (c_int, [_P]),
+    "amt_debug_scratch_check": (c_int, [_P, POINTER(c_int), POINTER(ctypes.c_uint64)]),
     "amt_stream_wait": (c_int, [_P, _P]),
     "amt_event_create": (c_int, [_P, POINTER(c_void_p)]),
     "amt_event_record": (c_int, [_P, _P]),
@@ -206,7 +207,7 @@ def hip_runtime() -> str:
 _BLOCKING = frozenset((
     "amt_sync", "amt_event_sync", "amt_memcpy_h2d", "amt_memcpy_d2h", "amt_memcpy_d2d", "amt_host_alloc", "amt_host_free",
     "amt_host_copy", "amt_host_minmax_int", "amt_host_narrow_i64_i32", "amt_ctx_create", "amt_ctx_create_on_stream",
-    "amt_ctx_destroy", "amt_malloc", "amt_free", "amt_timer_elapsed_ms",
+    "amt_ctx_destroy", "amt_malloc", "amt_free", "amt_timer_elapsed_ms", "amt_debug_scratch_check",
 ))
 
 

@@ -29,6 +29,13 @@ struct amt_ctx {
     hipEvent_t ev[4];
     bool aux_ready;
     int fork;  // amt_ctx_set_fork: how many auxiliary streams the ops of this context use (0..3)
+    // the last committed plan (offsets, exact lengths, total): what amt_debug_scratch_check scans the padding of
+    size_t plan_off[AMT_SCRATCH_SLOTS];
+    size_t plan_len[AMT_SCRATCH_SLOTS];
+    int plan_count;
+    size_t plan_total;
+    bool plan_valid;
+    unsigned long long* dbg_first;  // device word of amt_debug_scratch_check (allocated on its first use)
 };
 
 // fork: aux streams wait for everything enqueued so far on the main stream; join: main waits for them

@@ -78,6 +78,7 @@ extern "C" int amt_ctx_destroy(amt_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->arena) (void)hipFree(ctx->arena);
+    if (ctx->dbg_first) (void)hipFree(ctx->dbg_first);
     if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
     if (ctx->aux_ready) {
         for (int i = 0; i < 3; ++i) (void)hipStreamDestroy(ctx->aux_own[i]);
@@ -110,6 +111,7 @@ static bool poison_enabled() {
 
 int amt_scratch::commit() {
     AMT_REQUIRE(!overflow, "scratch plan: more than %d buffers declared", AMT_SCRATCH_SLOTS);
+    ctx->plan_valid = false;
     const size_t total_bytes = total + 4096;  // total is a multiple of 256
     if (total_bytes > ctx->arena_cap) {
         // previous users of the arena are ordered before us on the stream; drain it before freeing
@@ -127,6 +129,75 @@ int amt_scratch::commit() {
     }
     if (poison_enabled()) AMT_HIP_CHECK(hipMemsetAsync(ctx->arena, 0xCD, ctx->arena_cap, ctx->stream));
     fill(ctx->arena);
+    memcpy(ctx->plan_off, off, sizeof(size_t) * count);
+    memcpy(ctx->plan_len, len, sizeof(size_t) * count);
+    ctx->plan_count = count;
+    ctx->plan_total = total;
+    ctx->plan_valid = true;
+    return AMT_OK;
+}
+
+// ---- AMT_DEBUG_POISON=1: the padding behind every buffer of the last plan and the arena beyond its total are red zones
+// What a clean answer does NOT say: only the LAST committed plan is known, so an entry point that commits scratch more than
+// once (a sub-op with a plan of its own) is checked for its final plan alone; a write that lands inside a neighbouring
+// buffer (a take whose length is a multiple of 256 has no padding) is not seen; and the caller looks after the entry point
+// has returned, not between its kernels.
+// (commit() left 0xCD there and no kernel owns them).  ranges: [beg, end) byte offsets into the arena, the last one the tail.
+struct scratch_ranges {
+    unsigned long long beg[AMT_SCRATCH_SLOTS + 1], end[AMT_SCRATCH_SLOTS + 1];
+    int n;
+};
+
+__global__ void __launch_bounds__(256) scratch_check_kernel(const unsigned char* __restrict__ arena, scratch_ranges r,
+                                                            unsigned long long* __restrict__ first) {
+    const size_t gt = (size_t)blockIdx.x * 256 + threadIdx.x, nthreads = (size_t)gridDim.x * 256;
+    // paddings: shorter than 256 bytes each; a grid-stride loop over 256 byte positions per buffer, so that every
+    // buffer's padding is looked at however small the grid is
+    for (size_t k = gt; k < (size_t)(r.n - 1) * 256; k += nthreads) {
+        const unsigned long long o = r.beg[k / 256] + k % 256;
+        if (o < r.end[k / 256] && arena[o] != 0xCD) atomicMin(first, o);
+    }
+    // the tail starts on a 256-byte boundary: 4-byte words, then the odd bytes
+    const unsigned long long tb = r.beg[r.n - 1], te = r.end[r.n - 1];
+    const size_t words = (size_t)(te - tb) / 4;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(arena + tb);
+    for (size_t i = gt; i < words; i += nthreads) {
+        const uint32_t v = w[i] ^ 0xCDCDCDCDu;
+        if (v) atomicMin(first, tb + i * 4 + (unsigned)(__ffs((int)v) - 1) / 8);
+    }
+    for (unsigned long long o = tb + words * 4 + gt; o < te; o += nthreads)
+        if (arena[o] != 0xCD) atomicMin(first, o);
+}
+
+extern "C" int amt_debug_scratch_check(amt_ctx* ctx, int* slot, uint64_t* offset) {
+    AMT_TRY(amt_set_device(ctx));
+    AMT_REQUIRE(slot && offset, "amt_debug_scratch_check: null argument");
+    *slot = -1;
+    *offset = 0;
+    AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (!poison_enabled() || !ctx->plan_valid || !ctx->arena) return AMT_OK;
+    scratch_ranges r;
+    const int count = ctx->plan_count;
+    for (int i = 0; i < count; ++i) {
+        r.beg[i] = ctx->plan_off[i] + ctx->plan_len[i];
+        r.end[i] = i + 1 < count ? ctx->plan_off[i + 1] : ctx->plan_total;
+    }
+    r.beg[count] = ctx->plan_total;
+    r.end[count] = ctx->arena_cap;
+    r.n = count + 1;
+    if (!ctx->dbg_first) AMT_HIP_CHECK(hipMalloc((void**)&ctx->dbg_first, sizeof(unsigned long long)));
+    AMT_HIP_CHECK(hipMemsetAsync(ctx->dbg_first, 0xFF, sizeof(unsigned long long), ctx->stream));
+    const size_t work = (size_t)(r.end[count] - r.beg[count]) / 4 + (size_t)r.n * 256;
+    hipLaunchKernelGGL(scratch_check_kernel, dim3(amt_grid_for(work, 256 * 16, 4096)), dim3(256), 0, ctx->stream,
+                       (const unsigned char*)ctx->arena, r, ctx->dbg_first);
+    AMT_LAUNCH_CHECK();
+    unsigned long long first = 0;
+    AMT_HIP_CHECK(hipMemcpyAsync(&first, ctx->dbg_first, sizeof(first), hipMemcpyDeviceToHost, ctx->stream));
+    AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (first == ~0ull) return AMT_OK;
+    for (int i = 0; i <= count; ++i)
+        if (first >= r.beg[i] && first < r.end[i]) *slot = i;
+    *offset = first;
     return AMT_OK;
 }
 

@@ -1081,16 +1081,19 @@ static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, 
     amt_buf<int> multi(s, amt_i_ccl_scratch_ints(nplanes, H, W));
     amt_buf<int> T(s, (size_t)nplanes * n);
     amt_buf<int> rootlist(s, nlist * cap);
-    amt_buf<int> blk(s, (size_t)nplanes * nblk);
-    amt_buf<int> nroots(s, nlist);
-    amt_buf<unsigned long long> bitmap(s, (size_t)nplanes * nwords);
+    // chunk counts, list counts and the root bitmap are cleared by ONE fill: one buffer (the bitmap's 8-byte words first),
+    // carved below, so that the fill stays inside a declared buffer
+    const size_t nbitmap = (size_t)nplanes * nwords, nblkints = (size_t)nplanes * nblk;
+    amt_buf<unsigned long long> zeroed(s, nbitmap + (nblkints + nlist + 1) / 2);
     // run tables of the 0 / 1 mask path
     amt_buf<unsigned long long> tbits(s, (size_t)ntiles * 64, runs);
     amt_buf<unsigned short> rtab(s, (size_t)ntiles * RT_CAP, runs);
     amt_buf<int> nruns(s, (size_t)ntiles, runs);
     AMT_TRY(s.commit());
-    // chunk counts, list counts and the root bitmap are declared one after the other: ONE fill clears them
-    AMT_HIP_CHECK(hipMemsetAsync(blk, 0, (size_t)((char*)(bitmap + (size_t)nplanes * nwords) - (char*)blk.p), ctx->stream));
+    unsigned long long* const bitmap = zeroed;
+    int* const blk = (int*)(bitmap + nbitmap);
+    int* const nroots = blk + nblkints;
+    AMT_HIP_CHECK(hipMemsetAsync(zeroed, 0, nbitmap * 8 + (nblkints + nlist) * 4, ctx->stream));
     if (runs) {
         // 0 / 1 masks: run tables instead of a parent plane.  A batch that turns out to hold other byte values raises
         // *multi; every run-table kernel then stands down and the byte kernels -- which otherwise leave at once -- redo it

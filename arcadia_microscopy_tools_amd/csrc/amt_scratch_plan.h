@@ -2,6 +2,8 @@
 // An op declares every buffer once with take(); each take is rounded up to 256 bytes, offsets follow the order of the
 // declarations, and the reservation is the end of the last take.  The pointers are written by fill(), i.e. only once
 // the reservation of exactly that total exists; a pointer whose take was skipped by a condition stays nullptr.
+// len[] keeps every take's exact byte length: what lies between off[i] + len[i] and the next offset is padding no kernel
+// may write (amt_debug_scratch_check).
 #pragma once
 #include <cstddef>
 #include <cstring>
@@ -12,6 +14,7 @@ constexpr int AMT_SCRATCH_SLOTS = 48;
 struct amt_scratch_plan {
     void* slot[AMT_SCRATCH_SLOTS];  // address of the caller's pointer variable
     size_t off[AMT_SCRATCH_SLOTS];
+    size_t len[AMT_SCRATCH_SLOTS];  // exact bytes of the take (off[i] + len[i] <= the next offset)
     int count = 0;
     size_t total = 0;
     bool overflow = false;  // one take too many for the table: the plan must not be committed
@@ -24,7 +27,8 @@ struct amt_scratch_plan {
             return;
         }
         slot[count] = &p;
-        off[count++] = total;
+        off[count] = total;
+        len[count++] = n * sizeof(T);
         total += (n * sizeof(T) + 255) / 256 * 256;
     }
 

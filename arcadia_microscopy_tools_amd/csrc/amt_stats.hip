@@ -288,6 +288,8 @@ __global__ void __launch_bounds__(256) hist_f64_kernel(const double* __restrict_
     __syncthreads();
     uint32_t* mine = lh + (threadIdx.x >> 6) * nbins;
     const double norm = (double)nbins / (hi - lo);
+    // a constant plane: np.histogram widens its range to (v - 0.5, v + 0.5), so every sample sits in the middle bin
+    const bool flat = !(lo < hi);
     const double* src = in + (size_t)plane * n;
     const int lane = threadIdx.x & 63;
     // four CONSECUTIVE samples per thread and step (two 16-byte loads, ONE packed 4-byte store of their bins); a
@@ -311,7 +313,7 @@ __global__ void __launch_bounds__(256) hist_f64_kernel(const double* __restrict_
         for (int u = 0; u < 4; ++u) {
             const double v = v4[u];
             const bool ok = v >= lo && v <= hi;  // NaN / out of range: not counted
-            int b = ok ? (int)((v - lo) * norm) : 0;
+            int b = ok ? (flat ? nbins / 2 : (int)((v - lo) * norm)) : 0;
             b = b < 0 ? 0 : (b > nbins - 1 ? nbins - 1 : b);
             b4[u] = b;
             elo4[u] = (double)b * step + lo;  // == edges[b] (b < nbins), without the LDS round trip
@@ -323,12 +325,12 @@ __global__ void __launch_bounds__(256) hist_f64_kernel(const double* __restrict_
             const double v = v4[u];
             const bool ok = v >= lo && v <= hi;
             int b = b4[u];
-            if (ok && (v < elo4[u] || (b < nbins - 1 && v >= ehi4[u]))) {
+            if (ok && !flat && (v < elo4[u] || (b < nbins - 1 && v >= ehi4[u]))) {
                 while (b > 0 && v < edges[b]) --b;
                 while (b < nbins - 1 && v >= edges[b + 1]) ++b;
             }
             // (a constant plane has no bins: lo == hi makes the scaling infinite -- its bytes are 0 like its threshold's)
-            packed |= (unsigned)(ok && lo < hi ? b : 0) << (8 * u);
+            packed |= (unsigned)(ok && !flat ? b : 0) << (8 * u);
             const unsigned long long act = __ballot(ok);
             if (!act) continue;
             // two rounds of "first lane's bin, counted once for everyone who shares it" (64 same-address LDS atomics

@@ -206,6 +206,8 @@ class Context:
         self._stage_buf = None
         self._stage_cap = int(os.environ.get("AMT_STAGE_BYTES", str(256 << 20)))
         self._chunk_events: list[ctypes.c_void_p] = []
+        # AMT_DEBUG_POISON=1: a buffer taken back from the cache is filled with 0xCD like a fresh one (amt_malloc)
+        self._poison = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
 
     def _staging(self, nbytes: int):
         """A page-locked uint8 array of at least ``nbytes`` (None if the copy is too small to matter or too large)."""
@@ -281,6 +283,8 @@ class Context:
             ptr = lst.pop() if lst else 0
             if ptr:
                 self._pool_bytes -= nalloc
+        if ptr and self._poison:
+            _hip.check(self._lib.amt_memset(self.handle, ptr, 0xCD, nalloc), "amt_memset")
         if not ptr:
             p = ctypes.c_void_p()
             _hip.check(self._lib.amt_malloc(self.handle, nalloc, ctypes.byref(p)), "amt_malloc")
@@ -349,6 +353,16 @@ class Context:
 
     def synchronize(self):
         _hip.check(self._lib.amt_sync(self.handle), "amt_sync")
+
+    def scratch_check(self):
+        """Diagnostic (``AMT_DEBUG_POISON=1``): waits for the stream, then looks for writes into the padding behind the
+        scratch buffers of the last call that reserved scratch and into the arena beyond them.  None when they are clean
+        (or poisoning is off); else ``(slot, offset)``: the buffer, in declaration order, behind which the first stray
+        byte lies -- the number of buffers stands for the arena's tail -- and the byte's offset into the arena."""
+        slot, off = ctypes.c_int(-1), ctypes.c_uint64(0)
+        _hip.check(self._lib.amt_debug_scratch_check(self.handle, ctypes.byref(slot), ctypes.byref(off)),
+                   "amt_debug_scratch_check")
+        return None if slot.value < 0 else (int(slot.value), int(off.value))
 
     def copy_from_host_async(self, dst: "DeviceArray", src: np.ndarray):
         """Enqueue a host -> device copy on this context's stream WITHOUT waiting for it.  ``src`` must stay

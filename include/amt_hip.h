@@ -79,6 +79,12 @@ int amt_memcpy_d2h(amt_ctx* ctx, void* dst, const void* src, size_t bytes); /* a
 int amt_memcpy_d2d(amt_ctx* ctx, void* dst, const void* src, size_t bytes);
 int amt_memset(amt_ctx* ctx, void* dst, int value, size_t bytes);
 int amt_sync(amt_ctx* ctx);
+/* Diagnostic (AMT_DEBUG_POISON=1): synchronises the stream, then scans the padding behind every scratch buffer of the
+ * last call that reserved scratch, and the arena beyond that reservation, for bytes other than the 0xCD the reservation
+ * left there.  *slot = -1 when they are clean, when poisoning is off or before the first reservation; else the buffer
+ * (in declaration order) whose padding holds the first such byte -- the number of buffers stands for the arena's tail --
+ * and *offset = that byte's offset into the arena. */
+int amt_debug_scratch_check(amt_ctx* ctx, int* slot, uint64_t* offset);
 /* Order `ctx`'s stream after everything enqueued so far on `other`'s stream (same device), without
  * blocking the host: joins batch parts processed on separate streams before a collective. */
 int amt_stream_wait(amt_ctx* ctx, amt_ctx* other);
@@ -170,7 +176,8 @@ int amt_hist_u16(amt_ctx* ctx, const uint16_t* in, uint32_t* hist, int nplanes, 
 int amt_hist_range_f64(amt_ctx* ctx, const double* in, double lo, int64_t nbins, uint32_t* hist, int nplanes, size_t n);
 /* minmax_dev[plane] = {min, max} */
 int amt_minmax_f64(amt_ctx* ctx, const double* in, double* minmax_dev, int nplanes, size_t n);
-/* np.histogram(x, bins=nbins, range=(min,max)) counts per plane; edges follow np.linspace. */
+/* np.histogram(x, bins=nbins, range=(min,max)) counts per plane; edges follow np.linspace.  A constant plane counts in bin
+ * nbins / 2: numpy widens its range to (v - 0.5, v + 0.5). */
 int amt_hist_f64(amt_ctx* ctx, const double* in, const double* minmax_dev, uint32_t* hist, int nbins, int nplanes,
                  size_t n);
 /* np.percentile(x, q) (linear): q_host = nq percentiles in [0,100]; out_dev = nplanes x nq doubles.

@@ -5,10 +5,61 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from scipy import ndimage as ndi
-from arcadia_microscopy_tools_amd import hipops
 from arcadia_microscopy_tools_amd.device import get_context
-from arcadia_microscopy_tools_amd.operations import apply_threshold, rescale_by_percentile, subtract_background_dog
-from oracle import skops, regionprops as orp
+from arcadia_microscopy_tools_amd.operations import rescale_by_percentile, subtract_background_dog
+from oracle import skops
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # tests/: the sweep's table and checks
+import operator_sweep as sweep
+
+
+def draw(op):
+    """This case's parameter sets of one operator of the table: as before the campaign moved onto the table, one random
+    draw per operator and case (a mode, a footprint, a window), not the suite's full lists."""
+    P = list(op.params)
+    one = lambda sel: (lambda c: [c[int(rng.integers(0, len(c)))]])([p for p in P if sel(p)])
+    if op.name == "gaussian":
+        mode = ("nearest", "reflect", "mirror", "constant")[int(rng.integers(0, 4))]
+        return [("u16", sg, mode) for sg in (0.6, 2.0)]
+    if op.name == "apply_threshold global":
+        return [p for p in P if p[0] == "u16"]
+    if op.name == "window_threshold":
+        w = one(lambda p: p[0] == "u16")[0][2]
+        return [("u16", m, w) for m in ("niblack", "sauvola")]
+    if op.name in ("apply_threshold local", "median"):
+        return one(lambda p: p[0] == "u16")
+    if op.name == "grey morphology":
+        f = one(lambda p: p[0] == "u16")[0][2]
+        return [p for p in P if p[0] == "u16" and p[2] == f]
+    if op.name == "binary morphology":
+        f = one(lambda p: True)[0][1]
+        return [p for p in P if p[1] == f]
+    if op.name == "label":
+        return [("mask", 1), ("mask", 2), ("int32", 2)]
+    return [{"edt": "mask", "label operators": "clear_border", "regionprops": "u16"}[op.name]]
+
+
+def name_of(op, p):
+    """The check names this campaign has always printed."""
+    if op == "apply_threshold global":
+        return "threshold " + p[1]
+    if op == "window_threshold":
+        return "threshold " + p[1]
+    if op == "apply_threshold local":
+        return "threshold local"
+    if op == "grey morphology":
+        return p[1]
+    if op == "binary morphology":
+        return "binary_" + p[0]
+    if op == "label":
+        return "label int" if p[0] == "int32" else "label"
+    if op == "label operators":
+        return "clear_border"
+    return op
+
+
+SWEEP_OPS = {o.name: o for o in sweep.OPS if o.name in (
+    "gaussian", "apply_threshold global", "window_threshold", "apply_threshold local", "grey morphology", "median",
+    "binary morphology", "label", "edt", "label operators", "regionprops")}
 
 ncases = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -25,17 +76,6 @@ def check(name, ok, info):
         print("MISMATCH", name, info, flush=True)
 
 
-def blobs(H, W):
-    m = np.zeros((H, W), bool)
-    yy, xx = np.mgrid[0:H, 0:W]
-    for _ in range(int(rng.integers(1, 6))):
-        cy, cx, r = rng.integers(0, H), rng.integers(0, W), rng.integers(1, max(2, min(H, W) // 2 + 1))
-        m |= (yy - cy) ** 2 + (xx - cx) ** 2 <= r * r
-    if rng.random() < 0.3:
-        m |= rng.random((H, W)) < 0.15
-    return m
-
-
 for case in range(ncases):
     if rng.random() < 0.35:
         H, W = int(rng.integers(1, 12)), int(rng.integers(1, 12))
@@ -45,13 +85,6 @@ for case in range(ncases):
     img = rng.integers(0, 65536, shp).astype(np.uint16)
     if rng.random() < 0.3:  # smooth content: ties and plateaus
         img = (ndi.uniform_filter(img.astype(np.float64), 3) // 257 * 257).astype(np.uint16)
-    d = ctx.asarray(img)
-    # Gaussians
-    for sigma in (0.6, 2.0):
-        mode = ("nearest", "reflect", "mirror", "constant")[int(rng.integers(0, 4))]
-        got = hipops.gaussian(d, sigma, mode=mode).numpy()
-        exp = skops.gaussian(img, sigma, mode=mode)
-        check("gaussian", np.array_equal(got, exp), (shp, sigma, mode))
     got = subtract_background_dog(img, low_sigma=0.6, high_sigma=float(rng.choice([1.5, 4.0, 16.0])))
     check("dog finite", got.shape == shp and np.isfinite(got).all() and (got >= 0).all(), shp)
     dog = skops.difference_of_gaussians(img, 0.6, 3.0)
@@ -68,71 +101,14 @@ for case in range(ncases):
             exp = skops.rescale_intensity(img, (p1, p2), (0.0, 1.0)) if p1 != p2 else None
         if exp is not None:
             check("rescale", np.array_equal(got, exp), (shp, lo, hi))
-    # thresholds
-    for method in ("otsu", "li", "yen", "isodata", "triangle", "mean"):
-        got = apply_threshold(img, method=method)
-        if img.min() == img.max():
-            exp = np.zeros(shp, bool)
-        else:
-            exp = img > getattr(skops, "threshold_" + method)(img)
-        check("threshold " + method, np.array_equal(got, exp), shp)
-    w = int(rng.choice([3, 5, 9, 15]))
-    for method in ("niblack", "sauvola"):
-        got = apply_threshold(img, method=method, window_size=w)
-        exp = np.zeros(shp, bool) if img.min() == img.max() else \
-            img > getattr(skops, "threshold_" + method)(img, window_size=w)
-        check("threshold " + method, np.array_equal(got, exp), (shp, w))
-    b = int(rng.choice([3, 5, 11]))
-    got = apply_threshold(img, method="local", block_size=b)
-    exp = np.zeros(shp, bool) if img.min() == img.max() else img > skops.threshold_local(img, b)
-    check("threshold local", np.array_equal(got, exp), (shp, b))
-    # grey morphology / median
-    fps = [skops.disk(1), skops.disk(2), skops.disk(3), np.ones((3, 3), np.uint8), np.ones((1, 5), np.uint8),
-           np.ones((5, 1), np.uint8), np.ones((2, 2), np.uint8), np.ones((4, 3), np.uint8), skops.disk(7)]
-    fp = fps[int(rng.integers(0, len(fps)))]
-    for name in ("erosion", "dilation", "opening", "closing", "white_tophat"):
-        got = getattr(hipops, name)(d, fp).numpy()
-        exp = getattr(skops, name)(img, fp)
-        check(name, np.array_equal(got, exp), (shp, fp.shape))
-    mfp = fps[int(rng.integers(0, 6))]
-    mode = ("nearest", "reflect", "constant")[int(rng.integers(0, 3))]
-    check("median", np.array_equal(hipops.median(d, mfp, mode=mode).numpy(), skops.median(img, mfp, mode=mode)),
-          (shp, mfp.shape, mode))
-    # binary morphology, labels, EDT, props
-    m = blobs(H, W)
-    dm = ctx.asarray(m)
-    for name in ("binary_erosion", "binary_dilation", "binary_opening", "binary_closing"):
-        bfp = (skops.disk(1), skops.disk(2), np.ones((3, 3), np.uint8))[int(rng.integers(0, 3))]
-        check(name, np.array_equal(getattr(hipops, name)(dm, bfp).numpy(), getattr(skops, name)(m, bfp)), (shp, bfp.shape))
-    for conn in (1, 2):
-        lab, cnt = hipops.label(dm, connectivity=conn)
-        exp = skops.label(m, connectivity=conn)
-        check("label", np.array_equal(lab.numpy(), exp) and int(cnt.numpy()[0]) == exp.max(), (shp, conn))
-    ilab = (rng.integers(0, 4, shp) * m).astype(np.int32)
-    lab, cnt = hipops.label(ctx.asarray(ilab), connectivity=2)
-    exp = skops.label(ilab, connectivity=2)
-    check("label int", np.array_equal(lab.numpy(), exp), shp)
-    if m.any():
-        d2, e = hipops.edt(dm)
-        exp = skops.distance_transform_edt(m)
-        check("edt", np.array_equal(e.numpy(), exp) and np.array_equal(d2.numpy(), np.rint(exp * exp).astype(np.int64)), shp)
-    lab8 = skops.label(m, connectivity=2).astype(np.int32)
-    k = int(lab8.max())
-    if k:
-        cb = hipops.clear_border(ctx.asarray(lab8)).numpy()
-        check("clear_border", np.array_equal(cb, skops.clear_border(lab8)), shp)
-        chans = rng.integers(0, 65536, (2, H, W)).astype(np.uint16)
-        mt, it = hipops.regionprops_full(ctx.asarray(lab8[None]), ctx.asarray(chans[None]), k)
-        from arcadia_microscopy_tools_amd.segment import assemble_cell_properties
-        got = assemble_cell_properties(mt.numpy()[0][:k], it.numpy()[0][:k], ("A", "B"))
-        exp = orp.cell_properties(lab8.astype(np.int64), {"A": chans[0], "B": chans[1]})
-        okp = all(np.allclose(got[c], exp[c], rtol=1e-5, atol=1e-8, equal_nan=True) for c in exp if c != "orientation")
-        okp = okp and np.array_equal(got["area"], exp["area"]) and np.array_equal(got["label"], exp["label"])
-        if not okp:
-            for c in exp:
-                if not np.allclose(got[c], exp[c], rtol=1e-5, atol=1e-8, equal_nan=True):
-                    print("   column", c, got[c][:6], exp[c][:6])
-        check("regionprops", okp, (shp, k))
+    # Gaussians, thresholds, grey and binary morphology, median, labels, EDT, clear_border, region properties: the
+    # checks of the suite's operator sweep (tests/operator_sweep.py), on this case's shape and with planes of its own
+    sweep.set_seed(int(rng.integers(0, 2 ** 31)))
+    drawn = {name: draw(op) for name, op in SWEEP_OPS.items()}
+    for name, op in SWEEP_OPS.items():
+        by_repr = {repr(p): p for p in op.params}
+        for r in sweep.run(ctx, ops=[name], shapes=[shp], only=("single",), pick=lambda o, p: p in drawn[o.name])["records"]:
+            check(name_of(name, by_repr[r["param"]]), r["status"] == "pass", (shp, r["param"], r["index"]))
     if case % 50 == 49:
         print(f"{case + 1}/{ncases} cases, bad {bad}", flush=True)
 # config 3 end to end on small, non-square windows of synthetic FOVs (nuclei cut by the frame, a handful of cells)

@@ -34,6 +34,13 @@ int main() {
     const size_t want[5] = {0, 256, 768, 768, 1024};  // offsets follow the order of the declarations
     for (int i = 0; i < 5; ++i) CHECK(s.off[i] == want[i] && s.off[i] % 256 == 0);
     CHECK(s.total == 1024 + 512);  // the end of the last take
+    // every take's exact byte length is kept beside its offset: what follows it up to the next offset is padding
+    const size_t want_len[5] = {3 * sizeof(int), 33 * sizeof(double), 0, sizeof(short), 257};
+    for (int i = 0; i < 5; ++i) {
+        CHECK(s.len[i] == want_len[i]);
+        CHECK(s.off[i] + s.len[i] <= (i + 1 < 5 ? s.off[i + 1] : s.total));
+        CHECK((i + 1 < 5 ? s.off[i + 1] : s.total) - (s.off[i] + s.len[i]) < 256);  // less than one rounding unit
+    }
     s.fill(base);
     CHECK((char*)a == base && (char*)b == base + 256 && (char*)empty == base + 768 && (char*)(short*)h == base + 768);
     CHECK((char*)c == base + 1024);
@@ -43,6 +50,7 @@ int main() {
     int* p[AMT_SCRATCH_SLOTS + 1];
     for (int i = 0; i < AMT_SCRATCH_SLOTS; ++i) t.take(p[i], 1);
     CHECK(!t.overflow && t.count == AMT_SCRATCH_SLOTS && t.total == (size_t)256 * AMT_SCRATCH_SLOTS);
+    CHECK(t.len[0] == sizeof(int) && t.len[AMT_SCRATCH_SLOTS - 1] == sizeof(int));
     t.take(p[AMT_SCRATCH_SLOTS], 1);  // one take too many for the table is reported, not dropped silently
     CHECK(t.overflow && t.count == AMT_SCRATCH_SLOTS && p[AMT_SCRATCH_SLOTS] == nullptr);
     std::printf("ok\n");
