@@ -802,7 +802,17 @@ def _ws_dev(ctx, D, Hs, p):
     if p[0] == "edt":
         return _np(h.watershed_edt(D[0], D[1], D[2], seeds_first=True))
     mx = max(int(Hs[1].max()), 1)
-    return _np(*h.watershed_edt_cleared(D[0], D[1], D[2], D[3], mx, ctx.empty(D[0].shape, _I32)))
+    marker_list = None
+    if p[0] == "cleared list":
+        # every marker pixel per plane, as label_sparse(keep=) lists them: with W % 16 == 0 (and n % 16 == 0) the stage then
+        # works from the mask's run tables instead of the parent plane
+        n = Hs[1].shape[0]
+        klist, kcount = np.zeros((n, max(int(np.count_nonzero(m)) for m in Hs[1]) + 8), _I32), np.zeros(n, _I32)
+        for i, m in enumerate(Hs[1]):
+            idx = np.flatnonzero(m)
+            klist[i, :idx.size], kcount[i] = idx, idx.size
+        marker_list = (ctx.asarray(klist), ctx.asarray(kcount))
+    return _np(*h.watershed_edt_cleared(D[0], D[1], D[2], D[3], mx, ctx.empty(D[0].shape, _I32), marker_list=marker_list))
 
 
 def _ws_ref(ins, p):
@@ -816,7 +826,7 @@ def _ws_ref(ins, p):
 
 
 add("watershed", "edt, peaks and watershed", _ws_make, _ws_dev, _ws_ref, exact,
-    [("f64", 1), ("f64", 2), ("edt", 1), ("cleared", 1)], inkey=lambda p: p[0])
+    [("f64", 1), ("f64", 2), ("edt", 1), ("cleared", 1), ("cleared list", 1)], inkey=lambda p: p[0].split()[0])
 
 
 # ---- props, colocalisation and outlines ------------------------------------------------------------------------------------
