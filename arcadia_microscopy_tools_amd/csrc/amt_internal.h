@@ -2,6 +2,8 @@
 #pragma once
 #include "amt_common.h"
 
+#include <type_traits>
+
 // ---- exclusive prefix sum over int32 arrays: one 1024-thread workgroup per plane ---------------
 // data[plane][0..len) is replaced by its exclusive scan; total[plane] (optional) receives the sum.
 template <int ITEMS>
@@ -75,22 +77,32 @@ int amt_i_otsu_from_hist(amt_ctx* ctx, const uint32_t* hist, const double* minma
                          double* thr_code, int nplanes);
 
 // ---- connected components (amt_label.hip) -------------------------------------------------------
-// L[plane][p] = flat index of the component's first pixel (its union-find root), -1 for background.
-// Components are sets of equal-valued non-zero pixels; conn8 selects 8- vs 4-connectivity.
-// blk (nullable) = nplanes * amt_i_rank_blocks(n) ints receiving the per-block root counts for amt_i_rank_roots.
-int amt_i_ccl_roots(amt_ctx* ctx, const void* in, int in_dtype, int* L, int* blk, int nplanes, int H, int W,
-                    int conn8);
+// Tile geometry of a labelling of nplanes planes of H x W pixels, derived once (amt_i_ccl_geom) for every launch of
+// amt_label.hip and amt_watershed.hip.  Tiles are 64 x 64 pixels: `segs` per tile row, `trows` tile rows per plane.
+struct ccl_geom {
+    int nplanes, H, W;
+    size_t n;          // pixels of a plane
+    int segs, trows;   // 64-pixel column segments / 64-row tile rows of a plane
+    size_t ntiles;     // nplanes * trows * segs: an int in the kernels, which only paths that bound it may launch
+    size_t cap, nlist; // root lists (one per tile row): entries per list, number of lists = nplanes * trows
+    int nblk;          // chunks of a plane in the raster renumbering's root counts
+    int nrow_blocks;   // of gb.y, the blocks that stitch tile-row boundaries (the others: segment boundaries)
+    int jobs;          // seams between the run-table tiles of a plane
+    dim3 gs;           // a block per tile
+    dim3 gb;           // ccl_border_kernel (gb.y == 0: a single tile, nothing to stitch)
+    dim3 gseams;       // ccl_seams_runs_kernel: four jobs per block
+    dim3 glists;       // the kernels that walk the root lists
+    size_t multi_ints() const { return 16 + ntiles * 4; }  // scratch behind `multi`: the flag + two column words per tile
+};
+ccl_geom amt_i_ccl_geom(int nplanes, int H, int W);
 // 4-connected components of a uint8 mask without the per-pixel compression pass: pixels point at their tile-local
-// root; tile-local roots are appended to one list per TILE ROW, rootlist[(plane * amt_i_tile_rows(H) + tile_row) *
-// amt_i_rootlist_cap(W) ...], counted in nroots[plane * tile_rows + tile_row] (zero on entry).  Callers compress the
-// listed roots themselves and resolve a pixel as L[L[p]].
-int amt_i_tile_rows(int H);
-size_t amt_i_rootlist_cap(int W);
-// multi (nullable): one int of scratch; with it a 0 / 1 mask takes the bit-parallel tile kernel (other byte values
-// are detected and redone by the pixel kernel)
-size_t amt_i_ccl_scratch_ints(int nplanes, int H, int W);  // ints of scratch behind `multi`
-int amt_i_ccl_tileroots_u8(amt_ctx* ctx, const uint8_t* in, int* L, int* rootlist, int* nroots, int nplanes, int H,
-                           int W, int* multi = nullptr);
+// root; tile-local roots are appended to one list per TILE ROW, rootlist[(plane * trows + tile_row) * cap ...], counted
+// in nroots[plane * trows + tile_row] (zero on entry).  Callers compress the listed roots themselves and resolve a pixel
+// as L[L[p]].
+// multi (nullable): ccl_geom::multi_ints() of scratch; with it a 0 / 1 mask takes the bit-parallel tile kernel (other
+// byte values are detected and redone by the pixel kernel)
+int amt_i_ccl_tileroots_u8(amt_ctx* ctx, const ccl_geom& g, const uint8_t* in, int* L, int* rootlist, int* nroots,
+                           int* multi = nullptr);
 // Run tables of a 0 / 1 (or truth-value) mask, per 64 x 64 tile t = (plane * tile_rows + tile_row) * segments + segment:
 //   tbits[t * 64 + row]   the row's 64 pixels as a word (bit i = column i)
 //   rtab[t * RT_CAP + k]  for the tile's k-th run in raster order: (row << 6 | column) of the first pixel of its TILE ROOT
@@ -98,12 +110,16 @@ int amt_i_ccl_tileroots_u8(amt_ctx* ctx, const uint8_t* in, int* L, int* rootlis
 // A pixel's run: runs of the rows above (prefix sum of the rows' head counts) + heads at or before it in its own row.
 //   roff[t * 64 + row]    runs of the tile's rows above `row` (optional: random look-ups need it, tile-wide passes scan)
 constexpr int RT_CAP = 2048;  // 64 rows x at most 32 runs
-bool amt_i_ccl_runs_ok(const void* in, int H, int W, int nplanes);
+// What every run-table path asks of its mask: whole 16-byte groups of pixels per row and per plane, read aligned.  Each
+// caller adds the alignment of its own planes and the limit of the int index it forms from ntiles.
+static inline bool amt_i_ccl_runs_ok(const void* in, const ccl_geom& g) {
+    return g.W % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && g.n % 16 == 0;
+}
 // The watershed's labelling of its mask from run tables alone: 4-connected components of the NON-ZERO bytes; L is written
 // at the tile roots only (L[root] = root, then the seams' unions), the tile roots are listed as amt_i_ccl_tileroots_u8
 // lists them
-int amt_i_ccl_tileroots_runs_u8(amt_ctx* ctx, const uint8_t* in, int* L, int* rootlist, int* nroots, int nplanes, int H,
-                                int W, unsigned long long* tbits, unsigned short* rtab, int* nruns, unsigned short* roff);
+int amt_i_ccl_tileroots_runs_u8(amt_ctx* ctx, const ccl_geom& g, const uint8_t* in, int* L, int* rootlist, int* nroots,
+                                unsigned long long* tbits, unsigned short* rtab, int* nruns, unsigned short* roff);
 // what a kernel needs for random look-ups "pixel -> run -> component" (rcomp[t * RT_CAP + k] = the 1-based component id of
 // run k, written by the watershed's statistics pass); tbits == nullptr: no run tables, the caller reads its parent plane
 struct amt_runtabs {
@@ -115,20 +131,15 @@ struct amt_runtabs {
 };
 // A[t] = A[L[t]] for every listed tile root t (lists compressed): a pixel then reaches its component's entry of A
 // with one hop through its tile root
-int amt_i_propagate_roots(amt_ctx* ctx, int* A, const int* L, const int* rootlist, const int* nroots, int nplanes, int H,
-                          int W);
-// T[plane][root] = 1-based rank of the root in raster order; count_dev[plane] = number of roots.
-// blk = scratch of nplanes * amt_i_rank_blocks(n) ints.
-int amt_i_rank_blocks(size_t n);
-int amt_i_rank_roots(amt_ctx* ctx, const int* L, int* T, int* blk, int* count_dev, int nplanes, size_t n);
+int amt_i_propagate_roots(amt_ctx* ctx, const ccl_geom& g, int* A, const int* L, const int* rootlist, const int* nroots);
 
-// label map halves (amt_label.hip): see amt_i_presence_fill
-int amt_i_presence_fill(amt_ctx* ctx, int* P, const int* nlabels_dev, int max_label, int nplanes);
-int amt_i_drop_and_scan(amt_ctx* ctx, int* P, int max_label, int* count_dev, int nplanes);
+// runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
+template <typename F>
+static inline void amt_with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
 
-// Value of the neighbouring lane by DPP wave shift (a VALU move, no LDS crossbar as ds_bpermute needs): lane 0 of
-// amt_lane_left / lane 63 of amt_lane_right receive 0, every caller masks those lanes itself.  All 64 lanes must be
-// active (call from wave-uniform control flow only).
 #ifdef __HIPCC__
 // Lock-free union-find on an int array of parents (amt_label.hip's labelling, amt_edt.hip's peak markers): uf_* on a
 // plane or list in HBM, lds_* on one in LDS.  The root of a set is its smallest index.
@@ -214,6 +225,9 @@ __device__ __forceinline__ int amt_rt_run_root(const amt_runtabs& rt, long long 
     const int bx = (int)(t % rt.segs), ty = (int)((t / rt.segs) % rt.trows);
     return (ty * 64 + (e >> 6)) * W + bx * 64 + (e & 63);
 }
+// Value of the neighbouring lane by DPP wave shift (a VALU move, no LDS crossbar as ds_bpermute needs): lane 0 of
+// amt_lane_left / lane 63 of amt_lane_right receive 0, every caller masks those lanes itself.  All 64 lanes must be
+// active (call from wave-uniform control flow only).
 __device__ __forceinline__ int amt_lane_left(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ int amt_lane_right(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x130, 0xf, 0xf, false); }
 __device__ __forceinline__ long long amt_lane_left(long long v) {

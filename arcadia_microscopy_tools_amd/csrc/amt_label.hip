@@ -11,15 +11,6 @@
 
 #include <type_traits>
 
-__device__ __forceinline__ int uf_find(const int* __restrict__ L, int a) {
-    int p = L[a];
-    while (p != a) {
-        a = p;
-        p = L[a];
-    }
-    return a;
-}
-
 // ---- run-based, tile-local union-find -------------------------------------------------------------
 // Runs: maximal horizontal stretches of equal non-zero values inside one 64-pixel wave segment (found with
 // one ballot).  Every pixel initially points at the first pixel of its run, so whole runs are trees of depth 1
@@ -246,11 +237,6 @@ __global__ void __launch_bounds__(256) ccl_tile_fallback_kernel(const T* __restr
 //     its run's head by a count-leading-zeros on its row's word.
 // Values other than 0 / 1 (a uint8 image labelled "by equal value") set *multi, the caller resets the root lists and
 // ccl_tile_kernel redoes the planes.  Requires W % 16 == 0 and 16-byte aligned rows (the host checks).
-__device__ __forceinline__ int ccl_run_start(unsigned long long w, int x) {
-    const unsigned long long z = ~w & ((1ull << x) - 1ull);  // zeros below x
-    return z ? 64 - __clzll((long long)z) : 0;
-}
-
 // union-find over RUNS: entry of run id (row << 5 | ordinal of the run in its row; a row has at most 32 runs) =
 // parent id << 6 | the parent run's first column -- ids grow in raster order of the runs' first pixels, so "smaller entry
 // wins" is "smaller id wins", and a find returns the root's position along with its id
@@ -770,160 +756,124 @@ __global__ void __launch_bounds__(256) ccl_compress_count_kernel(int* __restrict
     if (threadIdx.x == 0) blockcnt[(size_t)blockIdx.y * nblk + blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
 
-// rank of every root (1-based) written at the root's own position of T.  A block owns RN_CHUNK pixels in the
-// order (k, thread): all eight loads are issued first, each wave ballots its root flags per k, and ONE barrier
-// later every root knows how many roots precede it in the block.
-__global__ void __launch_bounds__(256) root_rank_kernel(const int* __restrict__ L, const int* __restrict__ blockoff,
-                                                        int* __restrict__ T, size_t n, int nblk) {
-    const size_t base = (size_t)blockIdx.y * n;
-    const size_t start = (size_t)blockIdx.x * RN_CHUNK;
-    __shared__ int wtot[8][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int l[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const size_t i = start + (size_t)k * 256 + threadIdx.x;
-        l[k] = i < n ? L[base + i] : -1;
-    }
-    unsigned long long m[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const size_t i = start + (size_t)k * 256 + threadIdx.x;
-        m[k] = __ballot(l[k] == (int)i && i < n);
-        if (lane == 0) wtot[k][wave] = __popcll(m[k]);
-    }
-    __syncthreads();
-    int run = blockoff[(size_t)blockIdx.y * nblk + blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const size_t i = start + (size_t)k * 256 + threadIdx.x;
-        int before = run;
-        for (int w = 0; w < wave; ++w) before += wtot[k][w];
-        if ((m[k] >> lane) & 1ull) T[base + i] = before + __popcll(m[k] & ((1ull << lane) - 1ull)) + 1;
-        run += wtot[k][0] + wtot[k][1] + wtot[k][2] + wtot[k][3];
-    }
+ccl_geom amt_i_ccl_geom(int nplanes, int H, int W) {
+    ccl_geom g;
+    g.nplanes = nplanes, g.H = H, g.W = W;
+    g.n = (size_t)H * W;
+    g.segs = (W + 63) / 64;
+    g.trows = (H + TILE_R - 1) / TILE_R;
+    g.ntiles = (size_t)nplanes * g.trows * g.segs;
+    g.cap = (size_t)TILE_R * W;
+    g.nlist = (size_t)nplanes * g.trows;
+    g.nblk = (int)((g.n + RN_CHUNK - 1) / RN_CHUNK);
+    const int nrow_jobs = (H - 1) / TILE_R;   // tile boundaries
+    const int ncol_jobs = H * ((W - 1) / 64);  // (row, segment boundary) pairs
+    g.nrow_blocks = (nrow_jobs + 3) / 4;
+    g.jobs = g.segs * (g.trows - 1) + (g.segs - 1) * g.trows;
+    g.gs = dim3(g.segs, g.trows, nplanes);
+    g.gb = dim3(g.segs, g.nrow_blocks + (ncol_jobs + 256 * g.segs - 1) / (256 * g.segs), nplanes);
+    g.gseams = dim3((g.jobs + 3) / 4, 1, nplanes);
+    g.glists = dim3(4, g.trows, nplanes);
+    return g;
 }
 
-template <typename T>
-static int ccl_roots(amt_ctx* ctx, const T* in, int* L, int* blk, int nplanes, int H, int W, int conn8) {
-    const size_t n = (size_t)H * W;
-    const int nblk = amt_i_rank_blocks(n);
-    const int segs = (W + 63) / 64;
-    dim3 gs(segs, (H + TILE_R - 1) / TILE_R, nplanes);
-    const int nrow_jobs = (H - 1) / TILE_R;               // tile boundaries
-    const int nrow_blocks = (nrow_jobs + 3) / 4;
-    const int ncol_jobs = H * ((W - 1) / 64);             // (row, segment boundary) pairs
-    const int ncol_blocks = (ncol_jobs + 256 * segs - 1) / (256 * segs);
-    dim3 gb(segs, nrow_blocks + ncol_blocks, nplanes);
-    if (conn8) {
-        hipLaunchKernelGGL((ccl_tile_kernel<T, true>), gs, dim3(256), 0, ctx->stream, in, L, H, W, (int*)nullptr,
-                           (int*)nullptr, (size_t)0);
-        AMT_LAUNCH_CHECK();
-        if (gb.y > 0) hipLaunchKernelGGL((ccl_border_kernel<T, true>), gb, dim3(256), 0, ctx->stream, in, L, H, W, nrow_blocks);
-    } else {
-        hipLaunchKernelGGL((ccl_tile_kernel<T, false>), gs, dim3(256), 0, ctx->stream, in, L, H, W, (int*)nullptr,
-                           (int*)nullptr, (size_t)0);
-        AMT_LAUNCH_CHECK();
-        if (gb.y > 0) hipLaunchKernelGGL((ccl_border_kernel<T, false>), gb, dim3(256), 0, ctx->stream, in, L, H, W, nrow_blocks);
-    }
+// every pixel of L points at its component's root (amt_clear_border)
+static int ccl_roots(amt_ctx* ctx, const ccl_geom& g, const int32_t* in, int* L, int conn8) {
+    amt_with_bool(conn8 != 0, [&](auto c8) {
+        hipLaunchKernelGGL((ccl_tile_kernel<int32_t, decltype(c8)::value>), g.gs, dim3(256), 0, ctx->stream, in, L, g.H, g.W,
+                           (int*)nullptr, (int*)nullptr, (size_t)0);
+    });
     AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ccl_compress_count_kernel, dim3(nblk, nplanes), dim3(256), 0, ctx->stream, L, blk, n, nblk);
+    if (g.gb.y > 0) {
+        amt_with_bool(conn8 != 0, [&](auto c8) {
+            hipLaunchKernelGGL((ccl_border_kernel<int32_t, decltype(c8)::value>), g.gb, dim3(256), 0, ctx->stream, in, L, g.H, g.W,
+                               g.nrow_blocks);
+        });
+        AMT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(ccl_compress_count_kernel, dim3(g.nblk, g.nplanes), dim3(256), 0, ctx->stream, L, (int*)nullptr, g.n,
+                       g.nblk);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
 
-int amt_i_ccl_roots(amt_ctx* ctx, const void* in, int in_dtype, int* L, int* blk, int nplanes, int H, int W,
-                    int conn8) {
-    if (in_dtype == AMT_U8)
-        return ccl_roots<uint8_t>(ctx, (const uint8_t*)in, L, blk, nplanes, H, W, conn8);
-    return ccl_roots<int32_t>(ctx, (const int32_t*)in, L, blk, nplanes, H, W, conn8);
-}
-
-// 4-connected components of a uint8 mask WITHOUT the per-pixel compression pass: afterwards every foreground pixel
-// points at its tile-local root and every tile-local root is listed in rootlist (nroots[plane] entries, zero on
-// entry); the caller compresses the listed roots (find + path compression) and resolves pixels with two hops,
-// L[L[p]].
-int amt_i_tile_rows(int H) { return (H + TILE_R - 1) / TILE_R; }
-size_t amt_i_rootlist_cap(int W) { return (size_t)TILE_R * W; }
-
-// ints of scratch behind `multi`: the flag (16 ints) + two 64-bit column words per tile
-size_t amt_i_ccl_scratch_ints(int nplanes, int H, int W) {
-    return 16 + (size_t)nplanes * ((W + 63) / 64) * ((H + TILE_R - 1) / TILE_R) * 4;
-}
-
-// multi (nullable): amt_i_ccl_scratch_ints of scratch; with it, uint8 inputs take the bit-parallel tile kernel first
+// Components WITHOUT the per-pixel compression pass: afterwards every foreground pixel points at its tile-local root and
+// every tile-local root is listed in rootlist (nroots[plane * trows + tile row] entries, zero on entry); the caller
+// compresses the listed roots (find + path compression) and resolves pixels with two hops, L[L[p]].
+// multi (nullable): g.multi_ints() of scratch; with it, uint8 inputs take the bit-parallel tile kernel first
 template <typename T, bool CONN8>
-static int ccl_tileroots(amt_ctx* ctx, const T* in, int* L, int* rootlist, int* nroots, int nplanes, int H, int W,
+static int ccl_tileroots(amt_ctx* ctx, const ccl_geom& g, const T* in, int* L, int* rootlist, int* nroots,
                          int* multi = nullptr) {
-    const size_t cap = amt_i_rootlist_cap(W);
-    const int segs = (W + 63) / 64;
-    dim3 gs(segs, (H + TILE_R - 1) / TILE_R, nplanes);
-    const int nrow_jobs = (H - 1) / TILE_R;
-    const int nrow_blocks = (nrow_jobs + 3) / 4;
-    const int ncol_jobs = H * ((W - 1) / 64);
-    const int ncol_blocks = (ncol_jobs + 256 * segs - 1) / (256 * segs);
-    dim3 gb(segs, nrow_blocks + ncol_blocks, nplanes);
+    const int H = g.H, W = g.W;
     bool done = false;
-    if (std::is_same<T, uint8_t>::value && multi && W % 16 == 0 &&
-        (reinterpret_cast<uintptr_t>(in) & 15) == 0 && ((size_t)H * W) % 16 == 0) {
+    if (std::is_same<T, uint8_t>::value && multi && amt_i_ccl_runs_ok(in, g)) {
         // masks: the bit-parallel tile kernel; a plane batch that turns out to hold other byte values is redone below
         AMT_HIP_CHECK(hipMemsetAsync(multi, 0, sizeof(int), ctx->stream));
-        hipLaunchKernelGGL((ccl_tile_bits_kernel<CONN8>), gs, dim3(64), 0, ctx->stream, (const uint8_t*)in, L, H, W, rootlist,
-                           nroots, cap, multi, reinterpret_cast<unsigned long long*>(multi + 16));
+        hipLaunchKernelGGL((ccl_tile_bits_kernel<CONN8>), g.gs, dim3(64), 0, ctx->stream, (const uint8_t*)in, L, H, W, rootlist,
+                           nroots, g.cap, multi, reinterpret_cast<unsigned long long*>(multi + 16));
         AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ccl_reset_lists_kernel, dim3(8), dim3(256), 0, ctx->stream, nroots,
-                           (size_t)nplanes * gs.y, (const int*)multi);
+        hipLaunchKernelGGL(ccl_reset_lists_kernel, dim3(8), dim3(256), 0, ctx->stream, nroots, g.nlist, (const int*)multi);
         AMT_LAUNCH_CHECK();
         hipLaunchKernelGGL((ccl_tile_fallback_kernel<T, CONN8>), dim3(512), dim3(256), 0, ctx->stream, in, L, H, W, rootlist,
-                           nroots, cap, (const int*)multi, (int)gs.x, (int)gs.y, nplanes);
+                           nroots, g.cap, (const int*)multi, g.segs, g.trows, g.nplanes);
         AMT_LAUNCH_CHECK();
         done = true;
     }
     if (!done) {
-        hipLaunchKernelGGL((ccl_tile_kernel<T, CONN8>), gs, dim3(256), 0, ctx->stream, in, L, H, W, rootlist, nroots, cap);
+        hipLaunchKernelGGL((ccl_tile_kernel<T, CONN8>), g.gs, dim3(256), 0, ctx->stream, in, L, H, W, rootlist, nroots, g.cap);
         AMT_LAUNCH_CHECK();
     }
-    if (gb.y > 0) {
+    if (g.gb.y > 0) {
         // with the bit kernel's column words the byte version only stitches the rows (its column jobs leave at once
         // unless the batch turned out to hold other byte values)
-        hipLaunchKernelGGL((ccl_border_kernel<T, CONN8>), gb, dim3(256), 0, ctx->stream, in, L, H, W, nrow_blocks,
+        hipLaunchKernelGGL((ccl_border_kernel<T, CONN8>), g.gb, dim3(256), 0, ctx->stream, in, L, H, W, g.nrow_blocks,
                            done ? (const int*)multi : (const int*)nullptr);
         AMT_LAUNCH_CHECK();
-        if (done && segs > 1) {
-            const int jobs = (segs - 1) * (int)gs.y;
-            hipLaunchKernelGGL((ccl_border_cols_bits_kernel<CONN8>), dim3((jobs + 3) / 4, 1, nplanes), dim3(256), 0, ctx->stream,
-                               reinterpret_cast<const unsigned long long*>(multi + 16), L, H, W, segs, (int)gs.y,
-                               (const int*)multi);
+        if (done && g.segs > 1) {
+            hipLaunchKernelGGL((ccl_border_cols_bits_kernel<CONN8>), dim3(((g.segs - 1) * g.trows + 3) / 4, 1, g.nplanes),
+                               dim3(256), 0, ctx->stream, reinterpret_cast<const unsigned long long*>(multi + 16), L, H, W,
+                               g.segs, g.trows, (const int*)multi);
             AMT_LAUNCH_CHECK();
         }
     }
     return AMT_OK;
 }
 
-// the watershed's labelling of its mask from run tables (amt_internal.h)
-bool amt_i_ccl_runs_ok(const void* in, int H, int W, int nplanes) {
-    return W % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && ((size_t)H * W) % 16 == 0 &&
-           (size_t)nplanes * amt_i_tile_rows(H) * ((W + 63) / 64) * RT_CAP < 0x7fffffffull;  // run indices are ints
+int amt_i_ccl_tileroots_u8(amt_ctx* ctx, const ccl_geom& g, const uint8_t* in, int* L, int* rootlist, int* nroots,
+                           int* multi) {
+    return ccl_tileroots<uint8_t, false>(ctx, g, in, L, rootlist, nroots, multi);
 }
 
-int amt_i_ccl_tileroots_runs_u8(amt_ctx* ctx, const uint8_t* in, int* L, int* rootlist, int* nroots, int nplanes, int H,
-                                int W, unsigned long long* tbits, unsigned short* rtab, int* nruns, unsigned short* roff) {
-    const int segs = (W + 63) / 64, trows = amt_i_tile_rows(H);
-    hipLaunchKernelGGL((ccl_tile_runs_kernel<false, true>), dim3(segs, trows, nplanes), dim3(64), 0, ctx->stream, in, L, H, W,
-                       rootlist, nroots, amt_i_rootlist_cap(W), (int*)nullptr, tbits, rtab, nruns, roff);
+// Tile pass and seams of the run-table labelling.  ws: the watershed's tile kernel (truth values, roff stored); multi
+// (nullable, not with ws): the "other byte values" flag the tile pass raises and the seams stand down for
+static int ccl_tile_runs(amt_ctx* ctx, const ccl_geom& g, bool c8, bool ws, const uint8_t* in, int* L, int* rootlist,
+                         int* nroots, int* multi, unsigned long long* tbits, unsigned short* rtab, int* nruns,
+                         unsigned short* roff) {
+    amt_with_bool(c8, [&](auto C8) {
+        amt_with_bool(ws, [&](auto WS) {
+            hipLaunchKernelGGL((ccl_tile_runs_kernel<decltype(C8)::value, decltype(WS)::value>), g.gs, dim3(64), 0, ctx->stream, in, L, g.H, g.W,
+                               rootlist, nroots, g.cap, multi, tbits, rtab, nruns, roff);
+        });
+    });
     AMT_LAUNCH_CHECK();
-    const int jobs = segs * (trows - 1) + (segs - 1) * trows;
-    if (jobs > 0) {
-        hipLaunchKernelGGL((ccl_seams_runs_kernel<false>), dim3((jobs + 3) / 4, 1, nplanes), dim3(256), 0, ctx->stream, tbits,
-                           rtab, nruns, L, H, W, segs, trows, (const int*)nullptr);
-        AMT_LAUNCH_CHECK();
-    }
+    return AMT_OK;
+}
+static int ccl_seams_runs(amt_ctx* ctx, const ccl_geom& g, bool c8, int* L, const int* multi,
+                          const unsigned long long* tbits, const unsigned short* rtab, const int* nruns) {
+    if (g.jobs <= 0) return AMT_OK;
+    amt_with_bool(c8, [&](auto C8) {
+        hipLaunchKernelGGL((ccl_seams_runs_kernel<decltype(C8)::value>), g.gseams, dim3(256), 0, ctx->stream, tbits, rtab, nruns, L, g.H,
+                           g.W, g.segs, g.trows, multi);
+    });
+    AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
 
-int amt_i_ccl_tileroots_u8(amt_ctx* ctx, const uint8_t* in, int* L, int* rootlist, int* nroots, int nplanes, int H,
-                           int W, int* multi) {
-    return ccl_tileroots<uint8_t, false>(ctx, in, L, rootlist, nroots, nplanes, H, W, multi);
+// the watershed's labelling of its mask from run tables (amt_internal.h)
+int amt_i_ccl_tileroots_runs_u8(amt_ctx* ctx, const ccl_geom& g, const uint8_t* in, int* L, int* rootlist, int* nroots,
+                                unsigned long long* tbits, unsigned short* rtab, int* nruns, unsigned short* roff) {
+    AMT_TRY(ccl_tile_runs(ctx, g, false, true, in, L, rootlist, nroots, nullptr, tbits, rtab, nruns, roff));
+    return ccl_seams_runs(ctx, g, false, L, nullptr, tbits, rtab, nruns);
 }
 
 // A[t] = A[component root of t] for every listed tile root t (the lists must be compressed already): afterwards a
@@ -942,10 +892,8 @@ __global__ void __launch_bounds__(256) roots_propagate_kernel(int* __restrict__ 
     }
 }
 
-int amt_i_propagate_roots(amt_ctx* ctx, int* A, const int* L, const int* rootlist, const int* nroots, int nplanes, int H,
-                          int W) {
-    hipLaunchKernelGGL(roots_propagate_kernel, dim3(4, amt_i_tile_rows(H), nplanes), dim3(256), 0, ctx->stream, A, L,
-                       rootlist, nroots, amt_i_rootlist_cap(W), (size_t)H * W);
+int amt_i_propagate_roots(amt_ctx* ctx, const ccl_geom& g, int* A, const int* L, const int* rootlist, const int* nroots) {
+    hipLaunchKernelGGL(roots_propagate_kernel, g.glists, dim3(256), 0, ctx->stream, A, L, rootlist, nroots, g.cap, g.n);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -1027,29 +975,6 @@ __global__ void __launch_bounds__(256) apply_rank_kernel(const int* __restrict__
     }
 }
 
-int amt_i_rank_blocks(size_t n) { return (int)((n + RN_CHUNK - 1) / RN_CHUNK); }
-
-int amt_i_rank_roots(amt_ctx* ctx, const int* L, int* T, int* blk, int* count_dev, int nplanes, size_t n) {
-    const int nblk = amt_i_rank_blocks(n);  // blk holds the per-block root counts written by amt_i_ccl_roots
-    AMT_TRY(amt_scan_excl(ctx, blk, nblk, (size_t)nblk, count_dev, nplanes));
-    hipLaunchKernelGGL(root_rank_kernel, dim3(nblk, nplanes), dim3(256), 0, ctx->stream, L, blk, T, n, nblk);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-
-static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
-                      int connectivity, bool truth);
-
-extern "C" int amt_label(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, int32_t* count_dev, int nplanes,
-                         int H, int W, int connectivity) {
-    return label_impl(ctx, in, in_dtype, out, count_dev, nplanes, H, W, connectivity, false);
-}
-
-extern "C" int amt_label_mask(amt_ctx* ctx, const uint8_t* mask, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
-                              int connectivity) {
-    return label_impl(ctx, mask, AMT_U8, out, count_dev, nplanes, H, W, connectivity, true);
-}
-
 // truth: the uint8 input is a truth value (foreground = byte != 0, as for a bool array): the run-table path then needs no
 // "other byte values" flag and none of the byte kernels that stand by for it
 static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
@@ -1061,153 +986,98 @@ static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, 
     AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "label: plane too large");
     AMT_REQUIRE((const void*)in != (const void*)out, "label: in-place operation is not supported");
     if (nplanes == 0) return AMT_OK;
-    const size_t n = (size_t)H * W;
-    const int nblk = amt_i_rank_blocks(n);
+    const ccl_geom g = amt_i_ccl_geom(nplanes, H, W);
+    const size_t n = g.n;
+    const bool c8 = connectivity == 2;
+    // 0 / 1 masks: run tables instead of a parent plane.  The limit keeps the row-word index t * 64 + row of tbits, and
+    // with it the tile count the expansion takes, inside an int
+    const bool runs = in_dtype == AMT_U8 && amt_i_ccl_runs_ok(in, g) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
+                      g.ntiles * 64 < 0x7fffffffull;
     // union-find parents L, ranks T, the lists of tile-local roots (one list per tile row; components are sets of
     // EQUAL-valued pixels, so every pixel can be a root of its own), per-chunk root counts
-    const int trows = amt_i_tile_rows(H);
-    const size_t cap = amt_i_rootlist_cap(W);
-    const size_t nlist = (size_t)nplanes * trows;
-    const size_t nwords = (n + 63) / 64;
-    // tile-local union-find + seams; only the listed tile roots are compressed, pixels resolve in two hops
-    const int segs = (W + 63) / 64;
-    const int ntiles = nplanes * trows * segs;
-    const bool runs = in_dtype == AMT_U8 && W % 16 == 0 &&
-                      (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
-                      n % 16 == 0 && (size_t)ntiles * 64 < 0x7fffffffull;
     amt_scratch s(ctx);
     amt_buf<int> L(s, (size_t)nplanes * n);
     // "a byte other than 0 / 1 was seen" + the tiles' column words (ccl_tile_bits_kernel)
-    amt_buf<int> multi(s, amt_i_ccl_scratch_ints(nplanes, H, W));
+    amt_buf<int> multi(s, g.multi_ints());
     amt_buf<int> T(s, (size_t)nplanes * n);
-    amt_buf<int> rootlist(s, nlist * cap);
+    amt_buf<int> rootlist(s, g.nlist * g.cap);
     // chunk counts, list counts and the root bitmap are cleared by ONE fill: one buffer (the bitmap's 8-byte words first),
     // carved below, so that the fill stays inside a declared buffer
-    const size_t nbitmap = (size_t)nplanes * nwords, nblkints = (size_t)nplanes * nblk;
-    amt_buf<unsigned long long> zeroed(s, nbitmap + (nblkints + nlist + 1) / 2);
+    const size_t nbitmap = (size_t)nplanes * ((n + 63) / 64), nblkints = (size_t)nplanes * g.nblk;
+    amt_buf<unsigned long long> zeroed(s, nbitmap + (nblkints + g.nlist + 1) / 2);
     // run tables of the 0 / 1 mask path
-    amt_buf<unsigned long long> tbits(s, (size_t)ntiles * 64, runs);
-    amt_buf<unsigned short> rtab(s, (size_t)ntiles * RT_CAP, runs);
-    amt_buf<int> nruns(s, (size_t)ntiles, runs);
+    amt_buf<unsigned long long> tbits(s, g.ntiles * 64, runs);
+    amt_buf<unsigned short> rtab(s, g.ntiles * RT_CAP, runs);
+    amt_buf<int> nruns(s, g.ntiles, runs);
     AMT_TRY(s.commit());
     unsigned long long* const bitmap = zeroed;
     int* const blk = (int*)(bitmap + nbitmap);
     int* const nroots = blk + nblkints;
-    AMT_HIP_CHECK(hipMemsetAsync(zeroed, 0, nbitmap * 8 + (nblkints + nlist) * 4, ctx->stream));
+    AMT_HIP_CHECK(hipMemsetAsync(zeroed, 0, nbitmap * 8 + (nblkints + g.nlist) * 4, ctx->stream));
+    // tile-local union-find + seams; only the listed tile roots are compressed, pixels resolve in two hops
+    // flag: a batch that turns out to hold bytes other than 0 / 1 raises *multi; every run-table kernel then stands down
+    // and the byte kernels -- which otherwise leave at once -- redo it.  A truth-value mask has no flag, nothing stands by
+    int* const flag = runs && !truth ? multi.p : nullptr;
     if (runs) {
-        // 0 / 1 masks: run tables instead of a parent plane.  A batch that turns out to hold other byte values raises
-        // *multi; every run-table kernel then stands down and the byte kernels -- which otherwise leave at once -- redo it
         const uint8_t* in8 = (const uint8_t*)in;
-        const bool c8 = connectivity == 2;
-        dim3 gs(segs, trows, nplanes);
-        if (truth) {
-            // a truth-value mask: tile pass, seams, the numbering of the listed tile roots, expansion -- nothing stands by
-            if (c8)
-                hipLaunchKernelGGL((ccl_tile_runs_kernel<true, true>), gs, dim3(64), 0, ctx->stream, in8, L, H, W, rootlist, nroots,
-                                   cap, (int*)nullptr, tbits, rtab, nruns, (unsigned short*)nullptr);
-            else
-                hipLaunchKernelGGL((ccl_tile_runs_kernel<false, true>), gs, dim3(64), 0, ctx->stream, in8, L, H, W, rootlist, nroots,
-                                   cap, (int*)nullptr, tbits, rtab, nruns, (unsigned short*)nullptr);
+        if (flag) AMT_HIP_CHECK(hipMemsetAsync(multi, 0, sizeof(int), ctx->stream));
+        AMT_TRY(ccl_tile_runs(ctx, g, c8, truth, in8, L, rootlist, nroots, flag, tbits, rtab, nruns, nullptr));
+        if (flag) {
+            hipLaunchKernelGGL(ccl_reset_lists_kernel, dim3(8), dim3(256), 0, ctx->stream, nroots, g.nlist, flag);
             AMT_LAUNCH_CHECK();
-            const int jobs = segs * (trows - 1) + (segs - 1) * trows;
-            if (jobs > 0) {
-                if (c8)
-                    hipLaunchKernelGGL((ccl_seams_runs_kernel<true>), dim3((jobs + 3) / 4, 1, nplanes), dim3(256), 0, ctx->stream,
-                                       tbits, rtab, nruns, L, H, W, segs, trows, (const int*)nullptr);
-                else
-                    hipLaunchKernelGGL((ccl_seams_runs_kernel<false>), dim3((jobs + 3) / 4, 1, nplanes), dim3(256), 0, ctx->stream,
-                                       tbits, rtab, nruns, L, H, W, segs, trows, (const int*)nullptr);
+            amt_with_bool(c8, [&](auto C8) {
+                hipLaunchKernelGGL((ccl_tile_fallback_kernel<uint8_t, decltype(C8)::value>), dim3(512), dim3(256), 0, ctx->stream, in8, L, H,
+                                   W, rootlist, nroots, g.cap, flag, g.segs, g.trows, nplanes);
+            });
+            AMT_LAUNCH_CHECK();
+            if (g.gb.y > 0) {
+                amt_with_bool(c8, [&](auto C8) {
+                    hipLaunchKernelGGL((ccl_border_kernel<uint8_t, decltype(C8)::value>), g.gb, dim3(256), 0, ctx->stream, in8, L, H, W,
+                                       g.nrow_blocks, (const int*)nullptr, flag);
+                });
                 AMT_LAUNCH_CHECK();
             }
-            hipLaunchKernelGGL(roots_compress_count_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, L, rootlist,
-                               nroots, blk, bitmap, cap, n, nblk);
-            AMT_LAUNCH_CHECK();
-            AMT_TRY(amt_scan_excl(ctx, blk, nblk, (size_t)nblk, count_dev, nplanes));
-            hipLaunchKernelGGL(roots_rank_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, T, L, rootlist, nroots,
-                               blk, bitmap, cap, n, nblk);
-            AMT_LAUNCH_CHECK();
-            hipLaunchKernelGGL(ccl_expand_runs_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, tbits, rtab, nruns, T, out,
-                               H, W, segs, trows, ntiles, (const int*)nullptr);
-            AMT_LAUNCH_CHECK();
-            return AMT_OK;
         }
-        AMT_HIP_CHECK(hipMemsetAsync(multi, 0, sizeof(int), ctx->stream));
-        if (c8)
-            hipLaunchKernelGGL((ccl_tile_runs_kernel<true>), gs, dim3(64), 0, ctx->stream, in8, L, H, W, rootlist, nroots, cap,
-                               multi, tbits, rtab, nruns, (unsigned short*)nullptr);
-        else
-            hipLaunchKernelGGL((ccl_tile_runs_kernel<false>), gs, dim3(64), 0, ctx->stream, in8, L, H, W, rootlist, nroots, cap,
-                               multi, tbits, rtab, nruns, (unsigned short*)nullptr);
-        AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ccl_reset_lists_kernel, dim3(8), dim3(256), 0, ctx->stream, nroots, nlist, (const int*)multi);
-        AMT_LAUNCH_CHECK();
-        const int nrow_jobs = (H - 1) / TILE_R;
-        const int nrow_blocks = (nrow_jobs + 3) / 4;
-        const int ncol_jobs = H * ((W - 1) / 64);
-        const int ncol_blocks = (ncol_jobs + 256 * segs - 1) / (256 * segs);
-        dim3 gb(segs, nrow_blocks + ncol_blocks, nplanes);
-        if (c8) {
-            hipLaunchKernelGGL((ccl_tile_fallback_kernel<uint8_t, true>), dim3(512), dim3(256), 0, ctx->stream, in8, L, H, W,
-                               rootlist, nroots, cap, (const int*)multi, segs, trows, nplanes);
-            if (gb.y > 0)
-                hipLaunchKernelGGL((ccl_border_kernel<uint8_t, true>), gb, dim3(256), 0, ctx->stream, in8, L, H, W, nrow_blocks,
-                                   (const int*)nullptr, (const int*)multi);
-        } else {
-            hipLaunchKernelGGL((ccl_tile_fallback_kernel<uint8_t, false>), dim3(512), dim3(256), 0, ctx->stream, in8, L, H, W,
-                               rootlist, nroots, cap, (const int*)multi, segs, trows, nplanes);
-            if (gb.y > 0)
-                hipLaunchKernelGGL((ccl_border_kernel<uint8_t, false>), gb, dim3(256), 0, ctx->stream, in8, L, H, W, nrow_blocks,
-                                   (const int*)nullptr, (const int*)multi);
-        }
-        AMT_LAUNCH_CHECK();
-        const int jobs = segs * (trows - 1) + (segs - 1) * trows;
-        if (jobs > 0) {
-            if (c8)
-                hipLaunchKernelGGL((ccl_seams_runs_kernel<true>), dim3((jobs + 3) / 4, 1, nplanes), dim3(256), 0, ctx->stream,
-                                   tbits, rtab, nruns, L, H, W, segs, trows, (const int*)multi);
-            else
-                hipLaunchKernelGGL((ccl_seams_runs_kernel<false>), dim3((jobs + 3) / 4, 1, nplanes), dim3(256), 0, ctx->stream,
-                                   tbits, rtab, nruns, L, H, W, segs, trows, (const int*)multi);
-            AMT_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(roots_compress_count_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, L, rootlist,
-                           nroots, blk, bitmap, cap, n, nblk);
-        AMT_LAUNCH_CHECK();
-        AMT_TRY(amt_scan_excl(ctx, blk, nblk, (size_t)nblk, count_dev, nplanes));
-        hipLaunchKernelGGL(roots_rank_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, T, L, rootlist, nroots,
-                           blk, bitmap, cap, n, nblk);
-        AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ccl_expand_runs_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, tbits, rtab, nruns, T, out,
-                           H, W, segs, trows, ntiles, (const int*)multi);
-        AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(apply_rank_kernel, dim3(amt_grid_for(n, 1024, 256), nplanes), dim3(256), 0, ctx->stream, L, T, out, n,
-                           (const int*)multi);
-        AMT_LAUNCH_CHECK();
-        return AMT_OK;
-    }
-    if (in_dtype == AMT_U8) {
-        if (connectivity == 2)
-            AMT_TRY((ccl_tileroots<uint8_t, true>(ctx, (const uint8_t*)in, L, rootlist, nroots, nplanes, H, W, multi)));
-        else
-            AMT_TRY((ccl_tileroots<uint8_t, false>(ctx, (const uint8_t*)in, L, rootlist, nroots, nplanes, H, W, multi)));
+        AMT_TRY(ccl_seams_runs(ctx, g, c8, L, flag, tbits, rtab, nruns));
     } else {
-        if (connectivity == 2)
-            AMT_TRY((ccl_tileroots<int32_t, true>(ctx, (const int32_t*)in, L, rootlist, nroots, nplanes, H, W)));
-        else
-            AMT_TRY((ccl_tileroots<int32_t, false>(ctx, (const int32_t*)in, L, rootlist, nroots, nplanes, H, W)));
+        int rc = AMT_OK;
+        amt_with_bool(c8, [&](auto C8) {
+            rc = in_dtype == AMT_U8
+                     ? ccl_tileroots<uint8_t, decltype(C8)::value>(ctx, g, (const uint8_t*)in, L, rootlist, nroots, multi)
+                     : ccl_tileroots<int32_t, decltype(C8)::value>(ctx, g, (const int32_t*)in, L, rootlist, nroots);
+        });
+        AMT_TRY(rc);
     }
-    hipLaunchKernelGGL(roots_compress_count_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, L, rootlist,
-                       nroots, blk, bitmap, cap, n, nblk);
+    // raster numbering from the lists alone: compress the listed tile roots (counting the component roots per chunk),
+    // scan the counts, then rank every listed tile root
+    hipLaunchKernelGGL(roots_compress_count_kernel, g.glists, dim3(256), 0, ctx->stream, L, rootlist, nroots, blk, bitmap, g.cap,
+                       n, g.nblk);
     AMT_LAUNCH_CHECK();
-    // raster numbering from the lists alone: scan the per-chunk root counts, then rank every listed tile root
-    AMT_TRY(amt_scan_excl(ctx, blk, nblk, (size_t)nblk, count_dev, nplanes));
-    hipLaunchKernelGGL(roots_rank_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, T, L, rootlist, nroots,
-                       blk, bitmap, cap, n, nblk);
+    AMT_TRY(amt_scan_excl(ctx, blk, g.nblk, (size_t)g.nblk, count_dev, nplanes));
+    hipLaunchKernelGGL(roots_rank_kernel, g.glists, dim3(256), 0, ctx->stream, T, L, rootlist, nroots, blk, bitmap, g.cap, n,
+                       g.nblk);
     AMT_LAUNCH_CHECK();
-    dim3 g1(amt_grid_for(n, 1024, 4096), nplanes);
-    hipLaunchKernelGGL(apply_rank_kernel, g1, dim3(256), 0, ctx->stream, L, T, out, n);
+    if (runs) {
+        hipLaunchKernelGGL(ccl_expand_runs_kernel, dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0, ctx->stream, tbits, rtab,
+                           nruns, T, out, H, W, g.segs, g.trows, (int)g.ntiles, flag);
+        AMT_LAUNCH_CHECK();
+        if (!flag) return AMT_OK;
+    }
+    // pixel -> tile root -> rank; behind the run tables it only stands by for the flag: 256 blocks that leave at once
+    hipLaunchKernelGGL(apply_rank_kernel, dim3(amt_grid_for(n, 1024, runs ? 256 : 4096), nplanes), dim3(256), 0, ctx->stream, L,
+                       T, out, n, flag);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
+}
+
+extern "C" int amt_label(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, int32_t* count_dev, int nplanes,
+                         int H, int W, int connectivity) {
+    return label_impl(ctx, in, in_dtype, out, count_dev, nplanes, H, W, connectivity, false);
+}
+
+extern "C" int amt_label_mask(amt_ctx* ctx, const uint8_t* mask, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
+                              int connectivity) {
+    return label_impl(ctx, mask, AMT_U8, out, count_dev, nplanes, H, W, connectivity, true);
 }
 
 // ---- clear_border ------------------------------------------------------------------------------
@@ -1257,7 +1127,7 @@ extern "C" int amt_clear_border(amt_ctx* ctx, const int32_t* in, int32_t* out, i
     amt_buf<int> T(s, (size_t)nplanes * n);
     AMT_TRY(s.commit());
     AMT_HIP_CHECK(hipMemsetAsync(T, 0, (size_t)nplanes * n * 4, ctx->stream));
-    AMT_TRY(ccl_roots<int32_t>(ctx, in, L, nullptr, nplanes, H, W, 1));
+    AMT_TRY(ccl_roots(ctx, amt_i_ccl_geom(nplanes, H, W), in, L, 1));
     dim3 gf(amt_grid_for((size_t)2 * W + 2 * H, 256, 64), nplanes);
     hipLaunchKernelGGL(frame_flag_kernel, gf, dim3(256), 0, ctx->stream, L, T, H, W);
     AMT_LAUNCH_CHECK();
@@ -1397,24 +1267,6 @@ __global__ void __launch_bounds__(256) presence_fill_kernel(int* __restrict__ pr
     int* P = present + (size_t)blockIdx.y * (max_label + 1);
     const int k = nlabels[blockIdx.y] < max_label ? nlabels[blockIdx.y] : max_label;
     for (int l = blockIdx.x * 256 + threadIdx.x; l <= max_label; l += gridDim.x * 256) P[l] = (l >= 1 && l <= k) ? 1 : 0;
-}
-
-// the two halves of the label map for callers that find the frame-touching labels themselves (amt_watershed.hip's fused
-// watershed + clear_border + relabel): P = nplanes x (max_label + 1) ints; fill -> caller sets P[l] = 2 for every label
-// to drop -> drop_and_scan leaves P[l] = new label (0 = dropped) and the number of survivors in count_dev
-int amt_i_presence_fill(amt_ctx* ctx, int* P, const int* nlabels_dev, int max_label, int nplanes) {
-    hipLaunchKernelGGL(presence_fill_kernel, dim3(amt_grid_for((size_t)max_label + 1, 256, 64), nplanes), dim3(256), 0,
-                       ctx->stream, P, nlabels_dev, max_label);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-int amt_i_drop_and_scan(amt_ctx* ctx, int* P, int max_label, int* count_dev, int nplanes) {
-    hipLaunchKernelGGL(drop_flagged_kernel, dim3(amt_grid_for((size_t)max_label + 1, 256, 64), nplanes), dim3(256), 0,
-                       ctx->stream, P, max_label);
-    AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(presence_scan_kernel, dim3(nplanes), dim3(1024), 0, ctx->stream, P, max_label, count_dev);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
 }
 
 extern "C" int amt_clear_border_relabel(amt_ctx* ctx, const int32_t* in, int32_t* out, int32_t* count_dev, int nplanes,

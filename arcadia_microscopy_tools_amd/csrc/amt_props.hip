@@ -29,8 +29,6 @@ __global__ void __launch_bounds__(256) rp_init_kernel(u64* __restrict__ acc, int
     }
 }
 
-__device__ __forceinline__ u64 sum_sq_upto(u64 m) { return m * (m + 1) * (2 * m + 1) / 6; }  // 0^2 + ... + m^2
-
 // exact a*b - c*d for 64-bit operands, as a double (the difference itself must fit in 127 bits)
 __device__ __forceinline__ double diff_of_products(u64 a, u64 b, u64 c, u64 d) {
     u64 lo1 = a * b, hi1 = __umul64hi(a, b);

@@ -452,10 +452,6 @@ __device__ __forceinline__ uint4 mm_lane_left(uint4 v) {
     return make_uint4((unsigned)amt_lane_left((int)v.x), (unsigned)amt_lane_left((int)v.y),
                       (unsigned)amt_lane_left((int)v.z), (unsigned)amt_lane_left((int)v.w));
 }
-__device__ __forceinline__ uint4 mm_lane_right(uint4 v) {
-    return make_uint4((unsigned)amt_lane_right((int)v.x), (unsigned)amt_lane_right((int)v.y),
-                      (unsigned)amt_lane_right((int)v.z), (unsigned)amt_lane_right((int)v.w));
-}
 // the same shifts, but the lane without a source (lane 0 / lane 63) keeps `old` (DPP without bound_ctrl)
 __device__ __forceinline__ uint4 mm_lane_left_old(uint4 old, uint4 v) {
     return make_uint4((unsigned)__builtin_amdgcn_update_dpp((int)old.x, (int)v.x, 0x138, 0xf, 0xf, false),

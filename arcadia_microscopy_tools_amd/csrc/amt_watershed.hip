@@ -22,9 +22,11 @@
 //     independent work items:
 //       - a component whose marker pixels all carry ONE label ends up entirely with that label: it is
 //         filled by a pixel-parallel kernel, no flood at all;
-//       - otherwise the component is flooded sequentially by one lane.  If its bounding box fits an LDS
-//         tile (three size classes), a wave stages label / d2 / FIFO links in LDS, lane 0 floods at LDS
-//         latency, and the wave writes the labels back; larger components use queues in HBM.
+//       - otherwise the component is flooded on its own, by size class of its bounding box:
+//         S / M / M2 / L by ws_flood_persist_kernel, ONE persistent launch whose workgroups reserve LDS per
+//         component and flood a whole bucket per step; X -- the few boxes between L and the 15-bit index
+//         limit -- by the one-pop-at-a-time ws_flood_lds_kernel; anything larger (class G) by the HBM flood
+//         with its queues in global memory (ws_flood_edt_kernel, or ws_flood_heap_kernel for a float64 relief).
 //
 // amt_watershed_edt: relief = -sqrt(d2) with d2 an exact non-negative integer, so the priority queue
 // is a bucket queue indexed by d2 (largest d2 = lowest relief first) with a FIFO per bucket: insertion
@@ -37,7 +39,16 @@
 // component classes (the values of the LDS classes S .. X are consecutive: worklist k holds class CLS_S + k)
 enum { CLS_NONE = 0, CLS_UNIFORM = 1, CLS_S = 3, CLS_M = 4, CLS_M2 = 5, CLS_L = 6, CLS_X = 7, CLS_G = 9 };
 constexpr int WS_NLISTS = CLS_X - CLS_S + 1;  // worklists S, M, M2, L, X
-constexpr int WS_CTR = 24;  // ints per plane of the counters block (layout: watershed_common)
+// The counters block: WS_CTR ints per plane, each field an array over the planes (field k of plane p:
+// counters[k * nplanes + p]).  The host code names the fields; the kernels receive pointers to them.
+constexpr int WS_CTR = 24;
+enum {
+    WS_CTR_X = 0,      // work counter of the class-X flood
+    WS_CTR_HBM = 7,    // work counter of the HBM flood
+    WS_CTR_HASG = 8,   // has_g: the plane holds a component for the HBM flood
+    WS_CTR_WL = 9,     // [9 .. 9 + WS_NLISTS): worklist sizes of classes S / M / M2 / L / X
+    WS_CTR_NCOMP = 16  // number of components
+};
 // LDS tile classes: max pixels of the bounding box, max d2 (bucket count - 1).  S / M / M2 / L are flooded by
 // ws_flood_persist_kernel (LDS reserved per component: 4 bytes per cell, 2 per queue entry, 6 per bucket), X -- the few
 // boxes between L and the 15-bit index limit -- by the one-pop-at-a-time ws_flood_lds_kernel (4 bytes per pixel).
@@ -647,11 +658,6 @@ __global__ void __launch_bounds__(256) ws_init_kernel(int* __restrict__ a, int n
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nc; i += gridDim.x * 256) c[i] = 0;
 }
 
-__global__ void ws_zero_counters_kernel(int* c, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) c[i] = 0;
-}
-
 // One lane brings the marker pixels of its component into raster order (the entries are distinct).  A handful of markers
 // is the rule: insertion sort.  A component of thin or noisy content can hold tens of thousands (a comb over a 192 x 192
 // plane: 18,000), and n^2 / 4 dependent round trips to HBM took 4.4 s there -- in-place heapsort above 32 entries.
@@ -707,6 +713,9 @@ __device__ __forceinline__ void lane_sort(int* a, int n) {
 // compare / one masked ds_write; only the claimed neighbours (one per pop on average) go through the
 // scalar FIFO append.  The current bucket's head/tail live in scalar registers.  The sentinel ring
 // removes all bounds arithmetic.
+// Only <X_PX, X_NB, CLS_X> is instantiated: the smaller classes moved to ws_flood_persist_kernel.  Of the parameters
+// the body uses TILE_PX alone (where the bucket words start); NB and CLS remain because they are part of the kernel's
+// symbol, which profiles and traces are compared by.
 template <int TILE_PX, int NB, int CLS>
 __global__ void __launch_bounds__(64) ws_flood_lds_kernel(const int* __restrict__ d2all, const int* __restrict__ Lall,
                                                           const int* __restrict__ Tall, int* __restrict__ outall,
@@ -1811,41 +1820,6 @@ __device__ __forceinline__ int ws_pixel_label(int r, const int* __restrict__ F, 
     return f > 0 ? f : (f == 0 ? ws[base + i] : 0);
 }
 
-__global__ void __launch_bounds__(256) ws_frame_mark_kernel(const int* __restrict__ L, const int* __restrict__ F,
-                                                            const int* __restrict__ ws, int* __restrict__ present, int H,
-                                                            int W, int max_label, amt_runtabs rt) {
-    const size_t n = (size_t)H * W;
-    const size_t base = (size_t)blockIdx.y * n;
-    int* P = present + (size_t)blockIdx.y * (max_label + 1);
-    const int perim = 2 * W + 2 * H;
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < perim; k += gridDim.x * 256) {
-        int y, x;
-        if (k < W) {
-            y = 0;
-            x = k;
-        } else if (k < 2 * W) {
-            y = H - 1;
-            x = k - W;
-        } else if (k < 2 * W + H) {
-            y = k - 2 * W;
-            x = 0;
-        } else {
-            y = k - 2 * W - H;
-            x = W - 1;
-        }
-        const size_t i = (size_t)y * W + x;
-        int r;
-        if (rt.tbits) {
-            const long long ri = amt_rt_px_run(rt, blockIdx.y, y, x);
-            r = ri < 0 ? -1 : amt_rt_run_root(rt, ri, W);
-        } else {
-            r = L[base + i];
-        }
-        const int v = ws_pixel_label(r, F, ws, base, i);
-        if (v > 0 && v <= max_label) P[v] = 2;
-    }
-}
-
 // labels_out = map[label of the pixel]: the ONE full-plane pass of the fused path (16-byte loads of the parent plane,
 // 16-byte stores); the flood's plane is read only at pixels of flooded components
 __global__ void __launch_bounds__(256) ws_final_kernel(const int* __restrict__ L, const int* __restrict__ F,
@@ -1880,7 +1854,8 @@ __global__ void __launch_bounds__(256) ws_final_kernel(const int* __restrict__ L
     }
 }
 
-// presence_fill + ws_frame_mark + drop_flagged + presence_scan (amt_label.hip) for one plane per workgroup:
+// presence_fill + the marking of the frame-touching labels + drop_flagged + presence_scan (amt_label.hip) for one plane
+// per workgroup:
 // P[l] = new label of l (0 = absent or touching the frame), count[plane] = number of survivors
 __global__ void __launch_bounds__(1024) ws_label_map_kernel(const int* __restrict__ L, const int* __restrict__ F,
                                                             const int* __restrict__ ws, int* __restrict__ present,
@@ -2058,13 +2033,309 @@ __global__ void __launch_bounds__(256) ws_final_runs_kernel(const unsigned long 
     }
 }
 
+// the optional arguments of the fused call (amt_watershed_edt_cleared).  labels != nullptr: `out` is only the flood's
+// scratch plane; the result is clear_border + relabel_sequential of the watershed, written to labels / count
+// (connectivity 1 only)
+struct ws_fused {
+    int32_t* labels = nullptr;
+    int32_t* count = nullptr;
+    const int32_t* nlabels_dev = nullptr;
+    int max_label = 0;
+    const int32_t* mk_list = nullptr;  // every marker pixel per plane; nullptr = the dense statistics pass
+    const int32_t* mk_count = nullptr;
+    int mk_cap = 0;
+};
+
+// what the stages of one call share: its arguments and the sizes derived from them ...
+struct ws_args {
+    amt_ctx* ctx;
+    const void* relief;
+    bool use_d2;
+    const int32_t* markers;
+    const uint8_t* mask;
+    int32_t* out;
+    int nplanes, H, W, seeds_first;
+    ws_fused fu;
+    ccl_geom g;
+    size_t n, row_stride, bstride;
+    bool runs;  // the mask's run tables serve instead of the parent plane
+};
+// ... and the scratch buffers of watershed_components' plan as plain pointers, filled after its commit
+struct ws_bufs {
+    int *L, *T, *moff, *boff, *cursor, *mlist, *next, *F, *rootlist, *nroots;
+    comp_row* rows;
+    int *btot, *mtot, *counters, *wl, *pf_idx, *pf_ctl, *ccl_scratch, *ties, *P;
+    unsigned long long* tbits;
+    unsigned short* rtab;
+    int* nruns;
+    unsigned short* roff;
+    int *rcomp, *head, *tail;
+    hp_elem *gheap, *heap;
+    int *ncomp, *has_g, *wl_count;  // fields of `counters`
+    amt_runtabs rt;
+};
+
+// the sequential single-heap emulation of the planes whose `run` flag is set (nullptr: all), in `out`
+static int ws_emulate(amt_ctx* ctx, const void* relief, bool use_d2, const int32_t* markers, const uint8_t* mask, int32_t* out,
+                      hp_elem* gheap, const int* run, int nplanes, int H, int W, int conn) {
+    const size_t n = (size_t)H * W;
+    hipLaunchKernelGGL(ws_global_init_kernel, dim3(amt_grid_for(n, 256, 1024), nplanes), dim3(256), 0, ctx->stream, markers,
+                       mask, out, run, n);
+    AMT_LAUNCH_CHECK();
+    amt_with_bool(use_d2, [&](auto D2) {
+        hipLaunchKernelGGL((ws_global_kernel<decltype(D2)::value>), dim3(nplanes), dim3(64), GH_LDS_N * sizeof(gh_elem),
+                           ctx->stream, relief, mask, out, gheap, run, H, W, n, conn);
+    });
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// components of the mask with dense ids in T (the order of the ids is irrelevant: components are independent work items
+// and nothing in the output depends on their numbering), their statistics and classes, the fill value F per root
+static int ws_label_and_classify(const ws_args& a, const ws_bufs& b) {
+    amt_ctx* ctx = a.ctx;
+    const ccl_geom& g = a.g;
+    const int nplanes = a.nplanes, H = a.H, W = a.W;
+    // counters, tie flags and the root lists' counts in ONE launch (three trivial launches cost ~5 us each in a stage
+    // of 1.2 ms)
+    hipLaunchKernelGGL(ws_init_kernel, dim3(16), dim3(256), 0, ctx->stream, b.counters, nplanes * WS_CTR, b.ties, nplanes,
+                       b.nroots, (int)g.nlist);
+    AMT_LAUNCH_CHECK();
+    if (a.runs) AMT_TRY(amt_i_ccl_tileroots_runs_u8(ctx, g, a.mask, b.L, b.rootlist, b.nroots, b.tbits, b.rtab, b.nruns, b.roff));
+    else AMT_TRY(amt_i_ccl_tileroots_u8(ctx, g, a.mask, b.L, b.rootlist, b.nroots, b.ccl_scratch));
+    hipLaunchKernelGGL(ws_roots_kernel, g.glists, dim3(256), 0, ctx->stream, b.L, b.T, b.rootlist, b.nroots, b.ncomp, g.cap, a.n);
+    AMT_LAUNCH_CHECK();
+    AMT_TRY(amt_i_propagate_roots(ctx, g, b.T, b.L, b.rootlist, b.nroots));
+    hipLaunchKernelGGL(ws_rows_init_kernel, dim3(64, nplanes), dim3(256), 0, ctx->stream, b.rows, b.ncomp, a.row_stride);
+    AMT_LAUNCH_CHECK();
+    if (a.runs) {
+        hipLaunchKernelGGL(ws_stats_runs_kernel, dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0, ctx->stream,
+                           (const int*)a.relief, b.tbits, b.rtab, b.nruns, b.L, b.T, b.rows, a.row_stride, H, W, g.segs, g.trows,
+                           (int)g.ntiles, b.rcomp);
+    } else {
+        // the caller knows where the marker pixels are (mk_list): the dense pass skips the marker plane
+        amt_with_bool(!a.fu.mk_list, [&](auto MARKER_PLANE) {
+            hipLaunchKernelGGL((ws_stats_kernel<decltype(MARKER_PLANE)::value>), dim3((W + 63) / 64, (H + 31) / 32, nplanes),
+                               dim3(256), 0, ctx->stream, a.use_d2 ? (const int*)a.relief : (const int*)nullptr, b.L, b.T,
+                               a.markers, b.rows, a.row_stride, H, W, a.use_d2 ? 1 : 0);
+        });
+    }
+    AMT_LAUNCH_CHECK();
+    if (a.fu.mk_list) {
+        hipLaunchKernelGGL(ws_marker_stats_kernel, dim3(16, nplanes), dim3(256), 0, ctx->stream, a.fu.mk_list, a.fu.mk_count,
+                           a.fu.mk_cap, a.markers, b.L, b.T, b.rows, a.row_stride, a.n, b.rt, W);
+        AMT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(ws_classify_kernel, dim3(64, nplanes), dim3(256), 0, ctx->stream, b.rows, b.ncomp, b.moff, b.boff, b.has_g,
+                       b.wl, b.wl_count, b.F, a.n, nplanes, a.row_stride, a.use_d2 ? 1 : 0);
+    AMT_LAUNCH_CHECK();
+    return amt_i_propagate_roots(ctx, g, b.F, b.L, b.rootlist, b.nroots);
+}
+
+// the HBM flood's preparation: marker lists and queue offsets of the components too large for an LDS tile (usually none)
+static int ws_prepare_hbm(const ws_args& a, const ws_bufs& b, bool gprep) {
+    amt_ctx* ctx = a.ctx;
+    const int nplanes = a.nplanes;
+    if (gprep) {  // the fused chain: the whole preparation in one launch
+        hipLaunchKernelGGL(ws_g_prep_kernel, dim3(nplanes), dim3(1024), 0, ctx->stream, a.markers, b.L, b.T, b.F, a.out, b.rows,
+                           b.moff, b.boff, b.cursor, b.mlist, b.head, b.ncomp, b.mtot, b.btot, b.has_g, a.row_stride, a.n,
+                           a.bstride, b.rt, a.W);
+        AMT_LAUNCH_CHECK();
+        return AMT_OK;
+    }
+    // the marker lists of the HBM flood's components: nearly always no plane has one, and 4,096 workgroups per plane
+    // that only read a flag and leave cost 43 us per 48 planes -- 128 (grid-stride) do when a plane does have one
+    dim3 g1(amt_grid_for(a.n, 256, 128), nplanes);
+    // the seed pass gives `out` its final value everywhere except in flooded components.  The fused path needs no
+    // such plane (its final pass derives every pixel from F and the flood's sparse writes): it seeds only planes that
+    // hold a component for the HBM flood, which works in `out` itself -- same consideration for its grid
+    hipLaunchKernelGGL(ws_seed_kernel, dim3(amt_grid_for(a.n, 1024, a.fu.labels ? 128 : 4096), nplanes), dim3(256), 0,
+                       ctx->stream, a.markers, b.L, b.F, a.out, a.n, a.fu.labels ? (const int*)b.has_g : (const int*)nullptr,
+                       b.rt, a.W);
+    AMT_LAUNCH_CHECK();
+    // ---- HBM-path bookkeeping (usually empty: only components too large for an LDS tile) ----
+    AMT_TRY(amt_scan_excl_dev(ctx, b.moff, b.ncomp, a.row_stride, b.mtot, nplanes));
+    AMT_TRY(amt_scan_excl_dev(ctx, b.boff, b.ncomp, a.row_stride, b.btot, nplanes));
+    hipLaunchKernelGGL(ws_fill_value_kernel, dim3(64, nplanes), dim3(256), 0, ctx->stream, b.cursor, b.ncomp, a.row_stride, 0);
+    AMT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ws_fill_markers_kernel, g1, dim3(256), 0, ctx->stream, b.L, b.T, a.out, b.rows, b.moff, b.cursor, b.mlist,
+                       b.has_g, a.row_stride, a.n, b.rt, a.W);
+    AMT_LAUNCH_CHECK();
+    if (a.use_d2) {
+        hipLaunchKernelGGL(ws_fill_value_kernel, dim3(256, nplanes), dim3(256), 0, ctx->stream, b.head, b.btot, a.bstride, -1);
+        AMT_LAUNCH_CHECK();
+    }
+    return AMT_OK;
+}
+
+// the floods of the d2 relief.  The LDS classes and the HBM path are independent, latency-bound and use few waves each:
+// run them side by side (fork / join on the context's auxiliary streams)
+static int ws_floods_d2(const ws_args& a, const ws_bufs& b) {
+    amt_ctx* ctx = a.ctx;
+    const int nplanes = a.nplanes;
+    const size_t ldsX = (size_t)X_PX * 4 + (size_t)X_NB * 4;
+    AMT_TRY(amt_fork(ctx));
+    // Without auxiliary streams the floods still overlap: the first flood is an ordinary (barrier) launch, the
+    // others carry hipExtAnyOrderLaunch -- their packets have no barrier bit, so the command processor dispatches
+    // them while the earlier floods are still running; the next ordinary launch waits for all of them.
+    const int any = ctx->fork == 0 ? (int)hipExtAnyOrderLaunch : 0;
+    // one persistent launch for classes S / M / M2 / L (a workgroup of PF_NWAVES waves per CU with all its LDS),
+    // then X and the HBM flood beside it.  Measured on one box against one launch per class (watershed stage per
+    // 48 FOVs in one context / 48-FOV plate / 192-FOV default, FOV/s): class launches 2.53 ms / 10.4 k / 11.5-11.7 k;
+    // whole CU, 8 waves 2.11 / 10.4 k / 11.3 k; 10 waves 2.02 / 10.4 k / 11.6 k; 16 waves 2.10; 46 slots 2.16 /
+    // 10.2 k / 10.9 k; half a CU x 2 2.26 / 10.4 k / 11.1 k.  The stage gains 0.5 ms; with four contexts side by side
+    // the floods were already hidden behind the other contexts' streaming kernels, so the totals do not move.
+    hipLaunchKernelGGL(ws_flood_index_kernel, dim3(1), dim3(64), 0, ctx->stream, b.wl_count, b.pf_idx, b.pf_ctl, nplanes);
+    AMT_LAUNCH_CHECK();
+    const int* a_d2 = (const int*)a.relief;
+    {
+        void* args[] = {&a_d2, (void*)&b.L, (void*)&b.T, (void*)&a.out, (void*)&b.rows, (void*)&b.wl, (void*)&b.pf_idx,
+                        (void*)&b.pf_ctl, (void*)&a.row_stride, (void*)&a.H, (void*)&a.W, (void*)&a.seeds_first, (void*)&b.ties,
+                        (void*)&a.markers, (void*)&a.nplanes, (void*)&b.rt};
+        AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_persist_kernel, dim3(ctx->num_cus), dim3(PF_NWAVES * 64), args,
+                                         (size_t)(PF_SLOTS + 1) * PF_SLOT, ctx->stream, nullptr, nullptr, 0));
+    }
+    {
+        const int* a_wl = b.wl + (size_t)(CLS_X - CLS_S) * nplanes * a.row_stride;
+        const int* a_wlc = b.wl_count + (CLS_X - CLS_S) * nplanes;
+        int* a_cnt = b.counters + WS_CTR_X * nplanes;
+        void* args[] = {&a_d2, (void*)&b.L, (void*)&b.T, (void*)&a.out, (void*)&b.rows, &a_wl, &a_wlc, &a_cnt,
+                        (void*)&a.row_stride, (void*)&a.H, (void*)&a.W, (void*)&a.seeds_first, (void*)&b.ties, (void*)&a.markers,
+                        (void*)&b.rt};
+        // ws_flood_lds_kernel exists in this one instantiation (see the kernel)
+        AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_lds_kernel<X_PX, X_NB, CLS_X>, dim3(8, nplanes), dim3(64), args,
+                                         ldsX, ctx->stream, nullptr, nullptr, any));
+    }
+    {
+        int* a_cnt = b.counters + WS_CTR_HBM * nplanes;
+        void* args[] = {&a_d2, (void*)&a.mask, (void*)&a.out, (void*)&b.next, (void*)&b.head, (void*)&b.tail, (void*)&b.mlist,
+                        (void*)&b.rows, (void*)&b.moff, (void*)&b.boff, (void*)&b.ncomp, &a_cnt, (void*)&a.row_stride, (void*)&a.H,
+                        (void*)&a.W, (void*)&a.n, (void*)&a.bstride, (void*)&a.seeds_first, (void*)&b.ties};
+        AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_edt_kernel, dim3(4, nplanes), dim3(64), args, 0, ctx->aux[1],
+                                         nullptr, nullptr, any));
+    }
+    AMT_TRY(amt_join(ctx));
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// the flood of a float64 relief: a binary heap per component
+static int ws_flood_f64(const ws_args& a, const ws_bufs& b) {
+    amt_ctx* ctx = a.ctx;
+    hipLaunchKernelGGL(ws_flood_heap_kernel, dim3(64, a.nplanes), dim3(64), 0, ctx->stream, (const double*)a.relief, a.mask,
+                       a.out, b.heap, b.mlist, b.rows, b.moff, b.boff, b.ncomp, b.counters + WS_CTR_HBM * a.nplanes,
+                       a.row_stride, a.H, a.W, a.n, a.bstride, b.ties);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// the fused tail: the label map of clear_border + relabel_sequential -- present labels, frame-touching ones dropped,
+// survivors numbered: one workgroup per plane does the four steps (they were four launches over a few thousand
+// entries) -- then the one pass that writes the final labels
+static int ws_fused_tail(const ws_args& a, const ws_bufs& b) {
+    amt_ctx* ctx = a.ctx;
+    const ccl_geom& g = a.g;
+    const ws_fused& fu = a.fu;
+    hipLaunchKernelGGL(ws_label_map_kernel, dim3(a.nplanes), dim3(1024), 0, ctx->stream, b.L, b.F, a.out, b.P, fu.nlabels_dev,
+                       fu.count, a.H, a.W, fu.max_label, b.rt);
+    AMT_LAUNCH_CHECK();
+    if (a.runs) {
+        hipLaunchKernelGGL(ws_final_map_kernel, g.glists, dim3(256), 0, ctx->stream, b.F, b.P, b.rootlist, b.nroots, g.cap, a.n,
+                           fu.max_label);
+        AMT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ws_final_runs_kernel, dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0, ctx->stream, b.tbits, b.rtab,
+                           b.nruns, b.F, a.out, b.P, fu.labels, a.H, a.W, g.segs, g.trows, (int)g.ntiles, fu.max_label);
+    } else {
+        hipLaunchKernelGGL(ws_final_kernel, dim3(amt_grid_for(a.n, 1024, 4096), a.nplanes), dim3(256), 0, ctx->stream, b.L, b.F,
+                           a.out, b.P, fu.labels, a.n, fu.max_label);
+    }
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// connectivity 1: the mask's 4-connected components are independent work items.  exact: planes in which two markers of
+// one component tied are re-flooded by the single-heap emulation
+static int watershed_components(amt_ctx* ctx, const void* relief, bool use_d2, const int32_t* markers, const uint8_t* mask,
+                                int32_t* out, int nplanes, int H, int W, int seeds_first, bool exact, int32_t* ties_dev,
+                                const ws_fused& fu) {
+    ws_args a = {ctx, relief, use_d2, markers, mask, out, nplanes, H, W, seeds_first, fu, amt_i_ccl_geom(nplanes, H, W)};
+    const ccl_geom& g = a.g;
+    const size_t n = a.n = g.n;
+    const size_t np = (size_t)nplanes * n;
+    // per-component rows: a 4-connected component needs a background pixel between itself and the next one in
+    // its row, so a plane has at most ceil(n / 2) components; only the first ncomp[plane] rows are touched
+    const size_t row_stride = n / 2 + 1;
+    const size_t nr = (size_t)nplanes * row_stride;
+    // HBM queues: bucket mode needs <= n + ncomp ints for head and tail each (only the used prefix is
+    // initialised); the heap needs <= n elements per plane.
+    const size_t bstride = use_d2 ? n + row_stride : n;
+    a.row_stride = row_stride, a.bstride = bstride;
+    // the fused chain's path (d2 relief, marker list, clear_border + relabel fused): the mask's run tables serve the
+    // statistics and the final mapping instead of the parent plane.  The limit: the floods and the marker look-ups keep
+    // a run's index t * RT_CAP + k into rtab / rcomp in an int
+    const bool runs = a.runs = use_d2 && fu.labels && fu.mk_list && amt_i_ccl_runs_ok(mask, g) &&
+                               g.ntiles * RT_CAP < 0x7fffffffull && (reinterpret_cast<uintptr_t>(fu.labels) & 15) == 0 &&
+                               (reinterpret_cast<uintptr_t>(relief) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    amt_scratch s(ctx);
+    amt_buf<int> L(s, np);
+    amt_buf<int> T(s, np);
+    amt_buf<int> moff(s, nr);
+    amt_buf<int> boff(s, nr);
+    amt_buf<int> cursor(s, nr);
+    amt_buf<int> mlist(s, np);
+    amt_buf<int> next(s, np);
+    amt_buf<int> F(s, np);  // per-root fill value (only root positions are used)
+    amt_buf<int> rootlist(s, g.nlist * g.cap);  // tile-local roots, one list per tile row
+    amt_buf<int> nroots(s, g.nlist);
+    amt_buf<comp_row> rows(s, nr);
+    amt_buf<int> btot(s, nplanes);
+    amt_buf<int> mtot(s, nplanes);
+    amt_buf<int> counters(s, (size_t)nplanes * WS_CTR);  // layout: WS_CTR_*
+    amt_buf<int> wl(s, (size_t)WS_NLISTS * nr);  // worklists of the LDS classes
+    amt_buf<int> pf_idx(s, (size_t)PF_NCLS * (nplanes + 1));  // the persistent flood's item index
+    amt_buf<int> pf_ctl(s, 16);
+    // the tile labelling's flag + the tiles' column words
+    amt_buf<int> ccl_scratch(s, g.multi_ints());
+    amt_buf<int> ties_own(s, nplanes, !ties_dev);
+    amt_buf<int> P(s, (size_t)nplanes * ((size_t)fu.max_label + 1), fu.labels != nullptr);
+    amt_buf<unsigned long long> tbits(s, g.ntiles * 64, runs);
+    amt_buf<unsigned short> rtab(s, g.ntiles * RT_CAP, runs);
+    amt_buf<int> nruns(s, g.ntiles, runs);
+    amt_buf<unsigned short> roff(s, g.ntiles * 64, runs);
+    amt_buf<int> rcomp(s, g.ntiles * RT_CAP, runs);  // only the runs that exist are touched
+    // the sequential emulation's heap (every pixel is pushed at most once): the float64 path reuses its per-component
+    // heap space (bstride == n: those heaps are dead when the emulation starts), the bucket path needs it extra -- and
+    // only when ties are to be resolved exactly
+    amt_buf<int> head(s, (size_t)nplanes * bstride, use_d2);
+    amt_buf<int> tail(s, (size_t)nplanes * bstride, use_d2);
+    amt_buf<hp_elem> gheap_own(s, np, use_d2 && exact);
+    amt_buf<hp_elem> heap(s, (size_t)nplanes * bstride, !use_d2);
+    AMT_TRY(s.commit());
+    ws_bufs b = {};
+    b.L = L, b.T = T, b.moff = moff, b.boff = boff, b.cursor = cursor, b.mlist = mlist, b.next = next, b.F = F;
+    b.rootlist = rootlist, b.nroots = nroots, b.rows = rows, b.btot = btot, b.mtot = mtot, b.counters = counters, b.wl = wl;
+    b.pf_idx = pf_idx, b.pf_ctl = pf_ctl, b.ccl_scratch = ccl_scratch, b.P = P;
+    b.tbits = tbits, b.rtab = rtab, b.nruns = nruns, b.roff = roff, b.rcomp = rcomp, b.head = head, b.tail = tail;
+    b.ties = ties_dev ? ties_dev : ties_own.p;
+    b.heap = heap, b.gheap = use_d2 ? gheap_own.p : heap.p;
+    b.ncomp = b.counters + WS_CTR_NCOMP * (size_t)nplanes;
+    b.has_g = b.counters + WS_CTR_HASG * nplanes;
+    b.wl_count = b.counters + WS_CTR_WL * nplanes;  // [WS_NLISTS][nplanes]
+    // with run tables the parent plane holds tile roots only; every pixel look-up goes through the tables
+    b.rt = {tbits, roff, rtab, rcomp, g.segs, g.trows};
+
+    AMT_TRY(ws_label_and_classify(a, b));
+    AMT_TRY(ws_prepare_hbm(a, b, fu.labels && use_d2));
+    AMT_TRY(use_d2 ? ws_floods_d2(a, b) : ws_flood_f64(a, b));
+    // planes in which two markers of one component tied: scikit-image's answer comes from its single heap
+    if (exact) AMT_TRY(ws_emulate(ctx, relief, use_d2, markers, mask, out, b.gheap, b.ties, nplanes, H, W, 1));
+    if (fu.labels) AMT_TRY(ws_fused_tail(a, b));
+    return AMT_OK;
+}
+
 static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const int32_t* markers,
                             const uint8_t* mask, int32_t* out, int nplanes, int H, int W, int seeds_first,
-                            int connectivity, int tie_policy, int32_t* ties_dev, int32_t* fused_labels = nullptr,
-                            int32_t* fused_count = nullptr, const int32_t* nlabels_dev = nullptr, int max_label = 0,
-                            const int32_t* mk_list = nullptr, const int32_t* mk_count = nullptr, int mk_cap = 0) {
-    // fused_labels != nullptr: `out` is only the flood's scratch plane; the result is clear_border + relabel_sequential
-    // of the watershed, written to fused_labels / fused_count (connectivity 1 only)
+                            int connectivity, int tie_policy, int32_t* ties_dev, const ws_fused& fu) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(relief && markers && mask && out && nplanes >= 0 && H > 0 && W > 0, "watershed: bad arguments");
     AMT_REQUIRE((size_t)H * W < 0x3fffffffull, "watershed: plane too large");
@@ -2077,246 +2348,22 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
                 "watershed: connectivity 2 exists only as the sequential single-heap emulation (AMT_WS_TIES_EXACT)");
     if (nplanes == 0) return AMT_OK;
     const size_t n = (size_t)H * W;
-    const size_t np = (size_t)nplanes * n;
     // seeds_first cannot tie (marker pixels are spread first, in raster order, before anything is queued by value)
     const bool exact = tie_policy == AMT_WS_TIES_EXACT && !seeds_first;
     // the single-heap emulation packs a pixel as (y << 16 | x) and keeps heap slots in 32-bit arithmetic
     AMT_REQUIRE(!(exact || connectivity == 2) || (H <= 65535 && W <= 65535 && n <= ((size_t)1 << 26)),
                 "watershed: exact tie handling / connectivity 2 support planes of at most 2^26 pixels, got %d x %d", H, W);
-    if (connectivity == 2) {
-        // 8-connected floods: no component decomposition here -- every plane goes through the sequential emulation
-        amt_scratch s(ctx);
-        amt_buf<hp_elem> gheap(s, np);
-        AMT_TRY(s.commit());
-        if (ties_dev) {
-            hipLaunchKernelGGL(ws_set_flags_kernel, dim3((nplanes + 63) / 64), dim3(64), 0, ctx->stream, ties_dev, nplanes, 0);
-            AMT_LAUNCH_CHECK();
-        }
-        hipLaunchKernelGGL(ws_global_init_kernel, dim3(amt_grid_for(n, 256, 1024), nplanes), dim3(256), 0, ctx->stream,
-                           markers, mask, out, (const int*)nullptr, n);
-        AMT_LAUNCH_CHECK();
-        if (use_d2)
-            hipLaunchKernelGGL((ws_global_kernel<true>), dim3(nplanes), dim3(64), GH_LDS_N * sizeof(gh_elem), ctx->stream, relief, mask, out, gheap,
-                               (const int*)nullptr, H, W, n, 2);
-        else
-            hipLaunchKernelGGL((ws_global_kernel<false>), dim3(nplanes), dim3(64), GH_LDS_N * sizeof(gh_elem), ctx->stream, relief, mask, out, gheap,
-                               (const int*)nullptr, H, W, n, 2);
-        AMT_LAUNCH_CHECK();
-        return AMT_OK;
-    }
-    // per-component rows: a 4-connected component needs a background pixel between itself and the next one in
-    // its row, so a plane has at most ceil(n / 2) components; only the first ncomp[plane] rows are touched
-    const size_t row_stride = n / 2 + 1;
-    const size_t nr = (size_t)nplanes * row_stride;
-    // HBM queues: bucket mode needs <= n + ncomp ints for head and tail each (only the used prefix is
-    // initialised); the heap needs <= n elements per plane.
-    const size_t bstride = use_d2 ? n + row_stride : n;
-    const int trows = amt_i_tile_rows(H);
-    const size_t lcap = amt_i_rootlist_cap(W);
-    const size_t nlist = (size_t)nplanes * trows;
-    const size_t msz = (size_t)nplanes * ((size_t)max_label + 1);
-    // the fused chain's path (d2 relief, marker list, clear_border + relabel fused): the mask's run tables serve the
-    // statistics and the final mapping instead of the parent plane
-    const int segs = (W + 63) / 64;
-    const int ntiles = nplanes * trows * segs;
-    const bool runs = use_d2 && fused_labels && mk_list && amt_i_ccl_runs_ok(mask, H, W, nplanes) &&
-                      (reinterpret_cast<uintptr_t>(fused_labels) & 15) == 0 && (reinterpret_cast<uintptr_t>(relief) & 15) == 0 &&
-                      (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    if (connectivity == 1)
+        return watershed_components(ctx, relief, use_d2, markers, mask, out, nplanes, H, W, seeds_first, exact, ties_dev, fu);
+    // 8-connected floods: no component decomposition here -- every plane goes through the sequential emulation
     amt_scratch s(ctx);
-    amt_buf<int> L(s, np);
-    amt_buf<int> T(s, np);
-    amt_buf<int> moff(s, nr);
-    amt_buf<int> boff(s, nr);
-    amt_buf<int> cursor(s, nr);
-    amt_buf<int> mlist(s, np);
-    amt_buf<int> next(s, np);
-    amt_buf<int> F(s, np);  // per-root fill value (only root positions are used)
-    amt_buf<int> rootlist(s, nlist * lcap);  // tile-local roots, one list per tile row
-    amt_buf<int> nroots(s, nlist);
-    amt_buf<comp_row> rows(s, nr);
-    amt_buf<int> btot(s, nplanes);
-    amt_buf<int> mtot(s, nplanes);
-    // WS_CTR ints per plane, each field an array over the planes (field k of plane p: counters[k * nplanes + p]):
-    // [0] work counter of the class-X flood, [7] work counter of the HBM flood, [8] has_g,
-    // [9 .. 9 + WS_NLISTS) worklist sizes of classes S / M / M2 / L / X, [16] number of components
-    amt_buf<int> counters(s, (size_t)nplanes * WS_CTR);
-    amt_buf<int> wl(s, (size_t)WS_NLISTS * nr);  // worklists of the LDS classes
-    amt_buf<int> pf_idx(s, (size_t)PF_NCLS * (nplanes + 1));  // the persistent flood's item index
-    amt_buf<int> pf_ctl(s, 16);
-    // the tile labelling's flag + the tiles' column words
-    amt_buf<int> ccl_scratch(s, amt_i_ccl_scratch_ints(nplanes, H, W));
-    amt_buf<int> ties_own(s, nplanes, !ties_dev);
-    amt_buf<int> P(s, msz, fused_labels != nullptr);
-    amt_buf<unsigned long long> tbits(s, (size_t)ntiles * 64, runs);
-    amt_buf<unsigned short> rtab(s, (size_t)ntiles * RT_CAP, runs);
-    amt_buf<int> nruns(s, (size_t)ntiles, runs);
-    amt_buf<unsigned short> roff(s, (size_t)ntiles * 64, runs);
-    amt_buf<int> rcomp(s, (size_t)ntiles * RT_CAP, runs);  // only the runs that exist are touched
-    // the sequential emulation's heap (every pixel is pushed at most once): the float64 path reuses its per-component
-    // heap space (bstride == n: those heaps are dead when the emulation starts), the bucket path needs it extra -- and
-    // only when ties are to be resolved exactly
-    amt_buf<int> head(s, (size_t)nplanes * bstride, use_d2);
-    amt_buf<int> tail(s, (size_t)nplanes * bstride, use_d2);
-    amt_buf<hp_elem> gheap_own(s, np, use_d2 && exact);
-    amt_buf<hp_elem> heap(s, (size_t)nplanes * bstride, !use_d2);
+    amt_buf<hp_elem> gheap(s, (size_t)nplanes * n);
     AMT_TRY(s.commit());
-    int* ties = ties_dev ? ties_dev : ties_own.p;
-    hp_elem* gheap = use_d2 ? gheap_own.p : heap.p;
-    // with run tables the parent plane holds tile roots only; every pixel look-up goes through the tables
-    amt_runtabs rt = {tbits, roff, rtab, rcomp, segs, trows};
-
-    int* ncomp = counters + 16 * (size_t)nplanes;
-    // counters, tie flags and the root lists' counts in ONE launch (three trivial launches cost ~5 us each in a stage
-    // of 1.2 ms)
-    hipLaunchKernelGGL(ws_init_kernel, dim3(16), dim3(256), 0, ctx->stream, counters, nplanes * WS_CTR, ties, nplanes, nroots,
-                       (int)nlist);
-    AMT_LAUNCH_CHECK();
-    // components of the mask with dense ids in T (the order of the ids is irrelevant: components are
-    // independent work items and nothing in the output depends on their numbering)
-    if (runs) AMT_TRY(amt_i_ccl_tileroots_runs_u8(ctx, mask, L, rootlist, nroots, nplanes, H, W, tbits, rtab, nruns, roff));
-    else AMT_TRY(amt_i_ccl_tileroots_u8(ctx, mask, L, rootlist, nroots, nplanes, H, W, ccl_scratch));
-    hipLaunchKernelGGL(ws_roots_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, L, T, rootlist, nroots, ncomp,
-                       lcap, n);
-    AMT_LAUNCH_CHECK();
-    AMT_TRY(amt_i_propagate_roots(ctx, T, L, rootlist, nroots, nplanes, H, W));
-    hipLaunchKernelGGL(ws_rows_init_kernel, dim3(64, nplanes), dim3(256), 0, ctx->stream, rows, ncomp, row_stride);
-    AMT_LAUNCH_CHECK();
-    int* has_g = counters + 8 * nplanes;
-    int* wl_count = counters + 9 * nplanes;  // [WS_NLISTS][nplanes]
-    if (runs) {
-        hipLaunchKernelGGL(ws_stats_runs_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, (const int*)relief, tbits, rtab,
-                           nruns, L, T, rows, row_stride, H, W, segs, trows, ntiles, rcomp);
-        AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ws_marker_stats_kernel, dim3(16, nplanes), dim3(256), 0, ctx->stream, mk_list, mk_count, mk_cap,
-                           markers, L, T, rows, row_stride, n, rt, W);
-    } else if (mk_list) {
-        // the caller knows where the marker pixels are: the dense pass skips the marker plane
-        hipLaunchKernelGGL((ws_stats_kernel<false>), dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream,
-                           use_d2 ? (const int*)relief : (const int*)nullptr, L, T, markers, rows, row_stride, H, W,
-                           use_d2 ? 1 : 0);
-        AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ws_marker_stats_kernel, dim3(16, nplanes), dim3(256), 0, ctx->stream, mk_list, mk_count, mk_cap,
-                           markers, L, T, rows, row_stride, n, rt, W);
-    } else {
-        hipLaunchKernelGGL((ws_stats_kernel<true>), dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream,
-                           use_d2 ? (const int*)relief : (const int*)nullptr, L, T, markers, rows, row_stride, H, W,
-                           use_d2 ? 1 : 0);
-    }
-    AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ws_classify_kernel, dim3(64, nplanes), dim3(256), 0, ctx->stream, rows, ncomp, moff, boff, has_g,
-                       wl, wl_count, F, n, nplanes, row_stride, use_d2 ? 1 : 0);
-    AMT_LAUNCH_CHECK();
-    AMT_TRY(amt_i_propagate_roots(ctx, F, L, rootlist, nroots, nplanes, H, W));
-    const bool gprep = fused_labels && use_d2;  // the fused chain: the HBM flood's whole preparation in one launch
-    if (gprep) {
-        hipLaunchKernelGGL(ws_g_prep_kernel, dim3(nplanes), dim3(1024), 0, ctx->stream, markers, L, T, F, out, rows, moff, boff,
-                           cursor, mlist, head, ncomp, mtot, btot, has_g, row_stride, n, bstride, rt, W);
-        AMT_LAUNCH_CHECK();
-    } else {
-        // the marker lists of the HBM flood's components: nearly always no plane has one, and 4,096 workgroups per plane
-        // that only read a flag and leave cost 43 us per 48 planes -- 128 (grid-stride) do when a plane does have one
-        dim3 g1(amt_grid_for(n, 256, 128), nplanes);
-        // the seed pass gives `out` its final value everywhere except in flooded components.  The fused path needs no
-        // such plane (its final pass derives every pixel from F and the flood's sparse writes): it seeds only planes that
-        // hold a component for the HBM flood, which works in `out` itself -- same consideration for its grid
-        hipLaunchKernelGGL(ws_seed_kernel, dim3(amt_grid_for(n, 1024, fused_labels ? 128 : 4096), nplanes), dim3(256), 0,
-                           ctx->stream, markers, L, F, out, n, fused_labels ? (const int*)has_g : (const int*)nullptr, rt, W);
-        AMT_LAUNCH_CHECK();
-        // ---- HBM-path bookkeeping (usually empty: only components too large for an LDS tile) ----
-        AMT_TRY(amt_scan_excl_dev(ctx, moff, ncomp, row_stride, mtot, nplanes));
-        AMT_TRY(amt_scan_excl_dev(ctx, boff, ncomp, row_stride, btot, nplanes));
-        hipLaunchKernelGGL(ws_fill_value_kernel, dim3(64, nplanes), dim3(256), 0, ctx->stream, cursor, ncomp, row_stride, 0);
-        AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ws_fill_markers_kernel, g1, dim3(256), 0, ctx->stream, L, T, out, rows, moff, cursor, mlist,
-                           has_g, row_stride, n, rt, W);
+    if (ties_dev) {
+        hipLaunchKernelGGL(ws_set_flags_kernel, dim3((nplanes + 63) / 64), dim3(64), 0, ctx->stream, ties_dev, nplanes, 0);
         AMT_LAUNCH_CHECK();
     }
-    if (use_d2) {
-        const size_t ldsX = (size_t)X_PX * 4 + (size_t)X_NB * 4;
-        // the LDS classes and the HBM path are independent, latency-bound and use few waves each:
-        // run them side by side (fork / join on the context's auxiliary streams)
-        if (!gprep) {
-            hipLaunchKernelGGL(ws_fill_value_kernel, dim3(256, nplanes), dim3(256), 0, ctx->stream, head, btot, bstride, -1);
-            AMT_LAUNCH_CHECK();
-        }
-        AMT_TRY(amt_fork(ctx));
-        // Without auxiliary streams the floods still overlap: the first flood is an ordinary (barrier) launch, the
-        // others carry hipExtAnyOrderLaunch -- their packets have no barrier bit, so the command processor dispatches
-        // them while the earlier floods are still running; the next ordinary launch waits for all of them.
-        const int any = ctx->fork == 0 ? (int)hipExtAnyOrderLaunch : 0;
-        // one persistent launch for classes S / M / M2 / L (a workgroup of PF_NWAVES waves per CU with all its LDS),
-        // then X and the HBM flood beside it.  Measured on one box against one launch per class (watershed stage per
-        // 48 FOVs in one context / 48-FOV plate / 192-FOV default, FOV/s): class launches 2.53 ms / 10.4 k / 11.5-11.7 k;
-        // whole CU, 8 waves 2.11 / 10.4 k / 11.3 k; 10 waves 2.02 / 10.4 k / 11.6 k; 16 waves 2.10; 46 slots 2.16 /
-        // 10.2 k / 10.9 k; half a CU x 2 2.26 / 10.4 k / 11.1 k.  The stage gains 0.5 ms; with four contexts side by side
-        // the floods were already hidden behind the other contexts' streaming kernels, so the totals do not move.
-        hipLaunchKernelGGL(ws_flood_index_kernel, dim3(1), dim3(64), 0, ctx->stream, wl_count, pf_idx, pf_ctl, nplanes);
-        AMT_LAUNCH_CHECK();
-        {
-            const int* a_d2 = (const int*)relief;
-            void* args[] = {&a_d2, &L.p, &T.p, &out, &rows.p, &wl.p, &pf_idx.p, &pf_ctl.p, (void*)&row_stride, &H, &W, &seeds_first, &ties,
-                            (void*)&markers, &nplanes, &rt};
-            AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_persist_kernel, dim3(ctx->num_cus), dim3(PF_NWAVES * 64), args,
-                                             (size_t)(PF_SLOTS + 1) * PF_SLOT, ctx->stream, nullptr, nullptr, 0));
-        }
-        {
-            const int* a_d2 = (const int*)relief;
-            const int* a_wl = wl + (size_t)(CLS_X - CLS_S) * nplanes * row_stride;
-            const int* a_wlc = wl_count + (CLS_X - CLS_S) * nplanes;
-            void* args[] = {&a_d2, &L.p, &T.p, &out, &rows.p, &a_wl, &a_wlc, &counters.p, (void*)&row_stride, &H, &W, &seeds_first, &ties,
-                            (void*)&markers, &rt};
-            AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_lds_kernel<X_PX, X_NB, CLS_X>, dim3(8, nplanes), dim3(64), args,
-                                             ldsX, ctx->stream, nullptr, nullptr, any));
-        }
-        {
-            const int* a_d2 = (const int*)relief;
-            void* args[] = {&a_d2, (void*)&mask, &out, &next.p, &head.p, &tail.p, &mlist.p, &rows.p, &moff.p, &boff.p, &ncomp, nullptr,
-                            (void*)&row_stride, &H, &W, (void*)&n, (void*)&bstride, &seeds_first, &ties};
-            int* a_cnt = counters + 7 * nplanes;
-            args[11] = &a_cnt;
-            AMT_HIP_CHECK(hipExtLaunchKernel((const void*)ws_flood_edt_kernel, dim3(4, nplanes), dim3(64), args, 0, ctx->aux[1],
-                                             nullptr, nullptr, any));
-        }
-        AMT_TRY(amt_join(ctx));
-    } else {
-        hipLaunchKernelGGL(ws_flood_heap_kernel, dim3(64, nplanes), dim3(64), 0, ctx->stream, (const double*)relief,
-                           mask, out, heap, mlist, rows, moff, boff, ncomp, counters + 7 * nplanes, row_stride, H, W, n,
-                           bstride, ties);
-    }
-    AMT_LAUNCH_CHECK();
-    if (exact) {
-        // planes in which two markers of one component tied: scikit-image's answer comes from its single heap
-        hipLaunchKernelGGL(ws_global_init_kernel, dim3(amt_grid_for(n, 256, 1024), nplanes), dim3(256), 0, ctx->stream,
-                           markers, mask, out, (const int*)ties, n);
-        AMT_LAUNCH_CHECK();
-        if (use_d2)
-            hipLaunchKernelGGL((ws_global_kernel<true>), dim3(nplanes), dim3(64), GH_LDS_N * sizeof(gh_elem), ctx->stream, relief, mask, out, gheap,
-                               (const int*)ties, H, W, n, 1);
-        else
-            hipLaunchKernelGGL((ws_global_kernel<false>), dim3(nplanes), dim3(64), GH_LDS_N * sizeof(gh_elem), ctx->stream, relief, mask, out, gheap,
-                               (const int*)ties, H, W, n, 1);
-        AMT_LAUNCH_CHECK();
-    }
-    if (fused_labels) {
-        // the label map of clear_border + relabel_sequential: present labels, frame-touching ones dropped, survivors
-        // numbered -- one workgroup per plane does the four steps (they were four launches over a few thousand entries)
-        hipLaunchKernelGGL(ws_label_map_kernel, dim3(nplanes), dim3(1024), 0, ctx->stream, L, F, out, P, nlabels_dev, fused_count,
-                           H, W, max_label, rt);
-        AMT_LAUNCH_CHECK();
-        if (runs) {
-            hipLaunchKernelGGL(ws_final_map_kernel, dim3(4, trows, nplanes), dim3(256), 0, ctx->stream, F, P, rootlist, nroots, lcap,
-                               n, max_label);
-            AMT_LAUNCH_CHECK();
-        }
-        if (runs)
-            hipLaunchKernelGGL(ws_final_runs_kernel, dim3((ntiles + 3) / 4), dim3(256), 0, ctx->stream, tbits, rtab, nruns, F, out, P,
-                               fused_labels, H, W, segs, trows, ntiles, max_label);
-        else
-            hipLaunchKernelGGL(ws_final_kernel, dim3(amt_grid_for(n, 1024, 4096), nplanes), dim3(256), 0, ctx->stream, L, F, out,
-                               P, fused_labels, n, max_label);
-        AMT_LAUNCH_CHECK();
-    }
-    return AMT_OK;
+    return ws_emulate(ctx, relief, use_d2, markers, mask, out, gheap, nullptr, nplanes, H, W, 2);
 }
 
 // marker_list / marker_count (both or neither): every marker pixel per plane; NULL = the dense statistics pass
@@ -2329,20 +2376,22 @@ extern "C" int amt_watershed_edt_cleared(amt_ctx* ctx, const int32_t* d2, const 
     AMT_REQUIRE(!marker_list == !marker_count, "watershed_edt_cleared: marker_list and marker_count go together");
     AMT_REQUIRE(!marker_list || list_capacity > 0, "watershed_edt_cleared: list_capacity must be positive");
     AMT_REQUIRE(ws_scratch != labels_out, "watershed_edt_cleared: scratch and output must not alias");
-    return watershed_common(ctx, d2, true, markers, mask, ws_scratch, nplanes, H, W, 1, 1, AMT_WS_TIES_EXACT, nullptr,
-                            labels_out, count_dev, nlabels_dev, max_label, marker_list, marker_count,
-                            list_capacity);
+    ws_fused fu;
+    fu.labels = labels_out, fu.count = count_dev, fu.nlabels_dev = nlabels_dev, fu.max_label = max_label;
+    fu.mk_list = marker_list, fu.mk_count = marker_count, fu.mk_cap = list_capacity;
+    return watershed_common(ctx, d2, true, markers, mask, ws_scratch, nplanes, H, W, 1, 1, AMT_WS_TIES_EXACT, nullptr, fu);
 }
 
 extern "C" int amt_watershed_edt(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
                                  int32_t* out, int nplanes, int H, int W, int seeds_first, int connectivity,
                                  int tie_policy, int32_t* ties_dev) {
     return watershed_common(ctx, d2, true, markers, mask, out, nplanes, H, W, seeds_first, connectivity, tie_policy,
-                            ties_dev);
+                            ties_dev, ws_fused());
 }
 
 extern "C" int amt_watershed_f64(amt_ctx* ctx, const double* relief, const int32_t* markers, const uint8_t* mask,
                                  int32_t* out, int nplanes, int H, int W, int connectivity, int tie_policy,
                                  int32_t* ties_dev) {
-    return watershed_common(ctx, relief, false, markers, mask, out, nplanes, H, W, 0, connectivity, tie_policy, ties_dev);
+    return watershed_common(ctx, relief, false, markers, mask, out, nplanes, H, W, 0, connectivity, tie_policy, ties_dev,
+                            ws_fused());
 }

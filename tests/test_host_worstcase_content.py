@@ -60,7 +60,7 @@ def test_runs_per_tile_and_per_row(cen):
 
 
 def test_run_table_path_of_the_watershed(cen):
-    """`runs` in watershed_common needs the d2 relief, the fused tail, a marker list and W % 16 == 0: the chain's
+    """`runs` in watershed_components needs the d2 relief, the fused tail, a marker list and W % 16 == 0: the chain's
     marker-list route on (192, 192) and (130, 144).  There it meets noise (noise50), thin structures (serpentine, spiral,
     rings, combs: floods of one-pixel-wide components), tiles cut by both edges with RT_CAP runs (checker0 on (130, 144)),
     and tiles with no run at all (corners), whose rcomp entries stay untouched under poison."""
