@@ -200,3 +200,44 @@ def prefix_rule(v: np.ndarray, vmin: float, vmax: float, nbins: int = 256):
     above = vlo > centres[bins]
     undecided = ((bins < nbins - 1) & (vhi >= edges[bins + 1])) | (~above & (vhi > centres[bins]))
     return bins, above, undecided
+
+
+def prefix_rule_tables(vmin: float, vmax: float, nbins: int = 256) -> np.ndarray:
+    """The integer restatement of ``prefix_rule`` as prefix_codes_kernel builds it in LDS: a ``(nbins + 1, 4)`` uint32
+    table of thresholds for the upper half p of a non-negative float64 sample.  64-bit patterns of non-negative doubles
+    order like their values, so for a threshold T with halves (hT, lT), vlo = (p, 0) and vhi = (p, 0xFFFFFFFF):
+    ``vlo >= T`` is ``p >= hT + (lT != 0)``, ``vlo > T`` is ``p >= hT + 1``, ``vhi >= T`` is ``p >= hT`` and ``vhi > T``
+    is ``p >= hT + (lT == 0xFFFFFFFF)``.  Row b holds
+
+    ``AE[b]``    vlo >= edge b (0 in row 0: bins are floored at 0; 0xFFFFFFFF in the sentinel row nbins),
+    ``HE[b+1]``  vhi >= edge b + 1 (0xFFFFFFFF in row nbins - 1: the last bin is closed),
+    ``GC[b]``    vlo > centre b,
+    ``UC[b]``    vhi > centre b.
+
+    The edges and centres are the float64 values of ``prefix_rule``; ``prefix_classify`` applies the table."""
+    edges = np.linspace(vmin, vmax, nbins + 1)
+    if (edges < 0).any():
+        raise ValueError("the prefix order holds for non-negative thresholds only")
+    centres = (edges[:-1] + edges[1:]) / 2.0
+    eb, cb = edges.view(np.uint64), centres.view(np.uint64)
+    eh, el = eb >> np.uint64(32), eb & np.uint64(0xFFFFFFFF)
+    ch, cl = cb >> np.uint64(32), cb & np.uint64(0xFFFFFFFF)
+    t = np.full((nbins + 1, 4), 0xFFFFFFFF, np.uint64)
+    t[:nbins, 0] = eh[:nbins] + (el[:nbins] != 0)
+    t[0, 0] = 0
+    t[:nbins - 1, 1] = eh[1:nbins]
+    t[:nbins, 2] = ch + np.uint64(1)
+    t[:nbins, 3] = ch + (cl == np.uint64(0xFFFFFFFF))
+    return t.astype(np.uint32)
+
+
+def prefix_classify(p: np.ndarray, tables: np.ndarray):
+    """``(bins, above, undecided)`` of ``prefix_rule`` from the upper halves ``p`` (uint32) and ``prefix_rule_tables``:
+    the bin is the last row whose AE does not exceed p, and the rest is three unsigned comparisons with that row."""
+    p = np.asarray(p, dtype=np.uint32)
+    nbins = len(tables) - 1
+    bins = np.clip(np.searchsorted(tables[:nbins, 0], p, side="right") - 1, 0, nbins - 1)
+    row = tables[bins]
+    above = p >= row[..., 2]
+    undecided = (p >= row[..., 1]) | (~above & (p >= row[..., 3]))
+    return bins, above, undecided

@@ -1150,11 +1150,38 @@ __device__ __forceinline__ int gl_bin(double v, double lo, double hi, double ste
 // UNDECIDED: it is not counted, its code is left 0 and its index is appended to the plane's list (one atomic per wave
 // and step), for prefix_fixup_kernel to recompute.  A plane with more than PFX_CAP undecided samples (range of about a
 // grey level) stops being processed -- its count stays above PFX_CAP and gauss_lds_kernel<R, 2> redoes it as a whole.
+//
+// The pass is bound by vector issue, not by memory, so the comparisons are made on p itself.  64-bit patterns of
+// non-negative doubles order like their values; for a threshold T >= 0 with halves (hT, lT)
+//     vlo >= T  is  p >= hT + (lT != 0)        vlo > T  is  p >= hT + 1
+//     vhi >= T  is  p >= hT                    vhi > T  is  p >= hT + (lT == 0xffffffff)
+// and every block restates its plane's edges and centres -- the doubles of gl_edge and (e_b + e_b+1) / 2.0, nothing
+// else -- as one table row per bin (pfx_row; _thresholds.prefix_rule_tables is the host model):
+//     x = AE[b]   : vlo >= edge b          (0 in row 0: bins are floored at 0; 0xffffffff in the sentinel row GL_NBINS,
+//                                           which no sample reaches: p <= 0x7fefffff)
+//     y = HE[b+1] : vhi >= edge b + 1      (0xffffffff in row GL_NBINS - 1: the last bin is closed)
+//     z = GC[b]   : vlo >  centre b
+//     w = UC[b]   : vhi >  centre b
+// The bin of vlo is max{i : p >= AE[i]} (gl_bin's walk over monotone edges ends there): the scaled guess g, the only
+// float64 arithmetic left, is accepted where AE[g] <= p < AE[g+1] and repaired by the same walk otherwise.
+__device__ __forceinline__ uint4 pfx_row(double lo, double hi, double step, int b) {
+    const double e0 = gl_edge(lo, hi, step, b), e1 = gl_edge(lo, hi, step, b + 1);
+    const double c = (e0 + e1) / 2.0;
+    const uint32_t hc = (uint32_t)__double2hiint(c);
+    uint4 t;
+    t.x = b == 0 ? 0u : (uint32_t)__double2hiint(e0) + (__double2loint(e0) != 0 ? 1u : 0u);
+    t.y = b == GL_NBINS - 1 ? 0xffffffffu : (uint32_t)__double2hiint(e1);
+    t.z = hc + 1u;
+    t.w = hc + ((uint32_t)__double2loint(c) == 0xffffffffu ? 1u : 0u);
+    return t;
+}
+
 __global__ void __launch_bounds__(256) prefix_codes_kernel(const uint32_t* __restrict__ prefix,
                                                            const double* __restrict__ minmax,
                                                            uint32_t* __restrict__ hist, uint16_t* __restrict__ codes,
                                                            size_t n, uint32_t* __restrict__ und_count,
                                                            uint32_t* __restrict__ und_list) {
+    __shared__ uint4 tab[GL_NBINS + 1];
     __shared__ uint32_t lh[4 * GL_NBINS];
     const int plane = blockIdx.y;
     const int lane = threadIdx.x & 63;
@@ -1166,69 +1193,100 @@ __global__ void __launch_bounds__(256) prefix_codes_kernel(const uint32_t* __res
         for (size_t i0 = first; i0 < n; i0 += stride) *reinterpret_cast<uint2*>(dst + i0) = make_uint2(0u, 0u);
         return;
     }
+    const double step = (hi - lo) / (double)GL_NBINS, norm = (double)GL_NBINS / (hi - lo);
+    // the first trip's samples, in flight while the table is built (a thread beyond the plane reads its start, unused)
+    uint4 p4 = *reinterpret_cast<const uint4*>(src + (first < n ? first : 0));
     for (int i = threadIdx.x; i < 4 * GL_NBINS; i += 256) lh[i] = 0;
+    tab[threadIdx.x] = pfx_row(lo, hi, step, threadIdx.x);  // 256 threads, GL_NBINS rows
+    if (threadIdx.x == 0) tab[GL_NBINS] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
     __syncthreads();
     uint32_t* mine = lh + (threadIdx.x >> 6) * GL_NBINS;
-    const double step = (hi - lo) / (double)GL_NBINS, norm = (double)GL_NBINS / (hi - lo);
     uint32_t* cnt = und_count + (size_t)plane * PFX_CNT_STRIDE;
     uint32_t* list = und_list + (size_t)plane * PFX_CAP;
     // no look at the counter when a block starts: with every wave of the chip reading the one line that the appends keep
     // dirty the pass took 1.07 ms per 48 planes instead of 0.36 (rocprofv3); a wave of an overflowed plane learns it
     // from its own first append
     bool dead = false;
+    // The first trip's samples are awaited HERE (the empty asm reads them), not in the loop: vmcnt counts loads and
+    // stores in one queue, and a wait at the loop's head that has to cover the entry from above (one load pending)
+    // becomes vmcnt(0) -- which, on the way round, also waits for the previous trip's store of codes.
+    asm volatile("" : "+v"(p4.x), "+v"(p4.y), "+v"(p4.z), "+v"(p4.w));
     for (size_t i0 = first; i0 < n && !dead; i0 += stride) {
-        const uint4 p4 = *reinterpret_cast<const uint4*>(src + i0);
         const unsigned p[4] = {p4.x, p4.y, p4.z, p4.w};
-        int b4[4];
-        double elo4[4], ehi4[4];
+        if (i0 + stride < n) p4 = *reinterpret_cast<const uint4*>(src + i0 + stride);  // the next trip's, in flight
+        int b[4];
+        uint4 t[4];
+        bool ok[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {  // first guess of the bin of vlo and both of its edges (no dependent chain)
+        for (int u = 0; u < 4; ++u) {  // the guessed bin's row and the next row's AE (no dependent chain)
             const double vlo = __hiloint2double((int)p[u], 0);
-            int b = (int)((vlo - lo) * norm);
-            b = b < 0 ? 0 : (b > GL_NBINS - 1 ? GL_NBINS - 1 : b);
-            b4[u] = b;
-            elo4[u] = (double)b * step + lo;
-            ehi4[u] = gl_edge(lo, hi, step, b + 1);
+            int g = (int)((vlo - lo) * norm);
+            g = g < 0 ? 0 : (g > GL_NBINS - 1 ? GL_NBINS - 1 : g);
+            b[u] = g;
+            t[u] = tab[g];
+            ok[u] = p[u] - t[u].x < tab[g + 1].x - t[u].x;  // AE[g] <= p < AE[g+1], one unsigned comparison
         }
-        unsigned cd[4], undm = 0;
+        if (!(ok[0] & ok[1] & ok[2] & ok[3])) {  // rare: within rounding distance of an edge
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (!ok[u]) {
+                    int bb = b[u];
+                    while (bb > 0 && p[u] < tab[bb].x) --bb;
+                    while (bb < GL_NBINS - 1 && p[u] >= tab[bb + 1].x) ++bb;
+                    b[u] = bb;
+                    t[u] = tab[bb];
+                }
+        }
+        // Every predicate twice: per lane (und, rem: selects and branches) and as the wave's mask (undm, remm: counts and
+        // wave-uniform branches).  The masks are ballots of the bare comparisons combined by scalar instructions -- a
+        // ballot of a combined predicate costs two vector instructions, and the pass is bound by those.
+        const unsigned long long ex = __ballot(true);
+        unsigned cd[4];
+        bool und[4], rem[4];             // undecided; decided and not yet counted
+        unsigned long long undm[4], remm[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const double vlo = __hiloint2double((int)p[u], 0), vhi = __hiloint2double((int)p[u], (int)0xffffffffu);
-            int b = b4[u];
-            if (vlo < elo4[u] || (b < GL_NBINS - 1 && vlo >= ehi4[u])) {  // within rounding distance of an edge
-                b = gl_bin(vlo, lo, hi, step, norm);
-                elo4[u] = gl_edge(lo, hi, step, b);
-                ehi4[u] = gl_edge(lo, hi, step, b + 1);
-            }
-            const double ctr = (elo4[u] + ehi4[u]) / 2.0;
-            const bool gt = vlo > ctr;
+            const bool he = p[u] >= t[u].y, gt = p[u] >= t[u].z, uc = p[u] >= t[u].w;
             // bin(v) == bin(vlo) unless vhi reaches the next edge; (v > ctr) == (vlo > ctr) unless only vhi is above
-            const bool und = (b < GL_NBINS - 1 && vhi >= ehi4[u]) || (!gt && vhi > ctr);
-            undm |= (und ? 1u : 0u) << u;
-            cd[u] = und ? 0u : (((unsigned)b << 1) | (gt ? 1u : 0u));
-            const unsigned long long act = __ballot(!und);
-            if (!act) continue;
-            // two rounds of "first lane's bin, counted once for everyone who shares it", then lane by lane
-            // (as hist_f64_kernel: a smoothed background wave straddles at most one bin edge)
-            const int l0 = __ffsll((long long)act) - 1;
-            const int b0 = __shfl(b, l0);
-            const unsigned long long s0 = __ballot(!und && b == b0);
-            if (lane == l0) atomicAdd(&mine[b0], (unsigned)__popcll(s0));
-            unsigned long long rest = act & ~s0;
-            if (rest) {
-                const int l1 = __ffsll((long long)rest) - 1;
-                const int b1 = __shfl(b, l1);
-                const unsigned long long s1 = __ballot(!und && b == b1);
-                if (lane == l1) atomicAdd(&mine[b1], (unsigned)__popcll(s1));
-                rest &= ~s1;
-                if ((rest >> lane) & 1ull) atomicAdd(&mine[b], 1u);
-            }
+            und[u] = he | (!gt & uc);
+            undm[u] = __ballot(he) | (~__ballot(gt) & __ballot(uc));
+            cd[u] = und[u] ? 0u : (((unsigned)b[u] << 1) | (gt ? 1u : 0u));
+            rem[u] = !und[u];
+            remm[u] = ex & ~undm[u];
         }
         *reinterpret_cast<uint2*>(dst + i0) = make_uint2(cd[0] | (cd[1] << 16), cd[2] | (cd[3] << 16));
-        const unsigned long long any = __ballot(undm != 0);
+        // counting, once per trip: two rounds of "the bin of the first uncounted sample of the first lane that has one,
+        // counted once for every sample of the wave that shares it" (a lane holds four neighbours of a smoothed image
+        // and a background wave sits in one or two bins), then sample by sample.  The first lane is wave-uniform, so
+        // its bin comes through v_readlane and the four comparisons land in scalar masks: nothing waits on LDS.
+        unsigned long long act = remm[0] | remm[1] | remm[2] | remm[3];
+#pragma unroll
+        for (int round = 0; round < 2; ++round) {
+            if (act) {
+                const int l = __ffsll((long long)act) - 1;
+                const int fb = rem[0] ? b[0] : (rem[1] ? b[1] : (rem[2] ? b[2] : b[3]));
+                const int bl = __builtin_amdgcn_readlane(fb, l);
+                unsigned c = 0;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const bool same = b[u] == bl;
+                    const unsigned long long hit = remm[u] & __ballot(same);
+                    c += (unsigned)__popcll(hit);
+                    remm[u] &= ~hit;
+                    rem[u] = rem[u] & !same;
+                }
+                if (lane == l) atomicAdd(&mine[bl], c);
+                act = remm[0] | remm[1] | remm[2] | remm[3];
+            }
+        }
+        if (act) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (rem[u]) atomicAdd(&mine[b[u]], 1u);
+        }
+        const unsigned long long any = undm[0] | undm[1] | undm[2] | undm[3];
         if (any) {  // rare: append this wave's undecided samples with ONE atomic
-            const unsigned long long m0 = __ballot(undm & 1u), m1 = __ballot(undm & 2u), m2 = __ballot(undm & 4u),
-                                     m3 = __ballot(undm & 8u);
+            const unsigned long long m0 = undm[0], m1 = undm[1], m2 = undm[2], m3 = undm[3];
             const unsigned n0 = __popcll(m0), n1 = __popcll(m1), n2 = __popcll(m2), n3 = __popcll(m3);
             const int leader = __ffsll((long long)any) - 1;
             unsigned base = 0;
@@ -1240,7 +1298,7 @@ __global__ void __launch_bounds__(256) prefix_codes_kernel(const uint32_t* __res
                                      base + n0 + n1 + n2 + (unsigned)__popcll(m3 & below)};
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                if (((undm >> u) & 1u) && pos[u] < PFX_CAP) list[pos[u]] = (uint32_t)(i0 + u);
+                if (und[u] && pos[u] < PFX_CAP) list[pos[u]] = (uint32_t)(i0 + u);
             dead = base + n0 + n1 + n2 + n3 > PFX_CAP;  // wave-uniform: the whole plane will be redone
         }
     }
@@ -1313,15 +1371,16 @@ static int launch_codes(amt_ctx* ctx, const uint16_t* in, double scale, int npla
     int TH2 = 256;
     while (TH2 > 32 && (long long)gx2 * ((H + TH2 - 1) / TH2) * nplanes < 4LL * ctx->num_cus) TH2 >>= 1;
     dim3 grid2(gx2, (H + TH2 - 1) / TH2, nplanes);
-    AMT_TRY(amt_i_minmax_init(ctx, keys, nplanes));
     if (prefix) {
+        // the histograms and the list counters are cleared by the launch that resets the min / max keys: the Gaussian
+        // in between touches neither
+        AMT_TRY(amt_i_minmax_init(ctx, keys, nplanes, hist, (size_t)nplanes * GL_NBINS, und_count,
+                                  (size_t)nplanes * PFX_CNT_STRIDE));
         hipLaunchKernelGGL((gauss_lds_kernel<R, 3>), grid2, dim3(256), 0, ctx->stream, in, scale, (double*)nullptr, H, W,
                            wdev, mode, in_stride, TH2, keys, (const double*)nullptr, (uint32_t*)nullptr,
                            (uint16_t*)nullptr, prefix, (const uint32_t*)nullptr);
         AMT_LAUNCH_CHECK();
         AMT_TRY(amt_i_minmax_finish(ctx, keys, mm, nplanes));
-        AMT_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)nplanes * GL_NBINS * sizeof(uint32_t), ctx->stream));
-        AMT_HIP_CHECK(hipMemsetAsync(und_count, 0, (size_t)nplanes * PFX_CNT_STRIDE * sizeof(uint32_t), ctx->stream));
         const size_t n = (size_t)H * W;
         hipLaunchKernelGGL(prefix_codes_kernel, dim3(amt_grid_for(n, 256 * 16, 512), nplanes), dim3(256), 0, ctx->stream,
                            (const uint32_t*)prefix, (const double*)mm, hist, codes, n, und_count, und_list);
@@ -1337,6 +1396,7 @@ static int launch_codes(amt_ctx* ctx, const uint16_t* in, double scale, int npla
         AMT_LAUNCH_CHECK();
         return AMT_OK;
     }
+    AMT_TRY(amt_i_minmax_init(ctx, keys, nplanes));
     hipLaunchKernelGGL((gauss_lds_kernel<R, 1>), grid2, dim3(256), 0, ctx->stream, in, scale, (double*)nullptr, H, W,
                        wdev, mode, in_stride, TH2, keys, (const double*)nullptr, (uint32_t*)nullptr, (uint16_t*)nullptr,
                        (uint32_t*)nullptr, (const uint32_t*)nullptr);

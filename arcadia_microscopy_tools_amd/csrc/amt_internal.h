@@ -69,7 +69,9 @@ static inline int amt_scan_excl_dev(amt_ctx* ctx, int* data, const int* len_dev,
 
 // ---- float64 min / max per plane on ordered 64-bit keys (amt_stats.hip) ---------------------------
 // keys = 2 * nplanes scratch words; init -> (producers fold with atomicMin / atomicMax on amt_f64_key) -> finish
-int amt_i_minmax_init(amt_ctx* ctx, unsigned long long* keys, int nplanes);
+// zero_a / zero_b (nullable): na / nb 32-bit words cleared by the same launch
+int amt_i_minmax_init(amt_ctx* ctx, unsigned long long* keys, int nplanes, uint32_t* zero_a = nullptr, size_t na = 0,
+                      uint32_t* zero_b = nullptr, size_t nb = 0);
 int amt_i_minmax_finish(amt_ctx* ctx, const unsigned long long* keys, double* out, int nplanes);
 int amt_i_minmax_f64(amt_ctx* ctx, const double* in, unsigned long long* keys, double* out, int nplanes, size_t n);
 // Otsu threshold of float64 histograms (np.histogram edges from minmax); thr_code (nullable) = 2 * bin index

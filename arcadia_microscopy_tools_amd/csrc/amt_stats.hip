@@ -173,12 +173,15 @@ extern "C" int amt_hist_u16(amt_ctx* ctx, const uint16_t* in, uint32_t* hist, in
 // ------------------------------------------------------------------------------------------------
 // float64 min / max per plane (wave shuffle reduction -> one 64-bit atomic per wave on ordered keys)
 // ------------------------------------------------------------------------------------------------
-__global__ void minmax_init_kernel(unsigned long long* keys, int nplanes) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < nplanes) {
-        keys[2 * i] = ~0ull;
-        keys[2 * i + 1] = 0ull;
+__global__ void minmax_init_kernel(unsigned long long* keys, int nplanes, uint32_t* zero_a, size_t na, uint32_t* zero_b,
+                                   size_t nb) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x, step = (size_t)gridDim.x * blockDim.x;
+    for (size_t j = i; j < (size_t)nplanes; j += step) {
+        keys[2 * j] = ~0ull;
+        keys[2 * j + 1] = 0ull;
     }
+    for (size_t j = i; j < na; j += step) zero_a[j] = 0u;
+    for (size_t j = i; j < nb; j += step) zero_b[j] = 0u;
 }
 
 __global__ void __launch_bounds__(256) minmax_f64_kernel(const double* __restrict__ in,
@@ -219,8 +222,13 @@ __global__ void minmax_finish_kernel(const unsigned long long* keys, double* out
     if (i < 2 * nplanes) out[i] = amt_key_f64(keys[i]);
 }
 
-int amt_i_minmax_init(amt_ctx* ctx, unsigned long long* keys, int nplanes) {
-    hipLaunchKernelGGL(minmax_init_kernel, dim3((nplanes + 63) / 64), dim3(64), 0, ctx->stream, keys, nplanes);
+int amt_i_minmax_init(amt_ctx* ctx, unsigned long long* keys, int nplanes, uint32_t* zero_a, size_t na,
+                      uint32_t* zero_b, size_t nb) {
+    // the words to clear ride along (grid-stride, so the grid may stay small): one launch instead of a fill each
+    const size_t most = na > nb ? na : nb;
+    const size_t want = most > (size_t)nplanes ? most : (size_t)nplanes;
+    const unsigned blocks = (unsigned)((want + 63) / 64 < 1024 ? (want + 63) / 64 : 1024);
+    hipLaunchKernelGGL(minmax_init_kernel, dim3(blocks), dim3(64), 0, ctx->stream, keys, nplanes, zero_a, na, zero_b, nb);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -234,7 +242,8 @@ int amt_i_minmax_finish(amt_ctx* ctx, const unsigned long long* keys, double* ou
 
 static int minmax_f64_launch(amt_ctx* ctx, const double* in, unsigned long long* keys, double* out, int nplanes,
                              size_t n) {
-    hipLaunchKernelGGL(minmax_init_kernel, dim3((nplanes + 63) / 64), dim3(64), 0, ctx->stream, keys, nplanes);
+    hipLaunchKernelGGL(minmax_init_kernel, dim3((nplanes + 63) / 64), dim3(64), 0, ctx->stream, keys, nplanes,
+                       (uint32_t*)nullptr, (size_t)0, (uint32_t*)nullptr, (size_t)0);
     AMT_LAUNCH_CHECK();
     if (n) {
         dim3 grid(amt_grid_for(n, 256 * 16, 256), nplanes);
