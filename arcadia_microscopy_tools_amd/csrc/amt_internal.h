@@ -135,6 +135,11 @@ struct amt_runtabs {
 // with one hop through its tile root
 int amt_i_propagate_roots(amt_ctx* ctx, const ccl_geom& g, int* A, const int* L, const int* rootlist, const int* nroots);
 
+// scipy.ndimage.binary_fill_holes of nplanes truth-value masks (amt_binary_morph's AMT_MORPH_FILL_HOLES, which checks
+// the arguments): out = in != 0, or a background pixel whose 4-connected (c8: 8-connected) background component holds no
+// pixel of the 1-pixel frame.  out must not alias in.
+int amt_i_fill_holes(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8);
+
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>
 static inline void amt_with_bool(bool b, F&& f) {

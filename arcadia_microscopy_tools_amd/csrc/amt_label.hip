@@ -70,11 +70,18 @@ __device__ __forceinline__ void ccl_stitch_rows(int* L, int p, int pitch, int la
     }
 }
 
+// INV (uint8 masks only): the components of the COMPLEMENT -- a pixel's value is "the byte is zero", taken in the load
+// (binary_fill_holes; no inverted plane exists anywhere)
+template <bool INV, typename T>
+__device__ __forceinline__ T ccl_px(T raw) {
+    return INV ? (T)(raw == 0) : raw;
+}
+
 // rootlist / nroots (nullable): every tile-local root (global flat index) is appended to the list of its TILE ROW,
 // rootlist[(plane * tile_rows + tile_row) * cap ...] with cap = TILE_R * W entries (order arbitrary; one counter per
 // tile row keeps the reserving atomics of a plane off a single address) -- callers that only need roots compressed
 // walk these lists instead of the whole plane.
-template <typename T, bool CONN8>
+template <typename T, bool CONN8, bool INV = false>
 __device__ __forceinline__ void ccl_tile_do(const T* __restrict__ in, int* __restrict__ Lall, int H, int W,
                                             int* __restrict__ rootlist, int* __restrict__ nroots, size_t cap, int bx, int by,
                                             int bz, int ntr) {
@@ -102,7 +109,7 @@ __device__ __forceinline__ void ccl_tile_do(const T* __restrict__ in, int* __res
             raw[k] = img[(size_t)(y < H ? y : H - 1) * W + xc];
         }
 #pragma unroll
-        for (int k = 0; k < STRIP_R; ++k) v[k] = (x < W && ty0 + r0 + k < H) ? (V)raw[k] : NOVAL;
+        for (int k = 0; k < STRIP_R; ++k) v[k] = (x < W && ty0 + r0 + k < H) ? (V)ccl_px<INV>(raw[k]) : NOVAL;
     }
 #pragma unroll
     for (int k = 0; k < STRIP_R; ++k) {
@@ -201,11 +208,11 @@ __device__ __forceinline__ void ccl_tile_do(const T* __restrict__ in, int* __res
     }
 }
 
-template <typename T, bool CONN8>
+template <typename T, bool CONN8, bool INV = false>
 __global__ void __launch_bounds__(256) ccl_tile_kernel(const T* __restrict__ in, int* __restrict__ Lall, int H, int W,
                                                        int* __restrict__ rootlist, int* __restrict__ nroots,
                                                        size_t cap) {
-    ccl_tile_do<T, CONN8>(in, Lall, H, W, rootlist, nroots, cap, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y);
+    ccl_tile_do<T, CONN8, INV>(in, Lall, H, W, rootlist, nroots, cap, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.y);
 }
 
 // the fallback behind ccl_tile_bits_kernel: a few hundred workgroups that leave at once unless that kernel gave up
@@ -644,7 +651,7 @@ __global__ void ccl_reset_lists_kernel(int* __restrict__ nroots, size_t nlist, c
 }
 
 // blockIdx.y selects the job: [0, nrow_jobs) = strip-boundary rows, the rest = segment-boundary columns
-template <typename T, bool CONN8>
+template <typename T, bool CONN8, bool INV = false>
 __global__ void __launch_bounds__(256) ccl_border_kernel(const T* __restrict__ in, int* __restrict__ Lall, int H, int W,
                                                          int nrow_blocks, const int* __restrict__ cols_only_if = nullptr,
                                                          const int* __restrict__ all_only_if = nullptr) {
@@ -661,8 +668,8 @@ __global__ void __launch_bounds__(256) ccl_border_kernel(const T* __restrict__ i
         const int xc = x < W ? x : W - 1;
         typedef typename ccl_wide<T>::type V;
         constexpr V NOVAL = ccl_wide<T>::NOVAL;
-        const V v = x < W ? (V)img[(size_t)y * W + xc] : NOVAL;
-        const V up = x < W ? (V)img[(size_t)(y - 1) * W + xc] : NOVAL;
+        const V v = x < W ? (V)ccl_px<INV>(img[(size_t)y * W + xc]) : NOVAL;
+        const V up = x < W ? (V)ccl_px<INV>(img[(size_t)(y - 1) * W + xc]) : NOVAL;
         ccl_stitch_rows<CONN8, false>(L, y * W + xc, W, lane, v, up, NOVAL);
     } else {
         // column pairs (x-1, x) with x a multiple of 64; one thread per (row, boundary)
@@ -672,11 +679,11 @@ __global__ void __launch_bounds__(256) ccl_border_kernel(const T* __restrict__ i
         if (nbound == 0 || t >= H * nbound) return;
         const int y = t / nbound, x = (t % nbound + 1) * 64;
         const int pb = y * W + x, pa = pb - 1;
-        const T vb = img[pb], va = img[pa];
+        const T vb = ccl_px<INV>(img[pb]), va = ccl_px<INV>(img[pa]);
         if (vb != 0 && va == vb) uf_union(L, pb, pa);
         if (CONN8 && y > 0) {
-            if (vb != 0 && img[pa - W] == vb) uf_union(L, pb, pa - W);  // NW of b
-            if (va != 0 && img[pb - W] == va) uf_union(L, pa, pb - W);  // NE of a
+            if (vb != 0 && ccl_px<INV>(img[pa - W]) == vb) uf_union(L, pb, pa - W);  // NW of b
+            if (va != 0 && ccl_px<INV>(img[pb - W]) == va) uf_union(L, pa, pb - W);  // NE of a
         }
     }
 }
@@ -801,12 +808,13 @@ static int ccl_roots(amt_ctx* ctx, const ccl_geom& g, const int32_t* in, int* L,
 // every tile-local root is listed in rootlist (nroots[plane * trows + tile row] entries, zero on entry); the caller
 // compresses the listed roots (find + path compression) and resolves pixels with two hops, L[L[p]].
 // multi (nullable): g.multi_ints() of scratch; with it, uint8 inputs take the bit-parallel tile kernel first
-template <typename T, bool CONN8>
+// INV: the components of the complement of a uint8 truth-value mask (ccl_px); byte kernels only, so no multi
+template <typename T, bool CONN8, bool INV = false>
 static int ccl_tileroots(amt_ctx* ctx, const ccl_geom& g, const T* in, int* L, int* rootlist, int* nroots,
                          int* multi = nullptr) {
     const int H = g.H, W = g.W;
     bool done = false;
-    if (std::is_same<T, uint8_t>::value && multi && amt_i_ccl_runs_ok(in, g)) {
+    if (!INV && std::is_same<T, uint8_t>::value && multi && amt_i_ccl_runs_ok(in, g)) {
         // masks: the bit-parallel tile kernel; a plane batch that turns out to hold other byte values is redone below
         AMT_HIP_CHECK(hipMemsetAsync(multi, 0, sizeof(int), ctx->stream));
         hipLaunchKernelGGL((ccl_tile_bits_kernel<CONN8>), g.gs, dim3(64), 0, ctx->stream, (const uint8_t*)in, L, H, W, rootlist,
@@ -820,13 +828,13 @@ static int ccl_tileroots(amt_ctx* ctx, const ccl_geom& g, const T* in, int* L, i
         done = true;
     }
     if (!done) {
-        hipLaunchKernelGGL((ccl_tile_kernel<T, CONN8>), g.gs, dim3(256), 0, ctx->stream, in, L, H, W, rootlist, nroots, g.cap);
+        hipLaunchKernelGGL((ccl_tile_kernel<T, CONN8, INV>), g.gs, dim3(256), 0, ctx->stream, in, L, H, W, rootlist, nroots, g.cap);
         AMT_LAUNCH_CHECK();
     }
     if (g.gb.y > 0) {
         // with the bit kernel's column words the byte version only stitches the rows (its column jobs leave at once
         // unless the batch turned out to hold other byte values)
-        hipLaunchKernelGGL((ccl_border_kernel<T, CONN8>), g.gb, dim3(256), 0, ctx->stream, in, L, H, W, g.nrow_blocks,
+        hipLaunchKernelGGL((ccl_border_kernel<T, CONN8, INV>), g.gb, dim3(256), 0, ctx->stream, in, L, H, W, g.nrow_blocks,
                            done ? (const int*)multi : (const int*)nullptr);
         AMT_LAUNCH_CHECK();
         if (done && g.segs > 1) {
@@ -898,6 +906,19 @@ int amt_i_propagate_roots(amt_ctx* ctx, const ccl_geom& g, int* A, const int* L,
     return AMT_OK;
 }
 
+// the component root of the listed tile root t, with path compression: L[t] = root afterwards.  Other threads compress
+// other entries meanwhile; every value a find reads is an ancestor of its entry, so the walk ends at the same root
+__device__ __forceinline__ int roots_compress_one(int* __restrict__ L, int t) {
+    int r = L[t];
+    int p = L[r];
+    while (p != r) {
+        r = p;
+        p = L[r];
+    }
+    if (r != t) L[t] = r;
+    return r;
+}
+
 // compress the listed tile roots, count the component roots of every RN_CHUNK-pixel chunk (what the raster
 // renumbering scans) and set the root's bit in the plane's root bitmap; blockcnt and bitmap must be zero on entry
 __global__ void __launch_bounds__(256) roots_compress_count_kernel(int* __restrict__ Lall, const int* __restrict__ rootlist,
@@ -912,15 +933,8 @@ __global__ void __launch_bounds__(256) roots_compress_count_kernel(int* __restri
     unsigned long long* bm = bitmap + (size_t)plane * ((n + 63) / 64);
     for (int k = blockIdx.x * 256 + threadIdx.x; k < cnt; k += gridDim.x * 256) {
         const int t = lst[k];
-        int r = L[t];
-        int p = L[r];
-        while (p != r) {
-            r = p;
-            p = L[r];
-        }
-        if (r != t) {
-            L[t] = r;
-        } else {
+        const int r = roots_compress_one(L, t);
+        if (r == t) {
             atomicAdd(&blockcnt[(size_t)plane * nblk + t / RN_CHUNK], 1);
             atomicOr(&bm[t >> 6], 1ull << (t & 63));
         }
@@ -1133,6 +1147,243 @@ extern "C" int amt_clear_border(amt_ctx* ctx, const int32_t* in, int32_t* out, i
     AMT_LAUNCH_CHECK();
     dim3 g1(amt_grid_for(n, 256, 4096), nplanes);
     hipLaunchKernelGGL(clear_flagged_kernel, g1, dim3(256), 0, ctx->stream, in, L, T, out, n);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// ---- binary_fill_holes -----------------------------------------------------------------------------------------------
+// scipy.ndimage.binary_fill_holes for the 3 x 3 cross and the 3 x 3 all-ones structure: a hole is a component of the
+// BACKGROUND (4- resp. 8-connected) that holds no pixel of the 1-pixel frame.  The component analysis is amt_label's, run
+// on the complement, but the result is a set: no raster numbering, no scan, no int32 plane.
+//   tile pass   run tables of the complement (fill_tile_runs_kernel: the byte plane is read once, inverted in registers)
+//               or, for widths / addresses the run tables refuse, the byte union-find with the test inverted in the load;
+//               F[tile root] = 1 where a pixel of the tile root's tile-local component lies on the frame;
+//   seams       as for amt_label;
+//   flags       fill_roots_flag_kernel compresses the listed tile roots and raises F at the component root of every
+//               flagged tile root; the next launch (amt_i_propagate_roots) copies the component's flag back to them;
+//   write-out   original bit OR (background AND the component is unflagged), as bytes.
+// Workgroups exchange data between launches only; F is only ever raised (0 -> 1), so no result depends on an order.
+
+// a run's pixels as a word: the run that starts at bit b of w
+__device__ __forceinline__ unsigned long long ccl_run_mask(unsigned long long w, int b) {
+    const unsigned long long t = w >> b;
+    const int len = ~t ? __ffsll((long long)~t) - 1 : 64;  // trailing ones: the run's length
+    return (len >= 64 ? ~0ull : ((1ull << len) - 1ull)) << b;
+}
+
+template <bool CONN8>
+__global__ void __launch_bounds__(64) fill_tile_runs_kernel(const uint8_t* __restrict__ in, int* __restrict__ Lall,
+                                                            int* __restrict__ Fall, int H, int W, int* __restrict__ rootlist,
+                                                            int* __restrict__ nroots, size_t cap,
+                                                            unsigned long long* __restrict__ tbits,
+                                                            unsigned short* __restrict__ rtab, int* __restrict__ nruns) {
+    __shared__ int S[64 * 32];
+    __shared__ unsigned char touch[64 * 32];  // per run id: a run of the component it roots lies on the frame
+    const size_t n = (size_t)H * W;
+    const uint8_t* img = in + (size_t)blockIdx.z * n;
+    int* L = Lall + (size_t)blockIdx.z * n;
+    int* F = Fall + (size_t)blockIdx.z * n;
+    const int lane = threadIdx.x;
+    const int x0 = blockIdx.x * 64, ty0 = blockIdx.y * 64;
+    const int y = ty0 + lane;
+    const size_t tile = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    // the complement, inside the plane only: columns from W on and rows from H on are nobody's background
+    const int wcols = W - x0;  // > 0
+    const unsigned long long valid = wcols >= 64 ? ~0ull : ((1ull << wcols) - 1ull);
+    unsigned other;
+    const unsigned long long fg = ccl_bits_load_row<true>(img, H, W, x0, y, other);
+    const unsigned long long w = y < H ? (~fg & valid) : 0ull;
+    tbits[tile * 64 + lane] = w;
+    const unsigned long long heads = w & ~(w << 1);
+    const int nroot = ccl_bits_unionfind<CONN8>(S, w, heads, lane);
+    // the frame's pixels of this row
+    unsigned long long fr = (y == 0 || y == H - 1) ? valid : 0ull;
+    if (x0 == 0) fr |= 1ull;
+    if (wcols <= 64) fr |= 1ull << (wcols - 1);
+    {
+        int j = 0;
+        for (unsigned long long h = heads; h; h &= h - 1, ++j) touch[lane * 32 + j] = 0;
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    if (w & fr) {
+        int j = 0;
+        for (unsigned long long h = heads; h; h &= h - 1, ++j) {
+            const int b = __ffsll((long long)h) - 1;
+            if (ccl_run_mask(w, b) & fr) touch[S[lane * 32 + j] >> 6] = 1;  // lanes only ever store 1 here
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // run table, tile roots (L[root] = root, F[root] = its flag) and the tile's slice of its tile row's root list
+    const int cnt = __popcll(heads);
+    const int incl = ccl_wave_incl_scan(cnt, lane);
+    const int rincl = ccl_wave_incl_scan(nroot, lane);
+    const int tot = __shfl(rincl, 63);
+    int base = 0;
+    if (lane == 0 && tot) base = atomicAdd(&nroots[blockIdx.z * gridDim.y + blockIdx.y], tot);
+    size_t pos = (size_t)__builtin_amdgcn_readfirstlane(base) + (rincl - nroot);
+    unsigned short* rt = rtab + tile * RT_CAP + (incl - cnt);
+    int j = 0;
+    for (unsigned long long h = heads; h; h &= h - 1, ++j) {
+        const int own = lane * 32 + j;
+        const int e = S[own];
+        rt[j] = (unsigned short)(((e >> 11) << 6) | (e & 63));
+        if ((e >> 6) == own) {
+            const int pix = y * W + x0 + (e & 63);
+            L[pix] = pix;
+            F[pix] = touch[own];
+            if (pos < cap) rootlist[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * cap + pos] = pix;
+            ++pos;
+        }
+    }
+    if (lane == 63) nruns[tile] = incl;
+}
+
+// compress the listed tile roots (L[t] = component root) and raise the component root's flag for every flagged tile
+// root.  F is read at tile roots that are not component roots and written at component roots: no entry is both.
+__global__ void __launch_bounds__(256) fill_roots_flag_kernel(int* __restrict__ Lall, int* __restrict__ Fall,
+                                                              const int* __restrict__ rootlist,
+                                                              const int* __restrict__ nroots, size_t cap, size_t n) {
+    const int plane = blockIdx.z, shard = plane * gridDim.y + blockIdx.y;
+    int* L = Lall + (size_t)plane * n;
+    int* F = Fall + (size_t)plane * n;
+    const int cnt = nroots[shard] < (int)cap ? nroots[shard] : (int)cap;
+    const int* lst = rootlist + (size_t)shard * cap;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < cnt; k += gridDim.x * 256) {
+        const int t = lst[k];
+        const int r = roots_compress_one(L, t);
+        if (r != t && F[t]) F[r] = 1;
+    }
+}
+
+// four pixels of a word as 0 / 1 bytes
+__device__ __forceinline__ unsigned fill_spread4(unsigned nib) { return (nib * 0x00204081u) & 0x01010101u; }
+
+// the filled mask from (complement row words, run table, F at the tile roots): a wave per tile, four tiles (neighbours in
+// a tile row, so that a workgroup's stores of a row are 256 contiguous bytes) per workgroup; a lane gathers the flags of
+// its share of the runs, ORs the unflagged runs of its row into the original bits, and stores 16 pixels at a time
+__global__ void __launch_bounds__(256) fill_expand_runs_kernel(const unsigned long long* __restrict__ tbits,
+                                                               const unsigned short* __restrict__ rtab,
+                                                               const int* __restrict__ nruns, const int* __restrict__ Fall,
+                                                               uint8_t* __restrict__ outall, int H, int W, int segs,
+                                                               int trows, int ntiles) {
+    __shared__ unsigned char hole_s[4][RT_CAP];
+    __shared__ unsigned long long bits_s[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int t = blockIdx.x * 4 + wv;
+    if (t >= ntiles) return;  // whole wave
+    const int bx = t % segs, ty = (t / segs) % trows, plane = t / (segs * trows);
+    const size_t n = (size_t)H * W;
+    const int* F = Fall + (size_t)plane * n;
+    uint8_t* out = outall + (size_t)plane * n;
+    const int x0 = bx * 64, ty0 = ty * 64;
+    const int nr = nruns[t];
+    const unsigned long long w = tbits[(size_t)t * 64 + lane];
+    unsigned long long fill = 0;
+    if (nr) {  // uniform: a tile without background has nothing to look up
+        for (int k = lane; k < nr; k += 64) hole_s[wv][k] = F[ccl_rt_root(rtab, (size_t)t, k, ty, bx, W)] == 0;
+        const unsigned long long heads = w & ~(w << 1);
+        const int cnt = __popcll(heads);
+        const int off = ccl_wave_incl_scan(cnt, lane) - cnt;
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        int j = 0;
+        for (unsigned long long h = heads; h; h &= h - 1, ++j)
+            if (hole_s[wv][off + j]) fill |= ccl_run_mask(w, __ffsll((long long)h) - 1);
+    }
+    bits_s[wv][lane] = ~w | fill;  // bits beyond the plane are set and never stored
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    const int c16 = (lane & 3) * 16, rsub = lane >> 2;
+    const int xg = x0 + c16;
+    if (xg >= W) return;  // W % 16 == 0: the sixteen pixels are inside the plane together
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int row = rsub + 16 * j;
+        const int y = ty0 + row;
+        const unsigned s16 = (unsigned)(bits_s[wv][row] >> c16) & 0xFFFFu;
+        uint4 q;
+        q.x = fill_spread4(s16 & 15u);
+        q.y = fill_spread4((s16 >> 4) & 15u);
+        q.z = fill_spread4((s16 >> 8) & 15u);
+        q.w = fill_spread4(s16 >> 12);
+        if (y < H) *reinterpret_cast<uint4*>(out + (size_t)y * W + xg) = q;
+    }
+}
+
+// the general path's write-out: L[p] < 0 = foreground of the input; otherwise p's tile root carries its component's flag
+__global__ void __launch_bounds__(256) fill_write_kernel(const int* __restrict__ L, const int* __restrict__ F,
+                                                         uint8_t* __restrict__ out, size_t n) {
+    const size_t base = (size_t)blockIdx.y * n;
+    const bool al = (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+    for (size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (size_t)gridDim.x * 1024) {
+        if (al && i0 + 3 < n && ((base + i0) & 3) == 0) {
+            const int4 l = *reinterpret_cast<const int4*>(L + base + i0);
+            uchar4 o;
+            o.x = (l.x < 0 || F[base + l.x] == 0) ? 1 : 0;
+            o.y = (l.y < 0 || F[base + l.y] == 0) ? 1 : 0;
+            o.z = (l.z < 0 || F[base + l.z] == 0) ? 1 : 0;
+            o.w = (l.w < 0 || F[base + l.w] == 0) ? 1 : 0;
+            *reinterpret_cast<uchar4*>(out + base + i0) = o;
+        } else {
+            for (size_t i = i0; i < n && i < i0 + 4; ++i) {
+                const int l = L[base + i];
+                out[base + i] = (l < 0 || F[base + l] == 0) ? 1 : 0;
+            }
+        }
+    }
+}
+
+int amt_i_fill_holes(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8) {
+    AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "fill_holes: plane too large");
+    const ccl_geom g = amt_i_ccl_geom(nplanes, H, W);
+    const size_t n = g.n;
+    // run tables of the complement where amt_label would take them for the mask itself (same limits)
+    const bool runs = amt_i_ccl_runs_ok(in, g) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && g.ntiles * 64 < 0x7fffffffull;
+    amt_scratch s(ctx);
+    amt_buf<int> L(s, (size_t)nplanes * n);  // union-find parents; the run tables only touch the tile roots' entries
+    // "touches the frame", at the tile roots.  Like L a whole int32 plane of the arena of which the run-table path touches
+    // only the tile roots' entries (no traffic, but 4 B/px of reservation that amt_label does not need): flags indexed by
+    // the position in the root lists, or a bit of L, would do without it -- not done, the tile roots are addressed by
+    // pixel everywhere else (rtab, amt_i_propagate_roots)
+    amt_buf<int> F(s, (size_t)nplanes * n);
+    amt_buf<int> rootlist(s, g.nlist * g.cap);
+    amt_buf<int> nroots(s, g.nlist);
+    amt_buf<unsigned long long> tbits(s, g.ntiles * 64, runs);
+    amt_buf<unsigned short> rtab(s, g.ntiles * RT_CAP, runs);
+    amt_buf<int> nruns(s, g.ntiles, runs);
+    AMT_TRY(s.commit());
+    AMT_HIP_CHECK(hipMemsetAsync(nroots, 0, g.nlist * sizeof(int), ctx->stream));
+    if (runs) {
+        amt_with_bool(c8, [&](auto C8) {
+            hipLaunchKernelGGL((fill_tile_runs_kernel<decltype(C8)::value>), g.gs, dim3(64), 0, ctx->stream, in, L, F, H, W, rootlist,
+                               nroots, g.cap, tbits, rtab, nruns);
+        });
+        AMT_LAUNCH_CHECK();
+        AMT_TRY(ccl_seams_runs(ctx, g, c8, L, nullptr, tbits, rtab, nruns));
+    } else {
+        AMT_HIP_CHECK(hipMemsetAsync(F, 0, (size_t)nplanes * n * sizeof(int), ctx->stream));
+        int rc = AMT_OK;
+        amt_with_bool(c8, [&](auto C8) {
+            rc = ccl_tileroots<uint8_t, decltype(C8)::value, true>(ctx, g, in, L, rootlist, nroots);
+        });
+        AMT_TRY(rc);
+        // every pixel points at a tile root of its component here (its own, or for a tile root that a seam hung below
+        // another, that one): the frame's pixels flag those
+        hipLaunchKernelGGL(frame_flag_kernel, dim3(amt_grid_for((size_t)2 * W + 2 * H, 256, 64), nplanes), dim3(256), 0,
+                           ctx->stream, L, F, H, W);
+        AMT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(fill_roots_flag_kernel, g.glists, dim3(256), 0, ctx->stream, L, F, rootlist, nroots, g.cap, n);
+    AMT_LAUNCH_CHECK();
+    AMT_TRY(amt_i_propagate_roots(ctx, g, F, L, rootlist, nroots));
+    if (runs) {
+        hipLaunchKernelGGL(fill_expand_runs_kernel, dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0, ctx->stream, tbits, rtab,
+                           nruns, F, out, H, W, g.segs, g.trows, (int)g.ntiles);
+    } else {
+        hipLaunchKernelGGL(fill_write_kernel, dim3(amt_grid_for(n, 1024, 4096), nplanes), dim3(256), 0, ctx->stream, L, F, out, n);
+    }
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }

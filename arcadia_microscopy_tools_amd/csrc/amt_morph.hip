@@ -11,7 +11,7 @@
 // of (previous | current | next) word of row y + dy followed by an AND / OR, i.e. |S| word operations
 // per 64 pixels -- and the result is unpacked to bytes.  The packed plane (H * ceil(W / 64) words; 512 KB
 // at 2048^2) lives in L2, so an opening or closing costs one HBM read and one HBM write of the byte mask.
-#include "amt_common.h"
+#include "amt_internal.h"
 
 typedef unsigned long long u64;
 constexpr int MAX_OFFS = 1024;
@@ -226,12 +226,37 @@ static int build_offsets(const uint8_t* fp, int fh, int fw, int2* host, int* n) 
     return AMT_OK;
 }
 
-// op: AMT_MORPH_ERODE, AMT_MORPH_DILATE, AMT_MORPH_OPEN (erode then dilate), AMT_MORPH_CLOSE (dilate then erode)
+// op: AMT_MORPH_ERODE, AMT_MORPH_DILATE, AMT_MORPH_OPEN (erode then dilate), AMT_MORPH_CLOSE (dilate then erode),
+// AMT_MORPH_FILL_HOLES (amt_label.hip: amt_i_fill_holes)
 extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
                                 const uint8_t* footprint, int fh, int fw, int op, int border_value) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "binary morphology: bad arguments");
-    AMT_REQUIRE(op >= AMT_MORPH_ERODE && op <= AMT_MORPH_CLOSE, "binary morphology: op must be 0..3, got %d", op);
+    AMT_REQUIRE(op >= AMT_MORPH_ERODE && op <= AMT_MORPH_FILL_HOLES, "binary morphology: op must be 0..4, got %d", op);
+    if (op == AMT_MORPH_FILL_HOLES) {
+        // the two structures for which scipy's propagation from outside the image is "background components that hold
+        // no frame pixel": the 3 x 3 cross (4-connected background) and 3 x 3 all-ones (8-connected)
+        int cells = 0;
+        bool cross = footprint && fh == 3 && fw == 3;
+        if (cross)
+            for (int k = 0; k < 9; ++k) {
+                cells += footprint[k] != 0;
+                if ((k & 1) == 0 && k != 4 && footprint[k]) cross = false;  // a corner
+            }
+        const bool full = footprint && fh == 3 && fw == 3 && cells == 9;
+        cross = cross && cells == 5;
+        AMT_REQUIRE(cross || full,
+                    "fill_holes: the structure must be the 3 x 3 cross (4-connected background) or 3 x 3 all-ones "
+                    "(8-connected background)");
+        if (nplanes == 0) return AMT_OK;
+        {
+            // any overlap of the two batches, not only out == in: a plane's write-out would land in input still to be read
+            const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+            const size_t bytes = (size_t)nplanes * H * W;
+            AMT_REQUIRE(a + bytes <= b || b + bytes <= a, "fill_holes: out must not alias or overlap in");
+        }
+        return amt_i_fill_holes(ctx, in, out, nplanes, H, W, full);
+    }
     static thread_local int2 host[MAX_OFFS];
     int noffs = 0;
     AMT_TRY(build_offsets(footprint, fh, fw, host, &noffs));

@@ -503,7 +503,7 @@ def _fp(footprint, even: str = "scipy"):
     return np.ascontiguousarray(fp)
 
 
-_MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3}  # AMT_MORPH_*
+_MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3, "fill_holes": 4}  # AMT_MORPH_*
 
 
 def _binary(which: str, a: DeviceArray, footprint, out, border_value=None):
@@ -540,6 +540,42 @@ def binary_opening(a, footprint=None, out=None):
 def binary_closing(a, footprint=None, out=None):
     """``skimage.morphology.binary_closing`` = erosion(dilation(a)), fused (SK/morphology/binary.py:116-147)."""
     return _binary("close", a, footprint, out)
+
+
+def _fill_structure(structure) -> np.ndarray:
+    """The structure of ``binary_fill_holes`` as uint8 (3, 3): None is the cross; any array whose ``!= 0`` pattern is the
+    3 x 3 cross or 3 x 3 all-ones is taken, anything else refused (no device call is made)."""
+    if structure is None:
+        return cross3()
+    st = np.ascontiguousarray(np.asarray(structure) != 0, dtype=np.uint8)
+    if st.shape != (3, 3) or not (np.array_equal(st, cross3()) or st.all()):
+        raise ValueError("binary_fill_holes: structure must be the 3 x 3 cross (generate_binary_structure(2, 1)) or "
+                         "3 x 3 all-ones (generate_binary_structure(2, 2))")
+    return st
+
+
+def binary_fill_holes(a: DeviceArray, structure=None, out: DeviceArray | None = None) -> DeviceArray:
+    """``scipy.ndimage.binary_fill_holes(a != 0, structure)`` per plane of a (H, W) or (N, H, W) uint8 / bool mask: a
+    background pixel is filled when its background component (4-connected for the cross, 8-connected for all-ones)
+    holds no pixel of the image's 1-pixel frame (amt_binary_morph, AMT_MORPH_FILL_HOLES)."""
+    st = _fill_structure(structure)
+    if a.dtype != np.uint8:
+        raise TypeError("binary_fill_holes expects a uint8 / bool mask on the device")
+    if a.ndim not in (2, 3):
+        raise ValueError(f"binary_fill_holes takes (H, W) or (N, H, W) masks, got shape {a.shape}")
+    ctx = a.ctx
+    n, H, W = _planes(a)
+    o = _out(ctx, out, a.shape, np.uint8)
+    if o is a or (a.nbytes and o.ptr < a.ptr + a.nbytes and a.ptr < o.ptr + o.nbytes):
+        # any overlap, not only the same address: the write-out of one plane would land in input still to be read
+        raise ValueError("binary_fill_holes: out must not alias (or overlap) the input")
+    if a.size == 0:
+        o.is_bool = True
+        return o
+    _hip.check(_lib().amt_binary_morph(ctx.handle, a.ptr, o.ptr, n, H, W, st.ctypes.data_as(ctypes.c_void_p), 3, 3,
+                                       _MORPH_OPS["fill_holes"], 0), "amt_binary_morph")
+    o.is_bool = True
+    return o
 
 
 def threshold_otsu_bins(a: DeviceArray, minmax: DeviceArray, thr: DeviceArray, thr_code: DeviceArray,

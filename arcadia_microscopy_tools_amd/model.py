@@ -81,6 +81,7 @@ class SegmentationModel:
     opening_radius: int = 2
     network: Any = field(default=None, repr=False)
     compute_dtype: str = "bf16"
+    fill_holes: bool = False  # classical backend: scipy.ndimage.binary_fill_holes between the closing and the EDT
     _model: Any = field(default=None, init=False, repr=False)
     _net: Any = field(default=None, init=False, repr=False)
 
@@ -89,6 +90,9 @@ class SegmentationModel:
             raise ValueError(f"backend must be 'classical', 'cellpose' or 'cellpose-hip', got '{self.backend}'")
         if self.backend == "cellpose-hip" and self.network is None:
             raise ValueError("backend 'cellpose-hip' needs network= (a torch.nn.Module, or 'standin')")
+        if self.fill_holes and self.backend != "classical":
+            raise ValueError(f"fill_holes=True applies to backend='classical' only (the Cellpose route fills holes "
+                             f"itself), got backend '{self.backend}'")
         if self.device is None and self.backend in ("cellpose", "cellpose-hip"):
             self.device = self.find_best_available_device()
 
@@ -212,6 +216,8 @@ class SegmentationModel:
         m0 = hipops.greater_than(g, thr)
         fp = hipops.disk(self.opening_radius)
         m1 = hipops.binary_closing(hipops.binary_opening(m0, fp), fp)
+        if self.fill_holes:
+            m1 = hipops.binary_fill_holes(m1)
         d2, _ = hipops.edt(m1, want_edt=False)
         min_distance = max(1, int(round(params["diameter"] / 6.0)))
         peaks = hipops.peak_mask(d2, m1, min_distance)
@@ -287,12 +293,12 @@ class SegmentationModel:
         out: list = []
         for i0 in range(0, len(arrs), chunk):
             part = arrs[i0:i0 + chunk]
-            key = (len(part), H, W, min_distance, self.sigma, self.opening_radius, id(ctx))
+            key = (len(part), H, W, min_distance, self.sigma, self.opening_radius, self.fill_holes, id(ctx))
             seg = getattr(cache, "seg", None)
             if seg is None or getattr(cache, "key", None) != key:
                 seg = FovSegmenter(len(part), 1, H, W, sigma=self.sigma, radius=self.opening_radius,
                                    min_distance=min_distance, max_cells=max(4096, (H * W) // 64), dapi_index=0, ctx=ctx,
-                                   props=False, fused=False)
+                                   props=False, fused=False, fill_holes=self.fill_holes)
                 cache.seg, cache.key = seg, key
                 cache.inp = ctx.empty((len(part), 1, H, W), np.uint16)
             for j, a in enumerate(part):  # each plane converted on its way through the page-locked staging buffer
@@ -378,13 +384,13 @@ class SegmentationModel:
         min_distance = max(1, int(round(params["diameter"] / 6.0)))
         chunk = max(1, min(int(params["batch_size"]), len(images)))
         cache = self.__dict__.setdefault("_mask_cache", threading.local())
-        key = (chunk, C, H, W, nuclear, min_distance, self.sigma, self.opening_radius, id(ctx))
+        key = (chunk, C, H, W, nuclear, min_distance, self.sigma, self.opening_radius, self.fill_holes, id(ctx))
         mb = getattr(cache, "mb", None)
         if mb is None or cache.key != key:
             if mb is not None:
                 mb.close()
             mb = MaskBatcher(chunk, C, H, W, nuclear=nuclear, sigma=self.sigma, radius=self.opening_radius,
-                             min_distance=min_distance, ctx=ctx)
+                             min_distance=min_distance, ctx=ctx, fill_holes=self.fill_holes)
             cache.mb, cache.key = mb, key
         return mb.run(images)
 

@@ -235,6 +235,33 @@ def expand_labels(label_image, distance: float = 1):
     return hipops.expand_labels(d, distance).numpy(dtype=a.dtype)
 
 
+@device_operator
+def binary_fill_holes(mask, structure=None):
+    """``scipy.ndimage.binary_fill_holes(mask, structure)`` on a 2-D mask: the holes of the foreground (``mask != 0``) are
+    the background regions that cannot be reached from outside the image.  ``structure``: None or
+    ``generate_binary_structure(2, 1)`` (the cross: holes are 4-connected background) or ``generate_binary_structure(2,
+    2)`` (all-ones: 8-connected); other structures are refused.  A numpy bool / integer array gives a numpy bool array;
+    a ``DeviceArray`` (a uint8 / bool mask, e.g. ``apply_threshold``'s result in a ``Pipeline``) stays on the device.
+    Stacks are refused rather than treated as volumes (scipy would fill a 3-D volume): map planes with
+    ``Pipeline(parallel=True)`` or call ``hipops.binary_fill_holes``."""
+    st = hipops._fill_structure(structure)
+    if isinstance(mask, DeviceArray):
+        if mask.ndim != 2:
+            raise ValueError("mask must be a 2D array")
+        if mask.dtype != np.uint8:
+            raise TypeError(f"binary_fill_holes: device masks must be uint8 / bool, got {mask.dtype}")
+        return hipops.binary_fill_holes(mask, st)
+    a = np.asarray(mask)
+    if a.ndim != 2:
+        raise ValueError("mask must be a 2D array")
+    if a.dtype != np.bool_ and not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"binary_fill_holes: mask must have a bool or integer dtype, got {a.dtype}")
+    if a.size == 0:
+        return np.zeros(a.shape, dtype=bool)
+    d = get_context().asarray(np.ascontiguousarray(a != 0))
+    return hipops.binary_fill_holes(d, st).numpy()
+
+
 def _global_threshold(d: DeviceArray, method: str, kwargs: dict) -> float:
     """Threshold VALUE for the histogram-based methods: histogram on the device, selection on <= 65,536 counts."""
     nbins = int(kwargs.pop("nbins", 256))

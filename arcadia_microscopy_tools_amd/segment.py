@@ -2,7 +2,7 @@
 
 Stages (CPU restatement: oracle/chains.py):
   C2  Gaussian(sigma) -> Otsu -> '>' -> binary opening(disk r) -> binary closing(disk r) -> label (8-conn)
-  C3  C2 mask on the DAPI channel -> EDT -> peak markers (min_distance) -> watershed (seeded relief)
+  C3  C2 mask on the DAPI channel [-> binary_fill_holes if fill_holes=True] -> EDT -> peak markers (min_distance) -> watershed (seeded relief)
       -> clear_border -> relabel_sequential -> morphology table + per-channel intensity table
 
 ``FovSegmenter`` preallocates every buffer for a batch of B fields of view, enqueues the whole chain
@@ -47,7 +47,7 @@ class FovSegmenter:
     def __init__(self, batch: int, C: int, H: int, W: int, *, sigma: float = 2.0, radius: int = 2,
                  min_distance: int = 5, max_cells: int = 4096, dapi_index: int = 1, ctx: Context | None = None,
                  props: bool = True, profile: bool = False, fused: bool = True, low_traffic: bool = False, bin_plane: bool = True,
-                 prefix_plane: bool = True, relief: str = "seeded", ties: str = "exact"):
+                 prefix_plane: bool = True, relief: str = "seeded", ties: str = "exact", fill_holes: bool = False):
         self.ctx = ctx or get_context()
         self.B, self.C, self.H, self.W = int(batch), int(C), int(H), int(W)
         self.sigma, self.radius, self.min_distance = float(sigma), int(radius), int(min_distance)
@@ -77,6 +77,9 @@ class FovSegmenter:
         # reads those and leaves 2-byte codes -- 6 instead of 9 bytes per pixel held and moved, same masks and
         # thresholds.  False = the float64 plane + byte bins
         self.prefix_plane = bool(prefix_plane)
+        # fill_holes: scipy.ndimage.binary_fill_holes (cross structure) between the closing and the EDT, so that a
+        # nucleus whose dim centre left a ring in the mask is one basin, not arcs; the filled mask lands in mask_b
+        self.fill_holes = bool(fill_holes)
         self.footprint = hipops.disk(self.radius)
         c, B = self.ctx, self.B
         shp = (B, self.H, self.W)
@@ -169,6 +172,14 @@ class FovSegmenter:
                                     thr_code=self._thr_code)
         return self.mask_a
 
+    def _mask(self, fovs: DeviceArray) -> DeviceArray:
+        """``mask_chain``, and with ``fill_holes`` its result filled into ``mask_b``: what the stages downstream use."""
+        mask = self.mask_chain(fovs)
+        if not self.fill_holes:
+            return mask
+        self._stage("fill_holes")
+        return hipops.binary_fill_holes(mask, out=self.mask_b)
+
     @property
     def gauss(self) -> DeviceArray:
         """The float64 smoothed DAPI planes of the separate-operator path (allocated on first use)."""
@@ -181,7 +192,7 @@ class FovSegmenter:
         fovs = self._check_fovs(fovs)
         if self.labels8 is None:
             self.labels8 = self.ctx.empty((self.B, self.H, self.W), np.int32)
-        mask = self.mask_chain(fovs)
+        mask = self._mask(fovs)
         self._stage("label8")
         hipops.label(mask, 2, out=self.labels8, count=self.count8)
         self._end()
@@ -191,7 +202,7 @@ class FovSegmenter:
     def run_c3(self, fovs: DeviceArray) -> DeviceArray:
         """BASELINE configs[2]: nuclei watershed + morphology / intensity tables.  Returns int32 labels."""
         fovs = self._check_fovs(fovs)
-        mask = self.mask_chain(fovs)
+        mask = self._mask(fovs)
         self._stage("edt")
         hipops.edt(mask, want_edt=False, d2_out=self.d2)
         self._stage("peaks")

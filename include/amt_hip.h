@@ -234,11 +234,22 @@ int amt_threshold_gt_image(amt_ctx* ctx, const void* in, int in_dtype, const dou
  *   AMT_MORPH_ERODE   outside the image counts as `border_value` (skimage: 1);
  *   AMT_MORPH_DILATE  outside the image counts as `border_value` (skimage: 0);
  *   AMT_MORPH_OPEN    fused opening = dilate(erode(x)), AMT_MORPH_CLOSE fused closing = erode(dilate(x)), both with
- *                     skimage's border rules (erosion sees 1, dilation 0): border_value is ignored. */
+ *                     skimage's border rules (erosion sees 1, dilation 0): border_value is ignored;
+ *   AMT_MORPH_FILL_HOLES  scipy.ndimage.binary_fill_holes(in != 0, structure=footprint) per plane.  `in` is a truth
+ *                     value (foreground = byte != 0, on every width and alignment); `out` holds 0 / 1 bytes:
+ *                     out[p] = 1 iff in[p] != 0 or p lies in a component of the background that contains no pixel of
+ *                     the 1-pixel frame (row 0, row H-1, column 0, column W-1).  Background components are 4-connected
+ *                     for the 3 x 3 cross and 8-connected for the 3 x 3 all-ones footprint; any other footprint is
+ *                     AMT_EINVAL (for exactly these two, scipy's propagation from outside the image equals the
+ *                     component rule).  border_value is ignored.  out must not alias in, nor overlap it in part
+ *                     (AMT_EINVAL); nplanes == 0 is
+ *                     AMT_OK; H * W < 2^31 - 1 as for amt_label.
+ * Any other op is AMT_EINVAL. */
 #define AMT_MORPH_ERODE 0
 #define AMT_MORPH_DILATE 1
 #define AMT_MORPH_OPEN 2
 #define AMT_MORPH_CLOSE 3
+#define AMT_MORPH_FILL_HOLES 4
 int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
                      const uint8_t* footprint, int fh, int fw, int op, int border_value);
 /* Otsu threshold of a float64 image (as amt_threshold_value) that also leaves the byte plane of its 256-bin indices
