@@ -139,6 +139,12 @@ int amt_i_propagate_roots(amt_ctx* ctx, const ccl_geom& g, int* A, const int* L,
 // the arguments): out = in != 0, or a background pixel whose 4-connected (c8: 8-connected) background component holds no
 // pixel of the 1-pixel frame.  out must not alias in.
 int amt_i_fill_holes(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8);
+// The area filters of nplanes truth-value masks (amt_binary_morph's AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES, which
+// checks the arguments; size >= 1).  holes == false: out = in != 0 and the pixel's 4-connected (c8: 8-connected)
+// foreground component has at least `size` pixels; holes == true: out = in != 0, or the pixel's background component
+// has fewer than `size` pixels.  out must not alias in.
+int amt_i_area_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8, bool holes,
+                      int size);
 
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>

@@ -71,17 +71,19 @@ __device__ __forceinline__ void ccl_stitch_rows(int* L, int p, int pitch, int la
 }
 
 // INV (uint8 masks only): the components of the COMPLEMENT -- a pixel's value is "the byte is zero", taken in the load
-// (binary_fill_holes; no inverted plane exists anywhere)
-template <bool INV, typename T>
+// (binary_fill_holes; no inverted plane exists anywhere).  CCL_TRUTH: "the byte is not zero", the components of a
+// truth-value mask whatever its non-zero bytes are (remove_small_objects)
+constexpr int CCL_TRUTH = 2;
+template <int INV, typename T>
 __device__ __forceinline__ T ccl_px(T raw) {
-    return INV ? (T)(raw == 0) : raw;
+    return INV == CCL_TRUTH ? (T)(raw != 0) : INV ? (T)(raw == 0) : raw;
 }
 
 // rootlist / nroots (nullable): every tile-local root (global flat index) is appended to the list of its TILE ROW,
 // rootlist[(plane * tile_rows + tile_row) * cap ...] with cap = TILE_R * W entries (order arbitrary; one counter per
 // tile row keeps the reserving atomics of a plane off a single address) -- callers that only need roots compressed
 // walk these lists instead of the whole plane.
-template <typename T, bool CONN8, bool INV = false>
+template <typename T, bool CONN8, int INV = 0>
 __device__ __forceinline__ void ccl_tile_do(const T* __restrict__ in, int* __restrict__ Lall, int H, int W,
                                             int* __restrict__ rootlist, int* __restrict__ nroots, size_t cap, int bx, int by,
                                             int bz, int ntr) {
@@ -208,7 +210,7 @@ __device__ __forceinline__ void ccl_tile_do(const T* __restrict__ in, int* __res
     }
 }
 
-template <typename T, bool CONN8, bool INV = false>
+template <typename T, bool CONN8, int INV = 0>
 __global__ void __launch_bounds__(256) ccl_tile_kernel(const T* __restrict__ in, int* __restrict__ Lall, int H, int W,
                                                        int* __restrict__ rootlist, int* __restrict__ nroots,
                                                        size_t cap) {
@@ -651,7 +653,7 @@ __global__ void ccl_reset_lists_kernel(int* __restrict__ nroots, size_t nlist, c
 }
 
 // blockIdx.y selects the job: [0, nrow_jobs) = strip-boundary rows, the rest = segment-boundary columns
-template <typename T, bool CONN8, bool INV = false>
+template <typename T, bool CONN8, int INV = 0>
 __global__ void __launch_bounds__(256) ccl_border_kernel(const T* __restrict__ in, int* __restrict__ Lall, int H, int W,
                                                          int nrow_blocks, const int* __restrict__ cols_only_if = nullptr,
                                                          const int* __restrict__ all_only_if = nullptr) {
@@ -808,8 +810,9 @@ static int ccl_roots(amt_ctx* ctx, const ccl_geom& g, const int32_t* in, int* L,
 // every tile-local root is listed in rootlist (nroots[plane * trows + tile row] entries, zero on entry); the caller
 // compresses the listed roots (find + path compression) and resolves pixels with two hops, L[L[p]].
 // multi (nullable): g.multi_ints() of scratch; with it, uint8 inputs take the bit-parallel tile kernel first
-// INV: the components of the complement of a uint8 truth-value mask (ccl_px); byte kernels only, so no multi
-template <typename T, bool CONN8, bool INV = false>
+// INV: the components of the complement of a uint8 truth-value mask, CCL_TRUTH: those of the mask itself (ccl_px); byte
+// kernels only, so no multi
+template <typename T, bool CONN8, int INV = 0>
 static int ccl_tileroots(amt_ctx* ctx, const ccl_geom& g, const T* in, int* L, int* rootlist, int* nroots,
                          int* multi = nullptr) {
     const int H = g.H, W = g.W;
@@ -1384,6 +1387,261 @@ int amt_i_fill_holes(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes,
     } else {
         hipLaunchKernelGGL(fill_write_kernel, dim3(amt_grid_for(n, 1024, 4096), nplanes), dim3(256), 0, ctx->stream, L, F, out, n);
     }
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// ---- remove_small_objects / remove_small_holes ------------------------------------------------------------------------
+// skimage.morphology.remove_small_objects / remove_small_holes on truth-value masks: binary_fill_holes' component
+// analysis with a pixel COUNT where that one keeps a flag.  INV selects the polarity (false: the components of the
+// foreground, the objects; true: those of the complement, taken in registers, the holes -- frame-touching ones included).
+//   tile pass   run tables (area_tile_runs_kernel): the run lengths of every tile-local component are summed in LDS, an
+//               int per run id, and stored at the tile root, C[tile root]; or, for widths / addresses the run tables
+//               refuse, the byte union-find followed by area_count_pixels_kernel, which counts the pixels themselves;
+//   seams       as for amt_label;
+//   sums        area_roots_sum_kernel compresses the listed tile roots and adds the count of every tile root that a seam
+//               hung below another into the component root's; the next launch (amt_i_propagate_roots) copies the total
+//               back to them;
+//   write-out   objects: bit AND count >= size; holes: bit OR (background AND count < size), as bytes.
+// Workgroups exchange data between launches only; the counts are integer sums, so no result depends on an order.
+
+template <bool CONN8, bool INV>
+__global__ void __launch_bounds__(64) area_tile_runs_kernel(const uint8_t* __restrict__ in, int* __restrict__ Lall,
+                                                            int* __restrict__ Call, int H, int W, int* __restrict__ rootlist,
+                                                            int* __restrict__ nroots, size_t cap,
+                                                            unsigned long long* __restrict__ tbits,
+                                                            unsigned short* __restrict__ rtab, int* __restrict__ nruns) {
+    __shared__ int S[64 * 32];
+    __shared__ int area[64 * 32];  // per run id: the pixels of the tile-local component it roots
+    const size_t n = (size_t)H * W;
+    const uint8_t* img = in + (size_t)blockIdx.z * n;
+    int* L = Lall + (size_t)blockIdx.z * n;
+    int* C = Call + (size_t)blockIdx.z * n;
+    const int lane = threadIdx.x;
+    const int x0 = blockIdx.x * 64, ty0 = blockIdx.y * 64;
+    const int y = ty0 + lane;
+    const size_t tile = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    // inside the plane only: columns from W on and rows from H on belong to no component of either polarity
+    const int wcols = W - x0;  // > 0
+    const unsigned long long valid = wcols >= 64 ? ~0ull : ((1ull << wcols) - 1ull);
+    unsigned other;
+    const unsigned long long fg = ccl_bits_load_row<true>(img, H, W, x0, y, other);
+    const unsigned long long w = y < H ? ((INV ? ~fg : fg) & valid) : 0ull;
+    tbits[tile * 64 + lane] = w;
+    const unsigned long long heads = w & ~(w << 1);
+    const int nroot = ccl_bits_unionfind<CONN8>(S, w, heads, lane);
+    {
+        int j = 0;
+        for (unsigned long long h = heads; h; h &= h - 1, ++j) area[lane * 32 + j] = 0;
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    {
+        int j = 0;
+        for (unsigned long long h = heads; h; h &= h - 1, ++j) {
+            const int b = __ffsll((long long)h) - 1;
+            atomicAdd(&area[S[lane * 32 + j] >> 6], __popcll(ccl_run_mask(w, b)));  // LDS; integer, so any order
+        }
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // run table, tile roots (L[root] = root, C[root] = its count) and the tile's slice of its tile row's root list
+    const int cnt = __popcll(heads);
+    const int incl = ccl_wave_incl_scan(cnt, lane);
+    const int rincl = ccl_wave_incl_scan(nroot, lane);
+    const int tot = __shfl(rincl, 63);
+    int base = 0;
+    if (lane == 0 && tot) base = atomicAdd(&nroots[blockIdx.z * gridDim.y + blockIdx.y], tot);
+    size_t pos = (size_t)__builtin_amdgcn_readfirstlane(base) + (rincl - nroot);
+    unsigned short* rt = rtab + tile * RT_CAP + (incl - cnt);
+    int j = 0;
+    for (unsigned long long h = heads; h; h &= h - 1, ++j) {
+        const int own = lane * 32 + j;
+        const int e = S[own];
+        rt[j] = (unsigned short)(((e >> 11) << 6) | (e & 63));
+        if ((e >> 6) == own) {
+            const int pix = y * W + x0 + (e & 63);
+            L[pix] = pix;
+            C[pix] = area[own];
+            if (pos < cap) rootlist[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * cap + pos] = pix;
+            ++pos;
+        }
+    }
+    if (lane == 63) nruns[tile] = incl;
+}
+
+// the general path's counts, from the pixels: after the byte tile pass and the seams every pixel of the analysed
+// polarity points at a tile root of its component (its own, or for a tile root that a seam hung below another, that
+// one), and that entry of C (zero on entry) receives it.  Neighbouring lanes that point at the same entry add once.
+__global__ void __launch_bounds__(256) area_count_pixels_kernel(const int* __restrict__ L, int* __restrict__ C, size_t n) {
+    const size_t base = (size_t)blockIdx.y * n;
+    const int lane = threadIdx.x & 63;
+    const size_t span = ((n + 255) / 256) * 256;  // whole waves stay in the loop together: the shuffle needs them
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < span; i += (size_t)gridDim.x * 256) {
+        const int l = i < n ? L[base + i] : -1;
+        const int left = __shfl_up(l, 1);
+        const bool head = lane == 0 || left != l;
+        const unsigned long long heads = __ballot(head);
+        if (head && l >= 0) {
+            const unsigned long long after = lane < 63 ? heads >> (lane + 1) : 0ull;  // the next head ends this stretch
+            const int len = after ? __ffsll((long long)after) : 64 - lane;
+            atomicAdd(&C[base + l], len);
+        }
+    }
+}
+
+// compress the listed tile roots (L[t] = component root) and add the count of every tile root that is not its
+// component's root into the component root's.  C is read at tile roots that are not component roots and written at
+// component roots: no entry is both.
+__global__ void __launch_bounds__(256) area_roots_sum_kernel(int* __restrict__ Lall, int* __restrict__ Call,
+                                                             const int* __restrict__ rootlist,
+                                                             const int* __restrict__ nroots, size_t cap, size_t n) {
+    const int plane = blockIdx.z, shard = plane * gridDim.y + blockIdx.y;
+    int* L = Lall + (size_t)plane * n;
+    int* C = Call + (size_t)plane * n;
+    const int cnt = nroots[shard] < (int)cap ? nroots[shard] : (int)cap;
+    const int* lst = rootlist + (size_t)shard * cap;
+    for (int k = blockIdx.x * 256 + threadIdx.x; k < cnt; k += gridDim.x * 256) {
+        const int t = lst[k];
+        const int r = roots_compress_one(L, t);
+        if (r != t) atomicAdd(&C[r], C[t]);
+    }
+}
+
+// the filtered mask from (row words of the analysed polarity, run table, C at the tile roots), laid out as
+// fill_expand_runs_kernel: a lane gathers the verdicts of its share of the runs, collects the chosen runs of its row
+// (objects: the runs to keep; holes: the runs to fill) and stores 16 pixels at a time
+template <bool INV>
+__global__ void __launch_bounds__(256) area_expand_runs_kernel(const unsigned long long* __restrict__ tbits,
+                                                               const unsigned short* __restrict__ rtab,
+                                                               const int* __restrict__ nruns, const int* __restrict__ Call,
+                                                               uint8_t* __restrict__ outall, int H, int W, int segs,
+                                                               int trows, int ntiles, int size) {
+    __shared__ unsigned char pick_s[4][RT_CAP];
+    __shared__ unsigned long long bits_s[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int t = blockIdx.x * 4 + wv;
+    if (t >= ntiles) return;  // whole wave
+    const int bx = t % segs, ty = (t / segs) % trows, plane = t / (segs * trows);
+    const size_t n = (size_t)H * W;
+    const int* C = Call + (size_t)plane * n;
+    uint8_t* out = outall + (size_t)plane * n;
+    const int x0 = bx * 64, ty0 = ty * 64;
+    const int nr = nruns[t];
+    const unsigned long long w = tbits[(size_t)t * 64 + lane];
+    unsigned long long picked = 0;
+    if (nr) {  // uniform: a tile without a run has nothing to look up
+        for (int k = lane; k < nr; k += 64) {
+            const int c = C[ccl_rt_root(rtab, (size_t)t, k, ty, bx, W)];
+            pick_s[wv][k] = INV ? c < size : c >= size;
+        }
+        const unsigned long long heads = w & ~(w << 1);
+        const int cnt = __popcll(heads);
+        const int off = ccl_wave_incl_scan(cnt, lane) - cnt;
+        __builtin_amdgcn_s_waitcnt(0);
+        __builtin_amdgcn_wave_barrier();
+        int j = 0;
+        for (unsigned long long h = heads; h; h &= h - 1, ++j)
+            if (pick_s[wv][off + j]) picked |= ccl_run_mask(w, __ffsll((long long)h) - 1);
+    }
+    bits_s[wv][lane] = INV ? (~w | picked) : picked;  // INV: bits beyond the plane are set and never stored
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    const int c16 = (lane & 3) * 16, rsub = lane >> 2;
+    const int xg = x0 + c16;
+    if (xg >= W) return;  // W % 16 == 0: the sixteen pixels are inside the plane together
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int row = rsub + 16 * j;
+        const int y = ty0 + row;
+        const unsigned s16 = (unsigned)(bits_s[wv][row] >> c16) & 0xFFFFu;
+        uint4 q;
+        q.x = fill_spread4(s16 & 15u);
+        q.y = fill_spread4((s16 >> 4) & 15u);
+        q.z = fill_spread4((s16 >> 8) & 15u);
+        q.w = fill_spread4(s16 >> 12);
+        if (y < H) *reinterpret_cast<uint4*>(out + (size_t)y * W + xg) = q;
+    }
+}
+
+// the general path's write-out: L[p] < 0 = the pixel is of the other polarity; otherwise p's tile root carries its
+// component's count
+template <bool INV>
+__global__ void __launch_bounds__(256) area_write_kernel(const int* __restrict__ L, const int* __restrict__ C,
+                                                         uint8_t* __restrict__ out, size_t n, int size) {
+    const size_t base = (size_t)blockIdx.y * n;
+    const bool al = (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+    auto px = [&](int l) -> unsigned char {
+        if (l < 0) return INV ? 1 : 0;
+        const int c = C[base + l];
+        return (INV ? c < size : c >= size) ? 1 : 0;
+    };
+    for (size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (size_t)gridDim.x * 1024) {
+        if (al && i0 + 3 < n && ((base + i0) & 3) == 0) {
+            const int4 l = *reinterpret_cast<const int4*>(L + base + i0);
+            uchar4 o;
+            o.x = px(l.x);
+            o.y = px(l.y);
+            o.z = px(l.z);
+            o.w = px(l.w);
+            *reinterpret_cast<uchar4*>(out + base + i0) = o;
+        } else {
+            for (size_t i = i0; i < n && i < i0 + 4; ++i) out[base + i] = px(L[base + i]);
+        }
+    }
+}
+
+int amt_i_area_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8, bool holes,
+                      int size) {
+    AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "area filter: plane too large");
+    AMT_REQUIRE(size >= 1, "area filter: the size must be at least 1");
+    const ccl_geom g = amt_i_ccl_geom(nplanes, H, W);
+    const size_t n = g.n;
+    // run tables where binary_fill_holes takes them (same limits)
+    const bool runs = amt_i_ccl_runs_ok(in, g) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && g.ntiles * 64 < 0x7fffffffull;
+    amt_scratch s(ctx);
+    amt_buf<int> L(s, (size_t)nplanes * n);  // union-find parents; the run tables only touch the tile roots' entries
+    amt_buf<int> C(s, (size_t)nplanes * n);  // pixel counts, at the tile roots (as binary_fill_holes' F)
+    amt_buf<int> rootlist(s, g.nlist * g.cap);
+    amt_buf<int> nroots(s, g.nlist);
+    amt_buf<unsigned long long> tbits(s, g.ntiles * 64, runs);
+    amt_buf<unsigned short> rtab(s, g.ntiles * RT_CAP, runs);
+    amt_buf<int> nruns(s, g.ntiles, runs);
+    AMT_TRY(s.commit());
+    AMT_HIP_CHECK(hipMemsetAsync(nroots, 0, g.nlist * sizeof(int), ctx->stream));
+    if (runs) {
+        amt_with_bool(c8, [&](auto C8) {
+            amt_with_bool(holes, [&](auto INV) {
+                hipLaunchKernelGGL((area_tile_runs_kernel<decltype(C8)::value, decltype(INV)::value>), g.gs, dim3(64), 0, ctx->stream,
+                                   in, L, C, H, W, rootlist, nroots, g.cap, tbits, rtab, nruns);
+            });
+        });
+        AMT_LAUNCH_CHECK();
+        AMT_TRY(ccl_seams_runs(ctx, g, c8, L, nullptr, tbits, rtab, nruns));
+    } else {
+        AMT_HIP_CHECK(hipMemsetAsync(C, 0, (size_t)nplanes * n * sizeof(int), ctx->stream));
+        int rc = AMT_OK;
+        amt_with_bool(c8, [&](auto C8) {
+            amt_with_bool(holes, [&](auto INV) {
+                rc = ccl_tileroots<uint8_t, decltype(C8)::value, decltype(INV)::value ? 1 : CCL_TRUTH>(ctx, g, in, L, rootlist, nroots);
+            });
+        });
+        AMT_TRY(rc);
+        hipLaunchKernelGGL(area_count_pixels_kernel, dim3(amt_grid_for(n, 256, 4096), nplanes), dim3(256), 0, ctx->stream, L, C, n);
+        AMT_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(area_roots_sum_kernel, g.glists, dim3(256), 0, ctx->stream, L, C, rootlist, nroots, g.cap, n);
+    AMT_LAUNCH_CHECK();
+    AMT_TRY(amt_i_propagate_roots(ctx, g, C, L, rootlist, nroots));
+    amt_with_bool(holes, [&](auto INV) {
+        if (runs) {
+            hipLaunchKernelGGL((area_expand_runs_kernel<decltype(INV)::value>), dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0,
+                               ctx->stream, tbits, rtab, nruns, C, out, H, W, g.segs, g.trows, (int)g.ntiles, size);
+        } else {
+            hipLaunchKernelGGL((area_write_kernel<decltype(INV)::value>), dim3(amt_grid_for(n, 1024, 4096), nplanes), dim3(256), 0,
+                               ctx->stream, L, C, out, n, size);
+        }
+    });
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }

@@ -227,15 +227,19 @@ static int build_offsets(const uint8_t* fp, int fh, int fw, int2* host, int* n) 
 }
 
 // op: AMT_MORPH_ERODE, AMT_MORPH_DILATE, AMT_MORPH_OPEN (erode then dilate), AMT_MORPH_CLOSE (dilate then erode),
-// AMT_MORPH_FILL_HOLES (amt_label.hip: amt_i_fill_holes)
+// AMT_MORPH_FILL_HOLES (amt_label.hip: amt_i_fill_holes), AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES (amt_label.hip:
+// amt_i_area_filter, the size in border_value)
 extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
                                 const uint8_t* footprint, int fh, int fw, int op, int border_value) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "binary morphology: bad arguments");
-    AMT_REQUIRE(op >= AMT_MORPH_ERODE && op <= AMT_MORPH_FILL_HOLES, "binary morphology: op must be 0..4, got %d", op);
-    if (op == AMT_MORPH_FILL_HOLES) {
+    AMT_REQUIRE(op >= AMT_MORPH_ERODE && op <= AMT_MORPH_REMOVE_SMALL_HOLES, "binary morphology: op must be 0..6, got %d", op);
+    if (op >= AMT_MORPH_FILL_HOLES) {
+        const bool fill = op == AMT_MORPH_FILL_HOLES;
+        const char* name = fill ? "fill_holes" : op == AMT_MORPH_REMOVE_SMALL_OBJECTS ? "remove_small_objects" : "remove_small_holes";
         // the two structures for which scipy's propagation from outside the image is "background components that hold
-        // no frame pixel": the 3 x 3 cross (4-connected background) and 3 x 3 all-ones (8-connected)
+        // no frame pixel": the 3 x 3 cross (4-connected background) and 3 x 3 all-ones (8-connected); the area filters
+        // take their connectivity from the same two
         int cells = 0;
         bool cross = footprint && fh == 3 && fw == 3;
         if (cross)
@@ -246,16 +250,18 @@ extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, i
         const bool full = footprint && fh == 3 && fw == 3 && cells == 9;
         cross = cross && cells == 5;
         AMT_REQUIRE(cross || full,
-                    "fill_holes: the structure must be the 3 x 3 cross (4-connected background) or 3 x 3 all-ones "
-                    "(8-connected background)");
+                    "%s: the structure must be the 3 x 3 cross (4-connected %s) or 3 x 3 all-ones "
+                    "(8-connected %s)", name, fill ? "background" : "components", fill ? "background" : "components");
+        AMT_REQUIRE(fill || border_value >= 1, "%s: the size (border_value) must be at least 1, got %d", name, border_value);
         if (nplanes == 0) return AMT_OK;
         {
             // any overlap of the two batches, not only out == in: a plane's write-out would land in input still to be read
             const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
             const size_t bytes = (size_t)nplanes * H * W;
-            AMT_REQUIRE(a + bytes <= b || b + bytes <= a, "fill_holes: out must not alias or overlap in");
+            AMT_REQUIRE(a + bytes <= b || b + bytes <= a, "%s: out must not alias or overlap in", name);
         }
-        return amt_i_fill_holes(ctx, in, out, nplanes, H, W, full);
+        if (fill) return amt_i_fill_holes(ctx, in, out, nplanes, H, W, full);
+        return amt_i_area_filter(ctx, in, out, nplanes, H, W, full, op == AMT_MORPH_REMOVE_SMALL_HOLES, border_value);
     }
     static thread_local int2 host[MAX_OFFS];
     int noffs = 0;

@@ -10,6 +10,7 @@ The functions mirror the scikit-image / scipy calls the reference makes (file:li
 from __future__ import annotations
 
 import ctypes
+import operator
 
 import numpy as np
 
@@ -503,7 +504,8 @@ def _fp(footprint, even: str = "scipy"):
     return np.ascontiguousarray(fp)
 
 
-_MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3, "fill_holes": 4}  # AMT_MORPH_*
+_MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3, "fill_holes": 4, "remove_small_objects": 5,
+              "remove_small_holes": 6}  # AMT_MORPH_*
 
 
 def _binary(which: str, a: DeviceArray, footprint, out, border_value=None):
@@ -576,6 +578,51 @@ def binary_fill_holes(a: DeviceArray, structure=None, out: DeviceArray | None = 
                                        _MORPH_OPS["fill_holes"], 0), "amt_binary_morph")
     o.is_bool = True
     return o
+
+
+def _area_filter(which: str, a: DeviceArray, size, connectivity, out) -> DeviceArray:
+    """Both area filters: every refusal comes before the first device call; the size travels in ``border_value``."""
+    if connectivity not in (1, 2):
+        raise ValueError(f"{which}: connectivity must be 1 (4-connected) or 2 (8-connected), got {connectivity!r}")
+    size = int(operator.index(size))
+    if a.dtype != np.uint8:
+        raise TypeError(f"{which} expects a uint8 / bool mask on the device")
+    if a.ndim not in (2, 3):
+        raise ValueError(f"{which} takes (H, W) or (N, H, W) masks, got shape {a.shape}")
+    ctx = a.ctx
+    n, H, W = _planes(a)
+    o = _out(ctx, out, a.shape, np.uint8)
+    if o is a or (a.nbytes and o.ptr < a.ptr + a.nbytes and a.ptr < o.ptr + o.nbytes):
+        raise ValueError(f"{which}: out must not alias (or overlap) the input")
+    o.is_bool = True
+    if a.size == 0:
+        return o
+    if size <= 1 and a.is_bool:
+        # nothing can be removed (no component has fewer than one pixel): the 0 / 1 mask as it is
+        _hip.check(_lib().amt_memcpy_d2d(ctx.handle, o.ptr, a.ptr, a.nbytes), "amt_memcpy_d2d")
+        return o
+    # a uint8 plane that is not known to hold 0 / 1 goes through the filter at size 1, which writes its truth values
+    size = min(max(size, 1), H * W + 1)  # beyond H * W every size removes everything alike
+    st = cross3() if connectivity == 1 else np.ones((3, 3), np.uint8)
+    _hip.check(_lib().amt_binary_morph(ctx.handle, a.ptr, o.ptr, n, H, W, st.ctypes.data_as(ctypes.c_void_p), 3, 3,
+                                       _MORPH_OPS[which], size), "amt_binary_morph")
+    return o
+
+
+def remove_small_objects(a: DeviceArray, min_size: int = 64, connectivity: int = 1,
+                         out: DeviceArray | None = None) -> DeviceArray:
+    """``skimage.morphology.remove_small_objects(a != 0, min_size, connectivity)`` per plane of a (H, W) or (N, H, W)
+    uint8 / bool mask: a foreground pixel stays when its component (``connectivity`` 1: 4-connected, 2: 8-connected) has
+    at least ``min_size`` pixels (amt_binary_morph, AMT_MORPH_REMOVE_SMALL_OBJECTS)."""
+    return _area_filter("remove_small_objects", a, min_size, connectivity, out)
+
+
+def remove_small_holes(a: DeviceArray, area_threshold: int = 64, connectivity: int = 1,
+                       out: DeviceArray | None = None) -> DeviceArray:
+    """``skimage.morphology.remove_small_holes(a != 0, area_threshold, connectivity)`` per plane: a background pixel is
+    filled when its background component has fewer than ``area_threshold`` pixels, whether or not the component touches
+    the frame (amt_binary_morph, AMT_MORPH_REMOVE_SMALL_HOLES)."""
+    return _area_filter("remove_small_holes", a, area_threshold, connectivity, out)
 
 
 def threshold_otsu_bins(a: DeviceArray, minmax: DeviceArray, thr: DeviceArray, thr_code: DeviceArray,

@@ -38,7 +38,7 @@ class MaskBatcher:
     times: dict | None = None  # set to {} to collect where a call's host time goes (tools/masks_profile.py)
 
     def __init__(self, B: int, C: int, H: int, W: int, *, nuclear: int, sigma: float, radius: int, min_distance: int,
-                 ctx: Context, fill_holes: bool = False):
+                 ctx: Context, fill_holes: bool = False, min_size: int = 0):
         from .feeder import FovFeeder
         from .device import pinned_empty
         from .plate import packed_ncols
@@ -47,7 +47,8 @@ class MaskBatcher:
         self.B, self.C, self.H, self.W, self.ctx = B, C, H, W, ctx
         self.K = max(4096, (H * W) // 256)
         self.seg = FovSegmenter(B, C, H, W, sigma=sigma, radius=radius, min_distance=min_distance, max_cells=self.K,
-                                dapi_index=nuclear, ctx=ctx, props=True, fused=True, fill_holes=fill_holes)
+                                dapi_index=nuclear, ctx=ctx, props=True, fused=True, fill_holes=fill_holes,
+                                min_size=min_size)
         self.feeder = FovFeeder((B, C, H, W), ctx.device)
         for slot in range(2):
             self.feeder.host(slot)[...] = 0  # a short chunk leaves the rest of its block as it was: blank at first

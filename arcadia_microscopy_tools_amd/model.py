@@ -80,6 +80,9 @@ class SegmentationModel:
     sigma: float = 2.0
     opening_radius: int = 2
     network: Any = field(default=None, repr=False)
+    # classical backend: nuclei-mask components (4-connected) below this many pixels are removed before the EDT;
+    # keyword-only, so the positional order of the fields is what it was
+    min_size: int = field(default=0, kw_only=True)
     compute_dtype: str = "bf16"
     fill_holes: bool = False  # classical backend: scipy.ndimage.binary_fill_holes between the closing and the EDT
     _model: Any = field(default=None, init=False, repr=False)
@@ -93,6 +96,12 @@ class SegmentationModel:
         if self.fill_holes and self.backend != "classical":
             raise ValueError(f"fill_holes=True applies to backend='classical' only (the Cellpose route fills holes "
                              f"itself), got backend '{self.backend}'")
+        if isinstance(self.min_size, bool) or not isinstance(self.min_size, (int, np.integer)) or self.min_size < 0:
+            raise ValueError(f"min_size must be a non-negative int, got {self.min_size!r}")
+        self.min_size = int(self.min_size)
+        if self.min_size and self.backend != "classical":
+            raise ValueError(f"min_size= on the model applies to backend='classical' only (the Cellpose routes take "
+                             f"min_size as an eval option of segment / batch_segment), got backend '{self.backend}'")
         if self.device is None and self.backend in ("cellpose", "cellpose-hip"):
             self.device = self.find_best_available_device()
 
@@ -218,6 +227,8 @@ class SegmentationModel:
         m1 = hipops.binary_closing(hipops.binary_opening(m0, fp), fp)
         if self.fill_holes:
             m1 = hipops.binary_fill_holes(m1)
+        if self.min_size > 1:
+            m1 = hipops.remove_small_objects(m1, self.min_size, connectivity=1)
         d2, _ = hipops.edt(m1, want_edt=False)
         min_distance = max(1, int(round(params["diameter"] / 6.0)))
         peaks = hipops.peak_mask(d2, m1, min_distance)
@@ -293,12 +304,12 @@ class SegmentationModel:
         out: list = []
         for i0 in range(0, len(arrs), chunk):
             part = arrs[i0:i0 + chunk]
-            key = (len(part), H, W, min_distance, self.sigma, self.opening_radius, self.fill_holes, id(ctx))
+            key = (len(part), H, W, min_distance, self.sigma, self.opening_radius, self.fill_holes, self.min_size, id(ctx))
             seg = getattr(cache, "seg", None)
             if seg is None or getattr(cache, "key", None) != key:
                 seg = FovSegmenter(len(part), 1, H, W, sigma=self.sigma, radius=self.opening_radius,
                                    min_distance=min_distance, max_cells=max(4096, (H * W) // 64), dapi_index=0, ctx=ctx,
-                                   props=False, fused=False, fill_holes=self.fill_holes)
+                                   props=False, fused=False, fill_holes=self.fill_holes, min_size=self.min_size)
                 cache.seg, cache.key = seg, key
                 cache.inp = ctx.empty((len(part), 1, H, W), np.uint16)
             for j, a in enumerate(part):  # each plane converted on its way through the page-locked staging buffer
@@ -384,13 +395,13 @@ class SegmentationModel:
         min_distance = max(1, int(round(params["diameter"] / 6.0)))
         chunk = max(1, min(int(params["batch_size"]), len(images)))
         cache = self.__dict__.setdefault("_mask_cache", threading.local())
-        key = (chunk, C, H, W, nuclear, min_distance, self.sigma, self.opening_radius, self.fill_holes, id(ctx))
+        key = (chunk, C, H, W, nuclear, min_distance, self.sigma, self.opening_radius, self.fill_holes, self.min_size, id(ctx))
         mb = getattr(cache, "mb", None)
         if mb is None or cache.key != key:
             if mb is not None:
                 mb.close()
             mb = MaskBatcher(chunk, C, H, W, nuclear=nuclear, sigma=self.sigma, radius=self.opening_radius,
-                             min_distance=min_distance, ctx=ctx, fill_holes=self.fill_holes)
+                             min_distance=min_distance, ctx=ctx, fill_holes=self.fill_holes, min_size=self.min_size)
             cache.mb, cache.key = mb, key
         return mb.run(images)
 

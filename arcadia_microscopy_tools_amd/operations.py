@@ -262,6 +262,50 @@ def binary_fill_holes(mask, structure=None):
     return hipops.binary_fill_holes(d, st).numpy()
 
 
+def _area_filter_2d(which: str, mask, size, connectivity, integer_hint: str):
+    """The 2-D front of both area filters: numpy bool in, numpy bool out; a ``DeviceArray`` stays on the device."""
+    fn = getattr(hipops, which)
+    if connectivity not in (1, 2):
+        raise ValueError(f"{which}: connectivity must be 1 (4-connected) or 2 (8-connected), got {connectivity!r}")
+    if isinstance(mask, DeviceArray):
+        if mask.ndim != 2:
+            raise ValueError("mask must be a 2D array")
+        if mask.dtype != np.uint8:
+            raise TypeError(f"{which}: device masks must be uint8 / bool, got {mask.dtype}")
+        return fn(mask, size, connectivity)
+    a = np.asarray(mask)
+    if a.ndim != 2:
+        raise ValueError("mask must be a 2D array")
+    if a.dtype != np.bool_:
+        if np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"{which}: scikit-image treats an integer array as a label image and filters it by label "
+                            f"value, which this operator does not do; {integer_hint}")
+        raise TypeError(f"{which}: mask must have a bool dtype, got {a.dtype}")
+    if a.size == 0:
+        return np.zeros(a.shape, dtype=bool)
+    return fn(get_context().asarray(np.ascontiguousarray(a)), size, connectivity).numpy()
+
+
+@device_operator
+def remove_small_objects(mask, min_size: int = 64, connectivity: int = 1):
+    """``skimage.morphology.remove_small_objects(mask, min_size, connectivity)`` on a 2-D bool mask: foreground
+    components (``connectivity`` 1: 4-connected, 2: 8-connected) with fewer than ``min_size`` pixels are removed.  A
+    numpy bool array gives a numpy bool array; a ``DeviceArray`` (a uint8 / bool mask, e.g. ``apply_threshold``'s result
+    in a ``Pipeline``) stays on the device.  Integer numpy arrays are refused: scikit-image filters those by label
+    value -- for label images use ``SegmentationMask.filter("area", ...)``.  Stacks are refused rather than treated as
+    volumes: map planes with ``Pipeline(parallel=True)`` or call ``hipops.remove_small_objects``."""
+    return _area_filter_2d("remove_small_objects", mask, min_size, connectivity,
+                           'for label images use SegmentationMask.filter("area", ...), for masks pass a bool array')
+
+
+@device_operator
+def remove_small_holes(mask, area_threshold: int = 64, connectivity: int = 1):
+    """``skimage.morphology.remove_small_holes(mask, area_threshold, connectivity)`` on a 2-D bool mask: background
+    components with fewer than ``area_threshold`` pixels are filled, those on the image's frame included.  Types,
+    connectivity and stacks as for ``remove_small_objects``; integer numpy arrays are refused, pass a bool array."""
+    return _area_filter_2d("remove_small_holes", mask, area_threshold, connectivity, "pass a bool array (mask != 0)")
+
+
 def _global_threshold(d: DeviceArray, method: str, kwargs: dict) -> float:
     """Threshold VALUE for the histogram-based methods: histogram on the device, selection on <= 65,536 counts."""
     nbins = int(kwargs.pop("nbins", 256))

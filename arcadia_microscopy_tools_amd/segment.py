@@ -2,7 +2,8 @@
 
 Stages (CPU restatement: oracle/chains.py):
   C2  Gaussian(sigma) -> Otsu -> '>' -> binary opening(disk r) -> binary closing(disk r) -> label (8-conn)
-  C3  C2 mask on the DAPI channel [-> binary_fill_holes if fill_holes=True] -> EDT -> peak markers (min_distance) -> watershed (seeded relief)
+  C3  C2 mask on the DAPI channel [-> binary_fill_holes if fill_holes=True] [-> remove_small_objects if min_size > 1]
+      -> EDT -> peak markers (min_distance) -> watershed (seeded relief)
       -> clear_border -> relabel_sequential -> morphology table + per-channel intensity table
 
 ``FovSegmenter`` preallocates every buffer for a batch of B fields of view, enqueues the whole chain
@@ -47,7 +48,8 @@ class FovSegmenter:
     def __init__(self, batch: int, C: int, H: int, W: int, *, sigma: float = 2.0, radius: int = 2,
                  min_distance: int = 5, max_cells: int = 4096, dapi_index: int = 1, ctx: Context | None = None,
                  props: bool = True, profile: bool = False, fused: bool = True, low_traffic: bool = False, bin_plane: bool = True,
-                 prefix_plane: bool = True, relief: str = "seeded", ties: str = "exact", fill_holes: bool = False):
+                 prefix_plane: bool = True, relief: str = "seeded", ties: str = "exact", fill_holes: bool = False,
+                 min_size: int = 0):
         self.ctx = ctx or get_context()
         self.B, self.C, self.H, self.W = int(batch), int(C), int(H), int(W)
         self.sigma, self.radius, self.min_distance = float(sigma), int(radius), int(min_distance)
@@ -80,6 +82,12 @@ class FovSegmenter:
         # fill_holes: scipy.ndimage.binary_fill_holes (cross structure) between the closing and the EDT, so that a
         # nucleus whose dim centre left a ring in the mask is one basin, not arcs; the filled mask lands in mask_b
         self.fill_holes = bool(fill_holes)
+        # min_size > 1: skimage.morphology.remove_small_objects (4-connected, as the watershed's own mask labelling) after
+        # the closing and the hole filling, before the EDT: debris that survived the opening gets no peak, no marker, no
+        # basin and no feature row.  Written to the other of mask_a / mask_b; 0 (the default) launches nothing
+        if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 0:
+            raise ValueError(f"min_size must be a non-negative int, got {min_size!r}")
+        self.min_size = int(min_size)
         self.footprint = hipops.disk(self.radius)
         c, B = self.ctx, self.B
         shp = (B, self.H, self.W)
@@ -173,12 +181,17 @@ class FovSegmenter:
         return self.mask_a
 
     def _mask(self, fovs: DeviceArray) -> DeviceArray:
-        """``mask_chain``, and with ``fill_holes`` its result filled into ``mask_b``: what the stages downstream use."""
+        """``mask_chain``, with ``fill_holes`` its result filled into ``mask_b``, with ``min_size`` the small components
+        removed into the other of the two mask buffers: what the stages downstream use."""
         mask = self.mask_chain(fovs)
-        if not self.fill_holes:
-            return mask
-        self._stage("fill_holes")
-        return hipops.binary_fill_holes(mask, out=self.mask_b)
+        if self.fill_holes:
+            self._stage("fill_holes")
+            mask = hipops.binary_fill_holes(mask, out=self.mask_b)
+        if self.min_size > 1:
+            self._stage("remove_small")
+            mask = hipops.remove_small_objects(mask, self.min_size, connectivity=1,
+                                               out=self.mask_a if mask is self.mask_b else self.mask_b)
+        return mask
 
     @property
     def gauss(self) -> DeviceArray:

@@ -244,12 +244,26 @@ int amt_threshold_gt_image(amt_ctx* ctx, const void* in, int in_dtype, const dou
  *                     component rule).  border_value is ignored.  out must not alias in, nor overlap it in part
  *                     (AMT_EINVAL); nplanes == 0 is
  *                     AMT_OK; H * W < 2^31 - 1 as for amt_label.
- * Any other op is AMT_EINVAL. */
+ *   AMT_MORPH_REMOVE_SMALL_OBJECTS  skimage.morphology.remove_small_objects(in != 0, min_size=s, connectivity) per
+ *                     plane: out[p] = 1 iff in[p] != 0 and the foreground component of p has at least s pixels;
+ *   AMT_MORPH_REMOVE_SMALL_HOLES    skimage.morphology.remove_small_holes(in != 0, area_threshold=s, connectivity)
+ *                     per plane: out[p] = 1 iff in[p] != 0 or the background component of p has fewer than s pixels --
+ *                     unlike AMT_MORPH_FILL_HOLES this includes background components that touch the frame.
+ *                     For both: `in` is a truth value (byte != 0) and `out` holds 0 / 1 bytes, as for
+ *                     AMT_MORPH_FILL_HOLES; the size s travels in border_value, and s < 1 is AMT_EINVAL (a filter that
+ *                     can remove nothing is not an operation).  Components are 4-connected for the 3 x 3 cross
+ *                     (scikit-image's connectivity=1) and 8-connected for the 3 x 3 all-ones footprint
+ *                     (connectivity=2); any other footprint is AMT_EINVAL.  out must not alias in, nor overlap it in
+ *                     part (AMT_EINVAL); nplanes == 0 is AMT_OK; H * W < 2^31 - 1.  Sizes are exact pixel counts
+ *                     (integer sums), so two runs give identical bytes.
+ * Any other op (below 0, above 6) is AMT_EINVAL. */
 #define AMT_MORPH_ERODE 0
 #define AMT_MORPH_DILATE 1
 #define AMT_MORPH_OPEN 2
 #define AMT_MORPH_CLOSE 3
 #define AMT_MORPH_FILL_HOLES 4
+#define AMT_MORPH_REMOVE_SMALL_OBJECTS 5
+#define AMT_MORPH_REMOVE_SMALL_HOLES 6
 int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
                      const uint8_t* footprint, int fh, int fw, int op, int border_value);
 /* Otsu threshold of a float64 image (as amt_threshold_value) that also leaves the byte plane of its 256-bin indices
