@@ -117,6 +117,12 @@ constexpr int RT_CAP = 2048;  // 64 rows x at most 32 runs
 static inline bool amt_i_ccl_runs_ok(const void* in, const ccl_geom& g) {
     return g.W % 16 == 0 && (reinterpret_cast<uintptr_t>(in) & 15) == 0 && g.n % 16 == 0;
 }
+// ... and of an operation that expands the tables into planes at `out`, 16 bytes per lane (amt_label, the component
+// filters).  The limit keeps the row-word index t * 64 + row of tbits, and with it the tile count the expansion takes,
+// inside an int
+static inline bool amt_i_ccl_runs_out_ok(const void* in, const void* out, const ccl_geom& g) {
+    return amt_i_ccl_runs_ok(in, g) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && g.ntiles * 64 < 0x7fffffffull;
+}
 // The watershed's labelling of its mask from run tables alone: 4-connected components of the NON-ZERO bytes; L is written
 // at the tile roots only (L[root] = root, then the seams' unions), the tile roots are listed as amt_i_ccl_tileroots_u8
 // lists them
@@ -135,16 +141,17 @@ struct amt_runtabs {
 // with one hop through its tile root
 int amt_i_propagate_roots(amt_ctx* ctx, const ccl_geom& g, int* A, const int* L, const int* rootlist, const int* nroots);
 
-// scipy.ndimage.binary_fill_holes of nplanes truth-value masks (amt_binary_morph's AMT_MORPH_FILL_HOLES, which checks
-// the arguments): out = in != 0, or a background pixel whose 4-connected (c8: 8-connected) background component holds no
-// pixel of the 1-pixel frame.  out must not alias in.
-int amt_i_fill_holes(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8);
-// The area filters of nplanes truth-value masks (amt_binary_morph's AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES, which
-// checks the arguments; size >= 1).  holes == false: out = in != 0 and the pixel's 4-connected (c8: 8-connected)
-// foreground component has at least `size` pixels; holes == true: out = in != 0, or the pixel's background component
-// has fewer than `size` pixels.  out must not alias in.
-int amt_i_area_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8, bool holes,
-                      int size);
+// The component filters of nplanes truth-value masks (amt_binary_morph's AMT_MORPH_FILL_HOLES and
+// AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES, which checks the arguments).  With "component" the pixel's 4-connected (c8:
+// 8-connected) component of its own polarity:
+//   objects by area   out = in != 0 and the component has at least `size` pixels (size >= 1);
+//   holes by area     out = in != 0, or the background component has fewer than `size` pixels (size >= 1);
+//   holes by frame    scipy.ndimage.binary_fill_holes: out = in != 0, or the background component holds no pixel of the
+//                     1-pixel frame (size must be 1).
+// out must not alias in.
+enum amt_comp_what { AMT_COMP_OBJECTS_BY_AREA, AMT_COMP_HOLES_BY_AREA, AMT_COMP_HOLES_BY_FRAME };
+int amt_i_component_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8,
+                           amt_comp_what what, int size);
 
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>

@@ -1006,10 +1006,8 @@ static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, 
     const ccl_geom g = amt_i_ccl_geom(nplanes, H, W);
     const size_t n = g.n;
     const bool c8 = connectivity == 2;
-    // 0 / 1 masks: run tables instead of a parent plane.  The limit keeps the row-word index t * 64 + row of tbits, and
-    // with it the tile count the expansion takes, inside an int
-    const bool runs = in_dtype == AMT_U8 && amt_i_ccl_runs_ok(in, g) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 &&
-                      g.ntiles * 64 < 0x7fffffffull;
+    // 0 / 1 masks: run tables instead of a parent plane
+    const bool runs = in_dtype == AMT_U8 && amt_i_ccl_runs_out_ok(in, out, g);
     // union-find parents L, ranks T, the lists of tile-local roots (one list per tile row; components are sets of
     // EQUAL-valued pixels, so every pixel can be a root of its own), per-chunk root counts
     amt_scratch s(ctx);
@@ -1154,18 +1152,23 @@ extern "C" int amt_clear_border(amt_ctx* ctx, const int32_t* in, int32_t* out, i
     return AMT_OK;
 }
 
-// ---- binary_fill_holes -----------------------------------------------------------------------------------------------
-// scipy.ndimage.binary_fill_holes for the 3 x 3 cross and the 3 x 3 all-ones structure: a hole is a component of the
-// BACKGROUND (4- resp. 8-connected) that holds no pixel of the 1-pixel frame.  The component analysis is amt_label's, run
-// on the complement, but the result is a set: no raster numbering, no scan, no int32 plane.
-//   tile pass   run tables of the complement (fill_tile_runs_kernel: the byte plane is read once, inverted in registers)
-//               or, for widths / addresses the run tables refuse, the byte union-find with the test inverted in the load;
-//               F[tile root] = 1 where a pixel of the tile root's tile-local component lies on the frame;
+// ---- component filters: binary_fill_holes, remove_small_objects / remove_small_holes ------------------------------------
+// scipy.ndimage.binary_fill_holes (3 x 3 cross or all-ones structure) and skimage.morphology.remove_small_objects /
+// remove_small_holes on truth-value masks are one scheme: amt_label's component analysis of one polarity of the mask (the
+// foreground, or the complement, taken in registers) with an integer PAYLOAD per component where amt_label numbers them
+// -- the result is a set: no raster numbering, no scan, no int32 label plane.
+//   tile pass   run tables (comp_tile_runs_kernel: the byte plane is read once); the payload of every tile-local component
+//               is gathered in LDS and stored at its tile root, P[tile root]; or, for widths / addresses the run tables
+//               refuse, the byte union-find followed by a kernel that derives the payloads from the pixels;
 //   seams       as for amt_label;
-//   flags       fill_roots_flag_kernel compresses the listed tile roots and raises F at the component root of every
-//               flagged tile root; the next launch (amt_i_propagate_roots) copies the component's flag back to them;
-//   write-out   original bit OR (background AND the component is unflagged), as bytes.
-// Workgroups exchange data between launches only; F is only ever raised (0 -> 1), so no result depends on an order.
+//   sums        comp_roots_sum_kernel compresses the listed tile roots and adds the payload of every tile root that a seam
+//               hung below another into the component root's; the next launch (amt_i_propagate_roots) copies the total
+//               back to them;
+//   write-out   objects: bit AND payload >= size; holes: bit OR (background AND payload < size), as bytes.
+// The payloads: the component's pixels for the area filters (general path: area_count_pixels_kernel; holes that touch
+// the frame count like any other); for fill holes 1 where a pixel of the tile root's component lies on the 1-pixel frame
+// (general path: frame_flag_kernel), so the total is the number of flagged tile roots, and the holes are size = 1's.
+// Workgroups exchange data between launches only; the payloads are integer sums, so no result depends on an order.
 
 // a run's pixels as a word: the run that starts at bit b of w
 __device__ __forceinline__ unsigned long long ccl_run_mask(unsigned long long w, int b) {
@@ -1174,252 +1177,23 @@ __device__ __forceinline__ unsigned long long ccl_run_mask(unsigned long long w,
     return (len >= 64 ? ~0ull : ((1ull << len) - 1ull)) << b;
 }
 
-template <bool CONN8>
-__global__ void __launch_bounds__(64) fill_tile_runs_kernel(const uint8_t* __restrict__ in, int* __restrict__ Lall,
-                                                            int* __restrict__ Fall, int H, int W, int* __restrict__ rootlist,
+// WHAT: an amt_comp_what; pay, per run id, for the tile-local component the run roots: a byte for the frame flag (10 KB of
+// LDS with S), an int for the count (16 KB)
+template <bool CONN8, int WHAT>
+__global__ void __launch_bounds__(64) comp_tile_runs_kernel(const uint8_t* __restrict__ in, int* __restrict__ Lall,
+                                                            int* __restrict__ Pall, int H, int W, int* __restrict__ rootlist,
                                                             int* __restrict__ nroots, size_t cap,
                                                             unsigned long long* __restrict__ tbits,
                                                             unsigned short* __restrict__ rtab, int* __restrict__ nruns) {
+    constexpr bool INV = WHAT != AMT_COMP_OBJECTS_BY_AREA, FRAME = WHAT == AMT_COMP_HOLES_BY_FRAME;
     __shared__ int S[64 * 32];
-    __shared__ unsigned char touch[64 * 32];  // per run id: a run of the component it roots lies on the frame
+    __shared__ std::conditional_t<FRAME, unsigned char, int> pay[64 * 32];
     const size_t n = (size_t)H * W;
     const uint8_t* img = in + (size_t)blockIdx.z * n;
     int* L = Lall + (size_t)blockIdx.z * n;
-    int* F = Fall + (size_t)blockIdx.z * n;
+    int* P = Pall + (size_t)blockIdx.z * n;
     const int lane = threadIdx.x;
-    const int x0 = blockIdx.x * 64, ty0 = blockIdx.y * 64;
-    const int y = ty0 + lane;
-    const size_t tile = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    // the complement, inside the plane only: columns from W on and rows from H on are nobody's background
-    const int wcols = W - x0;  // > 0
-    const unsigned long long valid = wcols >= 64 ? ~0ull : ((1ull << wcols) - 1ull);
-    unsigned other;
-    const unsigned long long fg = ccl_bits_load_row<true>(img, H, W, x0, y, other);
-    const unsigned long long w = y < H ? (~fg & valid) : 0ull;
-    tbits[tile * 64 + lane] = w;
-    const unsigned long long heads = w & ~(w << 1);
-    const int nroot = ccl_bits_unionfind<CONN8>(S, w, heads, lane);
-    // the frame's pixels of this row
-    unsigned long long fr = (y == 0 || y == H - 1) ? valid : 0ull;
-    if (x0 == 0) fr |= 1ull;
-    if (wcols <= 64) fr |= 1ull << (wcols - 1);
-    {
-        int j = 0;
-        for (unsigned long long h = heads; h; h &= h - 1, ++j) touch[lane * 32 + j] = 0;
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    if (w & fr) {
-        int j = 0;
-        for (unsigned long long h = heads; h; h &= h - 1, ++j) {
-            const int b = __ffsll((long long)h) - 1;
-            if (ccl_run_mask(w, b) & fr) touch[S[lane * 32 + j] >> 6] = 1;  // lanes only ever store 1 here
-        }
-    }
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    // run table, tile roots (L[root] = root, F[root] = its flag) and the tile's slice of its tile row's root list
-    const int cnt = __popcll(heads);
-    const int incl = ccl_wave_incl_scan(cnt, lane);
-    const int rincl = ccl_wave_incl_scan(nroot, lane);
-    const int tot = __shfl(rincl, 63);
-    int base = 0;
-    if (lane == 0 && tot) base = atomicAdd(&nroots[blockIdx.z * gridDim.y + blockIdx.y], tot);
-    size_t pos = (size_t)__builtin_amdgcn_readfirstlane(base) + (rincl - nroot);
-    unsigned short* rt = rtab + tile * RT_CAP + (incl - cnt);
-    int j = 0;
-    for (unsigned long long h = heads; h; h &= h - 1, ++j) {
-        const int own = lane * 32 + j;
-        const int e = S[own];
-        rt[j] = (unsigned short)(((e >> 11) << 6) | (e & 63));
-        if ((e >> 6) == own) {
-            const int pix = y * W + x0 + (e & 63);
-            L[pix] = pix;
-            F[pix] = touch[own];
-            if (pos < cap) rootlist[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * cap + pos] = pix;
-            ++pos;
-        }
-    }
-    if (lane == 63) nruns[tile] = incl;
-}
-
-// compress the listed tile roots (L[t] = component root) and raise the component root's flag for every flagged tile
-// root.  F is read at tile roots that are not component roots and written at component roots: no entry is both.
-__global__ void __launch_bounds__(256) fill_roots_flag_kernel(int* __restrict__ Lall, int* __restrict__ Fall,
-                                                              const int* __restrict__ rootlist,
-                                                              const int* __restrict__ nroots, size_t cap, size_t n) {
-    const int plane = blockIdx.z, shard = plane * gridDim.y + blockIdx.y;
-    int* L = Lall + (size_t)plane * n;
-    int* F = Fall + (size_t)plane * n;
-    const int cnt = nroots[shard] < (int)cap ? nroots[shard] : (int)cap;
-    const int* lst = rootlist + (size_t)shard * cap;
-    for (int k = blockIdx.x * 256 + threadIdx.x; k < cnt; k += gridDim.x * 256) {
-        const int t = lst[k];
-        const int r = roots_compress_one(L, t);
-        if (r != t && F[t]) F[r] = 1;
-    }
-}
-
-// four pixels of a word as 0 / 1 bytes
-__device__ __forceinline__ unsigned fill_spread4(unsigned nib) { return (nib * 0x00204081u) & 0x01010101u; }
-
-// the filled mask from (complement row words, run table, F at the tile roots): a wave per tile, four tiles (neighbours in
-// a tile row, so that a workgroup's stores of a row are 256 contiguous bytes) per workgroup; a lane gathers the flags of
-// its share of the runs, ORs the unflagged runs of its row into the original bits, and stores 16 pixels at a time
-__global__ void __launch_bounds__(256) fill_expand_runs_kernel(const unsigned long long* __restrict__ tbits,
-                                                               const unsigned short* __restrict__ rtab,
-                                                               const int* __restrict__ nruns, const int* __restrict__ Fall,
-                                                               uint8_t* __restrict__ outall, int H, int W, int segs,
-                                                               int trows, int ntiles) {
-    __shared__ unsigned char hole_s[4][RT_CAP];
-    __shared__ unsigned long long bits_s[4][64];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int t = blockIdx.x * 4 + wv;
-    if (t >= ntiles) return;  // whole wave
-    const int bx = t % segs, ty = (t / segs) % trows, plane = t / (segs * trows);
-    const size_t n = (size_t)H * W;
-    const int* F = Fall + (size_t)plane * n;
-    uint8_t* out = outall + (size_t)plane * n;
-    const int x0 = bx * 64, ty0 = ty * 64;
-    const int nr = nruns[t];
-    const unsigned long long w = tbits[(size_t)t * 64 + lane];
-    unsigned long long fill = 0;
-    if (nr) {  // uniform: a tile without background has nothing to look up
-        for (int k = lane; k < nr; k += 64) hole_s[wv][k] = F[ccl_rt_root(rtab, (size_t)t, k, ty, bx, W)] == 0;
-        const unsigned long long heads = w & ~(w << 1);
-        const int cnt = __popcll(heads);
-        const int off = ccl_wave_incl_scan(cnt, lane) - cnt;
-        __builtin_amdgcn_s_waitcnt(0);
-        __builtin_amdgcn_wave_barrier();
-        int j = 0;
-        for (unsigned long long h = heads; h; h &= h - 1, ++j)
-            if (hole_s[wv][off + j]) fill |= ccl_run_mask(w, __ffsll((long long)h) - 1);
-    }
-    bits_s[wv][lane] = ~w | fill;  // bits beyond the plane are set and never stored
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    const int c16 = (lane & 3) * 16, rsub = lane >> 2;
-    const int xg = x0 + c16;
-    if (xg >= W) return;  // W % 16 == 0: the sixteen pixels are inside the plane together
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = rsub + 16 * j;
-        const int y = ty0 + row;
-        const unsigned s16 = (unsigned)(bits_s[wv][row] >> c16) & 0xFFFFu;
-        uint4 q;
-        q.x = fill_spread4(s16 & 15u);
-        q.y = fill_spread4((s16 >> 4) & 15u);
-        q.z = fill_spread4((s16 >> 8) & 15u);
-        q.w = fill_spread4(s16 >> 12);
-        if (y < H) *reinterpret_cast<uint4*>(out + (size_t)y * W + xg) = q;
-    }
-}
-
-// the general path's write-out: L[p] < 0 = foreground of the input; otherwise p's tile root carries its component's flag
-__global__ void __launch_bounds__(256) fill_write_kernel(const int* __restrict__ L, const int* __restrict__ F,
-                                                         uint8_t* __restrict__ out, size_t n) {
-    const size_t base = (size_t)blockIdx.y * n;
-    const bool al = (reinterpret_cast<uintptr_t>(out) & 3) == 0;
-    for (size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (size_t)gridDim.x * 1024) {
-        if (al && i0 + 3 < n && ((base + i0) & 3) == 0) {
-            const int4 l = *reinterpret_cast<const int4*>(L + base + i0);
-            uchar4 o;
-            o.x = (l.x < 0 || F[base + l.x] == 0) ? 1 : 0;
-            o.y = (l.y < 0 || F[base + l.y] == 0) ? 1 : 0;
-            o.z = (l.z < 0 || F[base + l.z] == 0) ? 1 : 0;
-            o.w = (l.w < 0 || F[base + l.w] == 0) ? 1 : 0;
-            *reinterpret_cast<uchar4*>(out + base + i0) = o;
-        } else {
-            for (size_t i = i0; i < n && i < i0 + 4; ++i) {
-                const int l = L[base + i];
-                out[base + i] = (l < 0 || F[base + l] == 0) ? 1 : 0;
-            }
-        }
-    }
-}
-
-int amt_i_fill_holes(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8) {
-    AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "fill_holes: plane too large");
-    const ccl_geom g = amt_i_ccl_geom(nplanes, H, W);
-    const size_t n = g.n;
-    // run tables of the complement where amt_label would take them for the mask itself (same limits)
-    const bool runs = amt_i_ccl_runs_ok(in, g) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && g.ntiles * 64 < 0x7fffffffull;
-    amt_scratch s(ctx);
-    amt_buf<int> L(s, (size_t)nplanes * n);  // union-find parents; the run tables only touch the tile roots' entries
-    // "touches the frame", at the tile roots.  Like L a whole int32 plane of the arena of which the run-table path touches
-    // only the tile roots' entries (no traffic, but 4 B/px of reservation that amt_label does not need): flags indexed by
-    // the position in the root lists, or a bit of L, would do without it -- not done, the tile roots are addressed by
-    // pixel everywhere else (rtab, amt_i_propagate_roots)
-    amt_buf<int> F(s, (size_t)nplanes * n);
-    amt_buf<int> rootlist(s, g.nlist * g.cap);
-    amt_buf<int> nroots(s, g.nlist);
-    amt_buf<unsigned long long> tbits(s, g.ntiles * 64, runs);
-    amt_buf<unsigned short> rtab(s, g.ntiles * RT_CAP, runs);
-    amt_buf<int> nruns(s, g.ntiles, runs);
-    AMT_TRY(s.commit());
-    AMT_HIP_CHECK(hipMemsetAsync(nroots, 0, g.nlist * sizeof(int), ctx->stream));
-    if (runs) {
-        amt_with_bool(c8, [&](auto C8) {
-            hipLaunchKernelGGL((fill_tile_runs_kernel<decltype(C8)::value>), g.gs, dim3(64), 0, ctx->stream, in, L, F, H, W, rootlist,
-                               nroots, g.cap, tbits, rtab, nruns);
-        });
-        AMT_LAUNCH_CHECK();
-        AMT_TRY(ccl_seams_runs(ctx, g, c8, L, nullptr, tbits, rtab, nruns));
-    } else {
-        AMT_HIP_CHECK(hipMemsetAsync(F, 0, (size_t)nplanes * n * sizeof(int), ctx->stream));
-        int rc = AMT_OK;
-        amt_with_bool(c8, [&](auto C8) {
-            rc = ccl_tileroots<uint8_t, decltype(C8)::value, true>(ctx, g, in, L, rootlist, nroots);
-        });
-        AMT_TRY(rc);
-        // every pixel points at a tile root of its component here (its own, or for a tile root that a seam hung below
-        // another, that one): the frame's pixels flag those
-        hipLaunchKernelGGL(frame_flag_kernel, dim3(amt_grid_for((size_t)2 * W + 2 * H, 256, 64), nplanes), dim3(256), 0,
-                           ctx->stream, L, F, H, W);
-        AMT_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(fill_roots_flag_kernel, g.glists, dim3(256), 0, ctx->stream, L, F, rootlist, nroots, g.cap, n);
-    AMT_LAUNCH_CHECK();
-    AMT_TRY(amt_i_propagate_roots(ctx, g, F, L, rootlist, nroots));
-    if (runs) {
-        hipLaunchKernelGGL(fill_expand_runs_kernel, dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0, ctx->stream, tbits, rtab,
-                           nruns, F, out, H, W, g.segs, g.trows, (int)g.ntiles);
-    } else {
-        hipLaunchKernelGGL(fill_write_kernel, dim3(amt_grid_for(n, 1024, 4096), nplanes), dim3(256), 0, ctx->stream, L, F, out, n);
-    }
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
-}
-
-// ---- remove_small_objects / remove_small_holes ------------------------------------------------------------------------
-// skimage.morphology.remove_small_objects / remove_small_holes on truth-value masks: binary_fill_holes' component
-// analysis with a pixel COUNT where that one keeps a flag.  INV selects the polarity (false: the components of the
-// foreground, the objects; true: those of the complement, taken in registers, the holes -- frame-touching ones included).
-//   tile pass   run tables (area_tile_runs_kernel): the run lengths of every tile-local component are summed in LDS, an
-//               int per run id, and stored at the tile root, C[tile root]; or, for widths / addresses the run tables
-//               refuse, the byte union-find followed by area_count_pixels_kernel, which counts the pixels themselves;
-//   seams       as for amt_label;
-//   sums        area_roots_sum_kernel compresses the listed tile roots and adds the count of every tile root that a seam
-//               hung below another into the component root's; the next launch (amt_i_propagate_roots) copies the total
-//               back to them;
-//   write-out   objects: bit AND count >= size; holes: bit OR (background AND count < size), as bytes.
-// Workgroups exchange data between launches only; the counts are integer sums, so no result depends on an order.
-
-template <bool CONN8, bool INV>
-__global__ void __launch_bounds__(64) area_tile_runs_kernel(const uint8_t* __restrict__ in, int* __restrict__ Lall,
-                                                            int* __restrict__ Call, int H, int W, int* __restrict__ rootlist,
-                                                            int* __restrict__ nroots, size_t cap,
-                                                            unsigned long long* __restrict__ tbits,
-                                                            unsigned short* __restrict__ rtab, int* __restrict__ nruns) {
-    __shared__ int S[64 * 32];
-    __shared__ int area[64 * 32];  // per run id: the pixels of the tile-local component it roots
-    const size_t n = (size_t)H * W;
-    const uint8_t* img = in + (size_t)blockIdx.z * n;
-    int* L = Lall + (size_t)blockIdx.z * n;
-    int* C = Call + (size_t)blockIdx.z * n;
-    const int lane = threadIdx.x;
-    const int x0 = blockIdx.x * 64, ty0 = blockIdx.y * 64;
-    const int y = ty0 + lane;
+    const int x0 = blockIdx.x * 64, y = blockIdx.y * 64 + lane;
     const size_t tile = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     // inside the plane only: columns from W on and rows from H on belong to no component of either polarity
     const int wcols = W - x0;  // > 0
@@ -1430,22 +1204,28 @@ __global__ void __launch_bounds__(64) area_tile_runs_kernel(const uint8_t* __res
     tbits[tile * 64 + lane] = w;
     const unsigned long long heads = w & ~(w << 1);
     const int nroot = ccl_bits_unionfind<CONN8>(S, w, heads, lane);
-    {
-        int j = 0;
-        for (unsigned long long h = heads; h; h &= h - 1, ++j) area[lane * 32 + j] = 0;
-    }
+    for (int j = __popcll(heads); j-- > 0;) pay[lane * 32 + j] = 0;
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
-    {
+    unsigned long long fr = 0;  // frame flag: the frame's pixels of this row
+    if (FRAME) {
+        fr = (y == 0 || y == H - 1) ? valid : 0ull;
+        if (x0 == 0) fr |= 1ull;
+        if (wcols <= 64) fr |= 1ull << (wcols - 1);
+    }
+    if (!FRAME || (w & fr)) {
         int j = 0;
         for (unsigned long long h = heads; h; h &= h - 1, ++j) {
-            const int b = __ffsll((long long)h) - 1;
-            atomicAdd(&area[S[lane * 32 + j] >> 6], __popcll(ccl_run_mask(w, b)));  // LDS; integer, so any order
+            const unsigned long long run = ccl_run_mask(w, __ffsll((long long)h) - 1);
+            auto* p = &pay[S[lane * 32 + j] >> 6];
+            if constexpr (!FRAME) atomicAdd(p, __popcll(run));  // LDS; integer, so any order
+            else if (run & fr) *p = 1;                          // lanes only ever store 1 here
         }
     }
     __builtin_amdgcn_s_waitcnt(0);
     __builtin_amdgcn_wave_barrier();
-    // run table, tile roots (L[root] = root, C[root] = its count) and the tile's slice of its tile row's root list
+    // run table, tile roots (L[root] = root, P[root] = its payload) and the tile's slice of its tile row's root list:
+    // ccl_tile_runs_kernel's second half
     const int cnt = __popcll(heads);
     const int incl = ccl_wave_incl_scan(cnt, lane);
     const int rincl = ccl_wave_incl_scan(nroot, lane);
@@ -1462,7 +1242,7 @@ __global__ void __launch_bounds__(64) area_tile_runs_kernel(const uint8_t* __res
         if ((e >> 6) == own) {
             const int pix = y * W + x0 + (e & 63);
             L[pix] = pix;
-            C[pix] = area[own];
+            P[pix] = pay[own];
             if (pos < cap) rootlist[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * cap + pos] = pix;
             ++pos;
         }
@@ -1490,31 +1270,36 @@ __global__ void __launch_bounds__(256) area_count_pixels_kernel(const int* __res
     }
 }
 
-// compress the listed tile roots (L[t] = component root) and add the count of every tile root that is not its
-// component's root into the component root's.  C is read at tile roots that are not component roots and written at
-// component roots: no entry is both.
-__global__ void __launch_bounds__(256) area_roots_sum_kernel(int* __restrict__ Lall, int* __restrict__ Call,
+// compress the listed tile roots (L[t] = component root) and add the payload of every tile root that is not its
+// component's root into the component root's (a frame flag may be 0: nothing to add).  P is read at tile roots that are
+// not component roots and written at component roots: no entry is both.
+__global__ void __launch_bounds__(256) comp_roots_sum_kernel(int* __restrict__ Lall, int* __restrict__ Pall,
                                                              const int* __restrict__ rootlist,
                                                              const int* __restrict__ nroots, size_t cap, size_t n) {
     const int plane = blockIdx.z, shard = plane * gridDim.y + blockIdx.y;
     int* L = Lall + (size_t)plane * n;
-    int* C = Call + (size_t)plane * n;
+    int* P = Pall + (size_t)plane * n;
     const int cnt = nroots[shard] < (int)cap ? nroots[shard] : (int)cap;
     const int* lst = rootlist + (size_t)shard * cap;
     for (int k = blockIdx.x * 256 + threadIdx.x; k < cnt; k += gridDim.x * 256) {
         const int t = lst[k];
         const int r = roots_compress_one(L, t);
-        if (r != t) atomicAdd(&C[r], C[t]);
+        const int v = r != t ? P[t] : 0;
+        if (v) atomicAdd(&P[r], v);
     }
 }
 
-// the filtered mask from (row words of the analysed polarity, run table, C at the tile roots), laid out as
-// fill_expand_runs_kernel: a lane gathers the verdicts of its share of the runs, collects the chosen runs of its row
-// (objects: the runs to keep; holes: the runs to fill) and stores 16 pixels at a time
+// four pixels of a word as 0 / 1 bytes
+__device__ __forceinline__ unsigned fill_spread4(unsigned nib) { return (nib * 0x00204081u) & 0x01010101u; }
+
+// the filtered mask from (row words of the analysed polarity, run table, P at the tile roots): a wave per tile, four
+// tiles (neighbours in a tile row, so that a workgroup's stores of a row are 256 contiguous bytes) per workgroup; a lane
+// gathers the verdicts of its share of the runs, collects the chosen runs of its row (objects: the runs to keep; holes:
+// the runs to fill) and stores 16 pixels at a time
 template <bool INV>
-__global__ void __launch_bounds__(256) area_expand_runs_kernel(const unsigned long long* __restrict__ tbits,
+__global__ void __launch_bounds__(256) comp_expand_runs_kernel(const unsigned long long* __restrict__ tbits,
                                                                const unsigned short* __restrict__ rtab,
-                                                               const int* __restrict__ nruns, const int* __restrict__ Call,
+                                                               const int* __restrict__ nruns, const int* __restrict__ Pall,
                                                                uint8_t* __restrict__ outall, int H, int W, int segs,
                                                                int trows, int ntiles, int size) {
     __shared__ unsigned char pick_s[4][RT_CAP];
@@ -1524,7 +1309,7 @@ __global__ void __launch_bounds__(256) area_expand_runs_kernel(const unsigned lo
     if (t >= ntiles) return;  // whole wave
     const int bx = t % segs, ty = (t / segs) % trows, plane = t / (segs * trows);
     const size_t n = (size_t)H * W;
-    const int* C = Call + (size_t)plane * n;
+    const int* P = Pall + (size_t)plane * n;
     uint8_t* out = outall + (size_t)plane * n;
     const int x0 = bx * 64, ty0 = ty * 64;
     const int nr = nruns[t];
@@ -1532,7 +1317,7 @@ __global__ void __launch_bounds__(256) area_expand_runs_kernel(const unsigned lo
     unsigned long long picked = 0;
     if (nr) {  // uniform: a tile without a run has nothing to look up
         for (int k = lane; k < nr; k += 64) {
-            const int c = C[ccl_rt_root(rtab, (size_t)t, k, ty, bx, W)];
+            const int c = P[ccl_rt_root(rtab, (size_t)t, k, ty, bx, W)];
             pick_s[wv][k] = INV ? c < size : c >= size;
         }
         const unsigned long long heads = w & ~(w << 1);
@@ -1565,15 +1350,15 @@ __global__ void __launch_bounds__(256) area_expand_runs_kernel(const unsigned lo
 }
 
 // the general path's write-out: L[p] < 0 = the pixel is of the other polarity; otherwise p's tile root carries its
-// component's count
+// component's payload
 template <bool INV>
-__global__ void __launch_bounds__(256) area_write_kernel(const int* __restrict__ L, const int* __restrict__ C,
+__global__ void __launch_bounds__(256) comp_write_kernel(const int* __restrict__ L, const int* __restrict__ P,
                                                          uint8_t* __restrict__ out, size_t n, int size) {
     const size_t base = (size_t)blockIdx.y * n;
     const bool al = (reinterpret_cast<uintptr_t>(out) & 3) == 0;
     auto px = [&](int l) -> unsigned char {
         if (l < 0) return INV ? 1 : 0;
-        const int c = C[base + l];
+        const int c = P[base + l];
         return (INV ? c < size : c >= size) ? 1 : 0;
     };
     for (size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4; i0 < n; i0 += (size_t)gridDim.x * 1024) {
@@ -1591,17 +1376,21 @@ __global__ void __launch_bounds__(256) area_write_kernel(const int* __restrict__
     }
 }
 
-int amt_i_area_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8, bool holes,
-                      int size) {
-    AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "area filter: plane too large");
-    AMT_REQUIRE(size >= 1, "area filter: the size must be at least 1");
+int amt_i_component_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8,
+                           amt_comp_what what, int size) {
+    const bool frame = what == AMT_COMP_HOLES_BY_FRAME;
+    AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "component filter: plane too large");
+    AMT_REQUIRE(frame ? size == 1 : size >= 1, "component filter: the size must be at least 1 (the frame flag: 1)");
     const ccl_geom g = amt_i_ccl_geom(nplanes, H, W);
     const size_t n = g.n;
-    // run tables where binary_fill_holes takes them (same limits)
-    const bool runs = amt_i_ccl_runs_ok(in, g) && (reinterpret_cast<uintptr_t>(out) & 15) == 0 && g.ntiles * 64 < 0x7fffffffull;
+    const bool runs = amt_i_ccl_runs_out_ok(in, out, g);
     amt_scratch s(ctx);
     amt_buf<int> L(s, (size_t)nplanes * n);  // union-find parents; the run tables only touch the tile roots' entries
-    amt_buf<int> C(s, (size_t)nplanes * n);  // pixel counts, at the tile roots (as binary_fill_holes' F)
+    // the payloads, at the tile roots.  Like L a whole int32 plane of the arena of which the run-table path touches only
+    // the tile roots' entries (no traffic, but 4 B/px of reservation that amt_label does not need): payloads indexed by
+    // the position in the root lists, or a bit of L, would do without it -- not done, the tile roots are addressed by
+    // pixel everywhere else (rtab, amt_i_propagate_roots)
+    amt_buf<int> P(s, (size_t)nplanes * n);
     amt_buf<int> rootlist(s, g.nlist * g.cap);
     amt_buf<int> nroots(s, g.nlist);
     amt_buf<unsigned long long> tbits(s, g.ntiles * 64, runs);
@@ -1611,35 +1400,45 @@ int amt_i_area_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes
     AMT_HIP_CHECK(hipMemsetAsync(nroots, 0, g.nlist * sizeof(int), ctx->stream));
     if (runs) {
         amt_with_bool(c8, [&](auto C8) {
-            amt_with_bool(holes, [&](auto INV) {
-                hipLaunchKernelGGL((area_tile_runs_kernel<decltype(C8)::value, decltype(INV)::value>), g.gs, dim3(64), 0, ctx->stream,
-                                   in, L, C, H, W, rootlist, nroots, g.cap, tbits, rtab, nruns);
-            });
+            constexpr bool c = decltype(C8)::value;
+            auto tile_pass = frame                             ? comp_tile_runs_kernel<c, AMT_COMP_HOLES_BY_FRAME>
+                             : what == AMT_COMP_HOLES_BY_AREA ? comp_tile_runs_kernel<c, AMT_COMP_HOLES_BY_AREA>
+                                                              : comp_tile_runs_kernel<c, AMT_COMP_OBJECTS_BY_AREA>;
+            hipLaunchKernelGGL(tile_pass, g.gs, dim3(64), 0, ctx->stream, in, L, P, H, W, rootlist, nroots, g.cap, tbits, rtab,
+                               nruns);
         });
         AMT_LAUNCH_CHECK();
         AMT_TRY(ccl_seams_runs(ctx, g, c8, L, nullptr, tbits, rtab, nruns));
     } else {
-        AMT_HIP_CHECK(hipMemsetAsync(C, 0, (size_t)nplanes * n * sizeof(int), ctx->stream));
+        AMT_HIP_CHECK(hipMemsetAsync(P, 0, (size_t)nplanes * n * sizeof(int), ctx->stream));
         int rc = AMT_OK;
         amt_with_bool(c8, [&](auto C8) {
-            amt_with_bool(holes, [&](auto INV) {
-                rc = ccl_tileroots<uint8_t, decltype(C8)::value, decltype(INV)::value ? 1 : CCL_TRUTH>(ctx, g, in, L, rootlist, nroots);
-            });
+            constexpr bool c = decltype(C8)::value;
+            rc = what == AMT_COMP_OBJECTS_BY_AREA ? ccl_tileroots<uint8_t, c, CCL_TRUTH>(ctx, g, in, L, rootlist, nroots)
+                                                  : ccl_tileroots<uint8_t, c, 1>(ctx, g, in, L, rootlist, nroots);
         });
         AMT_TRY(rc);
-        hipLaunchKernelGGL(area_count_pixels_kernel, dim3(amt_grid_for(n, 256, 4096), nplanes), dim3(256), 0, ctx->stream, L, C, n);
+        // every pixel of the analysed polarity points at a tile root of its component here (its own, or for a tile root
+        // that a seam hung below another, that one): the frame's pixels flag those, or all pixels are counted there
+        if (frame) {
+            hipLaunchKernelGGL(frame_flag_kernel, dim3(amt_grid_for((size_t)2 * W + 2 * H, 256, 64), nplanes), dim3(256), 0,
+                               ctx->stream, L, P, H, W);
+        } else {
+            hipLaunchKernelGGL(area_count_pixels_kernel, dim3(amt_grid_for(n, 256, 4096), nplanes), dim3(256), 0, ctx->stream, L, P,
+                               n);
+        }
         AMT_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(area_roots_sum_kernel, g.glists, dim3(256), 0, ctx->stream, L, C, rootlist, nroots, g.cap, n);
+    hipLaunchKernelGGL(comp_roots_sum_kernel, g.glists, dim3(256), 0, ctx->stream, L, P, rootlist, nroots, g.cap, n);
     AMT_LAUNCH_CHECK();
-    AMT_TRY(amt_i_propagate_roots(ctx, g, C, L, rootlist, nroots));
-    amt_with_bool(holes, [&](auto INV) {
+    AMT_TRY(amt_i_propagate_roots(ctx, g, P, L, rootlist, nroots));
+    amt_with_bool(what != AMT_COMP_OBJECTS_BY_AREA, [&](auto INV) {
         if (runs) {
-            hipLaunchKernelGGL((area_expand_runs_kernel<decltype(INV)::value>), dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0,
-                               ctx->stream, tbits, rtab, nruns, C, out, H, W, g.segs, g.trows, (int)g.ntiles, size);
+            hipLaunchKernelGGL((comp_expand_runs_kernel<decltype(INV)::value>), dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0,
+                               ctx->stream, tbits, rtab, nruns, P, out, H, W, g.segs, g.trows, (int)g.ntiles, size);
         } else {
-            hipLaunchKernelGGL((area_write_kernel<decltype(INV)::value>), dim3(amt_grid_for(n, 1024, 4096), nplanes), dim3(256), 0,
-                               ctx->stream, L, C, out, n, size);
+            hipLaunchKernelGGL((comp_write_kernel<decltype(INV)::value>), dim3(amt_grid_for(n, 1024, 4096), nplanes), dim3(256), 0,
+                               ctx->stream, L, P, out, n, size);
         }
     });
     AMT_LAUNCH_CHECK();

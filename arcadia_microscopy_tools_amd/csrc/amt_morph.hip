@@ -227,8 +227,8 @@ static int build_offsets(const uint8_t* fp, int fh, int fw, int2* host, int* n) 
 }
 
 // op: AMT_MORPH_ERODE, AMT_MORPH_DILATE, AMT_MORPH_OPEN (erode then dilate), AMT_MORPH_CLOSE (dilate then erode),
-// AMT_MORPH_FILL_HOLES (amt_label.hip: amt_i_fill_holes), AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES (amt_label.hip:
-// amt_i_area_filter, the size in border_value)
+// AMT_MORPH_FILL_HOLES, AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES (amt_label.hip: amt_i_component_filter, the area
+// filters' size in border_value)
 extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
                                 const uint8_t* footprint, int fh, int fw, int op, int border_value) {
     AMT_TRY(amt_set_device(ctx));
@@ -260,8 +260,9 @@ extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, i
             const size_t bytes = (size_t)nplanes * H * W;
             AMT_REQUIRE(a + bytes <= b || b + bytes <= a, "%s: out must not alias or overlap in", name);
         }
-        if (fill) return amt_i_fill_holes(ctx, in, out, nplanes, H, W, full);
-        return amt_i_area_filter(ctx, in, out, nplanes, H, W, full, op == AMT_MORPH_REMOVE_SMALL_HOLES, border_value);
+        const bool holes = op == AMT_MORPH_REMOVE_SMALL_HOLES;
+        const amt_comp_what what = fill ? AMT_COMP_HOLES_BY_FRAME : holes ? AMT_COMP_HOLES_BY_AREA : AMT_COMP_OBJECTS_BY_AREA;
+        return amt_i_component_filter(ctx, in, out, nplanes, H, W, full, what, fill ? 1 : border_value);
     }
     static thread_local int2 host[MAX_OFFS];
     int noffs = 0;

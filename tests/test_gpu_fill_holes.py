@@ -1,7 +1,7 @@
 """``binary_fill_holes`` on the device against ``scipy.ndimage.binary_fill_holes``, byte for byte: every generator of
 tests/fill_holes_reference.py on every shape it fits, both structures, as a single plane, as plane 1 of a stack and
 inside a batch (tests/fill_holes_cases.py); truth-value bytes; the run-table and the general path on the same plane;
-refusals; the unchanged operations 0..3; ``operations.binary_fill_holes``; the classical chain with ``fill_holes``; and
+the identity with ``remove_small_holes`` where no background touches the frame; refusals; the unchanged operations 0..3; ``operations.binary_fill_holes``; the classical chain with ``fill_holes``; and
 all cases once more in a child process with the scratch arena poisoned."""
 import ctypes
 import json
@@ -87,6 +87,42 @@ def test_truth_value_bytes(ctx, shape):
             assert np.array_equal(got, want), (shape, name, sname)
             stack = ctx.asarray(np.stack([loud, loud]))
             assert np.array_equal(hipops.binary_fill_holes(stack, st).numpy(dtype=np.uint8)[1], want), (shape, name, sname)
+
+
+@pytest.mark.parametrize("shape", [(64, 64), (65, 128), (70, 131)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_fill_holes_is_remove_small_holes_where_no_background_touches_the_frame(ctx, shape):
+    """Both operators are one component filter on the device; what ties them together, on one tile, across a seam of
+    the run tables and on the general path (W % 16 != 0).  Where no background component holds a frame pixel every one is
+    a hole, which is what ``remove_small_holes`` fills with a size above the plane's pixel count.  Conversely, where the
+    only background component touches the frame, nothing is filled by either: it is no hole, and no component is smaller
+    than 1."""
+    from scipy import ndimage as ndi
+
+    import area_filters_reference as aref
+
+    H, W = shape
+    frame = np.ones(shape, bool)
+    frame[1:-1, 1:-1] = False
+    for gen in (ref.nested, ref.seam_holes):
+        m = np.pad(gen((H - 2, W - 2)), 1, constant_values=1)  # inside a 1-pixel foreground frame
+        assert m.shape == shape
+        d = ctx.asarray(m)
+        for sname, st in ref.STRUCTURES:
+            lab, k = ndi.label(m == 0, structure=st)
+            assert k >= 2 and not lab[frame].any()  # the premise
+            want = ref.scipy_fill(m, st)
+            assert np.array_equal(want, aref.remove_small_holes(m, H * W + 1, st))
+            filled = hipops.binary_fill_holes(d, st).numpy(dtype=np.uint8)
+            by_area = hipops.remove_small_holes(d, H * W + 1, aref.CONNECTIVITY[sname]).numpy(dtype=np.uint8)
+            assert np.array_equal(filled, want), (shape, gen.__name__, sname)
+            assert np.array_equal(by_area, filled), (shape, gen.__name__, sname)
+    m = ref.nested_solid(shape)
+    d = ctx.asarray(m)
+    for sname, st in ref.STRUCTURES:
+        lab, k = ndi.label(m == 0, structure=st)
+        assert k == 1 and lab[frame].any()  # the premise
+        assert np.array_equal(hipops.binary_fill_holes(d, st).numpy(dtype=np.uint8), m), (shape, sname)
+        assert np.array_equal(hipops.remove_small_holes(d, 1, aref.CONNECTIVITY[sname]).numpy(dtype=np.uint8), m), (shape, sname)
 
 
 def test_result_is_a_bool_mask_and_out_is_used(ctx):
