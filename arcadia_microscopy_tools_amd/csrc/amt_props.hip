@@ -105,10 +105,192 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
     return v;
 }
 
+// Sums of 16 values per lane over the wave for 17 exchanges (one all-reduce each takes 96): every step halves what a lane
+// still carries -- it keeps one half of its values, hands the other half to the lane `4 * HALF` away and adds what that
+// lane hands over; the last two levels are an all-reduce.  On return lane L holds the wave's sum of value (L >> 2) & 15.
+// Integer sums: any order gives the same bits.
+template <int HALF>
+__device__ __forceinline__ void wave_scatter16_step(u64 (&t)[16], int lane) {
+    const bool up = (lane & (4 * HALF)) != 0;
+#pragma unroll
+    for (int i = 0; i < HALF; ++i) {
+        const u64 keep = up ? t[i + HALF] : t[i];
+        const u64 send = up ? t[i] : t[i + HALF];
+        t[i] = keep + __shfl_xor(send, 4 * HALF);
+    }
+}
+__device__ __forceinline__ u64 wave_reduce_scatter16(u64 (&t)[16], int lane) {
+    wave_scatter16_step<8>(t, lane);
+    wave_scatter16_step<4>(t, lane);
+    wave_scatter16_step<2>(t, lane);
+    wave_scatter16_step<1>(t, lane);
+    u64 v = t[0];
+    v += __shfl_xor(v, 2);
+    return v + __shfl_xor(v, 1);
+}
+// The same for the minima of 8 values per lane: on return lane L holds the wave's minimum of value (L >> 3) & 7.
+template <int HALF>
+__device__ __forceinline__ void wave_scatter8_min_step(unsigned (&t)[8], int lane) {
+    const bool up = (lane & (8 * HALF)) != 0;
+#pragma unroll
+    for (int i = 0; i < HALF; ++i) {
+        const unsigned keep = up ? t[i + HALF] : t[i];
+        const unsigned got = __shfl_xor(up ? t[i] : t[i + HALF], 8 * HALF);
+        t[i] = got < keep ? got : keep;
+    }
+}
+__device__ __forceinline__ unsigned wave_min_scatter8(unsigned (&t)[8], int lane) {
+    wave_scatter8_min_step<4>(t, lane);
+    wave_scatter8_min_step<2>(t, lane);
+    wave_scatter8_min_step<1>(t, lane);
+    unsigned v = t[0];
+#pragma unroll
+    for (int off = 4; off >= 1; off >>= 1) {
+        const unsigned o = __shfl_xor(v, off);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 // One wave per label scans the label's bounding box (and nothing else): exact integer moment sums,
 // per-row extents for the convex hull, and {sum, sum of squares, min, max} of up to 4 intensity channels
 // per call, all accumulated privately per lane and reduced once -- no atomics, run-to-run identical.
 constexpr int RP_MAXC = 4;
+constexpr int RPS = 3;  // row slots per step: their label and intensity loads are issued together
+__device__ __forceinline__ size_t rp_uniform(size_t v) {  // a wave-uniform value, kept in scalar registers
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((size_t)hi << 32) | lo;
+}
+struct RpSums {
+    u64 cnt, sy, sx, syy, sxx, sxy;
+    u64 s[RP_MAXC], q[RP_MAXC];
+    unsigned mn[RP_MAXC], mx[RP_MAXC];
+};
+
+// The scan of one box.  The wave covers 2^LC columns x (64 >> LC) rows per row slot: 16 x 4 and 32 x 2 for boxes of at
+// most 16 / 32 columns (a nucleus: ~28 of 64 lanes of a 64 x 1 slot hold a pixel of the box), 64 x 1 with a loop over
+// 64-column blocks otherwise.  A lane owns ONE column of a block, so sx, sxx and sxy follow from the lane's pixel count
+// and row sum (x * count, x^2 * count, x * sum of y); per row a lane only counts and adds y.
+// ONE round trip per step: the labels and the intensities of the step's RPS row slots are requested together,
+// unconditionally, from coordinates clamped into the box; what lies outside the box or the label is discarded where it is
+// used (a select next to a load is turned back into a branch around it, and its wait serialises the loads).
+// The kernel is bound by instruction issue, not by the round trips ("What the numbers say"): a second register
+// set that kept the loads of step s + 1 in flight while step s was consumed cost a fifth of the waves per SIMD and ran
+// 20-90 us slower per 48 planes.  What pays is fewer instructions per pixel and per wave.
+template <int LC>
+__device__ __forceinline__ void rp_label_scan(const int* __restrict__ L, const uint16_t* __restrict__ I, size_t n, int W,
+                                              int x0, int y0, int x1, int y1, int want, int nc, bool rows_ok,
+                                              int2* __restrict__ myrows, int lane, RpSums& a) {
+    constexpr int COLS = 1 << LC, RW = 64 >> LC;
+    const int col = lane & (COLS - 1), sub = lane >> LC;
+    // addresses: a wave-uniform base per row slot (scalar registers) and one small byte offset per lane, which the label
+    // and every channel share -- not 15 64-bit addresses per step in vector registers
+    size_t cofs[RP_MAXC];  // the channels past nc re-read channel 0 (and are not used)
+#pragma unroll
+    for (int c = 0; c < RP_MAXC; ++c) cofs[c] = rp_uniform((size_t)(c < nc ? c : 0) * n);
+    int lv[RPS];
+    unsigned iv[RPS][RP_MAXC] = {};
+    auto load_step = [&](int yb, int xb) {
+        const int xr = x1 - xb;
+        const unsigned cx = (unsigned)(col <= xr ? col : xr);
+#pragma unroll
+        for (int j = 0; j < RPS; ++j) {
+            const int yt = yb + j * RW, ys = yt <= y1 ? yt : y1;  // the slot's first row, uniform
+            const int y = yt + sub, yc = y <= y1 ? y : y1;
+            const unsigned off = (unsigned)(yc - ys) * (unsigned)W + cx;  // < RW * W + 64: see the dispatch
+            const size_t base = (size_t)ys * W + xb;
+            lv[j] = *(const int*)((const char*)(L + base) + off * 4u);
+            if (I) {
+#pragma unroll
+                for (int c = 0; c < RP_MAXC; ++c)
+                    iv[j][c] = *(const uint16_t*)((const char*)(I + cofs[c] + base) + off * 2u);
+            }
+        }
+    };
+    int nyb = y0, nxb = x0;
+    int rmin[RPS], rmax[RPS];     // LC == 6: a row's extent over the blocks of its row group
+    unsigned tcnt = 0;            // LC < 6: the lane's column is the same in every step,
+    u64 tsy = 0;                  //         so the closed forms are taken once at the end
+    do {
+        const int yb = nyb, xb = nxb;
+        load_step(yb, xb);
+        nxb = xb + 64;
+        if (LC < 6 || nxb > x1) {
+            nxb = x0;
+            nyb = yb + RPS * RW;
+        }
+        const int x = xb + col;
+        if (LC == 6 && xb == x0) {
+#pragma unroll
+            for (int j = 0; j < RPS; ++j) {
+                rmin[j] = 0x7fffffff;
+                rmax[j] = -1;
+            }
+        }
+        // a lane holds one pixel per row slot whatever the layout: RPS pixels per step, bsy <= RPS * (H - 1), no overflow
+        unsigned bcnt = 0, bsy = 0;
+        int2* steprows = myrows + (yb - y0 + sub);  // LC < 6: this lane's row of slot 0; the slots lie RW rows apart
+#pragma unroll
+        for (int j = 0; j < RPS; ++j) {
+            const int y = yb + j * RW + sub;
+            const bool m = x <= x1 && y <= y1 && lv[j] == want;
+            if (m) {
+                bcnt += 1u;
+                bsy += (unsigned)y;
+                a.syy += (u64)(unsigned)y * (unsigned)y;
+                if (I) {  // all RP_MAXC channels: a uniform branch per channel costs more than the sums of an unused one
+#pragma unroll
+                    for (int c = 0; c < RP_MAXC; ++c) {
+                        const unsigned v = iv[j][c];
+                        a.s[c] += v;
+                        a.q[c] += (u64)v * v;
+                        a.mn[c] = v < a.mn[c] ? v : a.mn[c];
+                        a.mx[c] = v > a.mx[c] ? v : a.mx[c];
+                    }
+                }
+            }
+            const u64 bal = __ballot(m);
+            if constexpr (LC == 6) {
+                if (bal) {
+                    const int first = xb + __ffsll((long long)bal) - 1;
+                    const int last = xb + 63 - __clzll((long long)bal);
+                    rmin[j] = first < rmin[j] ? first : rmin[j];
+                    rmax[j] = last > rmax[j] ? last : rmax[j];
+                }
+            } else {  // the box is one block wide: row y is bits [sub * COLS, (sub + 1) * COLS) of the ballot
+                const unsigned sm = (unsigned)(bal >> (sub * COLS)) & (0xffffffffu >> (32 - COLS));
+                if (rows_ok && col == 0 && y <= y1)
+                    steprows[j * RW] = sm ? make_int2(x0 + __ffs((int)sm) - 1, x0 + 31 - __clz((int)sm))
+                                          : make_int2(0x7fffffff, -1);
+            }
+        }
+        if constexpr (LC == 6) {
+            a.cnt += bcnt;
+            a.sy += bsy;
+            a.sx += (u64)(unsigned)x * bcnt;
+            a.sxx += (u64)(unsigned)x * (unsigned)x * bcnt;
+            a.sxy += (u64)(unsigned)x * bsy;
+            if (rows_ok && lane == 0 && nxb == x0) {  // last block of the row group
+#pragma unroll
+                for (int j = 0; j < RPS; ++j)
+                    if (yb + j <= y1) myrows[yb + j - y0] = make_int2(rmin[j], rmax[j]);
+            }
+        } else {
+            tcnt += bcnt;
+            tsy += bsy;
+        }
+    } while (nyb <= y1);
+    if constexpr (LC < 6) {
+        const unsigned x = (unsigned)(x0 + col);
+        a.cnt = tcnt;
+        a.sy = tsy;
+        a.sx = (u64)x * tcnt;
+        a.sxx = (u64)x * x * tcnt;
+        a.sxy = (u64)x * tsy;
+    }
+}
+
 __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
                                                       const int* __restrict__ hoff, const int* __restrict__ htot,
                                                       int2* __restrict__ rows, size_t cap, u64* __restrict__ acc,
@@ -127,133 +309,57 @@ __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ la
     const size_t n = (size_t)H * W;
     const int* L = labels + (size_t)plane * n;
     const uint16_t* I = inten ? inten + ((size_t)plane * C + c0) * n : nullptr;
-    const int want = l + 1;
     const bool rows_ok = want_morph && (size_t)htot[plane] <= cap;
     int2* myrows = rows + (size_t)plane * cap + (size_t)hoff[li];
-    u64 cnt = 0, sy = 0, sx = 0, syy = 0, sxx = 0, sxy = 0;
-    u64 s[RP_MAXC], q[RP_MAXC];
-    unsigned mn[RP_MAXC], mx[RP_MAXC];
+    RpSums a;
+    a.cnt = a.sy = a.sx = a.syy = a.sxx = a.sxy = 0;
 #pragma unroll
     for (int c = 0; c < RP_MAXC; ++c) {
-        s[c] = 0;
-        q[c] = 0;
-        mn[c] = 0xffffffffu;
-        mx[c] = 0;
+        a.s[c] = 0;
+        a.q[c] = 0;
+        a.mn[c] = 0xffffffffu;
+        a.mx[c] = 0;
     }
-    constexpr int RPS = 3;  // rows per step: their label loads are issued together, then the intensity loads of the hits
-    for (int yb = y0; yb <= y1; yb += RPS) {
-        int rmin[RPS], rmax[RPS];
+    // wave-uniform; the 2- and 4-row slots keep their per-lane byte offsets (< 4 * (3 * W + 64)) in 32 bits
+    const int w = W < (1 << 28) ? x1 - x0 + 1 : 64;
+    if (w <= 16) rp_label_scan<4>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, lane, a);
+    else if (w <= 32) rp_label_scan<5>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, lane, a);
+    else rp_label_scan<6>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, lane, a);
+    // ONE reduction of everything: the six moment sums in the order of the accumulator slots, then sum and sum of
+    // squares per channel; the extrema as minima (max v = ~min ~v)
+    static_assert(A_N == 0 && A_SXY == 5, "the moment sums are the first six accumulator slots");
+    u64 t[16];
+    t[A_N] = a.cnt, t[A_SY] = a.sy, t[A_SX] = a.sx, t[A_SYY] = a.syy, t[A_SXX] = a.sxx, t[A_SXY] = a.sxy;
+    unsigned e[2 * RP_MAXC];
 #pragma unroll
-        for (int j = 0; j < RPS; ++j) {
-            rmin[j] = 0x7fffffff;
-            rmax[j] = -1;
-        }
-        for (int xb = x0; xb <= x1; xb += 64) {
-            const int x = xb + lane;
-            // a lane's pixels of this block share ONE column: sx, sxx and sxy follow from the lane's pixel count and row
-            // sum at the end of the block (x * count, x^2 * count, x * sum of y) -- per row a lane only counts and adds y
-            unsigned bcnt = 0, bsy = 0;  // RPS rows: no overflow
-            // ONE round trip per step: the labels and the intensities of the step's RPS rows are requested together,
-            // unconditionally, from clamped coordinates (the intensities used to wait for the labels they depend on: two
-            // dependent round trips per step of a wave that has nothing else to do); what lies outside the box or the
-            // label is discarded where it is used
-            const int xc = x <= x1 ? x : x1;
-            int lv[RPS];
-#pragma unroll
-            for (int j = 0; j < RPS; ++j) {
-                const int yc = yb + j <= y1 ? yb + j : y1;
-                lv[j] = L[(size_t)yc * W + xc];
-            }
-            unsigned iv[RPS][RP_MAXC];
-            if (I) {
-#pragma unroll
-                for (int j = 0; j < RPS; ++j) {
-                    const int yc = yb + j <= y1 ? yb + j : y1;
-#pragma unroll
-                    for (int c = 0; c < RP_MAXC; ++c) iv[j][c] = I[(size_t)(c < nc ? c : 0) * n + (size_t)yc * W + xc];
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < RPS; ++j)
-                if (x > x1 || yb + j > y1) lv[j] = 0;
-#pragma unroll
-            for (int j = 0; j < RPS; ++j) {
-                const int y = yb + j;
-                const bool m = lv[j] == want;
-                if (m) {
-                    bcnt += 1u;
-                    bsy += (unsigned)y;
-                    syy += (u64)(unsigned)y * (unsigned)y;
-                    if (I) {
-#pragma unroll
-                        for (int c = 0; c < RP_MAXC; ++c)
-                            if (c < nc) {
-                                const unsigned v = iv[j][c];
-                                s[c] += v;
-                                q[c] += (u64)v * v;
-                                mn[c] = v < mn[c] ? v : mn[c];
-                                mx[c] = v > mx[c] ? v : mx[c];
-                            }
-                    }
-                }
-                const u64 bal = __ballot(m);
-                if (bal) {
-                    const int first = xb + __ffsll((long long)bal) - 1;
-                    const int last = xb + 63 - __clzll((long long)bal);
-                    rmin[j] = first < rmin[j] ? first : rmin[j];
-                    rmax[j] = last > rmax[j] ? last : rmax[j];
-                }
-            }
-            cnt += bcnt;
-            sy += bsy;
-            sx += (u64)(unsigned)x * bcnt;
-            sxx += (u64)(unsigned)x * (unsigned)x * bcnt;
-            sxy += (u64)(unsigned)x * bsy;
-        }
-        if (rows_ok && lane == 0) {
-#pragma unroll
-            for (int j = 0; j < RPS; ++j)
-                if (yb + j <= y1) myrows[yb + j - y0] = make_int2(rmin[j], rmax[j]);
-        }
+    for (int c = 0; c < RP_MAXC; ++c) {
+        t[6 + c] = a.s[c];
+        t[6 + RP_MAXC + c] = a.q[c];
+        e[c] = a.mn[c];
+        e[RP_MAXC + c] = ~a.mx[c];
     }
-    cnt = wave_sum_u64(cnt);
-    if (want_morph) {
-        sy = wave_sum_u64(sy);
-        sx = wave_sum_u64(sx);
-        syy = wave_sum_u64(syy);
-        sxx = wave_sum_u64(sxx);
-        sxy = wave_sum_u64(sxy);
-        if (lane == 0) {
-            u64* A = acc + li * A_NACC;
-            A[A_N] = cnt;
-            A[A_SY] = sy;
-            A[A_SX] = sx;
-            A[A_SYY] = syy;
-            A[A_SXX] = sxx;
-            A[A_SXY] = sxy;
-        }
-    }
+    t[14] = t[15] = 0;
+    const u64 red = wave_reduce_scatter16(t, lane);  // value k in the lanes 4 k .. 4 k + 3
+    if (want_morph && (lane & 3) == 0 && lane < 4 * 6) acc[li * A_NACC + (lane >> 2)] = red;
     if (itable) {
-#pragma unroll
-        for (int c = 0; c < RP_MAXC; ++c)
-            if (c < nc) {
-                const u64 S = wave_sum_u64(s[c]), Q = wave_sum_u64(q[c]);
-                const unsigned lo = wave_min_u32(mn[c]), hi = wave_max_u32(mx[c]);
-                if (lane == 0) {
-                    double* t = itable + (li * C + c0 + c) * 4;
-                    if (cnt == 0) {
-                        t[0] = t[1] = t[2] = t[3] = 0.0;
-                    } else {
-                        const double dn = (double)cnt;
-                        t[0] = (double)S / dn;
-                        t[1] = (double)hi;
-                        t[2] = (double)lo;
-                        const double nv = diff_of_products(cnt, Q, S, S);  // n*Sxx - Sx^2 = n^2 * var
-                        const double var = nv / (dn * dn);
-                        t[3] = sqrt(var < 0.0 ? 0.0 : var);
-                    }
-                }
+        const unsigned ext = wave_min_scatter8(e, lane);  // value k in the lanes 8 k .. 8 k + 7
+        // lane c finalises channel c
+        const u64 cnt = __shfl(red, 0), S = __shfl(red, 4 * (6 + lane)), Q = __shfl(red, 4 * (6 + RP_MAXC + lane));
+        const unsigned lo = __shfl(ext, 8 * lane), hi = ~__shfl(ext, 8 * (RP_MAXC + lane));
+        if (lane < nc) {
+            double* o = itable + (li * C + c0 + lane) * 4;
+            if (cnt == 0) {
+                o[0] = o[1] = o[2] = o[3] = 0.0;
+            } else {
+                const double dn = (double)cnt;
+                o[0] = (double)S / dn;
+                o[1] = (double)hi;
+                o[2] = (double)lo;
+                const double nv = diff_of_products(cnt, Q, S, S);  // n*Sxx - Sx^2 = n^2 * var
+                const double var = nv / (dn * dn);
+                o[3] = sqrt(var < 0.0 ? 0.0 : var);
             }
+        }
     }
 }
 
@@ -369,6 +475,14 @@ __global__ void __launch_bounds__(256) rp_heights_kernel(const int* __restrict__
 // labels of at most HULL_HMAX rows and HULL_WMAX columns go to rp_hull_lds_kernel, the rest to rp_hull_kernel
 constexpr int HULL_HMAX = 48, HULL_WMAX = 250;
 
+// area_convex and, with it, solidity = area / area_convex: rp_final_kernel has written the row's area (and a zero
+// solidity for an absent label) earlier on the stream, and a label's row is written by exactly one lane of one hull kernel
+__device__ __forceinline__ void rp_write_convex(double* __restrict__ trow, double convex) {
+    const double area = trow[AMT_RP_AREA];
+    trow[AMT_RP_AREA_CONVEX] = convex;
+    trow[AMT_RP_SOLIDITY] = area > 0.0 ? area / convex : 0.0;
+}
+
 __device__ __forceinline__ long long floor_div(long long a, long long b) {  // b > 0
     long long q = a / b;
     return (a % b != 0 && a < 0) ? q - 1 : q;
@@ -405,7 +519,7 @@ __global__ void __launch_bounds__(64) rp_hull_kernel(const int* __restrict__ bbo
     if (h <= skip_h && bbox[li * 4 + 3] - bbox[li * 4 + 1] + 1 <= HULL_WMAX) return;  // done by rp_hull_lds_kernel
     const size_t off = (size_t)hoff[li];
     if ((size_t)htot[plane] > cap || off + (size_t)h > cap) {  // capacity exceeded (fragmented labels)
-        if (!CROWS) trow[AMT_RP_AREA_CONVEX] = __longlong_as_double(0x7ff8000000000000ll);
+        if (!CROWS) rp_write_convex(trow, __longlong_as_double(0x7ff8000000000000ll));
         return;
     }
     const int2* r = rows + (size_t)plane * cap + off;
@@ -494,7 +608,7 @@ __global__ void __launch_bounds__(64) rp_hull_kernel(const int* __restrict__ bbo
         if (CROWS) crows[(size_t)plane * cap + off + (y - miny)] = make_int2((int)xmin, (int)xmax);
         else if (xmax >= xmin) count += xmax - xmin + 1;
     }
-    if (!CROWS) trow[AMT_RP_AREA_CONVEX] = (double)count;
+    if (!CROWS) rp_write_convex(trow, (double)count);
 }
 
 // The same hull for labels that fit a small box (at most HULL_HMAX rows and HULL_WMAX columns: every nucleus-sized
@@ -538,7 +652,7 @@ __global__ void __launch_bounds__(64) rp_hull_lds_kernel(const int* __restrict__
     if (h > HULL_HMAX || x1 - x0 + 1 > HULL_WMAX) return;  // rp_hull_kernel takes it
     const size_t off = (size_t)hoff[li];
     if ((size_t)htot[plane] > cap || off + (size_t)h > cap) {  // capacity exceeded (fragmented labels)
-        if (!CROWS && side == 0) trow[AMT_RP_AREA_CONVEX] = __longlong_as_double(0x7ff8000000000000ll);
+        if (!CROWS && side == 0) rp_write_convex(trow, __longlong_as_double(0x7ff8000000000000ll));
         return;
     }
     const int2* r = rows + (size_t)plane * cap + off;
@@ -615,7 +729,7 @@ __global__ void __launch_bounds__(64) rp_hull_lds_kernel(const int* __restrict__
             count += xmax - xmin + 1;
         }
     }
-    if (!CROWS && side == 0) trow[AMT_RP_AREA_CONVEX] = (double)count;
+    if (!CROWS && side == 0) rp_write_convex(trow, (double)count);
 }
 
 // ---- final per-label columns ------------------------------------------------------------------------
@@ -665,13 +779,6 @@ __global__ void __launch_bounds__(256) rp_final_kernel(const u64* __restrict__ a
             orient = 0.5 * atan2(-2.0 * b, c - a);
         }
         t[AMT_RP_ORIENTATION] = orient;
-    }
-}
-
-__global__ void __launch_bounds__(256) rp_solidity_kernel(double* __restrict__ table, size_t nlab) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nlab; i += (size_t)gridDim.x * 256) {
-        double* t = table + i * AMT_RP_NCOLS;
-        t[AMT_RP_SOLIDITY] = t[AMT_RP_AREA] > 0.0 ? t[AMT_RP_AREA] / t[AMT_RP_AREA_CONVEX] : 0.0;
     }
 }
 
@@ -726,6 +833,7 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
         hipLaunchKernelGGL(rp_final_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox,
                            table_dev, nlab);
         AMT_LAUNCH_CHECK();
+        // the hull kernels read the area that rp_final_kernel has just written: they write area_convex AND solidity
         const int skip_h = HULL_HMAX;
         hipLaunchKernelGGL(rp_hull_lds_kernel<false>, dim3((max_label + 31) / 32, nplanes), dim3(64), 0, ctx->stream, bbox,
                            hoff, htot, rows, cap, table_dev, max_label, (int2*)nullptr);
@@ -733,9 +841,6 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
         // labels taller than HULL_HMAX rows or wider than HULL_WMAX columns: chains in HBM scratch
         hipLaunchKernelGGL(rp_hull_kernel<false>, dim3((max_label + 63) / 64, nplanes), dim3(64), 0, ctx->stream, bbox,
                            hoff, htot, rows, chainL, chainR, cap, table_dev, max_label, skip_h, (int2*)nullptr);
-        AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(rp_solidity_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream,
-                           table_dev, nlab);
         AMT_LAUNCH_CHECK();
     }
     return AMT_OK;
