@@ -41,6 +41,11 @@ RPX_COLS = (
 )
 RPX_NCOLS = len(RPX_COLS)
 RPX_WCOLS = ("centroid_weighted-0", "centroid_weighted-1", "centroid_weighted_local-0", "centroid_weighted_local-1")
+# amt_regionprops_ext with AMT_RPX_RELATE: the bit, the four columns per (label, companion plane) (AMT_RPX_RCOL_*) and
+# the number of distinct partners of a label that are counted in LDS (AMT_RELATE_LDS_PARTNERS)
+RPX_RELATE = 1 << 8
+RPX_RCOLS = ("parent", "overlap", "partners", "area")
+RELATE_LDS_PARTNERS = 128
 # amt_colocalization: the columns of a (label, channel pair) row (AMT_COLOC_*)
 COLOC_COLS = ("pearson", "overlap", "m1", "m2", "intersection1", "intersection2")
 COLOC_NCOLS = len(COLOC_COLS)

@@ -1335,19 +1335,165 @@ __global__ void __launch_bounds__(64) rpx_weighted_kernel(const int* __restrict_
     }
 }
 
+// ---- relate two label images (AMT_RPX_RELATE) -----------------------------------------------------------------------
+// One wave per (label, plane) over the label's box, one companion label plane after the other: which companion values
+// lie under the label's pixels, and how often.  The (value, count) pairs live in an open-addressed LDS table of
+// RL_SLOTS slots (key 0 = empty: a partner is never 0), home slot = value mod RL_SLOTS, linear probing, claimed with a
+// compare-and-swap and counted with an add.  A probe sequence visits every slot once and then gives up, so the table
+// holds up to RL_SLOTS distinct partners however their values collide, and no lane ever waits for another.  Counts are
+// integer sums: the order in which the lanes arrive changes which slot a value gets, never a count.
+// A lane keeps the run of equal values it is reading down its column in registers and goes to the table when the value
+// changes: a nucleus inside one cell costs a lane one table update, not one per pixel.
+// LDS: 2 x 4 x RL_SLOTS = 1 KiB per workgroup of one wave, so the 32-wave cap of a CU binds (8 waves per SIMD), not
+// the LDS (160 workgroups' worth).
+// More than RL_SLOTS distinct partners (a lane found no slot): the table is dropped and the partners are selected one
+// by one in ascending order, one pass over the box each -- the pass that counts partner v also finds the smallest
+// value above v.  Every pass raises v, so there are (partners + 1) passes and then it ends.
+constexpr int RL_SLOTS = AMT_RELATE_LDS_PARTNERS;
+static_assert((RL_SLOTS & (RL_SLOTS - 1)) == 0 && RL_SLOTS >= 64, "slot index by mask; a lane reduces RL_SLOTS / 64 slots");
+
+// f(v) for the companion value v under every pixel of the label, each pixel once.  The wave covers 2^lc columns x
+// (64 >> lc) rows per row slot (rp_label_scan's layouts, and 8 x 8 for the smallest boxes); two row slots per step with
+// their four loads issued together from coordinates clamped into the box.
+template <typename F>
+__device__ __forceinline__ void rl_for_pixels(const int* __restrict__ L, const int* __restrict__ B, int W, int x0, int y0,
+                                              int x1, int y1, int want, int lc, int lane, F&& f) {
+    const int cols = 1 << lc, rw = 64 >> lc;
+    const int col = lane & (cols - 1), sub = lane >> lc;
+    for (int yb = y0 + sub; yb - sub <= y1; yb += 2 * rw) {
+        const int ya = yb, yc = yb + rw;
+        const size_t ra = (size_t)(ya <= y1 ? ya : y1) * W, rc = (size_t)(yc <= y1 ? yc : y1) * W;
+        for (int xb = x0; xb <= x1; xb += cols) {
+            const int x = xb + col, xc = x <= x1 ? x : x1;
+            const int la = L[ra + xc], lb = L[rc + xc];
+            const int va = B[ra + xc], vb = B[rc + xc];
+            if (x <= x1 && ya <= y1 && la == want) f(va);
+            if (x <= x1 && yc <= y1 && lb == want) f(vb);
+        }
+    }
+}
+
+// add `c` pixels of partner `v` (> 0) to the table; false when all RL_SLOTS slots belong to other values
+__device__ __forceinline__ bool rl_table_add(int* keys, unsigned* cnts, int v, unsigned c) {
+    unsigned s = (unsigned)v & (RL_SLOTS - 1);
+    for (int probe = 0; probe < RL_SLOTS; ++probe) {
+        int k = ((volatile int*)keys)[s];  // a key never changes once set: only an empty slot needs the exchange
+        if (k == 0) k = atomicCAS(&keys[s], 0, v);  // the value found there, 0 when this lane claimed the slot
+        if (k == 0 || k == v) {
+            atomicAdd(&cnts[s], c);
+            return true;
+        }
+        s = (s + 1) & (RL_SLOTS - 1);
+    }
+    return false;
+}
+
+__global__ void __launch_bounds__(64) rpx_relate_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                        const int* __restrict__ comp, int C, double* __restrict__ wtable,
+                                                        int H, int W, int max_label) {
+    __shared__ int keys[RL_SLOTS];
+    __shared__ unsigned cnts[RL_SLOTS];
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    double* out = wtable + li * (size_t)C * 4;
+    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    if (y1 < y0) {  // label absent from this plane
+        for (int i = lane; i < C * 4; i += 64) out[i] = 0.0;
+        return;
+    }
+    const size_t n = (size_t)H * W;
+    const int* L = labels + (size_t)plane * n;
+    const int w = x1 - x0 + 1;
+    const int lc = w <= 8 ? 3 : (w <= 16 ? 4 : (w <= 32 ? 5 : 6));
+    for (int c = 0; c < C; ++c) {
+        const int* B = comp + ((size_t)plane * C + c) * n;
+        for (int i = lane; i < RL_SLOTS; i += 64) {
+            keys[i] = 0;
+            cnts[i] = 0;
+        }
+        __syncthreads();
+        unsigned area = 0, runc = 0;
+        int runv = 0;
+        bool full = false;
+        rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, [&](int v) {
+            area += 1u;
+            if (v == runv) {
+                runc += 1u;
+            } else {
+                if (runv > 0 && !full) full = !rl_table_add(keys, cnts, runv, runc);
+                runv = v;
+                runc = 1u;
+            }
+        });
+        if (runv > 0 && !full) full = !rl_table_add(keys, cnts, runv, runc);
+        __syncthreads();
+        area = (unsigned)wave_sum_u64(area);  // a plane has fewer than 2^32 pixels
+        unsigned best = 0, bestv = 0, partners = 0;  // maximal count, the smallest value that has it
+        if (!__any(full)) {
+            for (int i = lane; i < RL_SLOTS; i += 64) {
+                const unsigned k = (unsigned)keys[i], cn = cnts[i];
+                if (k != 0) {
+                    partners += 1u;
+                    if (cn > best || (cn == best && k < bestv)) best = cn, bestv = k;
+                }
+            }
+            partners = (unsigned)wave_sum_u64(partners);
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const unsigned ob = __shfl_xor(best, o), ov = __shfl_xor(bestv, o);
+                if (ob > best || (ob == best && ob != 0 && ov < bestv)) best = ob, bestv = ov;
+            }
+        } else {
+            // smallest partner value first
+            unsigned cur = 0x7fffffffu;
+            rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, [&](int v) {
+                if (v > 0 && (unsigned)v < cur) cur = (unsigned)v;
+            });
+            cur = wave_min_u32(cur);
+            while (cur != 0x7fffffffu) {
+                unsigned cn = 0, next = 0x7fffffffu;
+                rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, [&](int v) {
+                    if ((unsigned)v == cur) cn += 1u;
+                    else if (v > 0 && (unsigned)v > cur && (unsigned)v < next) next = (unsigned)v;
+                });
+                cn = (unsigned)wave_sum_u64(cn);
+                next = wave_min_u32(next);
+                partners += 1u;
+                if (cn > best) best = cn, bestv = cur;  // ascending values: an equal count keeps the smaller one
+                cur = next;  // > the value just counted, or the end mark
+            }
+        }
+        if (lane == 0) {
+            out[c * 4 + AMT_RPX_RCOL_PARENT] = (double)bestv;
+            out[c * 4 + AMT_RPX_RCOL_OVERLAP] = (double)best;
+            out[c * 4 + AMT_RPX_RCOL_PARTNERS] = (double)partners;
+            out[c * 4 + AMT_RPX_RCOL_AREA] = (double)area;
+        }
+        __syncthreads();  // the table is cleared for the next companion
+    }
+}
+
 extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C,
                                    int columns, double* table_dev, double* wtable_dev, int nplanes, int H, int W,
                                    int max_label) {
     const unsigned cols = (unsigned)columns;
     const bool want_w = (cols & AMT_RPX_CENTROID_WEIGHTED) != 0;
-    const bool want_m = (cols & ~AMT_RPX_CENTROID_WEIGHTED) != 0;
-    AMT_REQUIRE(labels && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && cols != 0 && (cols & ~AMT_RPX_ALL) == 0,
+    const bool want_r = (cols & AMT_RPX_RELATE) != 0;
+    const bool want_c = want_w || want_r;  // the call has companion planes and a per-companion table
+    const bool want_m = (cols & ~(AMT_RPX_CENTROID_WEIGHTED | AMT_RPX_RELATE)) != 0;
+    AMT_REQUIRE(labels && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && cols != 0 &&
+                    (cols & ~(AMT_RPX_ALL | AMT_RPX_RELATE)) == 0,
                 "regionprops_ext: bad arguments");
+    AMT_REQUIRE(!(want_w && want_r),
+                "regionprops_ext: AMT_RPX_RELATE and AMT_RPX_CENTROID_WEIGHTED share the companion planes and their table: "
+                "one call, one of them");
     AMT_REQUIRE(!table_dev == !want_m, "regionprops_ext: the morphology table and its column bits go together");
-    AMT_REQUIRE(want_w == !!intensity && want_w == !!wtable_dev && (!want_w || C >= 1),
-                "regionprops_ext: the intensity planes (C >= 1), the weighted table and AMT_RPX_CENTROID_WEIGHTED go "
-                "together");
+    AMT_REQUIRE(want_c == !!intensity && want_c == !!wtable_dev && (!want_c || C >= 1),
+                "regionprops_ext: the intensity planes (C >= 1), the weighted table and AMT_RPX_CENTROID_WEIGHTED (or the "
+                "companion label planes, the relation table and AMT_RPX_RELATE) go together");
     AMT_REQUIRE(!want_w || in_code == AMT_U16 || in_code == AMT_F64, "regionprops_ext: intensity must be AMT_U16 or AMT_F64");
+    AMT_REQUIRE(want_r == (in_code == AMT_I32),
+                "regionprops_ext: AMT_I32 companion label planes and AMT_RPX_RELATE go together");
     AMT_TRY(amt_set_device(ctx));
     if (nplanes == 0 || max_label == 0) return AMT_OK;
     const bool euler = cols & (AMT_RPX_EULER_NUMBER | AMT_RPX_PERIMETER_CROFTON);
@@ -1419,6 +1565,11 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
         else
             hipLaunchKernelGGL((rpx_weighted_kernel<double, double>), dim3(max_label, nplanes), dim3(64), 0, ctx->stream,
                                labels, bbox, (const double*)intensity, C, wtable_dev, H, W, max_label);
+        AMT_LAUNCH_CHECK();
+    }
+    if (want_r) {
+        hipLaunchKernelGGL(rpx_relate_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,
+                           (const int*)intensity, C, wtable_dev, H, W, max_label);
         AMT_LAUNCH_CHECK();
     }
     return AMT_OK;

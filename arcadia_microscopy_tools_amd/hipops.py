@@ -1150,6 +1150,8 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
             if name not in _hip.RPX_BITS:
                 raise ValueError(f"unknown extended region property {name!r}")
             bits |= _hip.RPX_BITS[name]
+    if bits & _hip.RPX_RELATE:
+        raise ValueError("bit 8 (AMT_RPX_RELATE) relates two label images: call hipops.relate_labels")
     want_w = bool(bits & _hip.RPX_WEIGHTED)
     if want_w != (intensity is not None):
         raise ValueError("weighted centroids need intensity images, and intensity images are only used for them")
@@ -1169,6 +1171,38 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
                                           bits, None if o is None else o.ptr, None if wo is None else wo.ptr, n, H, W,
                                           int(max_label)), "amt_regionprops_ext")
     return o, wo
+
+
+def relate_labels(labels: DeviceArray, max_label: int, companions: DeviceArray, out=None) -> DeviceArray:
+    """How the labels of ``labels`` lie on other label images (``amt_regionprops_ext`` with ``AMT_RPX_RELATE``).
+
+    ``labels`` is int32 (..., Y, X); ``companions`` is int32 (..., C, Y, X) with one (C, Y, X) stack per label plane,
+    or (..., Y, X) of the labels' own shape for C = 1; values 0 (background) to 2**31 - 2.  A companion may be
+    ``labels`` itself.  Returns (nplanes, max_label, C, 4) float64 in ``_hip.RPX_RCOLS`` order: for label ``l`` and
+    companion ``B``, ``parent`` = the non-zero value of ``B`` that covers most pixels of ``l`` (the smallest among
+    equal counts, 0 when ``B`` is zero on all of ``l``), ``overlap`` = that count, ``partners`` = the number of
+    distinct non-zero values of ``B`` on ``l``, ``area`` = the pixel count of ``l``.  A label absent from its plane
+    gives four zeros.  All values are exact integers; two runs give identical bytes."""
+    ctx = labels.ctx
+    n, H, W = _planes(labels)
+    if labels.dtype != np.int32:
+        raise TypeError("relate_labels expects int32 labels")
+    if companions.dtype != np.int32:
+        raise TypeError("companion label images must be int32 on the device path")
+    if companions.ndim < 2 or companions.shape[-2:] != labels.shape[-2:]:
+        raise ValueError("companions must be (..., C, Y, X) or (..., Y, X) matching the label planes")
+    if tuple(companions.shape) == tuple(labels.shape):
+        C = 1
+    else:
+        if companions.ndim < 3:
+            raise ValueError("companions must be (..., C, Y, X) or (..., Y, X) matching the label planes")
+        C = int(companions.shape[-3])
+    if C < 1 or companions.size != n * C * H * W:
+        raise ValueError("companions / labels plane count mismatch")
+    o = _out(ctx, out, (n, max_label, C, 4), np.float64)
+    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, companions.ptr, _hip.I32, C, _hip.RPX_RELATE, None,
+                                          o.ptr, n, H, W, int(max_label)), "amt_regionprops_ext")
+    return o
 
 
 def colocalization_pairs(C: int, pairs=None) -> np.ndarray:

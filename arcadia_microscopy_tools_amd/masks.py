@@ -603,6 +603,66 @@ class SegmentationMask:
         lab, _ = hipops.relabel_sequential(annulus, k)
         return SegmentationMask._derived(self, lab, int(parents.size), parents)
 
+    def _companion_plane(self, other):
+        """``other`` of ``relate`` as an int32 (Y, X) device plane of this mask's shape."""
+        from .device import get_context
+
+        plane, _ = self._label_plane()
+        if isinstance(other, SegmentationMask):
+            comp, _ = other._label_plane()
+        else:
+            if not isinstance(other, np.ndarray):
+                raise TypeError("other must be a SegmentationMask or a numpy array")
+            if other.dtype.kind not in "iu":
+                raise TypeError("other must be an integer label array")
+            if other.ndim != 2:
+                raise ValueError("other must be a 2D array")
+            mn, mx = _extrema(other) if other.size else (0, 0)
+            if mn < 0:
+                raise ValueError("other must have non-negative values")
+            if mx >= 2**31 - 1:
+                raise ValueError("label values above 2**31 - 2 are not supported on the device path")
+            comp = get_context().asarray(other, dtype=np.int32)
+        if tuple(comp.shape) != tuple(plane.shape):
+            raise ValueError("other must have the same shape as this mask")
+        return comp
+
+    def relate(self, other) -> dict[str, ScalarArray]:
+        """How every cell of this mask lies on another label image, one entry per cell ordered by label like
+        ``cell_properties`` (CellProfiler's RelateObjects; a row of ``skimage.metrics.contingency_table``):
+
+        parent            the label of ``other`` that covers most pixels of the cell; among labels covering equally
+                          many the SMALLEST; 0 when the cell lies on ``other``'s background (int64)
+        overlap           the number of pixels the cell shares with its parent (int64)
+        partners          the number of different labels of ``other`` under the cell (int64)
+        area              the cell's pixel count (int64)
+        overlap_fraction  overlap / area (float64)
+
+        ``other`` is a ``SegmentationMask`` of the same shape (its ``label_image`` numbering is what ``parent``
+        holds; an ``expanded`` / ``ring`` mask works on either side) or a non-negative integer label array of the
+        same shape with values up to 2**31 - 2, whose values are used as they are.  Both label planes are related on
+        the device (``hipops.relate_labels``); a plane that is already there does not leave it, only the
+        (num_cells x 4) table comes back."""
+        from . import _hip, hipops
+
+        plane, k = self._label_plane()
+        comp = self._companion_plane(other)
+        shape = tuple(plane.shape)
+        table = hipops.relate_labels(plane.reshape((1,) + shape), max(k, 1), comp.reshape((1, 1) + shape)).numpy()
+        cols = table[0, :k, 0, :]
+        out = {name: cols[:, i].astype(np.int64) for i, name in enumerate(_hip.RPX_RCOLS)}
+        out["overlap_fraction"] = out["overlap"].astype(np.float64) / out["area"].astype(np.float64)
+        return out
+
+    def child_counts(self, other: "SegmentationMask") -> Int64Array:
+        """Per cell of this mask, the number of cells of ``other`` whose ``parent`` (``other.relate(self)``) it is:
+        nuclei per cell, spots per nucleus.  A cell of ``other`` that lies on this mask's background counts for
+        nobody."""
+        if not isinstance(other, SegmentationMask):
+            raise TypeError("other must be a SegmentationMask")
+        parent = other.relate(self)["parent"]
+        return np.bincount(parent, minlength=self.num_cells + 1)[1:self.num_cells + 1].astype(np.int64)
+
     def convert_properties_to_microns(self, pixel_size_um: float) -> dict[str, ScalarArray]:
         """Scale lengths / areas / volumes to microns with ``_um`` / ``_um2`` / ``_um3`` key suffixes
         (R/masks.py:420-467); dimensionless and intensity columns pass through."""

@@ -463,7 +463,27 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
  * x, weighted local y, weighted local x}, from intensity = nplanes x C planes of element type in_code (AMT_U16:
  * integer sums, exact; AMT_F64: float64 sums); intensity, C >= 1 and wtable_dev are given exactly when
  * AMT_RPX_CENTROID_WEIGHTED is set.  A label with zero total intensity gets NaN weighted centroids; labels absent
- * from a plane get 0 in every column. */
+ * from a plane get 0 in every column.
+ *
+ * ---- relating two label images: AMT_RPX_RELATE ----
+ * "Measure label image A with label image B as its intensity image": with AMT_RPX_RELATE set, intensity is
+ * nplanes x C COMPANION LABEL planes, one (C, Y, X) stack per label plane, in_code == AMT_I32, values 0 (background)
+ * to 2^31 - 2, C >= 1; a companion may be the very buffer `labels` points to.  wtable_dev = nplanes x max_label x C x 4
+ * doubles.  For label l with pixel set P and companion plane B the four columns are
+ *   AMT_RPX_RCOL_PARENT    the non-zero value v that maximises |{p in P : B[p] = v}|; among equal counts the smallest
+ *                          v wins; 0 when B is zero on all of P
+ *   AMT_RPX_RCOL_OVERLAP   that maximal count (0 without a parent)
+ *   AMT_RPX_RCOL_PARTNERS  the number of distinct non-zero values of B on P
+ *   AMT_RPX_RCOL_AREA      |P|
+ * A label absent from its plane gives 0, 0, 0, 0.  All four are exact integers held in doubles; counts are integer
+ * sums, so nothing depends on an order of accumulation and two runs give identical bytes.  Up to
+ * AMT_RELATE_LDS_PARTNERS distinct partners of a label are counted in LDS in one pass over its bounding box; a label
+ * with more is still exact, at one pass over its box per partner.
+ * AMT_RPX_RELATE and AMT_RPX_CENTROID_WEIGHTED in one call is AMT_EINVAL (they share intensity and wtable_dev); the
+ * morphology bits may be combined with either.  in_code != AMT_I32 with the bit set is AMT_EINVAL, and so is
+ * in_code == AMT_I32 without it.  intensity, C >= 1 and wtable_dev are given exactly when AMT_RPX_RELATE or
+ * AMT_RPX_CENTROID_WEIGHTED is set.  AMT_RPX_ALL stays the scikit-image columns; the accepted mask is
+ * AMT_RPX_ALL | AMT_RPX_RELATE.  nplanes == 0 or max_label == 0 is AMT_OK and writes nothing. */
 #define AMT_RPX_EULER_NUMBER (1u << 0)
 #define AMT_RPX_PERIMETER_CROFTON (1u << 1)
 #define AMT_RPX_AREA_FILLED (1u << 2)
@@ -473,6 +493,12 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
 #define AMT_RPX_INERTIA_EIGVALS (1u << 6)
 #define AMT_RPX_CENTROID_WEIGHTED (1u << 7)
 #define AMT_RPX_ALL 0xffu
+#define AMT_RPX_RELATE (1u << 8)
+#define AMT_RPX_RCOL_PARENT 0
+#define AMT_RPX_RCOL_OVERLAP 1
+#define AMT_RPX_RCOL_PARTNERS 2
+#define AMT_RPX_RCOL_AREA 3
+#define AMT_RELATE_LDS_PARTNERS 128
 #define AMT_RPX_COL_EULER_NUMBER 0
 #define AMT_RPX_COL_PERIMETER_CROFTON 1
 #define AMT_RPX_COL_AREA_FILLED 2
