@@ -797,6 +797,7 @@ static int launch_fused(amt_ctx* ctx, const TIn* in, double scale, double* out, 
 //               boundary-mapped rows.
 // ------------------------------------------------------------------------------------------------
 constexpr int H8G_CP = 256, H8G_PITCH = 258;
+constexpr size_t V8G_LDS_MAX = 160 * 1024;  // LDS of one gfx950 workgroup
 
 template <int H8G_ROWS, int RC = 0>
 __global__ void __launch_bounds__(256) conv_h8g_kernel(const double* __restrict__ in, double* out, int H, int W,
@@ -973,10 +974,13 @@ static int gaussian_typed(amt_ctx* ctx, const TIn* in, double scale, double* out
     const bool aligned = (reinterpret_cast<uintptr_t>(in) & 15) == 0 && (reinterpret_cast<uintptr_t>(tmp) & 15) == 0 &&
                          (in_stride * sizeof(TIn)) % 16 == 0;
     bool v_done = false, h_done = false;
-    if (aligned && W % 64 == 0 && H > 2 * r) {  // vertical pass, LDS-DMA staging
-        int TH = sizeof(TIn) == 2 ? 128 : 64;
-        const int rows_pad = (TH + 2 * r + 7) & ~7;
-        const size_t smem0 = (size_t)rows_pad * 64 * sizeof(TIn) + (size_t)(2 * r + 1) * 8 + (size_t)(TH + 2 * r);
+    // vertical pass, LDS-DMA staging -- unless its tile passes the 160 KiB of a workgroup (float64 from r = 125 on: 320 rows
+    // of 64 doubles alone fill it); conv_v8_kernel below halves its tile until it fits
+    const int TH_G = sizeof(TIn) == 2 ? 128 : 64;
+    const size_t smem_g = (size_t)((TH_G + 2 * r + 7) & ~7) * 64 * sizeof(TIn) + (size_t)(2 * r + 1) * 8 + (size_t)(TH_G + 2 * r);
+    if (aligned && W % 64 == 0 && H > 2 * r && smem_g <= V8G_LDS_MAX) {
+        const int TH = TH_G;
+        const size_t smem0 = smem_g;
         dim3 g0(W / 64, (H + TH - 1) / TH, nplanes);
         if (r == 64)
             hipLaunchKernelGGL((conv_v8g_kernel<TIn, 64>), g0, dim3(256), smem0, ctx->stream, in, scale, tmp, H, W, wdev, r,

@@ -548,13 +548,18 @@ __global__ void __launch_bounds__(1024) otsu_u16_kernel(const uint32_t* __restri
     if (t == 0) thr[plane] = (double)bi;
 }
 
+__device__ __forceinline__ double otsu_bin_centre(double lo, double hi, double step, int i, int nbins) {
+    return (linspace_edge(lo, hi, step, i, nbins) + linspace_edge(lo, hi, step, i + 1, nbins)) / 2.0;
+}
+
 // thr_code (nullable): 2 * (index of the threshold's bin), the threshold in the code space of amt_gaussian_otsu_codes
 __global__ void __launch_bounds__(256) otsu_f64_kernel(const uint32_t* __restrict__ hist,
                                                        const double* __restrict__ minmax, int nbins,
                                                        double* __restrict__ thr, double* __restrict__ thr_code) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* ctr = reinterpret_cast<double*>(smem_raw);  // nbins
-    double* w1 = ctr + nbins;
+    // four arrays of nbins doubles: 128 KiB at 4096 bins.  The bin centres are not kept (a fifth array would pass the
+    // 160 KiB of a workgroup from 4095 bins on): a centre is two edges away, computed where it is used
+    double* w1 = reinterpret_cast<double*>(smem_raw);
     double* w2 = w1 + nbins;
     double* m1 = w2 + nbins;
     double* m2 = m1 + nbins;
@@ -571,15 +576,11 @@ __global__ void __launch_bounds__(256) otsu_f64_kernel(const uint32_t* __restric
         return;
     }
     const double step = (hi - lo) / (double)nbins;
-    for (int i = threadIdx.x; i < nbins; i += 256) {
-        double e0 = linspace_edge(lo, hi, step, i, nbins), e1 = linspace_edge(lo, hi, step, i + 1, nbins);
-        ctr[i] = (e0 + e1) / 2.0;
-    }
     // counts and counts * centres into both directions' arrays (the running sums overwrite them in place)
     for (int i = threadIdx.x; i < nbins; i += 256) {
         const double c = (double)h[i];
         w1[i] = w2[i] = c;
-        m1[i] = m2[i] = c * ctr[i];
+        m1[i] = m2[i] = c * otsu_bin_centre(lo, hi, step, i, nbins);
     }
     __syncthreads();
     // the two cumulative sums are sequential by definition (np.cumsum's order fixes the rounding): one lane each, in
@@ -622,14 +623,14 @@ __global__ void __launch_bounds__(256) otsu_f64_kernel(const uint32_t* __restric
     int bi;
     block_argmax_first(best, best_idx, s_val, s_idx, bv, bi);
     if (threadIdx.x == 0) {
-        thr[plane] = ctr[bi == 0x7fffffff ? 0 : bi];
+        thr[plane] = otsu_bin_centre(lo, hi, step, bi == 0x7fffffff ? 0 : bi, nbins);
         if (thr_code) thr_code[plane] = (double)(2 * (bi == 0x7fffffff ? 0 : bi));
     }
 }
 
 int amt_i_otsu_from_hist(amt_ctx* ctx, const uint32_t* hist, const double* minmax, int nbins, double* thr,
                          double* thr_code, int nplanes) {
-    hipLaunchKernelGGL(otsu_f64_kernel, dim3(nplanes), dim3(256), (size_t)5 * nbins * sizeof(double), ctx->stream, hist,
+    hipLaunchKernelGGL(otsu_f64_kernel, dim3(nplanes), dim3(256), (size_t)4 * nbins * sizeof(double), ctx->stream, hist,
                        minmax, nbins, thr, thr_code);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
@@ -644,6 +645,8 @@ extern "C" int amt_threshold_value(amt_ctx* ctx, const void* in, int in_dtype, i
                 "threshold_value: only AMT_THR_OTSU runs fully on the device; other methods are evaluated by the "
                 "host layer on amt_hist_* output");
     AMT_REQUIRE(in_dtype == AMT_U16 || in_dtype == AMT_F64, "threshold_value: dtype must be AMT_U16 or AMT_F64");
+    // every refusal before the first byte is written (float64: the four Otsu arrays of nbins doubles fill 128 KiB of LDS)
+    AMT_REQUIRE(in_dtype == AMT_U16 || (nbins >= 2 && nbins <= 4096), "threshold_value: nbins %d out of range 2..4096", nbins);
     if (nplanes == 0) return AMT_OK;
     if (status_dev) AMT_HIP_CHECK(hipMemsetAsync(status_dev, 0, (size_t)nplanes * sizeof(int32_t), ctx->stream));
     if (in_dtype == AMT_U16) {
@@ -657,7 +660,6 @@ extern "C" int amt_threshold_value(amt_ctx* ctx, const void* in, int in_dtype, i
         AMT_LAUNCH_CHECK();
         return AMT_OK;
     }
-    AMT_REQUIRE(nbins >= 2 && nbins <= 4096, "threshold_value: nbins %d out of range", nbins);
     amt_scratch s(ctx);
     amt_buf<unsigned long long> keys(s, 2 * nplanes);
     amt_buf<double> mm_own(s, 2 * nplanes);

@@ -208,6 +208,7 @@ int amt_copy_rect(amt_ctx* ctx, const void* src, void* dst, int elem_size, int n
 #define AMT_THR_LI 6
 /* Global threshold value per plane (thr_dev[plane], float64 -- for integer images the bin centre).
  * status_dev[plane] != 0 flags "no threshold" (threshold_minimum: fewer/more than two maxima).
+ * nbins (float64 input; ignored for uint16): 2..4096, refused outside before anything is written.
  * minmax_dev (nullable, float64 input only) = precomputed [min, max] per plane (amt_gaussian / amt_minmax_f64). */
 int amt_threshold_value(amt_ctx* ctx, const void* in, int in_dtype, int method, int nbins, double* thr_dev,
                         int32_t* status_dev, int nplanes, size_t n, const double* minmax_dev);

@@ -33,7 +33,7 @@ EXEMPT = {
     **{n: "host helper (no GPU call)" for n in ("amt_host_alloc", "amt_host_copy", "amt_host_minmax_int",
                                                 "amt_host_narrow_i64_i32", "amt_host_free")},
     "amt_debug_scratch_check": "the diagnostic call of the poison pass itself",
-    "amt_nn_affine_act_bf16": "takes torch tensors; tests/test_gpu_cellpose.py covers it",
+    "amt_nn_affine_act_bf16": "takes torch tensors; tests/parameter_limits.py compares it with its definition",
 }
 
 _RESULTS: dict = {}

@@ -105,7 +105,9 @@ def test_histograms_otsu_threshold(ctx, ops, golden):
     assert tf == skops.threshold_otsu(gz)
     m = ops.greater_than(dg, ctx.asarray(np.array([tf]))).numpy()
     assert m.dtype == bool and np.array_equal(m, gz > tf)
-    # bright image: values above the LDS window of the histogram kernel
+    # bright image: values in the upper half of the range.  One small plane takes hist_u16_part_kernel (16-bit counters for
+    # all 65536 bins); the two-window hist_u16_kernel this case was written for is reached by batches of more than
+    # HIST_MAX_PARTS parts only, and is compared in tests/parameter_limits.py (the "hist_u16 ..." groups)
     big = (u.astype(np.uint32) * 5 % 65536).astype(np.uint16)
     assert np.array_equal(ops.histogram_u16(ctx.asarray(big)).numpy()[0], np.bincount(big.ravel(), minlength=65536))
     assert ops.threshold_otsu(ctx.asarray(big)).numpy()[0] == skops.threshold_otsu(big)
