@@ -46,6 +46,11 @@ RPX_WCOLS = ("centroid_weighted-0", "centroid_weighted-1", "centroid_weighted_lo
 RPX_RELATE = 1 << 8
 RPX_RCOLS = ("parent", "overlap", "partners", "area")
 RELATE_LDS_PARTNERS = 128
+# amt_regionprops_ext with AMT_RPX_ROBUST: the bit, the four columns per (label, channel) (AMT_RPX_QCOL_*) and the number
+# of LDS counters a uint16 selection spreads a label's value window over (AMT_ROBUST_LDS_BINS)
+RPX_ROBUST = 1 << 9
+RPX_QCOLS = ("q25", "median", "q75", "mad")
+ROBUST_LDS_BINS = 1024
 # amt_colocalization: the columns of a (label, channel pair) row (AMT_COLOC_*)
 COLOC_COLS = ("pearson", "overlap", "m1", "m2", "intersection1", "intersection2")
 COLOC_NCOLS = len(COLOC_COLS)

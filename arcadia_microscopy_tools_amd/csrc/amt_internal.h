@@ -153,6 +153,11 @@ enum amt_comp_what { AMT_COMP_OBJECTS_BY_AREA, AMT_COMP_HOLES_BY_AREA, AMT_COMP_
 int amt_i_component_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8,
                            amt_comp_what what, int size);
 
+// AMT_RPX_ROBUST of amt_regionprops_ext (amt_robust.hip), which checks the arguments and makes the bounding boxes:
+// wtable[plane][label][channel] = {q25, median, q75, MAD} of the AMT_U16 / AMT_F64 channel over the label
+int amt_i_robust_intensity(amt_ctx* ctx, const int* labels, const int* bbox, const void* intensity, int in_code, int C,
+                           double* wtable, int nplanes, int H, int W, int max_label);
+
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>
 static inline void amt_with_bool(bool b, F&& f) {

@@ -1479,19 +1479,21 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
     const unsigned cols = (unsigned)columns;
     const bool want_w = (cols & AMT_RPX_CENTROID_WEIGHTED) != 0;
     const bool want_r = (cols & AMT_RPX_RELATE) != 0;
-    const bool want_c = want_w || want_r;  // the call has companion planes and a per-companion table
-    const bool want_m = (cols & ~(AMT_RPX_CENTROID_WEIGHTED | AMT_RPX_RELATE)) != 0;
+    const bool want_q = (cols & AMT_RPX_ROBUST) != 0;
+    const bool want_c = want_w || want_r || want_q;  // the call has companion planes and a per-companion table
+    const bool want_m = (cols & ~(AMT_RPX_CENTROID_WEIGHTED | AMT_RPX_RELATE | AMT_RPX_ROBUST)) != 0;
     AMT_REQUIRE(labels && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && cols != 0 &&
-                    (cols & ~(AMT_RPX_ALL | AMT_RPX_RELATE)) == 0,
+                    (cols & ~(AMT_RPX_ALL | AMT_RPX_RELATE | AMT_RPX_ROBUST)) == 0,
                 "regionprops_ext: bad arguments");
-    AMT_REQUIRE(!(want_w && want_r),
-                "regionprops_ext: AMT_RPX_RELATE and AMT_RPX_CENTROID_WEIGHTED share the companion planes and their table: "
-                "one call, one of them");
+    AMT_REQUIRE((int)want_w + (int)want_r + (int)want_q <= 1,
+                "regionprops_ext: AMT_RPX_RELATE, AMT_RPX_ROBUST and AMT_RPX_CENTROID_WEIGHTED share the companion planes "
+                "and their table: one call, one of them");
     AMT_REQUIRE(!table_dev == !want_m, "regionprops_ext: the morphology table and its column bits go together");
     AMT_REQUIRE(want_c == !!intensity && want_c == !!wtable_dev && (!want_c || C >= 1),
-                "regionprops_ext: the intensity planes (C >= 1), the weighted table and AMT_RPX_CENTROID_WEIGHTED (or the "
-                "companion label planes, the relation table and AMT_RPX_RELATE) go together");
-    AMT_REQUIRE(!want_w || in_code == AMT_U16 || in_code == AMT_F64, "regionprops_ext: intensity must be AMT_U16 or AMT_F64");
+                "regionprops_ext: the intensity planes (C >= 1), the weighted table and AMT_RPX_CENTROID_WEIGHTED or "
+                "AMT_RPX_ROBUST (or the companion label planes, the relation table and AMT_RPX_RELATE) go together");
+    AMT_REQUIRE(!(want_w || want_q) || in_code == AMT_U16 || in_code == AMT_F64,
+                "regionprops_ext: intensity must be AMT_U16 or AMT_F64");
     AMT_REQUIRE(want_r == (in_code == AMT_I32),
                 "regionprops_ext: AMT_I32 companion label planes and AMT_RPX_RELATE go together");
     AMT_TRY(amt_set_device(ctx));
@@ -1572,6 +1574,7 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
                            (const int*)intensity, C, wtable_dev, H, W, max_label);
         AMT_LAUNCH_CHECK();
     }
+    if (want_q) AMT_TRY(amt_i_robust_intensity(ctx, labels, bbox, intensity, in_code, C, wtable_dev, nplanes, H, W, max_label));
     return AMT_OK;
 }
 

@@ -1152,6 +1152,8 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
             bits |= _hip.RPX_BITS[name]
     if bits & _hip.RPX_RELATE:
         raise ValueError("bit 8 (AMT_RPX_RELATE) relates two label images: call hipops.relate_labels")
+    if bits & _hip.RPX_ROBUST:
+        raise ValueError("bit 9 (AMT_RPX_ROBUST) measures quartiles and MAD per channel: call hipops.robust_intensity")
     want_w = bool(bits & _hip.RPX_WEIGHTED)
     if want_w != (intensity is not None):
         raise ValueError("weighted centroids need intensity images, and intensity images are only used for them")
@@ -1202,6 +1204,32 @@ def relate_labels(labels: DeviceArray, max_label: int, companions: DeviceArray, 
     o = _out(ctx, out, (n, max_label, C, 4), np.float64)
     _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, companions.ptr, _hip.I32, C, _hip.RPX_RELATE, None,
                                           o.ptr, n, H, W, int(max_label)), "amt_regionprops_ext")
+    return o
+
+
+def robust_intensity(labels: DeviceArray, intensity: DeviceArray, max_label: int, out=None) -> DeviceArray:
+    """Robust intensity table (nplanes, max_label, C, 4) float64 in ``_hip.RPX_QCOLS`` order (``amt_regionprops_ext``
+    with ``AMT_RPX_ROBUST``): ``np.percentile(V, 25 | 50 | 75)`` (method ``linear``) and the raw median absolute
+    deviation ``np.percentile(|V - median|, 50)`` of every channel over the pixels ``V`` of every label, bit for bit.
+
+    ``labels`` is int32 (..., Y, X); ``intensity`` is (..., C, Y, X) uint16 (exact selection on integers) or float64
+    (without NaN or infinities) with one (C, Y, X) stack per label plane.  A label absent from its plane gives four
+    NaNs; two runs give identical bytes."""
+    ctx = labels.ctx
+    n, H, W = _planes(labels)
+    if labels.dtype != np.int32:
+        raise TypeError("robust_intensity expects int32 labels")
+    if intensity.dtype not in (np.uint16, np.float64):
+        raise TypeError("intensity images must be uint16 or float64 on the device path")
+    if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
+        raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
+    C = int(intensity.shape[-3])
+    if C < 1 or intensity.size != n * C * H * W:
+        raise ValueError("intensity / labels plane count mismatch")
+    o = _out(ctx, out, (n, max_label, C, 4), np.float64)
+    code = _hip.U16 if intensity.dtype == np.uint16 else _hip.F64
+    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, intensity.ptr, code, C, _hip.RPX_ROBUST, None, o.ptr,
+                                          n, H, W, int(max_label)), "amt_regionprops_ext")
     return o
 
 

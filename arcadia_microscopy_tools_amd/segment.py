@@ -447,6 +447,14 @@ def colocalization_keys(channel_names, pairs=None) -> list[str]:
     return [f"{m}_{names[i]}_{names[j]}" for i, j in colocalization_pairs(channel_names, pairs) for m in _hip.COLOC_COLS]
 
 
+def robust_intensity_keys(channel_names) -> list[str]:
+    """The keys of ``SegmentationMask.cell_robust_intensity`` for these channels, in order (no device needed): channel
+    by channel ``f"intensity_{stat}_{channel}"`` for the statistics of ``_hip.RPX_QCOLS`` with the lower-cased channel
+    names, e.g. ``intensity_q25_dapi``, ``intensity_median_dapi``, ``intensity_q75_dapi``, ``intensity_mad_dapi``."""
+    names = [str(getattr(c, "name", c)).lower() for c in channel_names]
+    return [f"intensity_{stat}_{name}" for name in names for stat in _hip.RPX_QCOLS]
+
+
 def segment_fovs(fovs, *, ctx: Context | None = None, channel_names=DEFAULT_CHANNELS, **kw) -> SegmentationResult:
     """Convenience: (B, C, H, W) uint16 (numpy or DeviceArray) -> config-3 ``SegmentationResult``."""
     ctx = ctx or get_context()

@@ -466,6 +466,31 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
  * AMT_RPX_CENTROID_WEIGHTED is set.  A label with zero total intensity gets NaN weighted centroids; labels absent
  * from a plane get 0 in every column.
  *
+ * ---- robust intensity statistics per label: AMT_RPX_ROBUST ----
+ * With AMT_RPX_ROBUST set, intensity is nplanes x C planes of in_code AMT_U16 or AMT_F64, one (C, Y, X) stack per label
+ * plane, C >= 1, and wtable_dev = nplanes x max_label x C x 4 doubles.  For label l with the pixel multiset V of a
+ * channel the four columns are
+ *   AMT_RPX_QCOL_Q25 / AMT_RPX_QCOL_MEDIAN / AMT_RPX_QCOL_Q75
+ *                          np.percentile(V, 25 / 50 / 75), method 'linear': virtual index (n - 1) q / 100 with n = |V|,
+ *                          and numpy's lerp between the two neighbouring order statistics, bit for bit
+ *   AMT_RPX_QCOL_MAD       np.percentile(|V - median|, 50): the median absolute deviation around the column above, the
+ *                          differences taken in float64 (one rounding each); raw, without the factor 1.4826.  It is the
+ *                          50th percentile by the rule above, not np.median: for an even count those two differ in the
+ *                          last bit on float64 data
+ * For AMT_U16 every result is a multiple of 1/4 and exact; the selection runs on integer keys: the values, and
+ * |2 v - 2 median| for MAD, counted in AMT_ROBUST_LDS_BINS LDS counters per workgroup over the window [min, max] of the
+ * label (a window wider than the table is resolved by one more sweep over the label's box).  The cost per label and
+ * channel is at most 5 sweeps over its bounding box, whatever its area (up to the plane's 2^31 - 2 pixels) and values.
+ * AMT_F64 selects on order-preserving 64-bit keys, 8 bits per sweep (plain and untuned); images that hold NaN or
+ * infinities are not supported, and -0.0 sorts before +0.0.  A label absent from its plane gives four NaNs (numpy on an
+ * empty array).  Counts are integer sums: two runs give identical bytes.
+ * AMT_RPX_ROBUST together with AMT_RPX_CENTROID_WEIGHTED or AMT_RPX_RELATE is AMT_EINVAL (they share intensity and
+ * wtable_dev); the morphology bits may be combined with it, table_dev is then given and its columns equal those of a
+ * call of their own.  in_code other than AMT_U16 / AMT_F64 with the bit is AMT_EINVAL.  intensity, C >= 1 and
+ * wtable_dev are given exactly when one of AMT_RPX_CENTROID_WEIGHTED, AMT_RPX_RELATE and AMT_RPX_ROBUST is set; the
+ * accepted mask is AMT_RPX_ALL | AMT_RPX_RELATE | AMT_RPX_ROBUST.  nplanes == 0 or max_label == 0 is AMT_OK and writes
+ * nothing; every refusal happens before the first launch.
+ *
  * ---- relating two label images: AMT_RPX_RELATE ----
  * "Measure label image A with label image B as its intensity image": with AMT_RPX_RELATE set, intensity is
  * nplanes x C COMPANION LABEL planes, one (C, Y, X) stack per label plane, in_code == AMT_I32, values 0 (background)
@@ -500,6 +525,12 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
 #define AMT_RPX_RCOL_PARTNERS 2
 #define AMT_RPX_RCOL_AREA 3
 #define AMT_RELATE_LDS_PARTNERS 128
+#define AMT_RPX_ROBUST (1u << 9)
+#define AMT_RPX_QCOL_Q25 0
+#define AMT_RPX_QCOL_MEDIAN 1
+#define AMT_RPX_QCOL_Q75 2
+#define AMT_RPX_QCOL_MAD 3
+#define AMT_ROBUST_LDS_BINS 1024
 #define AMT_RPX_COL_EULER_NUMBER 0
 #define AMT_RPX_COL_PERIMETER_CROFTON 1
 #define AMT_RPX_COL_AREA_FILLED 2
