@@ -787,7 +787,7 @@ __global__ void __launch_bounds__(256) cp_seq_prepare_kernel(const int* __restri
     const int* kf = keep_flow + (size_t)blockIdx.y * (cap + 1);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         const int v = l[i];
-        o[i] = (v > 0 && kf[v]) ? v : 0;
+        o[i] = (v > 0 && v <= cap && kf[v]) ? v : 0;  // values above max_label are background (and index no flag)
     }
 }
 
@@ -869,7 +869,7 @@ static int cp_finish(amt_ctx* ctx, const cp_finish_scratch& fs, int32_t* labels_
 
 extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out,
                                      int32_t* count_dev, int nplanes, int H, int W, float cellprob_threshold, int niter,
-                                     int min_size, float max_size_fraction, int max_seeds, float flow_threshold,
+                                     int min_size, double max_size_fraction, int max_seeds, float flow_threshold,
                                      int fill_holes) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(dP && cellprob && labels_out && count_dev && nplanes >= 0, "cellpose_masks: bad arguments");
@@ -940,7 +940,9 @@ extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float*
     AMT_LAUNCH_CHECK();
     hipLaunchKernelGGL(cp_assign_kernel, gpx, dim3(256), 0, ctx->stream, pos, M, labels_out, count, first, n, Wp, hn, cap);
     AMT_LAUNCH_CHECK();
-    const long long big = (long long)((double)n * (double)max_size_fraction);
+    // int(H * W * max_size_fraction) in float64, as get_masks takes it: the fraction arrives as a double (as a float, 0.01
+    // of 2,000 pixels was 19.9999995 and a mask of exactly 20 pixels was dropped)
+    const long long big = (long long)((double)n * max_size_fraction);
     // with the later stages, get_masks applies only its size ceiling; the floor belongs to step 6
     hipLaunchKernelGGL(cp_map_kernel, dim3(amt_grid_for((size_t)cap, 256, 64), nplanes), dim3(256), 0, ctx->stream, count,
                        first, nseeds, map, count_dev, cap, post ? 0 : min_size, big);
@@ -1023,6 +1025,8 @@ extern "C" int amt_cellpose_flow_error(amt_ctx* ctx, const int32_t* labels, cons
     amt_buf<double> TA(s, (size_t)nplanes * n);
     amt_buf<double> TB(s, (size_t)nplanes * n);
     AMT_TRY(s.commit());
+    // cp_flow_error_kernel writes the slots 1..nlabels_dev[plane]; the slots up to max_label are handed out too: absent, 0
+    AMT_HIP_CHECK(hipMemsetAsync(err, 0, nl * 8, ctx->stream));
     AMT_TRY(cp_flow_errors(ctx, labels, dP, nlabels_dev, box, cnt, sums, center, nit, TA, TB, err, nplanes, H, W, cap, true));
     // err is (cap + 1) per plane with slot 0 unused: hand out slots 1..cap
     for (int p = 0; p < nplanes; ++p)

@@ -1302,7 +1302,8 @@ def cellpose_masks(dP: DeviceArray, cellprob: DeviceArray, cellprob_threshold: f
     unpinned): ``dP`` (..., 2, Y, X) float32 flows (dY, dX), ``cellprob`` (..., Y, X) float32 -> (int32 labels, counts).
     ``flow_threshold`` > 0 adds the flow-error filter (``remove_bad_flow_masks``), ``fill_holes`` the hole filling of
     ``fill_holes_and_remove_small_masks``; with neither, only the dynamics and the size filters run.  A plane that
-    produces more than ``max_seeds`` seeds reports count -1."""
+    produces more than ``max_seeds`` seeds reports count -1.  The size ceiling is ``int(Y * X * max_size_fraction)`` in
+    float64 (the fraction crosses the C interface as a double)."""
     ctx = dP.ctx
     if dP.dtype != np.float32 or cellprob.dtype != np.float32:
         raise TypeError("cellpose_masks expects float32 flows and cell probabilities")

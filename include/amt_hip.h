@@ -637,10 +637,11 @@ int amt_borders_emit(amt_ctx* ctx, const int32_t* labels, int H, int W, int nlab
  * flow_threshold == 0 and fill_holes == 0 stops after the first stage.  PARITY UNPINNED: cellpose is not available
  * offline and the reference holds no vector for it (oracle: oracle/cellpose_dynamics.py).
  *   dP = nplanes x 2 x H x W float32 (dY, dX), cellprob = nplanes x H x W float32, labels_out = nplanes x H x W int32,
- *   count_dev[plane] = number of masks, or -1 if the plane produced more than max_seeds seeds. */
+ *   count_dev[plane] = number of masks, or -1 if the plane produced more than max_seeds seeds.
+ *   max_size_fraction is a double: the ceiling is (long long)(H * W * max_size_fraction) in float64, as get_masks takes it. */
 int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float* cellprob, int32_t* labels_out, int32_t* count_dev,
                           int nplanes, int H, int W, float cellprob_threshold, int niter, int min_size,
-                          float max_size_fraction, int max_seeds, float flow_threshold, int fill_holes);
+                          double max_size_fraction, int max_seeds, float flow_threshold, int fill_holes);
 /* cellpose.utils.fill_holes_and_remove_small_masks on its own (the last step of amt_cellpose_masks_ex): labels_io =
  * nplanes x H x W int32 carrying labels 1..nlabels_dev[plane] (<= max_label; gaps allowed, larger values are treated as
  * background), in place: labels in ascending order, those with fewer than min_size pixels dropped, (fill_holes != 0)
@@ -649,7 +650,7 @@ int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float* cellprob, 
 int amt_fill_holes_remove_small(amt_ctx* ctx, int32_t* labels_io, const int32_t* nlabels_dev, int32_t* count_dev,
                                 int nplanes, int H, int W, int max_label, int min_size, int fill_holes);
 /* metrics.flow_error of cellpose on its own: labels = nplanes x H x W int32 carrying 1..nlabels_dev[plane] (<= max_label),
- * dP as above; err_out = nplanes x max_label float64 (absent labels 0). */
+ * dP as above; err_out = nplanes x max_label float64 (absent labels 0, the slots above nlabels_dev[plane] included). */
 int amt_cellpose_flow_error(amt_ctx* ctx, const int32_t* labels, const float* dP, const int32_t* nlabels_dev,
                             double* err_out, int nplanes, int H, int W, int max_label);
 
