@@ -76,6 +76,54 @@ void amt_set_error(const char* fmt, ...);
         if (_rc != AMT_OK) return _rc; \
     } while (0)
 
+// ---- operand aliasing (include/amt_hip.h, Conventions) ---------------------------------------------------------
+// Every entry point that writes device memory hands its device operands to amt_check_operands FIRST: before the context
+// is touched and before anything is reserved or launched (a refusal needs no device; a few pointer comparisons on the
+// host, no launch, no synchronisation).  Inputs may overlap inputs.  An output -- caller-owned scratch and in/out planes
+// included -- must not overlap any other operand, except that it may COINCIDE with the inputs named in `inplace` (a mask
+// over the indices of the operand list): same start, same byte length, same element size.  A null pointer or a length of
+// zero is an absent operand.
+struct amt_operand {
+    const char* name;
+    const void* ptr;
+    size_t bytes;
+    bool output;
+    unsigned inplace;  // outputs: bit i set = may coincide exactly with operand i of the list
+    size_t elem;       // element size, compared for an in-place pair
+};
+static inline amt_operand amt_in(const char* name, const void* p, size_t bytes, size_t elem = 1) {
+    return amt_operand{name, p, bytes, false, 0u, elem};
+}
+static inline amt_operand amt_out(const char* name, const void* p, size_t bytes, unsigned inplace = 0u, size_t elem = 1) {
+    return amt_operand{name, p, bytes, true, inplace, elem};
+}
+// elem * a * b * c * d bytes; 0 when a factor is not positive (the entry point's own argument checks refuse those)
+static inline size_t amt_span(size_t elem, long long a, long long b = 1, long long c = 1, long long d = 1) {
+    if (a <= 0 || b <= 0 || c <= 0 || d <= 0 || elem == 0) return 0;
+    const long long f[4] = {a, b, c, d};
+    size_t n = elem;
+    for (long long v : f) {
+        if (n > (SIZE_MAX >> 1) / (size_t)v) return SIZE_MAX >> 1;
+        n *= (size_t)v;
+    }
+    return n;
+}
+static inline size_t amt_esize(int dtype) {
+    switch (dtype) {
+        case AMT_U8: return 1;
+        case AMT_U16: return 2;
+        case AMT_I32: case AMT_F32: return 4;
+        case AMT_F64: case AMT_I64: return 8;
+        default: return 0;  // an unknown code: the operand counts as absent, the entry point refuses the code
+    }
+}
+int amt_check_operands(const char* op, const amt_operand* ops, int n);
+#define AMT_CHECK_OPERANDS(op, ...)                                                              \
+    do {                                                                                         \
+        const amt_operand _ops[] = {__VA_ARGS__};                                                \
+        AMT_TRY(amt_check_operands(op, _ops, (int)(sizeof(_ops) / sizeof(_ops[0]))));            \
+    } while (0)
+
 // ---- scratch ----------------------------------------------------------------------------------
 // An op declares its buffers into an amt_scratch (amt_scratch_plan.h: the layout rule), then commits once: commit()
 // reserves exactly the declared total in the context's arena (may reallocate: synchronises the stream first) and only

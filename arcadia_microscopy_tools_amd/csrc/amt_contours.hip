@@ -219,6 +219,10 @@ __global__ void __launch_bounds__(64) contours_emit_kernel(const int* __restrict
 extern "C" int amt_contours_find(amt_ctx* ctx, const int32_t* labels, int H, int W, int nlab, const int32_t* boxes_dev,
                                  const int64_t* voff_dev, uint8_t* visited_dev, size_t visited_bytes,
                                  int32_t* info_dev) {
+    AMT_CHECK_OPERANDS("amt_contours_find", amt_in("labels", labels, amt_span(4, H, W)), amt_in("boxes_dev", boxes_dev, amt_span(4, nlab, 5)),
+                       amt_in("voff_dev", voff_dev, amt_span(8, (long long)nlab + 1)),
+                       amt_out("visited_dev", visited_dev, amt_span(1, (long long)visited_bytes)),
+                       amt_out("info_dev", info_dev, amt_span(4, nlab, 4)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && H > 0 && W > 0 && nlab >= 0, "contours_find: bad arguments");
     if (nlab == 0) return AMT_OK;
@@ -232,6 +236,10 @@ extern "C" int amt_contours_find(amt_ctx* ctx, const int32_t* labels, int H, int
 
 extern "C" int amt_contours_emit(amt_ctx* ctx, const int32_t* labels, int H, int W, int nlab, const int32_t* boxes_dev,
                                  const int32_t* info_dev, const int64_t* poff_dev, double* points_dev) {
+    // the length of points_dev is poff_dev[nlab], which only the device knows: the check sees its first point
+    AMT_CHECK_OPERANDS("amt_contours_emit", amt_in("labels", labels, amt_span(4, H, W)), amt_in("boxes_dev", boxes_dev, amt_span(4, nlab, 5)),
+                       amt_in("info_dev", info_dev, amt_span(4, nlab, 4)), amt_in("poff_dev", poff_dev, amt_span(8, (long long)nlab + 1)),
+                       amt_out("points_dev", points_dev, nlab > 0 ? 16 : 0));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && H > 0 && W > 0 && nlab >= 0, "contours_emit: bad arguments");
     if (nlab == 0) return AMT_OK;
@@ -389,6 +397,8 @@ __global__ void __launch_bounds__(64) borders_emit_kernel(const int* __restrict_
 
 extern "C" int amt_borders_find(amt_ctx* ctx, const int32_t* labels, int H, int W, int nlab, const int32_t* boxes_dev,
                                 int8_t* marks_dev, int32_t* info_dev) {
+    AMT_CHECK_OPERANDS("amt_borders_find", amt_in("labels", labels, amt_span(4, H, W)), amt_in("boxes_dev", boxes_dev, amt_span(4, nlab, 5)),
+                       amt_out("marks_dev", marks_dev, nlab > 0 ? amt_span(1, H, W) : 0), amt_out("info_dev", info_dev, amt_span(4, nlab, 3)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && H > 0 && W > 0 && nlab >= 0, "borders_find: bad arguments");
     if (nlab == 0) return AMT_OK;
@@ -402,6 +412,10 @@ extern "C" int amt_borders_find(amt_ctx* ctx, const int32_t* labels, int H, int 
 
 extern "C" int amt_borders_emit(amt_ctx* ctx, const int32_t* labels, int H, int W, int nlab, const int32_t* boxes_dev,
                                 const int32_t* info_dev, const int64_t* poff_dev, int32_t* points_dev) {
+    // the length of points_dev is poff_dev[nlab], which only the device knows: the check sees its first point
+    AMT_CHECK_OPERANDS("amt_borders_emit", amt_in("labels", labels, amt_span(4, H, W)), amt_in("boxes_dev", boxes_dev, amt_span(4, nlab, 5)),
+                       amt_in("info_dev", info_dev, amt_span(4, nlab, 3)), amt_in("poff_dev", poff_dev, amt_span(8, (long long)nlab + 1)),
+                       amt_out("points_dev", points_dev, nlab > 0 ? 8 : 0));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && H > 0 && W > 0 && nlab >= 0, "borders_emit: bad arguments");
     if (nlab == 0) return AMT_OK;

@@ -12,6 +12,37 @@ void amt_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
+int amt_check_operands(const char* op, const amt_operand* ops, int n) {
+    for (int i = 0; i < n; ++i) {
+        const amt_operand& a = ops[i];
+        if (!a.ptr || !a.bytes) continue;
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.ptr);
+        const uintptr_t a1 = a.bytes > UINTPTR_MAX - a0 ? UINTPTR_MAX : a0 + a.bytes;
+        for (int j = i + 1; j < n; ++j) {
+            const amt_operand& b = ops[j];
+            if (!b.ptr || !b.bytes || !(a.output || b.output)) continue;
+            const uintptr_t b0 = reinterpret_cast<uintptr_t>(b.ptr);
+            const uintptr_t b1 = b.bytes > UINTPTR_MAX - b0 ? UINTPTR_MAX : b0 + b.bytes;
+            if (a1 <= b0 || b1 <= a0) continue;
+            const amt_operand& o = a.output ? a : b;   // the output of the pair names it first
+            const amt_operand& x = a.output ? b : a;
+            const bool allowed = (a.output && !b.output && ((a.inplace >> j) & 1u)) ||
+                                 (b.output && !a.output && ((b.inplace >> i) & 1u));
+            if (!allowed) {
+                amt_set_error("%s: %s must not alias %s, nor overlap it in part", op, o.name, x.name);
+                return AMT_EINVAL;
+            }
+            if (a0 != b0 || a.bytes != b.bytes || a.elem != b.elem) {
+                amt_set_error("%s: %s may alias %s only in place (same start, same length, same element size); this "
+                              "overlap is partial",
+                              op, o.name, x.name);
+                return AMT_EINVAL;
+            }
+        }
+    }
+    return AMT_OK;
+}
+
 extern "C" const char* amt_last_error(void) { return g_err; }
 extern "C" const char* amt_version(void) { return "amt_hip 0.1 (gfx950)"; }
 

@@ -871,6 +871,11 @@ extern "C" int amt_cellpose_masks_ex(amt_ctx* ctx, const float* dP, const float*
                                      int32_t* count_dev, int nplanes, int H, int W, float cellprob_threshold, int niter,
                                      int min_size, double max_size_fraction, int max_seeds, float flow_threshold,
                                      int fill_holes) {
+    // cellprob (float32) and labels_out (int32) are both 4 bytes per pixel: the labels onto the probabilities would fit
+    AMT_CHECK_OPERANDS("amt_cellpose_masks_ex", amt_in("dP", dP, amt_span(4, nplanes, 2, H, W)),
+                       amt_in("cellprob", cellprob, amt_span(4, nplanes, H, W)),
+                       amt_out("labels_out", labels_out, amt_span(4, nplanes, H, W)),
+                       amt_out("count_dev", count_dev, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(dP && cellprob && labels_out && count_dev && nplanes >= 0, "cellpose_masks: bad arguments");
     AMT_REQUIRE(H >= 2 && W >= 2 && H + 2 * CP_RPAD < 65536 && W + 2 * CP_RPAD < 65536,
@@ -1008,6 +1013,9 @@ static int cp_finish(amt_ctx* ctx, const cp_finish_scratch& fs, int32_t* labels_
 
 extern "C" int amt_cellpose_flow_error(amt_ctx* ctx, const int32_t* labels, const float* dP, const int32_t* nlabels_dev,
                                        double* err_out, int nplanes, int H, int W, int max_label) {
+    AMT_CHECK_OPERANDS("amt_cellpose_flow_error", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
+                       amt_in("dP", dP, amt_span(4, nplanes, 2, H, W)), amt_in("nlabels_dev", nlabels_dev, amt_span(4, nplanes)),
+                       amt_out("err_out", err_out, amt_span(8, nplanes, max_label)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && dP && nlabels_dev && err_out && nplanes >= 0 && H >= 1 && W >= 1 && max_label >= 1,
                 "cellpose_flow_error: bad arguments");
@@ -1037,6 +1045,9 @@ extern "C" int amt_cellpose_flow_error(amt_ctx* ctx, const int32_t* labels, cons
 
 extern "C" int amt_fill_holes_remove_small(amt_ctx* ctx, int32_t* labels_io, const int32_t* nlabels_dev, int32_t* count_dev,
                                            int nplanes, int H, int W, int max_label, int min_size, int fill_holes) {
+    // labels_io is in/out by design; it must not overlap the counts on either side
+    AMT_CHECK_OPERANDS("amt_fill_holes_remove_small", amt_out("labels_io", labels_io, amt_span(4, nplanes, H, W)),
+                       amt_in("nlabels_dev", nlabels_dev, amt_span(4, nplanes)), amt_out("count_dev", count_dev, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels_io && nlabels_dev && count_dev && nplanes >= 0 && H >= 1 && W >= 1 && max_label >= 1 && min_size >= 0,
                 "fill_holes_remove_small: bad arguments");

@@ -231,6 +231,8 @@ __global__ void __launch_bounds__(256) edt_bits_kernel(const unsigned long long*
 
 extern "C" int amt_edt(amt_ctx* ctx, const uint8_t* mask, int32_t* d2_out, double* edt_out, int nplanes, int H,
                        int W) {
+    AMT_CHECK_OPERANDS("amt_edt", amt_in("mask", mask, amt_span(1, nplanes, H, W)), amt_out("d2_out", d2_out, amt_span(4, nplanes, H, W)),
+                       amt_out("edt_out", edt_out, amt_span(8, nplanes, H, W)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(mask && (d2_out || edt_out) && nplanes >= 0 && H > 0 && W > 0, "edt: bad arguments");
     AMT_REQUIRE(H <= 32768 && W <= 32768, "edt: image larger than 32768 pixels per side");
@@ -385,6 +387,12 @@ extern "C" int amt_peak_mask(amt_ctx* ctx, const int32_t* d2, const uint8_t* mas
     AMT_REQUIRE(!prev_list == !prev_count && !prev_list == !prev_status,
                 "peak_mask: the previous run's peak lists, counts and label counts go together");
     AMT_REQUIRE(!prev_list || capacity >= 1, "peak_mask: the previous run's list capacity must be positive");
+    // mask and peaks are both byte planes: peaks onto the mask would pass every type check
+    AMT_CHECK_OPERANDS("amt_peak_mask", amt_in("d2", d2, amt_span(4, nplanes, H, W)), amt_in("mask", mask, amt_span(1, nplanes, H, W)),
+                       amt_out("peaks", peaks, amt_span(1, nplanes, H, W)),
+                       amt_in("prev_list", prev_list, amt_span(4, nplanes, capacity)),
+                       amt_in("prev_count", prev_count, amt_span(4, nplanes)),
+                       amt_in("prev_status", prev_status, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(d2 && mask && peaks && nplanes >= 0 && H > 0 && W > 0, "peak_mask: bad arguments");
     AMT_REQUIRE(min_distance >= 0 && min_distance <= PK_MAXM, "peak_mask: min_distance %d out of range 0..%d",
@@ -575,6 +583,11 @@ extern "C" int amt_peak_markers(amt_ctx* ctx, const int32_t* d2, const uint8_t* 
                                 int32_t* count_dev, int nplanes, int H, int W, int min_distance, int connectivity,
                                 int capacity, int32_t* keep_list, int32_t* keep_count) {
     AMT_REQUIRE(!keep_list == !keep_count, "peak_markers: keep_list and keep_count go together");
+    AMT_CHECK_OPERANDS("amt_peak_markers", amt_in("d2", d2, amt_span(4, nplanes, H, W)), amt_in("mask", mask, amt_span(1, nplanes, H, W)),
+                       amt_out("peaks", peaks, amt_span(1, nplanes, H, W)), amt_out("markers", markers, amt_span(4, nplanes, H, W)),
+                       amt_out("count_dev", count_dev, amt_span(4, nplanes)),
+                       amt_out("keep_list", keep_list, amt_span(4, nplanes, capacity)),
+                       amt_out("keep_count", keep_count, amt_span(4, nplanes)));
     AMT_REQUIRE(d2 && mask && peaks && markers && count_dev && nplanes >= 0 && H > 0 && W > 0,
                 "peak_markers: bad arguments");
     AMT_REQUIRE(min_distance >= 0 && min_distance <= PK_MAXM, "peak_markers: min_distance %d out of range 0..%d",

@@ -263,8 +263,10 @@ __global__ void __launch_bounds__(256) expand_labels_kernel(const unsigned long 
 
 extern "C" int amt_expand_labels(amt_ctx* ctx, const int32_t* labels, int32_t* out, int nplanes, int H, int W, int64_t nmax,
                                  int ring) {
+    AMT_CHECK_OPERANDS("amt_expand_labels", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
+                       amt_out("out", out, amt_span(4, nplanes, H, W)));
     AMT_TRY(amt_set_device(ctx));
-    AMT_REQUIRE(labels && out && labels != out && nplanes >= 0 && H > 0 && W > 0, "expand_labels: bad arguments");
+    AMT_REQUIRE(labels && out && nplanes >= 0 && H > 0 && W > 0, "expand_labels: bad arguments");
     AMT_REQUIRE(H <= 32768 && W <= 32768, "expand_labels: image larger than 32768 pixels per side");
     AMT_REQUIRE(nplanes <= 65535, "expand_labels: more than 65535 planes in one call");
     if (nplanes == 0) return AMT_OK;
@@ -300,6 +302,9 @@ __global__ void __launch_bounds__(256) cast_labels_kernel(const TI* __restrict__
 }
 
 extern "C" int amt_cast_labels(amt_ctx* ctx, const void* in, int in_dtype, void* out, int out_dtype, size_t n) {
+    // the two element sizes differ for every pair the cast accepts: never in place
+    AMT_CHECK_OPERANDS("amt_cast_labels", amt_in("in", in, amt_span(amt_esize(in_dtype), (long long)n)),
+                       amt_out("out", out, amt_span(amt_esize(out_dtype), (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out, "cast_labels: bad arguments");
     if (n == 0) return AMT_OK;

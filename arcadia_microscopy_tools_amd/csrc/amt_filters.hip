@@ -1070,6 +1070,7 @@ __global__ void copy_f64_kernel(const double* __restrict__ in, double* __restric
 }
 
 extern "C" int amt_convert_u16_f64(amt_ctx* ctx, const uint16_t* in, double scale, double* out, size_t n) {
+    AMT_CHECK_OPERANDS("amt_convert_u16_f64", amt_in("in", in, amt_span(2, (long long)n)), amt_out("out", out, amt_span(8, (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out, "convert_u16_f64: null pointer");
     if (n == 0) return AMT_OK;
@@ -1082,6 +1083,17 @@ extern "C" int amt_convert_u16_f64(amt_ctx* ctx, const uint16_t* in, double scal
 extern "C" int amt_gaussian(amt_ctx* ctx, const void* in, int in_dtype, double scale, double* out, int nplanes, int H,
                             int W, const double* weights, int radius, int mode, double cval, size_t in_plane_stride,
                             double* minmax_dev) {
+    {
+        // the input's planes lie in_plane_stride elements apart: its span reaches from the first plane to the end of the last
+        const size_t esz = amt_esize(in_dtype == AMT_U16 ? AMT_U16 : AMT_F64), plane = amt_span(esz, H, W);
+        size_t in_bytes = amt_span(esz, nplanes, H, W);
+        if (in_plane_stride > (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) && plane && nplanes > 0)
+            in_bytes = amt_span(esz, nplanes - 1, (long long)in_plane_stride) + plane;
+        // no pair in place: the fused kernel (radius <= FR_MAX) reads a halo its neighbour tiles overwrite; the two-pass
+        // form goes through scratch, and the contract does not depend on which of them the radius picks
+        AMT_CHECK_OPERANDS("amt_gaussian", amt_in("in", in, in_bytes), amt_out("out", out, amt_span(8, nplanes, H, W)),
+                           amt_out("minmax_dev", minmax_dev, amt_span(8, nplanes, 2)));
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_TRY(check_gauss_args(in, in_dtype, out, nplanes, H, W, weights, radius));
     AMT_REQUIRE(in_plane_stride == 0 || in_plane_stride >= (size_t)H * W, "gaussian: in_plane_stride smaller than a plane");
@@ -1424,6 +1436,17 @@ extern "C" int amt_gaussian_otsu_codes(amt_ctx* ctx, const uint16_t* in, double 
                                        const double* weights, int radius, int mode, size_t in_plane_stride,
                                        double* minmax_dev, uint32_t* hist_dev, double* thr_dev, double* thr_code_dev,
                                        uint16_t* codes, uint32_t* prefix) {
+    {
+        const size_t plane = amt_span(2, H, W);
+        size_t in_bytes = amt_span(2, nplanes, H, W);
+        if (in_plane_stride > (size_t)(H > 0 ? H : 0) * (size_t)(W > 0 ? W : 0) && plane && nplanes > 0)
+            in_bytes = amt_span(2, nplanes - 1, (long long)in_plane_stride) + plane;
+        AMT_CHECK_OPERANDS("amt_gaussian_otsu_codes", amt_in("in", in, in_bytes),
+                           amt_out("minmax_dev", minmax_dev, amt_span(8, nplanes, 2)),
+                           amt_out("hist_dev", hist_dev, amt_span(4, nplanes, 256)), amt_out("thr_dev", thr_dev, amt_span(8, nplanes)),
+                           amt_out("thr_code_dev", thr_code_dev, amt_span(8, nplanes)),
+                           amt_out("codes", codes, amt_span(2, nplanes, H, W)), amt_out("prefix", prefix, amt_span(4, nplanes, H, W)));
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && weights && minmax_dev && hist_dev && thr_dev && thr_code_dev && codes && nplanes >= 0,
                 "gaussian_otsu_codes: bad arguments");
@@ -1482,10 +1505,11 @@ __global__ void sub_inplace_kernel(double* __restrict__ a, const double* __restr
 // filters the axes of an n-D image one after the other, leading axes first; the last two axes go through amt_gaussian).
 extern "C" int amt_convolve_axis0(amt_ctx* ctx, const void* in, int in_dtype, double scale, double* out, int nplanes, int L,
                                   int inner, const double* weights, int radius, int mode, double cval) {
+    AMT_CHECK_OPERANDS("amt_convolve_axis0", amt_in("in", in, amt_span(in_dtype == AMT_U16 ? 2 : 8, nplanes, L, inner)),
+                       amt_out("out", out, amt_span(8, nplanes, L, inner)));
     AMT_TRY(amt_set_device(ctx));
     AMT_TRY(check_gauss_args(in, in_dtype, out, nplanes, L, inner, weights, radius));
     AMT_REQUIRE(radius >= 1, "convolve_axis0: radius must be >= 1");
-    AMT_REQUIRE((const void*)in != (const void*)out, "convolve_axis0: in-place operation is not supported");
     if (nplanes == 0) return AMT_OK;
     const int r = radius;
     amt_scratch s(ctx);
@@ -1509,6 +1533,9 @@ extern "C" int amt_convolve_axis0(amt_ctx* ctx, const void* in, int in_dtype, do
 
 extern "C" int amt_dog(amt_ctx* ctx, const void* in, int in_dtype, double scale, double* out, int nplanes, int H,
                        int W, const double* w_lo, int r_lo, const double* w_hi, int r_hi, int mode, double cval) {
+    // the first Gaussian is written to `out` before the second reads `in`: never in place
+    AMT_CHECK_OPERANDS("amt_dog", amt_in("in", in, amt_span(in_dtype == AMT_U16 ? 2 : 8, nplanes, H, W)),
+                       amt_out("out", out, amt_span(8, nplanes, H, W)));
     AMT_TRY(amt_set_device(ctx));
     AMT_TRY(check_gauss_args(in, in_dtype, out, nplanes, H, W, w_lo, r_lo));
     AMT_TRY(check_gauss_args(in, in_dtype, out, nplanes, H, W, w_hi, r_hi));
@@ -1539,8 +1566,8 @@ extern "C" int amt_dog(amt_ctx* ctx, const void* in, int in_dtype, double scale,
 }
 
 // ---- elementwise -------------------------------------------------------------------------------
-__global__ void sub_clip0_kernel(const double* __restrict__ in, const double* __restrict__ level,
-                                 double* __restrict__ out, size_t n) {
+// out may be in itself (amt_sub_clip0_f64 allows the pair in place): neither carries __restrict__
+__global__ void sub_clip0_kernel(const double* in, const double* __restrict__ level, double* out, size_t n) {
     const double lv = level[blockIdx.y];
     const size_t base = (size_t)blockIdx.y * n;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1554,6 +1581,10 @@ __global__ void sub_clip0_kernel(const double* __restrict__ in, const double* __
 
 extern "C" int amt_sub_clip0_f64(amt_ctx* ctx, const double* in, const double* level_dev, double* out, int nplanes,
                                  size_t n) {
+    // in place: one kernel, element i of `in` -> element i of `out` within one thread (operations.subtract_background_dog)
+    AMT_CHECK_OPERANDS("amt_sub_clip0_f64", amt_in("in", in, amt_span(8, nplanes, (long long)n), 8),
+                       amt_in("level_dev", level_dev, amt_span(8, nplanes)),
+                       amt_out("out", out, amt_span(8, nplanes, (long long)n), 1u << 0, 8));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && level_dev && out, "sub_clip0: null pointer");
     if (nplanes == 0 || n == 0) return AMT_OK;
@@ -1567,8 +1598,8 @@ extern "C" int amt_sub_clip0_f64(amt_ctx* ctx, const double* in, const double* l
 // (np.clip of a uint16 array with float bounds yields float64), then (image - imin) / (imax - imin),
 // then * (omax - omin) + omin.  imin == imax -> clip(image, omin, omax).
 template <typename TIn>
-__global__ void rescale_kernel(const TIn* __restrict__ in, const double* __restrict__ range, double omin, double omax,
-                               double* __restrict__ out, size_t n) {
+__global__ void rescale_kernel(const TIn* in, const double* __restrict__ range, double omin, double omax, double* out,
+                               size_t n) {  // a float64 `in` may be `out` itself: no __restrict__ on the pair
     const double imin = range[2 * blockIdx.y], imax = range[2 * blockIdx.y + 1];
     const size_t base = (size_t)blockIdx.y * n;
     const double den = imax - imin;
@@ -1590,6 +1621,10 @@ __global__ void rescale_kernel(const TIn* __restrict__ in, const double* __restr
 
 extern "C" int amt_rescale(amt_ctx* ctx, const void* in, int in_dtype, const double* range_dev, double omin,
                            double omax, double* out, int nplanes, size_t n) {
+    // in place for float64 input (the element sizes agree): one kernel, element i -> element i within one thread
+    AMT_CHECK_OPERANDS("amt_rescale", amt_in("in", in, amt_span(amt_esize(in_dtype), nplanes, (long long)n), amt_esize(in_dtype)),
+                       amt_in("range_dev", range_dev, amt_span(8, nplanes, 2)),
+                       amt_out("out", out, amt_span(8, nplanes, (long long)n), 1u << 0, 8));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && range_dev && out, "rescale: null pointer");
     AMT_REQUIRE(in_dtype == AMT_U16 || in_dtype == AMT_F64, "rescale: in_dtype must be AMT_U16 or AMT_F64");
@@ -1606,13 +1641,19 @@ extern "C" int amt_rescale(amt_ctx* ctx, const void* in, int in_dtype, const dou
 }
 
 template <typename T>
-__global__ void subtract_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t n) {
+__global__ void subtract_kernel(const T* a, const T* b, T* out, size_t n) {  // out may be a or b: no __restrict__
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t stride = (size_t)gridDim.x * blockDim.x;
     for (; i < n; i += stride) out[i] = (T)(a[i] - b[i]);
 }
 
 extern "C" int amt_subtract(amt_ctx* ctx, const void* a, const void* b, void* out, int dtype, size_t n) {
+    {
+        // in place with a, with b or with both (amt_rank_filter's white top-hat subtracts into its own output)
+        const size_t e = amt_esize(dtype), bytes = amt_span(e, (long long)n);
+        AMT_CHECK_OPERANDS("amt_subtract", amt_in("a", a, bytes, e), amt_in("b", b, bytes, e),
+                           amt_out("out", out, bytes, (1u << 0) | (1u << 1), e));
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(a && b && out, "subtract: null pointer");
     if (n == 0) return AMT_OK;
@@ -1652,6 +1693,8 @@ __global__ void deinterleave_u16_kernel(const uint16_t* __restrict__ yxc, uint16
 
 extern "C" int amt_deinterleave_u16(amt_ctx* ctx, const uint16_t* yxc, uint16_t* cyx, int nplanes, int H, int W,
                                     int C) {
+    AMT_CHECK_OPERANDS("amt_deinterleave_u16", amt_in("yxc", yxc, amt_span(2, nplanes, H, W, C)),
+                       amt_out("cyx", cyx, amt_span(2, nplanes, H, W, C)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(yxc && cyx && H > 0 && W > 0 && C > 0, "deinterleave: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -1662,13 +1705,15 @@ extern "C" int amt_deinterleave_u16(amt_ctx* ctx, const uint16_t* yxc, uint16_t*
     return AMT_OK;
 }
 
-__global__ void add_scalar_kernel(const double* __restrict__ in, double s, double* __restrict__ out, size_t n) {
+__global__ void add_scalar_kernel(const double* in, double s, double* out, size_t n) {  // out may be in: no __restrict__
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         out[i] = in[i] + s;
 }
 
 // out = in + s  (threshold_local's "thresh_image - offset", SK/filters/thresholding.py:236)
 extern "C" int amt_add_scalar_f64(amt_ctx* ctx, const double* in, double s, double* out, size_t n) {
+    AMT_CHECK_OPERANDS("amt_add_scalar_f64", amt_in("in", in, amt_span(8, (long long)n), 8),
+                       amt_out("out", out, amt_span(8, (long long)n), 1u << 0, 8));  // in place: element i -> element i
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out, "add_scalar_f64: null pointer");
     if (n == 0) return AMT_OK;
@@ -1704,6 +1749,10 @@ __global__ void pad_edge_kernel(const uint8_t* __restrict__ src, uint8_t* __rest
 
 extern "C" int amt_pad_edge(amt_ctx* ctx, const void* src, void* dst, int elem_size, int nplanes, int H, int W, int py,
                             int px) {
+    // source and destination differ in size: H x W against (H + 2 py) x (W + 2 px) per plane
+    AMT_CHECK_OPERANDS("amt_pad_edge", amt_in("src", src, amt_span(elem_size > 0 ? elem_size : 0, nplanes, H, W)),
+                       amt_out("dst", dst, amt_span(elem_size > 0 ? elem_size : 0, nplanes, (long long)H + 2ll * (py > 0 ? py : 0),
+                                                    (long long)W + 2ll * (px > 0 ? px : 0))));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(src && dst && elem_size > 0 && nplanes >= 0 && H > 0 && W > 0 && py >= 0 && px >= 0,
                 "pad_edge: bad arguments");
@@ -1718,6 +1767,9 @@ extern "C" int amt_pad_edge(amt_ctx* ctx, const void* src, void* dst, int elem_s
 
 extern "C" int amt_copy_rect(amt_ctx* ctx, const void* src, void* dst, int elem_size, int nplanes, int H, int W,
                              int top, int left, int h, int w) {
+    // the source is the whole H x W batch, the destination h x w per plane
+    AMT_CHECK_OPERANDS("amt_copy_rect", amt_in("src", src, amt_span(elem_size > 0 ? elem_size : 0, nplanes, H, W)),
+                       amt_out("dst", dst, amt_span(elem_size > 0 ? elem_size : 0, nplanes, h, w)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(src && dst && elem_size > 0 && nplanes >= 0 && H > 0 && W > 0, "copy_rect: bad arguments");
     AMT_REQUIRE(top >= 0 && left >= 0 && h >= 0 && w >= 0 && top + h <= H && left + w <= W,

@@ -996,12 +996,14 @@ __global__ void __launch_bounds__(256) apply_rank_kernel(const int* __restrict__
 // "other byte values" flag and none of the byte kernels that stand by for it
 static int label_impl(amt_ctx* ctx, const void* in, int in_dtype, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
                       int connectivity, bool truth) {
+    AMT_CHECK_OPERANDS(truth ? "amt_label_mask" : "amt_label",
+                       amt_in(truth ? "mask" : "in", in, amt_span(in_dtype == AMT_I32 ? 4 : 1, nplanes, H, W)),
+                       amt_out("out", out, amt_span(4, nplanes, H, W)), amt_out("count_dev", count_dev, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "label: bad arguments");
     AMT_REQUIRE(in_dtype == AMT_U8 || in_dtype == AMT_I32, "label: in_dtype must be AMT_U8 or AMT_I32");
     AMT_REQUIRE(connectivity == 1 || connectivity == 2, "label: connectivity must be 1 or 2");
     AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "label: plane too large");
-    AMT_REQUIRE((const void*)in != (const void*)out, "label: in-place operation is not supported");
     if (nplanes == 0) return AMT_OK;
     const ccl_geom g = amt_i_ccl_geom(nplanes, H, W);
     const size_t n = g.n;
@@ -1120,9 +1122,9 @@ __global__ void __launch_bounds__(256) frame_flag_kernel(const int* __restrict__
     }
 }
 
-__global__ void __launch_bounds__(256) clear_flagged_kernel(const int* __restrict__ in, const int* __restrict__ L,
-                                                            const int* __restrict__ T, int* __restrict__ out,
-                                                            size_t n) {
+// out may be in itself (amt_clear_border allows the pair in place): neither carries __restrict__
+__global__ void __launch_bounds__(256) clear_flagged_kernel(const int* in, const int* __restrict__ L,
+                                                            const int* __restrict__ T, int* out, size_t n) {
     const size_t base = (size_t)blockIdx.y * n;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         int l = L[base + i];
@@ -1132,6 +1134,9 @@ __global__ void __launch_bounds__(256) clear_flagged_kernel(const int* __restric
 }
 
 extern "C" int amt_clear_border(amt_ctx* ctx, const int32_t* in, int32_t* out, int nplanes, int H, int W) {
+    // in place: the labelling and the frame flags only read `in`; clear_flagged_kernel maps pixel i to pixel i in one thread
+    AMT_CHECK_OPERANDS("amt_clear_border", amt_in("in", in, amt_span(4, nplanes, H, W), 4),
+                       amt_out("out", out, amt_span(4, nplanes, H, W), 1u << 0, 4));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "clear_border: bad arguments");
     AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "clear_border: plane too large");
@@ -1488,8 +1493,10 @@ __global__ void __launch_bounds__(1024) presence_scan_kernel(int* __restrict__ p
     if (threadIdx.x == 0 && count_dev) count_dev[blockIdx.x] = carry;
 }
 
-__global__ void __launch_bounds__(256) map_labels_kernel(const int* __restrict__ in, const int* __restrict__ map,
-                                                         int* __restrict__ out, size_t n, int max_label) {
+// out may be in itself (amt_relabel_sequential and amt_clear_border_relabel allow the pair in place; a thread stores the
+// four pixels it loaded, on the int4 path as on the scalar one): neither carries __restrict__
+__global__ void __launch_bounds__(256) map_labels_kernel(const int* in, const int* __restrict__ map, int* out, size_t n,
+                                                         int max_label) {
     const size_t base = (size_t)blockIdx.y * n;
     const int* M = map + (size_t)blockIdx.y * (max_label + 1);
     const unsigned ml = (unsigned)max_label;
@@ -1513,6 +1520,10 @@ __global__ void __launch_bounds__(256) map_labels_kernel(const int* __restrict__
 
 extern "C" int amt_relabel_sequential(amt_ctx* ctx, const int32_t* in, int32_t* out, int32_t* count_dev, int nplanes,
                                       size_t n, int max_label) {
+    // in place: the presence pass only reads `in`; map_labels_kernel maps pixel i to pixel i within one thread
+    AMT_CHECK_OPERANDS("amt_relabel_sequential", amt_in("in", in, amt_span(4, nplanes, (long long)n), 4),
+                       amt_out("out", out, amt_span(4, nplanes, (long long)n), 1u << 0, 4),
+                       amt_out("count_dev", count_dev, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && max_label >= 0, "relabel_sequential: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -1579,6 +1590,11 @@ __global__ void __launch_bounds__(256) presence_fill_kernel(int* __restrict__ pr
 
 extern "C" int amt_clear_border_relabel(amt_ctx* ctx, const int32_t* in, int32_t* out, int32_t* count_dev, int nplanes,
                                         int H, int W, int max_label, const int32_t* nlabels_dev) {
+    // in place: presence, frame marks and the scan only read `in`; map_labels_kernel maps pixel i to pixel i in one thread
+    AMT_CHECK_OPERANDS("amt_clear_border_relabel", amt_in("in", in, amt_span(4, nplanes, H, W), 4),
+                       amt_out("out", out, amt_span(4, nplanes, H, W), 1u << 0, 4),
+                       amt_out("count_dev", count_dev, amt_span(4, nplanes)),
+                       amt_in("nlabels_dev", nlabels_dev, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0, "clear_border_relabel: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -1609,8 +1625,8 @@ extern "C" int amt_clear_border_relabel(amt_ctx* ctx, const int32_t* in, int32_t
     return AMT_OK;
 }
 
-__global__ void __launch_bounds__(256) keep_labels_kernel(const int* __restrict__ in, const uint8_t* __restrict__ keep,
-                                                          int* __restrict__ out, size_t n, int max_label) {
+__global__ void __launch_bounds__(256) keep_labels_kernel(const int* in, const uint8_t* __restrict__ keep, int* out,
+                                                          size_t n, int max_label) {  // out may be in: no __restrict__
     const size_t base = (size_t)blockIdx.y * n;
     const uint8_t* K = keep + (size_t)blockIdx.y * (max_label + 1);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
@@ -1621,6 +1637,9 @@ __global__ void __launch_bounds__(256) keep_labels_kernel(const int* __restrict_
 
 extern "C" int amt_keep_labels(amt_ctx* ctx, const int32_t* in, const uint8_t* keep_dev, int32_t* out, int nplanes,
                                size_t n, int max_label) {
+    AMT_CHECK_OPERANDS("amt_keep_labels", amt_in("in", in, amt_span(4, nplanes, (long long)n), 4),
+                       amt_in("keep_dev", keep_dev, amt_span(1, nplanes, (long long)max_label + 1)),
+                       amt_out("out", out, amt_span(4, nplanes, (long long)n), 1u << 0, 4));  // in place: pixel i -> pixel i
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && keep_dev && out && nplanes >= 0 && max_label >= 0, "keep_labels: bad arguments");
     if (nplanes == 0 || n == 0) return AMT_OK;
@@ -1636,6 +1655,7 @@ __global__ void cast_i32_i64_kernel(const int* __restrict__ in, long long* __res
 }
 
 extern "C" int amt_cast_i32_i64(amt_ctx* ctx, const int32_t* in, int64_t* out, size_t n) {
+    AMT_CHECK_OPERANDS("amt_cast_i32_i64", amt_in("in", in, amt_span(4, (long long)n)), amt_out("out", out, amt_span(8, (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out, "cast_i32_i64: null pointer");
     if (n == 0) return AMT_OK;
@@ -1665,6 +1685,8 @@ __global__ void fill_i32_kernel(int* p, int v, int n) {
 }
 
 extern "C" int amt_max_i32(amt_ctx* ctx, const int32_t* in, int32_t* max_dev, int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_max_i32", amt_in("in", in, amt_span(4, nplanes, (long long)n)),
+                       amt_out("max_dev", max_dev, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && max_dev && nplanes >= 0, "max_i32: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -1826,6 +1848,10 @@ __global__ void __launch_bounds__(256) sp_unwrite_kernel(const int* __restrict__
 extern "C" int amt_label_sparse(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H,
                                 int W, int connectivity, int capacity, int32_t* keep_list, int32_t* keep_count) {
     AMT_REQUIRE(!keep_list == !keep_count, "label_sparse: keep_list and keep_count go together");
+    AMT_CHECK_OPERANDS("amt_label_sparse", amt_in("in", in, amt_span(1, nplanes, H, W)), amt_out("out", out, amt_span(4, nplanes, H, W)),
+                       amt_out("count_dev", count_dev, amt_span(4, nplanes)),
+                       amt_out("keep_list", keep_list, amt_span(4, nplanes, capacity)),
+                       amt_out("keep_count", keep_count, amt_span(4, nplanes)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "label_sparse: bad arguments");
     AMT_REQUIRE(connectivity == 1 || connectivity == 2, "label_sparse: connectivity must be 1 or 2");

@@ -85,6 +85,13 @@ __global__ void __launch_bounds__(256) nn_affine_act_kernel(const uint4* __restr
 extern "C" int amt_nn_affine_act_bf16(amt_ctx* ctx, const void* x, const void* y, const float* style,
                                       const float* pre_bias, const float* scale, const float* shift, void* out, void* sum_out, int N, int H, int W, int C, int relu,
                                       int upsample) {
+    {
+        // x is a quarter of the output's size when it is upsampled on the way in
+        const size_t full = amt_span(2, N, H, W, C), xs = upsample ? amt_span(2, N, H / 2, W / 2, C) : full;
+        AMT_CHECK_OPERANDS("amt_nn_affine_act_bf16", amt_in("x", x, xs), amt_in("y", y, full), amt_in("style", style, amt_span(4, N, C)),
+                           amt_in("pre_bias", pre_bias, amt_span(4, C)), amt_in("scale", scale, amt_span(4, C)),
+                           amt_in("shift", shift, amt_span(4, C)), amt_out("out", out, full), amt_out("sum_out", sum_out, full));
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(x && scale && shift && out && N >= 0 && H > 0 && W > 0 && C > 0, "nn_affine_act: bad arguments");
     AMT_REQUIRE(C % 8 == 0, "nn_affine_act: the channel count must be a multiple of 8, got %d", C);

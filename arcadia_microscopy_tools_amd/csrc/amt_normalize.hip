@@ -169,6 +169,7 @@ bool aligned16(const void* a, const void* b) {
 }  // namespace
 
 extern "C" int amt_convert_f32_f64(amt_ctx* ctx, const float* in, double* out, size_t n) {
+    AMT_CHECK_OPERANDS("amt_convert_f32_f64", amt_in("in", in, amt_span(4, (long long)n)), amt_out("out", out, amt_span(8, (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out, "convert_f32_f64: null pointer");
     if (n == 0) return AMT_OK;
@@ -180,6 +181,9 @@ extern "C" int amt_convert_f32_f64(amt_ctx* ctx, const float* in, double* out, s
 
 extern "C" int amt_normalize_planes_f32(amt_ctx* ctx, const void* in, int in_dtype, const void* lohi_dev, int lohi_dtype,
                                         int invert, float* out, int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_normalize_planes_f32", amt_in("in", in, amt_span(amt_esize(in_dtype), nplanes, (long long)n)),
+                       amt_in("lohi_dev", lohi_dev, amt_span(amt_esize(lohi_dtype), nplanes, 2)),
+                       amt_out("out", out, amt_span(4, nplanes, (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && lohi_dev && out, "normalize_planes_f32: null pointer");
     AMT_REQUIRE(in_dtype == AMT_U16 || in_dtype == AMT_F32 || in_dtype == AMT_F64,
@@ -187,7 +191,6 @@ extern "C" int amt_normalize_planes_f32(amt_ctx* ctx, const void* in, int in_dty
     AMT_REQUIRE(lohi_dtype == AMT_F32 || lohi_dtype == AMT_F64,
                 "normalize_planes_f32: lohi_dtype must be AMT_F32 or AMT_F64");
     AMT_REQUIRE(nplanes >= 0 && nplanes <= 65535, "normalize_planes_f32: %d planes (0..65535 per call)", nplanes);
-    AMT_REQUIRE((const void*)in != (const void*)out, "normalize_planes_f32: in-place operation is not supported");
     if (nplanes == 0 || n == 0) return AMT_OK;
     const int vec = aligned16(in, out) ? 1 : 0;
     const size_t per_trip = (size_t)NRM_V * NRM_GROUPS;

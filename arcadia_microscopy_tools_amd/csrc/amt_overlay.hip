@@ -63,6 +63,18 @@ __global__ void __launch_bounds__(256) overlay_kernel(const double* __restrict__
 extern "C" int amt_overlay(amt_ctx* ctx, const double* background, const double* const* layers_host, int nlayers,
                            const double* luts_host, const double* opacity_host, const int32_t* mode_host,
                            double* out_rgb, int H, int W) {
+    {
+        // the layers' device pointers travel inside the host table: each of them is an operand of its own
+        static const char* const lname[OV_MAX_LAYERS] = {"layers_host[0]", "layers_host[1]", "layers_host[2]", "layers_host[3]",
+                                                         "layers_host[4]", "layers_host[5]", "layers_host[6]", "layers_host[7]"};
+        amt_operand ops[2 + OV_MAX_LAYERS];
+        int k = 0;
+        ops[k++] = amt_in("background", background, amt_span(8, H, W));
+        ops[k++] = amt_out("out_rgb", out_rgb, amt_span(8, H, W, 3));
+        for (int l = 0; layers_host && l < nlayers && l < OV_MAX_LAYERS; ++l)
+            ops[k++] = amt_in(lname[l], layers_host[l], amt_span(8, H, W));
+        AMT_TRY(amt_check_operands("amt_overlay", ops, k));
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(background && out_rgb && H > 0 && W > 0, "overlay: bad arguments");
     AMT_REQUIRE(nlayers >= 0 && nlayers <= OV_MAX_LAYERS, "overlay: at most %d layers per call (got %d)", OV_MAX_LAYERS,

@@ -56,6 +56,11 @@ __global__ void __launch_bounds__(256) pack_rows_kernel(const double* __restrict
 extern "C" int amt_pack_plate_rows(amt_ctx* ctx, const double* table_dev, const double* itable_dev,
                                    const int32_t* ncells_dev, int B, int K, int C, const int32_t* fov_index_dev,
                                    int fov_index0, double* rows_dev, size_t rows_cap, int64_t* nrows_dev) {
+    AMT_CHECK_OPERANDS("amt_pack_plate_rows", amt_in("table_dev", table_dev, amt_span(8, B, K, AMT_RP_NCOLS)),
+                       amt_in("itable_dev", itable_dev, amt_span(8, B, K, C, 4)), amt_in("ncells_dev", ncells_dev, amt_span(4, B)),
+                       amt_in("fov_index_dev", fov_index_dev, amt_span(4, B)),
+                       amt_out("rows_dev", rows_dev, amt_span(8, (long long)rows_cap, 16 + 4ll * (C > 0 ? C : 0))),
+                       amt_out("nrows_dev", nrows_dev, 8));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(table_dev && ncells_dev && rows_dev && nrows_dev && B >= 0 && K >= 1 && C >= 0,
                 "pack_plate_rows: bad arguments");

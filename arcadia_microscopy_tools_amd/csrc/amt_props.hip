@@ -789,6 +789,10 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
                 "regionprops: bad arguments");
     AMT_REQUIRE(!intensity == !itable_dev && (!itable_dev || C >= 1),
                 "regionprops: the intensity planes (C >= 1) and the intensity table go together");
+    AMT_CHECK_OPERANDS("amt_regionprops", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
+                       amt_in("intensity", intensity, amt_span(2, nplanes, C, H, W)),
+                       amt_out("table_dev", table_dev, amt_span(8, nplanes, max_label, AMT_RP_NCOLS)),
+                       amt_out("itable_dev", itable_dev, amt_span(8, nplanes, max_label, C, 4)));
     AMT_TRY(amt_set_device(ctx));
     const bool want_morph = table_dev != nullptr;
     if (nplanes == 0 || max_label == 0) return AMT_OK;
@@ -918,6 +922,9 @@ __global__ void __launch_bounds__(64) rp_intensity_f64_kernel(const int* __restr
 
 extern "C" int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const double* intensity, int C,
                                              double* table_dev, int nplanes, int H, int W, int max_label) {
+    AMT_CHECK_OPERANDS("amt_regionprops_intensity_f64", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
+                       amt_in("intensity", intensity, amt_span(8, nplanes, C, H, W)),
+                       amt_out("table_dev", table_dev, amt_span(8, nplanes, max_label, C, 4)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && intensity && table_dev && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && C >= 1,
                 "regionprops_intensity_f64: bad arguments");
@@ -939,6 +946,8 @@ extern "C" int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels
 
 extern "C" int amt_label_bboxes(amt_ctx* ctx, const int32_t* labels, int32_t* bbox_dev, int nplanes, int H, int W,
                                 int max_label) {
+    AMT_CHECK_OPERANDS("amt_label_bboxes", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
+                       amt_out("bbox_dev", bbox_dev, amt_span(4, nplanes, max_label, 4)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && bbox_dev && nplanes >= 0 && H > 0 && W > 0 && max_label >= 1, "label_bboxes: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -1496,6 +1505,11 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
                 "regionprops_ext: intensity must be AMT_U16 or AMT_F64");
     AMT_REQUIRE(want_r == (in_code == AMT_I32),
                 "regionprops_ext: AMT_I32 companion label planes and AMT_RPX_RELATE go together");
+    // labels and intensity are both inputs: a companion may be the very buffer `labels` points to
+    AMT_CHECK_OPERANDS("amt_regionprops_ext", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
+                       amt_in("intensity", intensity, amt_span(amt_esize(in_code), nplanes, C, H, W)),
+                       amt_out("table_dev", table_dev, amt_span(8, nplanes, max_label, AMT_RPX_NCOLS)),
+                       amt_out("wtable_dev", wtable_dev, amt_span(8, nplanes, max_label, C, 4)));
     AMT_TRY(amt_set_device(ctx));
     if (nplanes == 0 || max_label == 0) return AMT_OK;
     const bool euler = cols & (AMT_RPX_EULER_NUMBER | AMT_RPX_PERIMETER_CROFTON);
@@ -1855,6 +1869,10 @@ extern "C" int amt_colocalization(amt_ctx* ctx, const int32_t* labels, const voi
         AMT_REQUIRE(i >= 0 && i < C && j >= 0 && j < C && i != j,
                     "colocalization: pair %d = (%d, %d) must name two different channels below %d", p, i, j, C);
     }
+    AMT_CHECK_OPERANDS("amt_colocalization", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
+                       amt_in("intensity", intensity, amt_span(amt_esize(in_code), nplanes, C, H, W)),
+                       amt_in("thresholds_dev", thresholds_dev, amt_span(8, nplanes, C)),
+                       amt_out("table_dev", table_dev, amt_span(8, nplanes, max_label, npairs, AMT_COLOC_NCOLS)));
     AMT_TRY(amt_set_device(ctx));
     if (nplanes == 0 || max_label == 0) return AMT_OK;
     const size_t nlab = (size_t)nplanes * max_label;

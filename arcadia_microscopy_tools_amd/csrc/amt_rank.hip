@@ -923,7 +923,6 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
                             const void* minuend, int* fused) {
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && footprint && nplanes >= 0 && H > 0 && W > 0, "rank_filter: bad arguments");
-    AMT_REQUIRE(in != out, "rank_filter: in-place operation is not supported");
     AMT_REQUIRE(dtype == AMT_U16 || dtype == AMT_F64, "rank_filter: dtype must be AMT_U16 or AMT_F64");
     AMT_REQUIRE(op >= 0 && op <= 2, "rank_filter: op must be 0 (erosion), 1 (dilation) or 2 (median)");
     AMT_REQUIRE((fh & 1) && (fw & 1) && fh >= 1 && fw >= 1 && fh <= 63 && fw <= 63,
@@ -1129,7 +1128,11 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
 extern "C" int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
                                const uint8_t* footprint, int fh, int fw, int op, int mode, double cval,
                                const void* minuend) {
-    AMT_REQUIRE(!minuend || minuend != out, "rank_filter: minuend must differ from out");
+    AMT_REQUIRE(!minuend || minuend != out, "amt_rank_filter: minuend must differ from out (out must not alias minuend)");
+    {
+        const size_t bytes = amt_span(amt_esize(dtype), nplanes, H, W);
+        AMT_CHECK_OPERANDS("amt_rank_filter", amt_in("in", in, bytes), amt_out("out", out, bytes), amt_in("minuend", minuend, bytes));
+    }
     int fused = 0;
     AMT_TRY(rank_filter_impl(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, minuend, &fused));
     if (!minuend || fused) return AMT_OK;

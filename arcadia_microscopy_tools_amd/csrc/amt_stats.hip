@@ -160,6 +160,8 @@ static int hist_u16_launch(amt_ctx* ctx, const uint16_t* in, uint32_t* hist, int
 }
 
 extern "C" int amt_hist_u16(amt_ctx* ctx, const uint16_t* in, uint32_t* hist, int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_hist_u16", amt_in("in", in, amt_span(2, nplanes, (long long)n)),
+                       amt_out("hist", hist, amt_span(4, nplanes, 65536)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && hist && nplanes >= 0, "hist_u16: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -261,6 +263,8 @@ int amt_i_minmax_f64(amt_ctx* ctx, const double* in, unsigned long long* keys, d
 }
 
 extern "C" int amt_minmax_f64(amt_ctx* ctx, const double* in, double* minmax_dev, int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_minmax_f64", amt_in("in", in, amt_span(8, nplanes, (long long)n)),
+                       amt_out("minmax_dev", minmax_dev, amt_span(8, nplanes, 2)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && minmax_dev && nplanes >= 0, "minmax_f64: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -390,6 +394,8 @@ static int hist_f64_launch(amt_ctx* ctx, const double* in, const double* minmax,
 
 extern "C" int amt_hist_f64(amt_ctx* ctx, const double* in, const double* minmax_dev, uint32_t* hist, int nbins,
                             int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_hist_f64", amt_in("in", in, amt_span(8, nplanes, (long long)n)),
+                       amt_in("minmax_dev", minmax_dev, amt_span(8, nplanes, 2)), amt_out("hist", hist, amt_span(4, nplanes, nbins)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && minmax_dev && hist && nplanes >= 0, "hist_f64: bad arguments");
     AMT_REQUIRE(nbins >= 1 && nbins <= 4096, "hist_f64: nbins %d out of range 1..4096", nbins);
@@ -415,6 +421,8 @@ __global__ void __launch_bounds__(256) hist_range_kernel(const double* __restric
 
 extern "C" int amt_hist_range_f64(amt_ctx* ctx, const double* in, double lo, int64_t nbins, uint32_t* hist, int nplanes,
                                   size_t n) {
+    AMT_CHECK_OPERANDS("amt_hist_range_f64", amt_in("in", in, amt_span(8, nplanes, (long long)n)),
+                       amt_out("hist", hist, amt_span(4, nplanes, (long long)nbins)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && hist && nplanes >= 0 && nbins >= 1, "hist_range_f64: bad arguments");
     AMT_REQUIRE(nbins <= (1ll << 28), "hist_range_f64: %lld bins are more than 2^28", (long long)nbins);
@@ -638,6 +646,9 @@ int amt_i_otsu_from_hist(amt_ctx* ctx, const uint32_t* hist, const double* minma
 
 extern "C" int amt_threshold_value(amt_ctx* ctx, const void* in, int in_dtype, int method, int nbins, double* thr_dev,
                                    int32_t* status_dev, int nplanes, size_t n, const double* minmax_dev) {
+    AMT_CHECK_OPERANDS("amt_threshold_value", amt_in("in", in, amt_span(amt_esize(in_dtype), nplanes, (long long)n)),
+                       amt_out("thr_dev", thr_dev, amt_span(8, nplanes)), amt_out("status_dev", status_dev, amt_span(4, nplanes)),
+                       amt_in("minmax_dev", minmax_dev, amt_span(8, nplanes, 2)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_dev && nplanes >= 0, "threshold_value: bad arguments");
     AMT_REQUIRE(!minmax_dev || in_dtype == AMT_F64, "threshold_value: minmax_dev applies to float64 input only");
@@ -675,6 +686,10 @@ extern "C" int amt_threshold_value(amt_ctx* ctx, const void* in, int in_dtype, i
 // behind as a byte plane: thr_dev = the threshold (bit-identical to amt_threshold_value), thr_code_dev = 2 * its bin.
 extern "C" int amt_otsu_f64_bins(amt_ctx* ctx, const double* in, const double* minmax_dev, double* thr_dev,
                                  double* thr_code_dev, uint8_t* bins, int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_otsu_f64_bins", amt_in("in", in, amt_span(8, nplanes, (long long)n)),
+                       amt_in("minmax_dev", minmax_dev, amt_span(8, nplanes, 2)), amt_out("thr_dev", thr_dev, amt_span(8, nplanes)),
+                       amt_out("thr_code_dev", thr_code_dev, amt_span(8, nplanes)),
+                       amt_out("bins", bins, amt_span(1, nplanes, (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && minmax_dev && thr_dev && thr_code_dev && bins && nplanes >= 0, "otsu_f64_bins: bad arguments");
     if (nplanes == 0) return AMT_OK;
@@ -717,6 +732,9 @@ __global__ void threshold_gt_kernel(const T* __restrict__ in, const double* __re
 
 extern "C" int amt_threshold_gt(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_dev, uint8_t* out,
                                 int nplanes, size_t n) {
+    // 8- or 2-byte samples against 1-byte results: no pair in place
+    AMT_CHECK_OPERANDS("amt_threshold_gt", amt_in("in", in, amt_span(amt_esize(in_dtype), nplanes, (long long)n)),
+                       amt_in("thr_dev", thr_dev, amt_span(8, nplanes)), amt_out("out", out, amt_span(1, nplanes, (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_dev && out && nplanes >= 0, "threshold_gt: bad arguments");
     if (nplanes == 0 || n == 0) return AMT_OK;
@@ -744,6 +762,8 @@ __global__ void threshold_gt_image_kernel(const T* __restrict__ in, const double
 
 extern "C" int amt_threshold_gt_image(amt_ctx* ctx, const void* in, int in_dtype, const double* thr_image,
                                       uint8_t* out, size_t n) {
+    AMT_CHECK_OPERANDS("amt_threshold_gt_image", amt_in("in", in, amt_span(amt_esize(in_dtype), (long long)n)),
+                       amt_in("thr_image", thr_image, amt_span(8, (long long)n)), amt_out("out", out, amt_span(1, (long long)n)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_image && out, "threshold_gt_image: bad arguments");
     if (n == 0) return AMT_OK;
@@ -839,6 +859,8 @@ __global__ void __launch_bounds__(1024) percentile_u16_kernel(const uint32_t* __
 
 extern "C" int amt_percentile_u16(amt_ctx* ctx, const uint16_t* in, const double* q_host, int nq, double* out_dev,
                                   int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_percentile_u16", amt_in("in", in, amt_span(2, nplanes, (long long)n)),
+                       amt_out("out_dev", out_dev, amt_span(8, nplanes, nq)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && q_host && out_dev && nplanes >= 0, "percentile_u16: bad arguments");
     AMT_REQUIRE(nq >= 1 && nq <= 64, "percentile_u16: nq %d out of range 1..64", nq);
@@ -1592,6 +1614,8 @@ static int percentile_f64_radix(amt_ctx* ctx, const double* in, const rank_req* 
 
 extern "C" int amt_percentile_f64(amt_ctx* ctx, const double* in, const double* q_host, int nq, double* out_dev,
                                   int nplanes, size_t n) {
+    AMT_CHECK_OPERANDS("amt_percentile_f64", amt_in("in", in, amt_span(8, nplanes, (long long)n)),
+                       amt_out("out_dev", out_dev, amt_span(8, nplanes, nq)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && q_host && out_dev && nplanes >= 0, "percentile_f64: bad arguments");
     AMT_REQUIRE(nq >= 1 && nq <= 8, "percentile_f64: nq %d out of range 1..8", nq);
@@ -1770,6 +1794,8 @@ __global__ void masked_sums_final_kernel(const double* __restrict__ partial, dou
 
 extern "C" int amt_masked_sums_f64(amt_ctx* ctx, const double* in, const double* thr_dev, double* out_dev, int nplanes,
                                    size_t n) {
+    AMT_CHECK_OPERANDS("amt_masked_sums_f64", amt_in("in", in, amt_span(8, nplanes, (long long)n)),
+                       amt_in("thr_dev", thr_dev, amt_span(8, nplanes)), amt_out("out_dev", out_dev, amt_span(8, nplanes, 4)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_dev && out_dev && nplanes >= 0, "masked_sums_f64: bad arguments");
     if (nplanes == 0) return AMT_OK;

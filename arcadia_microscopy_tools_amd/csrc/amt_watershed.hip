@@ -2339,7 +2339,6 @@ static int watershed_common(amt_ctx* ctx, const void* relief, bool use_d2, const
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(relief && markers && mask && out && nplanes >= 0 && H > 0 && W > 0, "watershed: bad arguments");
     AMT_REQUIRE((size_t)H * W < 0x3fffffffull, "watershed: plane too large");
-    AMT_REQUIRE((const void*)markers != (const void*)out, "watershed: markers and out must not alias");
     AMT_REQUIRE(connectivity == 1 || connectivity == 2, "watershed: connectivity must be 1 or 2, got %d", connectivity);
     AMT_REQUIRE(tie_policy == AMT_WS_TIES_EXACT || tie_policy == AMT_WS_TIES_RASTER || tie_policy == AMT_WS_TIES_REPORT,
                 "watershed: unknown tie policy %d", tie_policy);
@@ -2375,7 +2374,13 @@ extern "C" int amt_watershed_edt_cleared(amt_ctx* ctx, const int32_t* d2, const 
                 "watershed_edt_cleared: bad arguments");
     AMT_REQUIRE(!marker_list == !marker_count, "watershed_edt_cleared: marker_list and marker_count go together");
     AMT_REQUIRE(!marker_list || list_capacity > 0, "watershed_edt_cleared: list_capacity must be positive");
-    AMT_REQUIRE(ws_scratch != labels_out, "watershed_edt_cleared: scratch and output must not alias");
+    AMT_CHECK_OPERANDS("amt_watershed_edt_cleared", amt_in("d2", d2, amt_span(4, nplanes, H, W)),
+                       amt_in("markers", markers, amt_span(4, nplanes, H, W)), amt_in("mask", mask, amt_span(1, nplanes, H, W)),
+                       amt_out("ws_scratch", ws_scratch, amt_span(4, nplanes, H, W)),
+                       amt_out("labels_out", labels_out, amt_span(4, nplanes, H, W)),
+                       amt_out("count_dev", count_dev, amt_span(4, nplanes)), amt_in("nlabels_dev", nlabels_dev, amt_span(4, nplanes)),
+                       amt_in("marker_list", marker_list, amt_span(4, nplanes, list_capacity)),
+                       amt_in("marker_count", marker_count, amt_span(4, nplanes)));
     ws_fused fu;
     fu.labels = labels_out, fu.count = count_dev, fu.nlabels_dev = nlabels_dev, fu.max_label = max_label;
     fu.mk_list = marker_list, fu.mk_count = marker_count, fu.mk_cap = list_capacity;
@@ -2385,6 +2390,10 @@ extern "C" int amt_watershed_edt_cleared(amt_ctx* ctx, const int32_t* d2, const 
 extern "C" int amt_watershed_edt(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
                                  int32_t* out, int nplanes, int H, int W, int seeds_first, int connectivity,
                                  int tie_policy, int32_t* ties_dev) {
+    // d2, markers and out are all int32 planes: the flood onto its own relief would pass every type check
+    AMT_CHECK_OPERANDS("amt_watershed_edt", amt_in("d2", d2, amt_span(4, nplanes, H, W)),
+                       amt_in("markers", markers, amt_span(4, nplanes, H, W)), amt_in("mask", mask, amt_span(1, nplanes, H, W)),
+                       amt_out("out", out, amt_span(4, nplanes, H, W)), amt_out("ties_dev", ties_dev, amt_span(4, nplanes)));
     return watershed_common(ctx, d2, true, markers, mask, out, nplanes, H, W, seeds_first, connectivity, tie_policy,
                             ties_dev, ws_fused());
 }
@@ -2392,6 +2401,9 @@ extern "C" int amt_watershed_edt(amt_ctx* ctx, const int32_t* d2, const int32_t*
 extern "C" int amt_watershed_f64(amt_ctx* ctx, const double* relief, const int32_t* markers, const uint8_t* mask,
                                  int32_t* out, int nplanes, int H, int W, int connectivity, int tie_policy,
                                  int32_t* ties_dev) {
+    AMT_CHECK_OPERANDS("amt_watershed_f64", amt_in("relief", relief, amt_span(8, nplanes, H, W)),
+                       amt_in("markers", markers, amt_span(4, nplanes, H, W)), amt_in("mask", mask, amt_span(1, nplanes, H, W)),
+                       amt_out("out", out, amt_span(4, nplanes, H, W)), amt_out("ties_dev", ties_dev, amt_span(4, nplanes)));
     return watershed_common(ctx, relief, false, markers, mask, out, nplanes, H, W, 0, connectivity, tie_policy, ties_dev,
                             ws_fused());
 }

@@ -183,6 +183,9 @@ __global__ void __launch_bounds__(256) win_finish_kernel(const T* __restrict__ S
 
 extern "C" int amt_window_threshold(amt_ctx* ctx, const void* in, int in_dtype, double* thr_image, int nplanes, int H,
                                     int W, int window_y, int window_x, int method, double k, double r) {
+    // a float64 image and its float64 threshold image have the same shape: the window sums read what a neighbour wrote
+    AMT_CHECK_OPERANDS("amt_window_threshold", amt_in("in", in, amt_span(amt_esize(in_dtype), nplanes, H, W)),
+                       amt_out("thr_image", thr_image, amt_span(8, nplanes, H, W)));
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_image && nplanes >= 0 && H > 0 && W > 0, "window_threshold: bad arguments");
     AMT_REQUIRE(in_dtype == AMT_U16 || in_dtype == AMT_F64, "window_threshold: dtype must be AMT_U16 or AMT_F64");
@@ -252,6 +255,13 @@ static int window_nd_tail(amt_ctx* ctx, T* S, T* Q, T* S2, T* Q2, double* thr_im
 extern "C" int amt_window_threshold_nd(amt_ctx* ctx, const void* in, int in_dtype, double* thr_image, int nlead,
                                        const int* lead_shape, const int* lead_window, int H, int W, int window_y,
                                        int window_x, int method, double k, double r) {
+    {
+        // the planes in front of (H, W): the product of lead_shape (a host table)
+        long long lead = 1;
+        for (int a = 0; lead_shape && a < nlead && a < 6; ++a) lead = lead_shape[a] > 0 && lead < (1ll << 31) ? lead * lead_shape[a] : 0;
+        AMT_CHECK_OPERANDS("amt_window_threshold_nd", amt_in("in", in, amt_span(amt_esize(in_dtype), lead, H, W)),
+                           amt_out("thr_image", thr_image, amt_span(8, lead, H, W)));
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && thr_image && H > 0 && W > 0 && nlead >= 0 && nlead <= 6 && (nlead == 0 || (lead_shape && lead_window)),
                 "window_threshold_nd: bad arguments");

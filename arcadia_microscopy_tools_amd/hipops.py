@@ -43,6 +43,32 @@ def _out(ctx: Context, out, shape, dtype) -> DeviceArray:
     return out
 
 
+def _span(x):
+    """(start, byte length, element size) of a DeviceArray; an explicit triple stands for a strided view."""
+    if x is None or isinstance(x, tuple):
+        return x
+    return int(x.ptr), int(x.nbytes), int(x.dtype.itemsize)
+
+
+def _no_alias(op: str, ins: dict, outs: dict, inplace=()):
+    """The aliasing rule of include/amt_hip.h (Conventions) on ``DeviceArray.ptr`` / ``nbytes``, before any device access:
+    inputs may overlap inputs; an output must not overlap any other operand, not even in part, except that the
+    (output, input) pairs named in ``inplace`` may coincide exactly -- same start, same byte length, same element size."""
+    spans = [(n, _span(a), False) for n, a in ins.items()] + [(n, _span(a), True) for n, a in outs.items()]
+    spans = [s for s in spans if s[1] is not None and s[1][1] > 0]
+    for i, (na, sa, oa) in enumerate(spans):
+        for nb, sb, ob in spans[i + 1:]:
+            if not (oa or ob) or sa[0] + sa[1] <= sb[0] or sb[0] + sb[1] <= sa[0]:
+                continue
+            o, x = (na, nb) if oa else (nb, na)
+            if oa != ob and (o, x) in inplace:
+                if sa == sb:
+                    continue
+                raise ValueError(f"{op}: {o} may alias {x} only in place (same start, same length, same element size); "
+                                 "this overlap is partial")
+            raise ValueError(f"{op}: {o} must not alias {x}, nor overlap it in part")
+
+
 def _in_code(a: DeviceArray) -> int:
     if a.dtype == np.uint16:
         return _hip.U16
@@ -94,6 +120,9 @@ def gaussian(a: DeviceArray, sigma: float, mode: str = "nearest", cval: float = 
         scale = 1.0 / 65535 if a.dtype == np.uint16 else 1.0
     if minmax_out is not None and (minmax_out.dtype != np.float64 or minmax_out.size != 2 * n):
         raise ValueError("minmax_out must be a float64 DeviceArray with 2 values per output plane")
+    isz = a.dtype.itemsize  # the planes of a channel lie `stride` elements apart: first plane to the end of the last
+    src = (int(ptr), ((n - 1) * stride + H * W) * isz if stride and n else n * H * W * isz, isz)
+    _no_alias("gaussian", {"a": src}, {"out": o, "minmax_out": minmax_out})
     _hip.check(_lib().amt_gaussian(ctx.handle, ptr, _in_code(a), float(scale), o.ptr, n, H, W, wp, r,
                                    _hip.MODES[mode], float(cval), stride,
                                    minmax_out.ptr if minmax_out is not None else None), "amt_gaussian")
@@ -169,6 +198,9 @@ def gaussian_otsu_codes(a: DeviceArray, sigma: float, codes: DeviceArray, thr: D
             raise ValueError(f"{name} must be a {np.dtype(dt).name} DeviceArray of {size} elements")
         if arr.ctx is not ctx:
             raise ValueError(f"{name} belongs to another context than the input")
+    src = (int(ptr), ((n - 1) * stride + H * W) * 2 if stride and n else n * H * W * 2, 2)
+    _no_alias("gaussian_otsu_codes", {"a": src}, {"codes": codes, "thr": thr, "thr_code": thr_code, "minmax": minmax,
+                                                  "hist": hist, "prefix": prefix})
     w = gaussian_weights(sigma, truncate)
     r = (len(w) - 1) // 2
     wa, wp = _host_f64(w)
@@ -187,6 +219,7 @@ def difference_of_gaussians(a: DeviceArray, low_sigma: float, high_sigma: float,
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, a.shape, np.float64)
+    _no_alias("difference_of_gaussians", {"a": a}, {"out": o})
     wl, wh = gaussian_weights(low_sigma, truncate), gaussian_weights(high_sigma, truncate)
     wla, wlp = _host_f64(wl)
     wha, whp = _host_f64(wh)
@@ -215,6 +248,7 @@ def sub_clip0(a: DeviceArray, level: DeviceArray, out: DeviceArray | None = None
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, a.shape, np.float64)
+    _no_alias("sub_clip0", {"a": a, "level": level}, {"out": o}, inplace={("out", "a")})
     _hip.check(_lib().amt_sub_clip0_f64(ctx.handle, a.ptr, level.ptr, o.ptr, n, H * W), "amt_sub_clip0_f64")
     return o
 
@@ -225,6 +259,7 @@ def rescale(a: DeviceArray, in_range: DeviceArray, out_range=(0.0, 1.0), out: De
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, a.shape, np.float64)
+    _no_alias("rescale", {"a": a, "in_range": in_range}, {"out": o}, inplace={("out", "a")})  # float64 planes only: the sizes
     _hip.check(_lib().amt_rescale(ctx.handle, a.ptr, _in_code(a), in_range.ptr, float(out_range[0]),
                                   float(out_range[1]), o.ptr, n, H * W), "amt_rescale")
     return o
@@ -238,6 +273,7 @@ def uniform_filter(a: DeviceArray, size: int, mode: str = "reflect", cval: float
     if size % 2 == 0:
         raise ValueError("uniform_filter: size must be odd")
     o = _out(ctx, out, a.shape, np.float64)
+    _no_alias("uniform_filter", {"a": a}, {"out": o})
     w = 1.0 / size * np.ones((size,))
     wa, wp = _host_f64(w)
     _hip.check(_lib().amt_gaussian(ctx.handle, a.ptr, _in_code(a), 1.0, o.ptr, n, H, W, wp, (size - 1) // 2,
@@ -252,11 +288,13 @@ def to_float64(a: DeviceArray, scale: float = 1.0, out=None) -> DeviceArray:
         if scale != 1.0:
             raise ValueError("to_float64 of a float32 array takes no scale")
         o = _out(a.ctx, out, a.shape, np.float64)
+        _no_alias("to_float64", {"a": a}, {"out": o})
         _hip.check(_lib().amt_convert_f32_f64(a.ctx.handle, a.ptr, o.ptr, a.size), "amt_convert_f32_f64")
         return o
     if a.dtype != np.uint16:
         raise TypeError("to_float64 expects uint16 or float32")
     o = _out(a.ctx, out, a.shape, np.float64)
+    _no_alias("to_float64", {"a": a}, {"out": o})
     _hip.check(_lib().amt_convert_u16_f64(a.ctx.handle, a.ptr, float(scale), o.ptr, a.size), "amt_convert_u16_f64")
     return o
 
@@ -280,7 +318,8 @@ def normalize_planes(planes: DeviceArray, lohi: DeviceArray, invert: bool = Fals
     if lohi.ctx is not ctx:
         raise ValueError("lohi belongs to another context than the planes; bind it with DeviceArray.on(ctx)")
     o = _out(ctx, out, planes.shape, np.float32)
-    codes = {np.dtype(np.uint16): _hip.U16, np.dtype(np.float32): _hip.F32, np.dtype(np.float64): _hip.F64}
+    _no_alias("normalize_planes", {"planes": planes, "lohi": lohi}, {"out": o})
+    codes ={np.dtype(np.uint16): _hip.U16, np.dtype(np.float32): _hip.F32, np.dtype(np.float64): _hip.F64}
     _hip.check(_lib().amt_normalize_planes_f32(ctx.handle, planes.ptr, codes[planes.dtype], lohi.ptr, codes[lohi.dtype],
                                                1 if invert else 0, o.ptr, n, H * W), "amt_normalize_planes_f32")
     return o
@@ -288,6 +327,7 @@ def normalize_planes(planes: DeviceArray, lohi: DeviceArray, invert: bool = Fals
 
 def add_scalar(a: DeviceArray, s: float, out=None) -> DeviceArray:
     o = _out(a.ctx, out, a.shape, np.float64)
+    _no_alias("add_scalar", {"a": a}, {"out": o}, inplace={("out", "a")})
     _hip.check(_lib().amt_add_scalar_f64(a.ctx.handle, a.ptr, float(s), o.ptr, a.size), "amt_add_scalar_f64")
     return o
 
@@ -301,6 +341,7 @@ def deinterleave(yxc: DeviceArray, C: int, out: DeviceArray | None = None) -> De
     lead = yxc.shape[:-3]
     n = int(np.prod(lead, dtype=np.int64)) if lead else 1
     o = _out(ctx, out, tuple(lead) + (C, H, W), np.uint16)
+    _no_alias("deinterleave", {"yxc": yxc}, {"out": o})
     _hip.check(_lib().amt_deinterleave_u16(ctx.handle, yxc.ptr, o.ptr, n, H, W, C), "amt_deinterleave_u16")
     return o
 
@@ -313,6 +354,7 @@ def histogram_u16(a: DeviceArray, out: DeviceArray | None = None) -> DeviceArray
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, (n, 65536), np.uint32)
+    _no_alias("histogram_u16", {"a": a}, {"out": o})
     _hip.check(_lib().amt_hist_u16(ctx.handle, a.ptr, o.ptr, n, H * W), "amt_hist_u16")
     return o
 
@@ -333,6 +375,7 @@ def minmax(a: DeviceArray, out: DeviceArray | None = None) -> DeviceArray:
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, (n, 2), np.float64)
+    _no_alias("minmax", {"a": a}, {"out": o})
     _hip.check(_lib().amt_minmax_f64(ctx.handle, a.ptr, o.ptr, n, H * W), "amt_minmax_f64")
     return o
 
@@ -344,6 +387,7 @@ def histogram_f64(a: DeviceArray, nbins: int = 256, mm: DeviceArray | None = Non
     if mm is None:
         mm = minmax(a)
     o = _out(ctx, out, (n, nbins), np.uint32)
+    _no_alias("histogram_f64", {"a": a, "mm": mm}, {"out": o})
     _hip.check(_lib().amt_hist_f64(ctx.handle, a.ptr, mm.ptr, o.ptr, nbins, n, H * W), "amt_hist_f64")
     return o, mm
 
@@ -356,6 +400,7 @@ def percentile(a: DeviceArray, q, out: DeviceArray | None = None) -> DeviceArray
     if np.any(qa < 0) or np.any(qa > 100):
         raise ValueError("Percentiles must be in the range [0, 100]")
     o = _out(ctx, out, (n, len(qa)), np.float64)
+    _no_alias("percentile", {"a": a}, {"out": o})
     qh, qp = _host_f64(qa)
     if a.dtype == np.uint16:
         _hip.check(_lib().amt_percentile_u16(ctx.handle, a.ptr, qp, len(qa), o.ptr, n, H * W), "amt_percentile_u16")
@@ -373,6 +418,7 @@ def masked_sums(a: DeviceArray, thr: DeviceArray, out: DeviceArray | None = None
     if a.dtype != np.float64:
         raise TypeError("masked_sums expects float64")
     o = _out(ctx, out, (n, 4), np.float64)
+    _no_alias("masked_sums", {"a": a, "thr": thr}, {"out": o})
     _hip.check(_lib().amt_masked_sums_f64(ctx.handle, a.ptr, thr.ptr, o.ptr, n, H * W), "amt_masked_sums_f64")
     return o
 
@@ -382,6 +428,7 @@ def crop(a: DeviceArray, top: int, left: int, h: int, w: int, out: DeviceArray |
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, a.shape[:-2] + (h, w), a.dtype)
+    _no_alias("crop", {"a": a}, {"out": o})
     _hip.check(_lib().amt_copy_rect(ctx.handle, a.ptr, o.ptr, a.dtype.itemsize, n, H, W, int(top), int(left), int(h),
                                     int(w)), "amt_copy_rect")
     o.is_bool = a.is_bool
@@ -407,6 +454,7 @@ def threshold_otsu(a: DeviceArray, nbins: int = 256, out: DeviceArray | None = N
     o = _out(ctx, out, (n,), np.float64)
     if minmax is not None and (a.dtype != np.float64 or minmax.dtype != np.float64 or minmax.size != 2 * n):
         raise ValueError("minmax needs a float64 image and 2 float64 values per plane")
+    _no_alias("threshold_otsu", {"a": a, "minmax": minmax}, {"out": o})
     _hip.check(_lib().amt_threshold_value(ctx.handle, a.ptr, _in_code(a), _hip.THR_OTSU, nbins, o.ptr, None, n, H * W,
                                           minmax.ptr if minmax is not None else None), "amt_threshold_value")
     return o
@@ -417,6 +465,7 @@ def greater_than(a: DeviceArray, thr: DeviceArray, out: DeviceArray | None = Non
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, a.shape, np.uint8)
+    _no_alias("greater_than", {"a": a, "thr": thr}, {"out": o})
     _hip.check(_lib().amt_threshold_gt(ctx.handle, a.ptr, _in_code(a), thr.ptr, o.ptr, n, H * W), "amt_threshold_gt")
     o.is_bool = True
     return o
@@ -445,6 +494,7 @@ def window_threshold(a: DeviceArray, window_size=15, method: str = "niblack", k:
     if r is None:
         r = 0.5 * 65535 if a.dtype == np.uint16 else 1.0  # 0.5 * (imax - imin); float range is (-1, 1)
     o = _out(ctx, out, a.shape, np.float64)
+    _no_alias("window_threshold", {"a": a}, {"out": o})
     meth = 0 if method == "niblack" else 1
     if nlead and any(v != 1 for v in ws[:nlead]):
         import ctypes
@@ -462,6 +512,7 @@ def window_threshold(a: DeviceArray, window_size=15, method: str = "niblack", k:
 def greater_than_image(a: DeviceArray, thr_image: DeviceArray, out: DeviceArray | None = None) -> DeviceArray:
     ctx = a.ctx
     o = _out(ctx, out, a.shape, np.uint8)
+    _no_alias("greater_than_image", {"a": a, "thr_image": thr_image}, {"out": o})
     _hip.check(_lib().amt_threshold_gt_image(ctx.handle, a.ptr, _in_code(a), thr_image.ptr, o.ptr, a.size),
                "amt_threshold_gt_image")
     o.is_bool = True
@@ -515,6 +566,7 @@ def _binary(which: str, a: DeviceArray, footprint, out, border_value=None):
     n, H, W = _planes(a)
     fp = _fp(footprint)
     o = _out(ctx, out, a.shape, np.uint8)
+    _no_alias("binary_" + which, {"a": a}, {"out": o})
     op = _MORPH_OPS[which]
     if border_value is None or op >= _MORPH_OPS["open"]:  # open / close apply skimage's border rules themselves
         border_value = 1 if which == "erode" else 0
@@ -568,9 +620,10 @@ def binary_fill_holes(a: DeviceArray, structure=None, out: DeviceArray | None = 
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, a.shape, np.uint8)
-    if o is a or (a.nbytes and o.ptr < a.ptr + a.nbytes and a.ptr < o.ptr + o.nbytes):
-        # any overlap, not only the same address: the write-out of one plane would land in input still to be read
-        raise ValueError("binary_fill_holes: out must not alias (or overlap) the input")
+    if o is a:
+        raise ValueError("binary_fill_holes: out must not alias the input")
+    # any overlap, not only the same address: the write-out of one plane would land in input still to be read
+    _no_alias("binary_fill_holes", {"a": a}, {"out": o})
     if a.size == 0:
         o.is_bool = True
         return o
@@ -592,8 +645,9 @@ def _area_filter(which: str, a: DeviceArray, size, connectivity, out) -> DeviceA
     ctx = a.ctx
     n, H, W = _planes(a)
     o = _out(ctx, out, a.shape, np.uint8)
-    if o is a or (a.nbytes and o.ptr < a.ptr + a.nbytes and a.ptr < o.ptr + o.nbytes):
-        raise ValueError(f"{which}: out must not alias (or overlap) the input")
+    if o is a:
+        raise ValueError(f"{which}: out must not alias the input")
+    _no_alias(which, {"a": a}, {"out": o})
     o.is_bool = True
     if a.size == 0:
         return o
@@ -637,6 +691,7 @@ def threshold_otsu_bins(a: DeviceArray, minmax: DeviceArray, thr: DeviceArray, t
     for arr, size in ((minmax, 2 * n), (thr, n), (thr_code, n)):
         if arr.dtype != np.float64 or arr.size != size:
             raise ValueError("threshold_otsu_bins: minmax (n, 2), thr (n,), thr_code (n,) must be float64")
+    _no_alias("threshold_otsu_bins", {"a": a, "minmax": minmax}, {"thr": thr, "thr_code": thr_code, "bins": bins})
     _hip.check(_lib().amt_otsu_f64_bins(ctx.handle, a.ptr, minmax.ptr, thr.ptr, thr_code.ptr, bins.ptr, n, H * W),
                "amt_otsu_f64_bins")
     return thr
@@ -649,6 +704,7 @@ def threshold_open_close(a: DeviceArray, thr: DeviceArray, footprint=None, out=N
     n, H, W = _planes(a)
     fp = _fp(footprint)
     o = _out(ctx, out, a.shape, np.uint8)
+    _no_alias("threshold_open_close", {"a": a, "thr": thr, "bins": bins, "thr_code": thr_code}, {"out": o})
     _hip.check(_lib().amt_threshold_open_close(ctx.handle, a.ptr, _in_code(a), thr.ptr, o.ptr, n, H, W,
                                                fp.ctypes.data_as(ctypes.c_void_p), fp.shape[0], fp.shape[1],
                                                None if bins is None else bins.ptr,
@@ -664,6 +720,7 @@ def _rank(a: DeviceArray, footprint, op: int, mode: str, cval: float, out, minue
     n, H, W = _planes(a)
     fp = _fp(footprint)  # callers that follow scikit-image's even-size rule pass an odd footprint already
     o = _out(ctx, out, a.shape, a.dtype)
+    _no_alias("rank filter", {"a": a, "minuend": minuend}, {"out": o})
     _hip.check(_lib().amt_rank_filter(ctx.handle, a.ptr, o.ptr, _in_code(a), n, H, W,
                                       fp.ctypes.data_as(ctypes.c_void_p), fp.shape[0], fp.shape[1], op,
                                       _hip.MODES[mode], float(cval), None if minuend is None else minuend.ptr),
@@ -739,6 +796,7 @@ def label(a: DeviceArray, connectivity: int = 2, out: DeviceArray | None = None,
         raise TypeError(f"label: unsupported dtype {a.dtype}")
     o = _out(ctx, out, a.shape, np.int32)
     c = _out(ctx, count, (n,), np.int32)
+    _no_alias("label", {"a": a}, {"out": o, "count": c})
     if code == _hip.U8 and a.is_bool:
         # a bool array (0 / 1 bytes by construction): the truth-value entry point, whose run-table path launches nothing
         # that stands by for other byte values
@@ -775,6 +833,7 @@ def label_sparse(a: DeviceArray, connectivity: int = 2, capacity: int | None = N
         if klist.dtype != np.int32 or klist.size != n * int(capacity) or kcount.dtype != np.int32 or kcount.size != n:
             raise ValueError("keep must be (int32 (n, capacity), int32 (n,))")
         klist_ptr, kcount_ptr = klist.ptr, kcount.ptr
+    _no_alias("label_sparse", {"a": a}, {"out": o, "count": c, "keep list": keep and keep[0], "keep counts": keep and keep[1]})
     _hip.check(_lib().amt_label_sparse(ctx.handle, a.ptr, o.ptr, c.ptr, n, H, W, int(connectivity), int(capacity),
                                        klist_ptr, kcount_ptr), "amt_label_sparse")
     return o, c
@@ -787,6 +846,7 @@ def clear_border(labels: DeviceArray, out: DeviceArray | None = None) -> DeviceA
     if labels.dtype != np.int32:
         raise TypeError("clear_border expects int32 labels on the device")
     o = _out(ctx, out, labels.shape, np.int32)
+    _no_alias("clear_border", {"labels": labels}, {"out": o}, inplace={("out", "labels")})
     _hip.check(_lib().amt_clear_border(ctx.handle, labels.ptr, o.ptr, n, H, W), "amt_clear_border")
     return o
 
@@ -797,6 +857,7 @@ def relabel_sequential(labels: DeviceArray, max_label: int, out=None, count=None
     n, H, W = _planes(labels)
     o = _out(ctx, out, labels.shape, np.int32)
     c = _out(ctx, count, (n,), np.int32)
+    _no_alias("relabel_sequential", {"labels": labels}, {"out": o, "count": c}, inplace={("out", "labels")})
     _hip.check(_lib().amt_relabel_sequential(ctx.handle, labels.ptr, o.ptr, c.ptr, n, H * W, int(max_label)),
                "amt_relabel_sequential")
     return o, c
@@ -813,6 +874,7 @@ def clear_border_relabel(labels: DeviceArray, max_label: int, out=None, count=No
     c = _out(ctx, count, (n,), np.int32)
     if nlabels is not None and (nlabels.dtype != np.int32 or nlabels.size != n):
         raise ValueError("nlabels must hold one int32 per plane")
+    _no_alias("clear_border_relabel", {"labels": labels, "nlabels": nlabels}, {"out": o, "count": c}, inplace={("out", "labels")})
     _hip.check(_lib().amt_clear_border_relabel(ctx.handle, labels.ptr, o.ptr, c.ptr, n, H, W, int(max_label),
                                                nlabels.ptr if nlabels is not None else None),
                "amt_clear_border_relabel")
@@ -824,6 +886,7 @@ def keep_labels(labels: DeviceArray, keep: DeviceArray, max_label: int, out=None
     ctx = labels.ctx
     n, H, W = _planes(labels)
     o = _out(ctx, out, labels.shape, np.int32)
+    _no_alias("keep_labels", {"labels": labels, "keep": keep}, {"out": o}, inplace={("out", "labels")})
     _hip.check(_lib().amt_keep_labels(ctx.handle, labels.ptr, keep.ptr, o.ptr, n, H * W, int(max_label)),
                "amt_keep_labels")
     return o
@@ -831,6 +894,7 @@ def keep_labels(labels: DeviceArray, keep: DeviceArray, max_label: int, out=None
 
 def to_int64(labels: DeviceArray, out=None) -> DeviceArray:
     o = _out(labels.ctx, out, labels.shape, np.int64)
+    _no_alias("to_int64", {"labels": labels}, {"out": o})
     _hip.check(_lib().amt_cast_i32_i64(labels.ctx.handle, labels.ptr, o.ptr, labels.size), "amt_cast_i32_i64")
     return o
 
@@ -839,6 +903,7 @@ def max_per_plane(labels: DeviceArray, out=None) -> DeviceArray:
     ctx = labels.ctx
     n, H, W = _planes(labels)
     o = _out(ctx, out, (n,), np.int32)
+    _no_alias("max_per_plane", {"labels": labels}, {"out": o})
     _hip.check(_lib().amt_max_i32(ctx.handle, labels.ptr, o.ptr, n, H * W), "amt_max_i32")
     return o
 
@@ -851,6 +916,7 @@ def cast_labels(labels: DeviceArray, dtype, out=None) -> DeviceArray:
     if np.dtype(np.int32) not in pair or not all(d in (np.uint8, np.uint16, np.int32) for d in pair) or pair[0] == pair[1]:
         raise TypeError(f"cast_labels converts uint8 / uint16 to int32 and back, not {pair[0]} to {pair[1]}")
     codes = {np.dtype(np.uint8): _hip.U8, np.dtype(np.uint16): _hip.U16, np.dtype(np.int32): _hip.I32}
+    _no_alias("cast_labels", {"labels": labels}, {"out": o})
     _hip.check(_lib().amt_cast_labels(labels.ctx.handle, labels.ptr, codes[pair[0]], o.ptr, codes[pair[1]], labels.size),
                "amt_cast_labels")
     return o
@@ -893,8 +959,7 @@ def expand_labels(labels: DeviceArray, distance: float, ring: bool = False, out=
         raise TypeError("expand_labels expects int32 labels on the device")
     n, H, W = _planes(labels)
     o = _out(ctx, out, labels.shape, np.int32)
-    if o.ptr == labels.ptr:
-        raise ValueError("expand_labels cannot work in place: out must be another buffer than labels")
+    _no_alias("expand_labels", {"labels": labels}, {"out": o})  # cannot work in place: out is another buffer than labels
     _hip.check(_lib().amt_expand_labels(ctx.handle, labels.ptr, o.ptr, n, H, W, expand_nmax(distance), int(bool(ring))),
                "amt_expand_labels")
     return o
@@ -909,6 +974,7 @@ def edt(mask: DeviceArray, want_d2: bool = True, want_edt: bool = True, d2_out=N
     n, H, W = _planes(mask)
     d2 = _out(ctx, d2_out, mask.shape, np.int32) if want_d2 else None
     e = _out(ctx, edt_out, mask.shape, np.float64) if want_edt else None
+    _no_alias("edt", {"mask": mask}, {"d2_out": d2, "edt_out": e})
     _hip.check(_lib().amt_edt(ctx.handle, mask.ptr, d2.ptr if d2 else None, e.ptr if e else None, n, H, W), "amt_edt")
     return d2, e
 
@@ -926,6 +992,8 @@ def peak_mask(d2: DeviceArray, mask: DeviceArray, min_distance: int = 5, out=Non
             raise ValueError("keep= needs the caller's persistent out= plane and the previous counts (status=)")
         klist, kcount = keep
         prev = (klist.ptr, kcount.ptr, klist.size // n, status.ptr)
+    _no_alias("peak_mask", {"d2": d2, "mask": mask, "keep list": keep and keep[0], "keep counts": keep and keep[1],
+                            "status": status}, {"out": o})
     _hip.check(_lib().amt_peak_mask(ctx.handle, d2.ptr, mask.ptr, o.ptr, n, H, W, int(min_distance), *prev),
                "amt_peak_mask")
     o.is_bool = True
@@ -960,6 +1028,8 @@ def peak_markers(d2: DeviceArray, mask: DeviceArray, min_distance: int = 5, conn
     pk = _out(ctx, peaks, d2.shape, np.uint8)
     mk = _out(ctx, markers, d2.shape, np.int32)
     c = _out(ctx, count, (n,), np.int32)
+    _no_alias("peak_markers", {"d2": d2, "mask": mask}, {"peaks": pk, "markers": mk, "count": c, "keep list": keep and keep[0],
+                                                         "keep counts": keep and keep[1]})
     _hip.check(_lib().amt_peak_markers(ctx.handle, d2.ptr, mask.ptr, pk.ptr, mk.ptr, c.ptr, n, H, W, int(min_distance),
                                        int(connectivity), int(capacity), klist_ptr, kcount_ptr), "amt_peak_markers")
     pk.is_bool = True
@@ -997,6 +1067,7 @@ def watershed_edt(d2: DeviceArray, markers: DeviceArray, mask: DeviceArray, seed
     n, H, W = _planes(d2)
     o = _out(ctx, out, d2.shape, np.int32)
     t = _ws_ties(ctx, n, ties, ties_out)
+    _no_alias("watershed_edt", {"d2": d2, "markers": markers, "mask": mask}, {"out": o, "ties_out": t})
     _hip.check(_lib().amt_watershed_edt(ctx.handle, d2.ptr, markers.ptr, mask.ptr, o.ptr, n, H, W,
                                         1 if seeds_first else 0, int(connectivity), _hip.WS_TIES[ties],
                                         None if t is None else t.ptr),
@@ -1025,6 +1096,10 @@ def watershed_edt_cleared(d2: DeviceArray, markers: DeviceArray, mask: DeviceArr
         if klist.dtype != np.int32 or kcount.dtype != np.int32 or kcount.size != n or klist.size % n:
             raise ValueError("marker_list must be (int32 (n, capacity), int32 (n,))")
         mk = (klist.ptr, kcount.ptr, klist.size // n)
+    _no_alias("watershed_edt_cleared", {"d2": d2, "markers": markers, "mask": mask, "nlabels": nlabels,
+                                        "marker list": marker_list and marker_list[0],
+                                        "marker counts": marker_list and marker_list[1]},
+              {"scratch": scratch, "out": o, "count": c})
     _hip.check(_lib().amt_watershed_edt_cleared(ctx.handle, d2.ptr, markers.ptr, mask.ptr, scratch.ptr, o.ptr, c.ptr, n, H,
                                                 W, int(max_label), nlabels.ptr, *mk), "amt_watershed_edt_cleared")
     return o, c
@@ -1038,6 +1113,7 @@ def watershed(relief: DeviceArray, markers: DeviceArray, mask: DeviceArray, out=
     n, H, W = _planes(relief)
     o = _out(ctx, out, relief.shape, np.int32)
     t = _ws_ties(ctx, n, ties, ties_out)
+    _no_alias("watershed", {"relief": relief, "markers": markers, "mask": mask}, {"out": o, "ties_out": t})
     _hip.check(_lib().amt_watershed_f64(ctx.handle, relief.ptr, markers.ptr, mask.ptr, o.ptr, n, H, W,
                                         int(connectivity), _hip.WS_TIES[ties], None if t is None else t.ptr),
                "amt_watershed_f64")
@@ -1053,6 +1129,7 @@ def regionprops(labels: DeviceArray, max_label: int, out=None) -> DeviceArray:
     ctx = labels.ctx
     n, H, W = _planes(labels)
     o = _out(ctx, out, (n, max_label, _hip.RP_NCOLS), np.float64)
+    _no_alias("regionprops", {"labels": labels}, {"out": o})
     _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, None, 0, o.ptr, None, n, H, W, int(max_label)),
                "amt_regionprops")
     return o
@@ -1071,6 +1148,7 @@ def regionprops_full(labels: DeviceArray, intensity: DeviceArray, max_label: int
         raise ValueError("intensity / labels plane count mismatch")
     o = _out(ctx, out, (n, max_label, _hip.RP_NCOLS), np.float64)
     io = _out(ctx, iout, (n, max_label, C, 4), np.float64)
+    _no_alias("regionprops_full", {"labels": labels, "intensity": intensity}, {"out": o, "iout": io})
     _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, intensity.ptr, C, o.ptr, io.ptr, n, H, W, int(max_label)),
                "amt_regionprops")
     return o, io
@@ -1101,6 +1179,8 @@ def pack_plate_rows(table: DeviceArray, itable, ncells: DeviceArray, fov_index0:
     elif out.dtype != np.float64 or out.ndim != 2 or out.shape[1] != ncols or out.shape[0] < B * K:
         raise ValueError(f"out must be (>= {B * K}, {ncols}) float64, got {out.shape} {out.dtype}")
     nr = _out(ctx, nrows_out, (1,), np.int64)
+    _no_alias("pack_plate_rows", {"table": table, "itable": itable, "ncells": ncells, "fov_index": fov_index},
+              {"out": out, "nrows_out": nr})
     _hip.check(_lib().amt_pack_plate_rows(ctx.handle, table.ptr, None if itable is None else itable.ptr, ncells.ptr,
                                           B, K, C, None if fov_index is None else fov_index.ptr, int(fov_index0),
                                           out.ptr, int(out.shape[0]), nr.ptr), "amt_pack_plate_rows")
@@ -1120,6 +1200,7 @@ def regionprops_intensity(labels: DeviceArray, intensity: DeviceArray, max_label
     if intensity.size != n * C * H * W:
         raise ValueError("intensity / labels plane count mismatch")
     o = _out(ctx, out, (n, max_label, C, 4), np.float64)
+    _no_alias("regionprops_intensity", {"labels": labels, "intensity": intensity}, {"out": o})
     if intensity.dtype == np.uint16:  # exact integer accumulation
         _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, intensity.ptr, C, None, o.ptr, n, H, W,
                                           int(max_label)), "amt_regionprops")
@@ -1169,6 +1250,7 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
         code = _hip.U16 if intensity.dtype == np.uint16 else _hip.F64
     o = _out(ctx, out, (n, max_label, _hip.RPX_NCOLS), np.float64) if bits & ~_hip.RPX_WEIGHTED else None
     wo = _out(ctx, wout, (n, max_label, C, 4), np.float64) if want_w else None
+    _no_alias("regionprops_ext", {"labels": labels, "intensity": intensity}, {"out": o, "wout": wo})
     _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, None if intensity is None else intensity.ptr, code, C,
                                           bits, None if o is None else o.ptr, None if wo is None else wo.ptr, n, H, W,
                                           int(max_label)), "amt_regionprops_ext")
@@ -1202,6 +1284,7 @@ def relate_labels(labels: DeviceArray, max_label: int, companions: DeviceArray, 
     if C < 1 or companions.size != n * C * H * W:
         raise ValueError("companions / labels plane count mismatch")
     o = _out(ctx, out, (n, max_label, C, 4), np.float64)
+    _no_alias("relate_labels", {"labels": labels, "companions": companions}, {"out": o})  # a companion may be `labels`
     _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, companions.ptr, _hip.I32, C, _hip.RPX_RELATE, None,
                                           o.ptr, n, H, W, int(max_label)), "amt_regionprops_ext")
     return o
@@ -1227,6 +1310,7 @@ def robust_intensity(labels: DeviceArray, intensity: DeviceArray, max_label: int
     if C < 1 or intensity.size != n * C * H * W:
         raise ValueError("intensity / labels plane count mismatch")
     o = _out(ctx, out, (n, max_label, C, 4), np.float64)
+    _no_alias("robust_intensity", {"labels": labels, "intensity": intensity}, {"out": o})
     code = _hip.U16 if intensity.dtype == np.uint16 else _hip.F64
     _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, intensity.ptr, code, C, _hip.RPX_ROBUST, None, o.ptr,
                                           n, H, W, int(max_label)), "amt_regionprops_ext")
@@ -1289,6 +1373,7 @@ def colocalization(labels: DeviceArray, intensity: DeviceArray, max_label: int, 
         thr = ctx.asarray(np.ascontiguousarray(host))
     pr = colocalization_pairs(C, pairs)
     o = _out(ctx, out, (n, max_label, len(pr), _hip.COLOC_NCOLS), np.float64)
+    _no_alias("colocalization", {"labels": labels, "intensity": intensity, "thresholds": thr}, {"out": o})
     _hip.check(_lib().amt_colocalization(ctx.handle, labels.ptr, intensity.ptr, _hip.U16 if intensity.dtype == np.uint16
                                          else _hip.F64, C, thr.ptr, pr.ctypes.data_as(ctypes.c_void_p), len(pr), o.ptr,
                                          n, H, W, int(max_label)), "amt_colocalization")
@@ -1316,6 +1401,7 @@ def cellpose_masks(dP: DeviceArray, cellprob: DeviceArray, cellprob_threshold: f
         raise ValueError(f"flow_threshold must be non-negative, got {flow_threshold}")
     o = _out(ctx, out, cellprob.shape, np.int32)
     c = _out(ctx, count, (n,), np.int32)
+    _no_alias("cellpose_masks", {"dP": dP, "cellprob": cellprob}, {"out": o, "count": c})
     _hip.check(_lib().amt_cellpose_masks_ex(ctx.handle, dP.ptr, cellprob.ptr, o.ptr, c.ptr, n, H, W,
                                             float(cellprob_threshold), int(niter), int(min_size),
                                             float(max_size_fraction), int(max_seeds), float(flow_threshold),

@@ -23,6 +23,18 @@
  *     library checks this (pointers carry no owner); a binding that keeps arrays with their context should refuse
  *     mixed-context calls, as the Python binding does for `out=` (tests/test_gpu_api.py::test_stream_rule_at_the_boundary).
  *     Host memory handed to amt_memcpy_h2d / amt_memcpy_d2h must stay valid until the stream has passed the copy.
+ *   - ALIASING: inputs may overlap inputs (amt_subtract(a, a, ...), a RELATE companion that is `labels` itself).  An
+ *     output -- every non-const device pointer: results, caller-owned scratch, persistent in/out planes, lists, counts --
+ *     must not overlap any other operand of the call, not even in part; the byte range of an operand follows from the
+ *     arguments (strides, paddings and rectangles included).  The one exception is a pair an entry point declares IN PLACE
+ *     below: it may coincide exactly -- same start, same byte length, same element size -- and every other overlap of that
+ *     pair (a plane further, 8 bytes further) is refused too.  A refusal is AMT_EINVAL with a message that names the entry
+ *     point and both operands ("... must not alias ..."); it comes before the context is touched and before anything is
+ *     reserved or launched, so a refused call has written nothing.  The verdict of a pair never depends on which kernel
+ *     the arguments select.  In place today: amt_sub_clip0_f64, amt_add_scalar_f64, amt_rescale (float64 input),
+ *     amt_subtract (out with a, with b or with both), amt_clear_border, amt_relabel_sequential, amt_clear_border_relabel and
+ *     amt_keep_labels, each `out` with `in`.  The output of amt_contours_emit / amt_borders_emit has a length only the
+ *     device knows: its first point is checked.
  */
 #ifndef AMT_HIP_H
 #define AMT_HIP_H
@@ -157,14 +169,14 @@ int amt_dog(amt_ctx* ctx, const void* in, int in_dtype, double scale, double* ou
             const double* w_lo, int r_lo, const double* w_hi, int r_hi, int mode, double cval);
 
 /* ---- elementwise (R/operations.py:50,97; SK/exposure/exposure.py:405-428) ------------------- */
-/* out = max(in - level[plane], 0)  -- np.clip(dog - background_level, 0, None) */
+/* out = max(in - level[plane], 0)  -- np.clip(dog - background_level, 0, None); out may be in (in place) */
 int amt_sub_clip0_f64(amt_ctx* ctx, const double* in, const double* level_dev, double* out, int nplanes, size_t n);
 /* rescale_intensity with tuple ranges: clip to [imin,imax]; (x-imin)/(imax-imin)*(omax-omin)+omin.
- * range_dev = nplanes x {imin, imax} doubles on the device. */
+ * range_dev = nplanes x {imin, imax} doubles on the device.  A float64 `in` may be `out` itself (in place). */
 int amt_rescale(amt_ctx* ctx, const void* in, int in_dtype, const double* range_dev, double omin, double omax,
                 double* out, int nplanes, size_t n);
 int amt_convert_u16_f64(amt_ctx* ctx, const uint16_t* in, double scale, double* out, size_t n);
-/* out = in + s (threshold_local subtracts its offset this way, SK/filters/thresholding.py:236) */
+/* out = in + s (threshold_local subtracts its offset this way, SK/filters/thresholding.py:236); out may be in (in place) */
 int amt_add_scalar_f64(amt_ctx* ctx, const double* in, double s, double* out, size_t n);
 
 /* ---- statistics: np.percentile (R/operations.py:47,94), histogram (SK/exposure/exposure.py) -- */
@@ -286,7 +298,7 @@ int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const d
  * footprints subtract inside the filter kernel, everything else filters into `out` and subtracts in place. */
 int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
                     const uint8_t* footprint, int fh, int fw, int op, int mode, double cval, const void* minuend);
-/* out = a - b (same dtype; white_tophat = image - opening) */
+/* out = a - b (same dtype; white_tophat = image - opening); out may be a, b or both (in place) */
 int amt_subtract(amt_ctx* ctx, const void* a, const void* b, void* out, int dtype, size_t n);
 
 /* ---- labelling: R/masks.py:56-65 (clear_border, label, relabel_sequential) ------------------- */
@@ -311,20 +323,21 @@ int amt_label_mask(amt_ctx* ctx, const uint8_t* mask, int32_t* out, int32_t* cou
 int amt_label_sparse(amt_ctx* ctx, const uint8_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H, int W,
                      int connectivity, int capacity, int32_t* keep_list, int32_t* keep_count);
 /* skimage.segmentation.clear_border(labels) with buffer_size=0: zero every 8-connected component of
- * equal-valued pixels that touches the 1-px frame; other pixels keep their value. */
+ * equal-valued pixels that touches the 1-px frame; other pixels keep their value.  out may be in (in place). */
 int amt_clear_border(amt_ctx* ctx, const int32_t* in, int32_t* out, int nplanes, int H, int W);
 /* relabel_sequential: surviving labels -> 1..K in ascending order of the old label; count_dev = K.
- * max_label = upper bound of label values in `in` (any plane). */
+ * max_label = upper bound of label values in `in` (any plane).  out may be in (in place). */
 int amt_relabel_sequential(amt_ctx* ctx, const int32_t* in, int32_t* out, int32_t* count_dev, int nplanes, size_t n,
                            int max_label);
 /* clear_border followed by relabel_sequential (R/masks.py:56,65) in one pass, valid when every label of
  * `in` is a single connected component (outputs of amt_label and amt_watershed_*): a label is removed
  * iff one of its pixels lies on the 1-px frame; survivors -> 1..K in ascending old-label order.
  * nlabels_dev (nullable): the caller vouches that plane p holds exactly the labels 1..nlabels_dev[p] (true for a
- * watershed of a mask from markers numbered 1..K that lie inside the mask); the presence pass is then skipped. */
+ * watershed of a mask from markers numbered 1..K that lie inside the mask); the presence pass is then skipped.
+ * out may be in (in place). */
 int amt_clear_border_relabel(amt_ctx* ctx, const int32_t* in, int32_t* out, int32_t* count_dev, int nplanes, int H,
                              int W, int max_label, const int32_t* nlabels_dev);
-/* np.where(np.isin(labels, keep), labels, 0): keep_dev = nplanes x (max_label+1) uint8 flags */
+/* np.where(np.isin(labels, keep), labels, 0): keep_dev = nplanes x (max_label+1) uint8 flags; out may be in (in place) */
 int amt_keep_labels(amt_ctx* ctx, const int32_t* in, const uint8_t* keep_dev, int32_t* out, int nplanes, size_t n,
                     int max_label);
 int amt_cast_i32_i64(amt_ctx* ctx, const int32_t* in, int64_t* out, size_t n);

@@ -74,17 +74,18 @@ def test_optional_pointer_groups_are_all_or_none():
     """An entry point whose optional pointers come as a group refuses a partial group before it touches the context
     (so this runs without a GPU: a complete group gets as far as the null-context check)."""
     lib = _hip.load_library()
-    buf = np.zeros(64, np.int32)
-    p, q = buf.ctypes.data, buf[32:].ctypes.data
+    buf = np.zeros(16 * 512, np.int32)
+    # every operand in 2 KiB of its own: an output that overlapped another operand would be refused for that instead
+    p, q, a, b, c, d, e, f, g = (buf[k * 512:].ctypes.data for k in range(9))
     fp = np.ones((3, 3), np.uint8).ctypes.data
     calls = {  # name: (arguments with a partial group, the same with the group complete)
-        "amt_threshold_open_close": ([None, p, _hip.F64, p, p, 1, 4, 4, fp, 3, 3, p, None],
-                                     [None, p, _hip.F64, p, p, 1, 4, 4, fp, 3, 3, p, p]),
-        "amt_label_sparse": ([None, p, p, p, 1, 4, 4, 1, 4, None, p], [None, p, p, p, 1, 4, 4, 1, 4, p, p]),
-        "amt_peak_mask": ([None, p, p, p, 1, 4, 4, 1, p, p, 4, None], [None, p, p, p, 1, 4, 4, 1, p, p, 4, p]),
-        "amt_watershed_edt_cleared": ([None, p, p, p, p, q, p, 1, 4, 4, 8, p, p, None, 4],
-                                      [None, p, p, p, p, q, p, 1, 4, 4, 8, p, p, p, 4]),
-        "amt_regionprops": ([None, p, None, 1, p, p, 1, 4, 4, 8], [None, p, p, 1, p, p, 1, 4, 4, 8]),
+        "amt_threshold_open_close": ([None, p, _hip.F64, a, b, 1, 4, 4, fp, 3, 3, c, None],
+                                     [None, p, _hip.F64, a, b, 1, 4, 4, fp, 3, 3, c, d]),
+        "amt_label_sparse": ([None, p, a, b, 1, 4, 4, 1, 4, None, c], [None, p, a, b, 1, 4, 4, 1, 4, d, c]),
+        "amt_peak_mask": ([None, p, a, b, 1, 4, 4, 1, c, d, 4, None], [None, p, a, b, 1, 4, 4, 1, c, d, 4, e]),
+        "amt_watershed_edt_cleared": ([None, p, a, b, c, q, d, 1, 4, 4, 8, e, f, None, 4],
+                                      [None, p, a, b, c, q, d, 1, 4, 4, 8, e, f, g, 4]),
+        "amt_regionprops": ([None, p, None, 1, a, b, 1, 4, 4, 8], [None, p, c, 1, a, b, 1, 4, 4, 8]),
     }
     for name, (partial, complete) in calls.items():
         assert getattr(lib, name)(*partial) == -1, name

@@ -21,10 +21,11 @@ def test_symbol_is_declared_and_exported():
 
 def test_bad_arguments_return_minus_one():
     lib = _hip.load_library()
-    buf = np.zeros(64, np.int32)
-    p = buf.ctypes.data
+    buf = np.zeros(7 * 64, np.int32)
+    # every operand in 256 bytes of its own: an output that overlapped another operand would be refused for that instead
+    d2, mask, peaks, markers, count, klist, kcount = (buf[k * 64:].ctypes.data for k in range(7))
     #       ctx   d2 mask peaks markers count n  H  W  m  conn cap list count
-    good = [None, p, p, p, p, p, 1, 4, 4, 1, 1, 4, p, p]
+    good = [None, d2, mask, peaks, markers, count, 1, 4, 4, 1, 1, 4, klist, kcount]
     assert lib.amt_peak_markers(*good) == -1
     assert lib.amt_last_error() == b"null context"  # every argument passed: only the context is missing
 
@@ -48,5 +49,7 @@ def test_bad_arguments_return_minus_one():
     refused(11, 0, b"capacity")
     huge = list(good)
     huge[7] = huge[8] = 65536  # 2^32 pixels do not fit the int32 pixel indices of the lists
+    for k, index in enumerate((1, 2, 3, 4, 5, 12, 13)):
+        huge[index] = (k + 1) << 40  # planes of 2^34 bytes at addresses of their own (nothing is read: refused first)
     assert lib.amt_peak_markers(*huge) == -1 and b"too large" in lib.amt_last_error()
     assert not buf.any()
