@@ -51,6 +51,12 @@ RELATE_LDS_PARTNERS = 128
 RPX_ROBUST = 1 << 9
 RPX_QCOLS = ("q25", "median", "q75", "mad")
 ROBUST_LDS_BINS = 1024
+# amt_regionprops_ext with AMT_RPX_NEIGHBORS (the contact census per (label, companion plane), AMT_RPX_NCOL_*) and with
+# AMT_RPX_NEAREST (the two nearest labels by centroid, AMT_RPX_DCOL_*)
+RPX_NEIGHBORS = 1 << 10
+RPX_NCOLS4 = ("count", "touching", "ring", "main")
+RPX_NEAREST = 1 << 11
+RPX_DCOLS = ("first", "first_distance", "second", "second_distance")
 # amt_colocalization: the columns of a (label, channel pair) row (AMT_COLOC_*)
 COLOC_COLS = ("pearson", "overlap", "m1", "m2", "intersection1", "intersection2")
 COLOC_NCOLS = len(COLOC_COLS)

@@ -1397,6 +1397,77 @@ __device__ __forceinline__ bool rl_table_add(int* keys, unsigned* cnts, int v, u
     return false;
 }
 
+// The census of the values one wave is handed: `each(f)` calls f(v) once for every pixel that counts, every call of
+// `each` in the same order.  Values <= 0 and the value `skip` are seen and not counted.  total = all values seen,
+// counted = those that count, partners = the distinct ones among them, best / bestv = the maximal count of one value and
+// the smallest value that has it (0, 0 without any).  keys / cnts: the wave's table of RL_SLOTS slots.
+struct rl_census_t {
+    unsigned total, counted, partners, best, bestv;
+};
+template <typename Each>
+__device__ __forceinline__ rl_census_t rl_census(int* keys, unsigned* cnts, int lane, int skip, Each&& each) {
+    for (int i = lane; i < RL_SLOTS; i += 64) {
+        keys[i] = 0;
+        cnts[i] = 0;
+    }
+    __syncthreads();
+    rl_census_t r = {0, 0, 0, 0, 0};
+    unsigned runc = 0;
+    int runv = 0;
+    bool full = false;
+    each([&](int v) {
+        r.total += 1u;
+        if (v > 0 && v != skip) r.counted += 1u;
+        if (v == runv) {
+            runc += 1u;
+        } else {
+            if (runv > 0 && runv != skip && !full) full = !rl_table_add(keys, cnts, runv, runc);
+            runv = v;
+            runc = 1u;
+        }
+    });
+    if (runv > 0 && runv != skip && !full) full = !rl_table_add(keys, cnts, runv, runc);
+    __syncthreads();
+    r.total = (unsigned)wave_sum_u64(r.total);  // a plane has fewer than 2^32 pixels
+    r.counted = (unsigned)wave_sum_u64(r.counted);
+    if (!__any(full)) {
+        for (int i = lane; i < RL_SLOTS; i += 64) {
+            const unsigned k = (unsigned)keys[i], cn = cnts[i];
+            if (k != 0) {
+                r.partners += 1u;
+                if (cn > r.best || (cn == r.best && k < r.bestv)) r.best = cn, r.bestv = k;
+            }
+        }
+        r.partners = (unsigned)wave_sum_u64(r.partners);
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const unsigned ob = __shfl_xor(r.best, o), ov = __shfl_xor(r.bestv, o);
+            if (ob > r.best || (ob == r.best && ob != 0 && ov < r.bestv)) r.best = ob, r.bestv = ov;
+        }
+    } else {
+        // smallest value first
+        unsigned cur = 0x7fffffffu;
+        each([&](int v) {
+            if (v > 0 && v != skip && (unsigned)v < cur) cur = (unsigned)v;
+        });
+        cur = wave_min_u32(cur);
+        while (cur != 0x7fffffffu) {
+            unsigned cn = 0, next = 0x7fffffffu;
+            each([&](int v) {
+                if ((unsigned)v == cur) cn += 1u;
+                else if (v > 0 && v != skip && (unsigned)v > cur && (unsigned)v < next) next = (unsigned)v;
+            });
+            cn = (unsigned)wave_sum_u64(cn);
+            next = wave_min_u32(next);
+            r.partners += 1u;
+            if (cn > r.best) r.best = cn, r.bestv = cur;  // ascending values: an equal count keeps the smaller one
+            cur = next;  // > the value just counted, or the end mark
+        }
+    }
+    __syncthreads();  // the table may be cleared for the next census
+    return r;
+}
+
 __global__ void __launch_bounds__(64) rpx_relate_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
                                                         const int* __restrict__ comp, int C, double* __restrict__ wtable,
                                                         int H, int W, int max_label) {
@@ -1416,69 +1487,174 @@ __global__ void __launch_bounds__(64) rpx_relate_kernel(const int* __restrict__ 
     const int lc = w <= 8 ? 3 : (w <= 16 ? 4 : (w <= 32 ? 5 : 6));
     for (int c = 0; c < C; ++c) {
         const int* B = comp + ((size_t)plane * C + c) * n;
-        for (int i = lane; i < RL_SLOTS; i += 64) {
-            keys[i] = 0;
-            cnts[i] = 0;
-        }
-        __syncthreads();
-        unsigned area = 0, runc = 0;
-        int runv = 0;
-        bool full = false;
-        rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, [&](int v) {
-            area += 1u;
-            if (v == runv) {
-                runc += 1u;
-            } else {
-                if (runv > 0 && !full) full = !rl_table_add(keys, cnts, runv, runc);
-                runv = v;
-                runc = 1u;
-            }
+        const rl_census_t r = rl_census(keys, cnts, lane, 0, [&](auto&& f) {
+            rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, f);
         });
-        if (runv > 0 && !full) full = !rl_table_add(keys, cnts, runv, runc);
-        __syncthreads();
-        area = (unsigned)wave_sum_u64(area);  // a plane has fewer than 2^32 pixels
-        unsigned best = 0, bestv = 0, partners = 0;  // maximal count, the smallest value that has it
-        if (!__any(full)) {
-            for (int i = lane; i < RL_SLOTS; i += 64) {
-                const unsigned k = (unsigned)keys[i], cn = cnts[i];
-                if (k != 0) {
-                    partners += 1u;
-                    if (cn > best || (cn == best && k < bestv)) best = cn, bestv = k;
-                }
-            }
-            partners = (unsigned)wave_sum_u64(partners);
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const unsigned ob = __shfl_xor(best, o), ov = __shfl_xor(bestv, o);
-                if (ob > best || (ob == best && ob != 0 && ov < bestv)) best = ob, bestv = ov;
-            }
-        } else {
-            // smallest partner value first
-            unsigned cur = 0x7fffffffu;
-            rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, [&](int v) {
-                if (v > 0 && (unsigned)v < cur) cur = (unsigned)v;
-            });
-            cur = wave_min_u32(cur);
-            while (cur != 0x7fffffffu) {
-                unsigned cn = 0, next = 0x7fffffffu;
-                rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, [&](int v) {
-                    if ((unsigned)v == cur) cn += 1u;
-                    else if (v > 0 && (unsigned)v > cur && (unsigned)v < next) next = (unsigned)v;
-                });
-                cn = (unsigned)wave_sum_u64(cn);
-                next = wave_min_u32(next);
-                partners += 1u;
-                if (cn > best) best = cn, bestv = cur;  // ascending values: an equal count keeps the smaller one
-                cur = next;  // > the value just counted, or the end mark
-            }
-        }
         if (lane == 0) {
-            out[c * 4 + AMT_RPX_RCOL_PARENT] = (double)bestv;
-            out[c * 4 + AMT_RPX_RCOL_OVERLAP] = (double)best;
-            out[c * 4 + AMT_RPX_RCOL_PARTNERS] = (double)partners;
-            out[c * 4 + AMT_RPX_RCOL_AREA] = (double)area;
+            out[c * 4 + AMT_RPX_RCOL_PARENT] = (double)r.bestv;
+            out[c * 4 + AMT_RPX_RCOL_OVERLAP] = (double)r.best;
+            out[c * 4 + AMT_RPX_RCOL_PARTNERS] = (double)r.partners;
+            out[c * 4 + AMT_RPX_RCOL_AREA] = (double)r.total;
         }
-        __syncthreads();  // the table is cleared for the next companion
+    }
+}
+
+// ---- a label's neighbours (AMT_RPX_NEIGHBORS) -----------------------------------------------------------------------
+// The same census, taken on the label's RING: the pixels that do not carry the label and have an 8-neighbour that does.
+// One wave per (label, plane) over the label's box grown by one pixel and clamped to the plane (outside it no pixel has
+// such a neighbour).  The wave covers 2^lc columns; its 64 >> lc lane groups share the rows of the grown box in bands of
+// consecutive rows, and a lane walks down its column of its band.  With m = (labels == label) and h = m of the pixel
+// and its two neighbours in the row, a pixel is on the ring when it is not m and h of its row, the row above or the row
+// below is set: a lane carries h of the rows y - 1 and y, gets m of x - 1 / x + 1 in row y + 1 from the lanes beside it
+// and, in the first and last column of the tile, from one halo load -- two loads per lane and row instead of nine.
+// Rows go four at a time, their loads issued together from coordinates clamped into the grown box; the companion is read
+// only where a row of the four has a ring pixel in the wave, and not at all when it is the label plane itself.
+constexpr int NB_ROWS = 4;
+template <typename F>
+__device__ __forceinline__ void nb_for_ring(const int* __restrict__ L, const int* __restrict__ B, int W, int gx0, int gy0,
+                                            int gx1, int gy1, int want, int lc, int lane, F&& f) {
+    const int cols = 1 << lc, rw = 64 >> lc;
+    const int col = lane & (cols - 1), sub = lane >> lc;
+    const int bh = (gy1 - gy0 + rw) / rw;  // rows per band, rounded up
+    const int ya = gy0 + sub * bh;         // this lane's band: rows ya .. yz (none when yz < ya)
+    const int yz = ya + bh - 1 <= gy1 ? ya + bh - 1 : gy1;
+    const bool self = L == B;
+    const bool first = col == 0, last = col == cols - 1;
+    for (int xb = gx0; xb <= gx1; xb += cols) {
+        const int x = xb + col;
+        const bool inx = x <= gx1;
+        const int xc = inx ? x : gx1;
+        const int hx = first ? x - 1 : x + 1;  // the halo column of the tile's first / last lane
+        const bool halo = (first || last) && hx >= gx0 && hx <= gx1;
+        bool hprev = false, hcur = false;  // h of the rows y - 1 and y
+        int lcur = want;                   // labels[y][x]; rows before the band are never emitted
+        // the row in hand is y = ya - 2 + k: two steps fill the window before the band's first row
+        for (int k0 = 0; k0 < bh + 2; k0 += NB_ROWS) {
+            int ln[NB_ROWS], lh[NB_ROWS];
+#pragma unroll
+            for (int j = 0; j < NB_ROWS; ++j) {  // the rows below the rows in hand
+                const int yn = ya - 1 + k0 + j;
+                const size_t row = (size_t)(yn < gy0 ? gy0 : (yn > gy1 ? gy1 : yn)) * W;
+                ln[j] = L[row + xc];
+                lh[j] = halo ? L[row + hx] : 0;
+            }
+            bool ring[NB_ROWS];
+            int lab[NB_ROWS];
+            bool any = false;
+#pragma unroll
+            for (int j = 0; j < NB_ROWS; ++j) {
+                const int y = ya - 2 + k0 + j, yn = y + 1;
+                const bool rown = yn >= gy0 && yn <= gy1;
+                const bool m = rown && inx && ln[j] == want;
+                const bool mh = rown && halo && lh[j] == want;
+                const bool left = __shfl_up((int)m, 1) != 0, right = __shfl_down((int)m, 1) != 0;
+                const bool hnext = m || (first ? mh : left) || (last ? mh : right);
+                ring[j] = y >= ya && y <= yz && inx && lcur != want && (hprev || hcur || hnext);
+                lab[j] = lcur;
+                any = any || ring[j];
+                hprev = hcur;
+                hcur = hnext;
+                lcur = ln[j];
+            }
+            if (!__any(any)) continue;
+            int v[NB_ROWS];
+#pragma unroll
+            for (int j = 0; j < NB_ROWS; ++j) {
+                const int y = ya - 2 + k0 + j;
+                v[j] = self ? lab[j] : B[(size_t)(y < gy0 ? gy0 : (y > gy1 ? gy1 : y)) * W + xc];
+            }
+#pragma unroll
+            for (int j = 0; j < NB_ROWS; ++j)
+                if (ring[j]) f(v[j]);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64) rpx_neighbors_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
+                                                           const int* __restrict__ comp, int C,
+                                                           double* __restrict__ wtable, int H, int W, int max_label) {
+    __shared__ int keys[RL_SLOTS];
+    __shared__ unsigned cnts[RL_SLOTS];
+    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
+    const size_t li = (size_t)plane * max_label + l;
+    double* out = wtable + li * (size_t)C * 4;
+    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    if (y1 < y0) {  // label absent from this plane
+        for (int i = lane; i < C * 4; i += 64) out[i] = 0.0;
+        return;
+    }
+    const size_t n = (size_t)H * W;
+    const int* L = labels + (size_t)plane * n;
+    const int gy0 = y0 > 0 ? y0 - 1 : 0, gx0 = x0 > 0 ? x0 - 1 : 0;
+    const int gy1 = y1 < H - 1 ? y1 + 1 : H - 1, gx1 = x1 < W - 1 ? x1 + 1 : W - 1;
+    const int w = gx1 - gx0 + 1;
+    const int lc = w <= 8 ? 3 : (w <= 16 ? 4 : (w <= 32 ? 5 : 6));
+    for (int c = 0; c < C; ++c) {
+        const int* B = comp + ((size_t)plane * C + c) * n;
+        const rl_census_t r = rl_census(keys, cnts, lane, l + 1, [&](auto&& f) {
+            nb_for_ring(L, B, W, gx0, gy0, gx1, gy1, l + 1, lc, lane, f);
+        });
+        if (lane == 0) {
+            out[c * 4 + AMT_RPX_NCOL_COUNT] = (double)r.partners;
+            out[c * 4 + AMT_RPX_NCOL_TOUCHING] = (double)r.counted;
+            out[c * 4 + AMT_RPX_NCOL_RING] = (double)r.total;
+            out[c * 4 + AMT_RPX_NCOL_MAIN] = (double)r.bestv;
+        }
+    }
+}
+
+// ---- the two nearest labels by centroid (AMT_RPX_NEAREST) -----------------------------------------------------------
+// centroid table: (cy, cx) of every (plane, label) from the integer sums of rp_label_kernel; cy = NaN marks a label that
+// is absent from its plane
+__global__ void __launch_bounds__(256) rpx_centroid_kernel(const u64* __restrict__ acc, double2* __restrict__ cen,
+                                                           size_t nlab) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nlab; i += (size_t)gridDim.x * 256) {
+        const u64* A = acc + i * A_NACC;
+        const u64 n = A[A_N];
+        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        cen[i] = n != 0 ? make_double2((double)A[A_SY] / (double)n, (double)A[A_SX] / (double)n) : make_double2(nan, nan);
+    }
+}
+
+// One lane per query label; the labels of the plane pass through LDS in chunks of the workgroup's size (every lane reads
+// the same entry: a broadcast).  Candidates arrive in ascending label order, so "strictly nearer" keeps the smallest
+// label among equal distances.  max_label^2 distances per plane: a plane of a thousand cells is a million of them.
+constexpr int NN_CHUNK = 256;
+__global__ void __launch_bounds__(NN_CHUNK) rpx_nearest_kernel(const double2* __restrict__ cen, double* __restrict__ wtable,
+                                                               int max_label) {
+    __shared__ double2 chunk[NN_CHUNK];
+    const int plane = blockIdx.y, tid = threadIdx.x;
+    const int l = blockIdx.x * NN_CHUNK + tid;
+    const double2* P = cen + (size_t)plane * max_label;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double2 me = l < max_label ? P[l] : make_double2(nan, nan);
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    double d1 = inf, d2 = inf;  // centroids lie inside the plane: every distance is finite
+    int m1 = 0, m2 = 0;
+    for (int base = 0; base < max_label; base += NN_CHUNK) {
+        __syncthreads();  // the chunk before has been read
+        if (base + tid < max_label) chunk[tid] = P[base + tid];
+        __syncthreads();
+        const int cnt = max_label - base < NN_CHUNK ? max_label - base : NN_CHUNK;
+        for (int i = 0; i < cnt; ++i) {
+            const double2 o = chunk[i];
+            const double dy = o.x - me.x, dx = o.y - me.y;
+            const double d = dy * dy + dx * dx;  // NaN when either label is absent: no comparison below holds
+            if (base + i == l) continue;
+            if (d < d1) {
+                d2 = d1, m2 = m1;
+                d1 = d, m1 = base + i + 1;
+            } else if (d < d2) {
+                d2 = d, m2 = base + i + 1;
+            }
+        }
+    }
+    if (l < max_label) {
+        double* out = wtable + ((size_t)plane * max_label + l) * 4;
+        out[AMT_RPX_DCOL_FIRST] = (double)m1;
+        out[AMT_RPX_DCOL_FIRST_DISTANCE] = m1 ? sqrt(d1) : nan;
+        out[AMT_RPX_DCOL_SECOND] = (double)m2;
+        out[AMT_RPX_DCOL_SECOND_DISTANCE] = m2 ? sqrt(d2) : nan;
     }
 }
 
@@ -1489,22 +1665,29 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
     const bool want_w = (cols & AMT_RPX_CENTROID_WEIGHTED) != 0;
     const bool want_r = (cols & AMT_RPX_RELATE) != 0;
     const bool want_q = (cols & AMT_RPX_ROBUST) != 0;
-    const bool want_c = want_w || want_r || want_q;  // the call has companion planes and a per-companion table
-    const bool want_m = (cols & ~(AMT_RPX_CENTROID_WEIGHTED | AMT_RPX_RELATE | AMT_RPX_ROBUST)) != 0;
+    const bool want_n = (cols & AMT_RPX_NEIGHBORS) != 0;
+    const bool want_d = (cols & AMT_RPX_NEAREST) != 0;
+    const bool want_c = want_w || want_r || want_q || want_n;  // the call has companion planes
+    const bool want_t = want_c || want_d;                      // ... and the table of four columns per companion
+    const unsigned table_bits =
+        AMT_RPX_CENTROID_WEIGHTED | AMT_RPX_RELATE | AMT_RPX_ROBUST | AMT_RPX_NEIGHBORS | AMT_RPX_NEAREST;
+    const bool want_m = (cols & ~table_bits) != 0;
     AMT_REQUIRE(labels && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && cols != 0 &&
-                    (cols & ~(AMT_RPX_ALL | AMT_RPX_RELATE | AMT_RPX_ROBUST)) == 0,
+                    (cols & ~(AMT_RPX_ALL | AMT_RPX_RELATE | AMT_RPX_ROBUST | AMT_RPX_NEIGHBORS | AMT_RPX_NEAREST)) == 0,
                 "regionprops_ext: bad arguments");
-    AMT_REQUIRE((int)want_w + (int)want_r + (int)want_q <= 1,
-                "regionprops_ext: AMT_RPX_RELATE, AMT_RPX_ROBUST and AMT_RPX_CENTROID_WEIGHTED share the companion planes "
-                "and their table: one call, one of them");
+    AMT_REQUIRE((int)want_w + (int)want_r + (int)want_q + (int)want_n + (int)want_d <= 1,
+                "regionprops_ext: AMT_RPX_CENTROID_WEIGHTED, AMT_RPX_RELATE, AMT_RPX_ROBUST, AMT_RPX_NEIGHBORS and "
+                "AMT_RPX_NEAREST share the table of four columns per companion: one call, one of them");
     AMT_REQUIRE(!table_dev == !want_m, "regionprops_ext: the morphology table and its column bits go together");
-    AMT_REQUIRE(want_c == !!intensity && want_c == !!wtable_dev && (!want_c || C >= 1),
+    AMT_REQUIRE(want_c == !!intensity && want_t == !!wtable_dev && (!want_c || C >= 1),
                 "regionprops_ext: the intensity planes (C >= 1), the weighted table and AMT_RPX_CENTROID_WEIGHTED or "
-                "AMT_RPX_ROBUST (or the companion label planes, the relation table and AMT_RPX_RELATE) go together");
+                "AMT_RPX_ROBUST (or the companion label planes, the relation table and AMT_RPX_RELATE or "
+                "AMT_RPX_NEIGHBORS) go together; AMT_RPX_NEAREST takes the table alone");
+    AMT_REQUIRE(!want_d || (in_code == 0 && C == 1), "regionprops_ext: AMT_RPX_NEAREST takes in_code 0 and C == 1");
     AMT_REQUIRE(!(want_w || want_q) || in_code == AMT_U16 || in_code == AMT_F64,
                 "regionprops_ext: intensity must be AMT_U16 or AMT_F64");
-    AMT_REQUIRE(want_r == (in_code == AMT_I32),
-                "regionprops_ext: AMT_I32 companion label planes and AMT_RPX_RELATE go together");
+    AMT_REQUIRE((want_r || want_n) == (in_code == AMT_I32),
+                "regionprops_ext: AMT_I32 companion label planes and AMT_RPX_RELATE or AMT_RPX_NEIGHBORS go together");
     // labels and intensity are both inputs: a companion may be the very buffer `labels` points to
     AMT_CHECK_OPERANDS("amt_regionprops_ext", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
                        amt_in("intensity", intensity, amt_span(amt_esize(in_code), nplanes, C, H, W)),
@@ -1515,7 +1698,7 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
     const bool euler = cols & (AMT_RPX_EULER_NUMBER | AMT_RPX_PERIMETER_CROFTON);
     const bool filled = cols & AMT_RPX_AREA_FILLED, feret = cols & AMT_RPX_FERET_DIAMETER_MAX;
     const bool moments = cols & (AMT_RPX_CENTROID_LOCAL | AMT_RPX_INERTIA_TENSOR | AMT_RPX_INERTIA_EIGVALS);
-    const bool scan = filled || feret || moments;  // rp_label_kernel: pixel counts, moment sums, row extents
+    const bool scan = filled || feret || moments || want_d;  // rp_label_kernel: pixel counts, moment sums, row extents
     const size_t n = (size_t)H * W;
     const size_t nlab = (size_t)nplanes * max_label;
     const size_t cap = feret ? n : 1;
@@ -1530,6 +1713,7 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
     amt_buf<int2> chainL(s, (size_t)nplanes * 3 * cap);
     amt_buf<int2> chainR(s, (size_t)nplanes * 3 * cap);
     amt_buf<u64> hscratch(s, (size_t)nplanes * 2 * hwords);
+    amt_buf<double2> cen(s, nlab, want_d);
     AMT_TRY(s.commit());
     hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
     AMT_LAUNCH_CHECK();
@@ -1586,6 +1770,19 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
     if (want_r) {
         hipLaunchKernelGGL(rpx_relate_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,
                            (const int*)intensity, C, wtable_dev, H, W, max_label);
+        AMT_LAUNCH_CHECK();
+    }
+    if (want_n) {
+        hipLaunchKernelGGL(rpx_neighbors_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,
+                           (const int*)intensity, C, wtable_dev, H, W, max_label);
+        AMT_LAUNCH_CHECK();
+    }
+    if (want_d) {
+        hipLaunchKernelGGL(rpx_centroid_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, cen,
+                           nlab);
+        AMT_LAUNCH_CHECK();
+        hipLaunchKernelGGL(rpx_nearest_kernel, dim3((max_label + NN_CHUNK - 1) / NN_CHUNK, nplanes), dim3(NN_CHUNK), 0,
+                           ctx->stream, cen, wtable_dev, max_label);
         AMT_LAUNCH_CHECK();
     }
     if (want_q) AMT_TRY(amt_i_robust_intensity(ctx, labels, bbox, intensity, in_code, C, wtable_dev, nplanes, H, W, max_label));

@@ -1235,6 +1235,9 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
         raise ValueError("bit 8 (AMT_RPX_RELATE) relates two label images: call hipops.relate_labels")
     if bits & _hip.RPX_ROBUST:
         raise ValueError("bit 9 (AMT_RPX_ROBUST) measures quartiles and MAD per channel: call hipops.robust_intensity")
+    if bits & (_hip.RPX_NEIGHBORS | _hip.RPX_NEAREST):
+        raise ValueError("bits 10 and 11 (AMT_RPX_NEIGHBORS, AMT_RPX_NEAREST) measure a label's surroundings: call "
+                         "hipops.neighbor_census or hipops.nearest_labels")
     want_w = bool(bits & _hip.RPX_WEIGHTED)
     if want_w != (intensity is not None):
         raise ValueError("weighted centroids need intensity images, and intensity images are only used for them")
@@ -1267,10 +1270,15 @@ def relate_labels(labels: DeviceArray, max_label: int, companions: DeviceArray, 
     equal counts, 0 when ``B`` is zero on all of ``l``), ``overlap`` = that count, ``partners`` = the number of
     distinct non-zero values of ``B`` on ``l``, ``area`` = the pixel count of ``l``.  A label absent from its plane
     gives four zeros.  All values are exact integers; two runs give identical bytes."""
+    return _companion_table("relate_labels", _hip.RPX_RELATE, labels, max_label, companions, out)
+
+
+def _companion_table(op: str, bit: int, labels: DeviceArray, max_label: int, companions: DeviceArray, out) -> DeviceArray:
+    """``amt_regionprops_ext`` with one of the bits that take int32 companion label planes -> (nplanes, max_label, C, 4)"""
     ctx = labels.ctx
     n, H, W = _planes(labels)
     if labels.dtype != np.int32:
-        raise TypeError("relate_labels expects int32 labels")
+        raise TypeError(f"{op} expects int32 labels")
     if companions.dtype != np.int32:
         raise TypeError("companion label images must be int32 on the device path")
     if companions.ndim < 2 or companions.shape[-2:] != labels.shape[-2:]:
@@ -1284,9 +1292,44 @@ def relate_labels(labels: DeviceArray, max_label: int, companions: DeviceArray, 
     if C < 1 or companions.size != n * C * H * W:
         raise ValueError("companions / labels plane count mismatch")
     o = _out(ctx, out, (n, max_label, C, 4), np.float64)
-    _no_alias("relate_labels", {"labels": labels, "companions": companions}, {"out": o})  # a companion may be `labels`
-    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, companions.ptr, _hip.I32, C, _hip.RPX_RELATE, None,
-                                          o.ptr, n, H, W, int(max_label)), "amt_regionprops_ext")
+    _no_alias(op, {"labels": labels, "companions": companions}, {"out": o})  # a companion may be `labels`
+    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, companions.ptr, _hip.I32, C, bit, None, o.ptr, n, H, W,
+                                          int(max_label)), "amt_regionprops_ext")
+    return o
+
+
+def neighbor_census(labels: DeviceArray, max_label: int, companions: DeviceArray | None = None, out=None) -> DeviceArray:
+    """Which objects touch every label (``amt_regionprops_ext`` with ``AMT_RPX_NEIGHBORS``; CellProfiler's
+    MeasureObjectNeighbors).
+
+    ``labels`` is int32 (..., Y, X); ``companions`` as for ``relate_labels``, ``None`` for ``labels`` itself (the usual
+    call: the neighbours among the labels' own plane).  The RING of label ``l`` is the set of pixels that do not carry
+    ``l`` and have an 8-neighbour that does (clipped by the plane's border); its neighbour values are the positive
+    companion values other than ``l`` on the ring.  Returns (nplanes, max_label, C, 4) float64 in ``_hip.RPX_NCOLS4``
+    order: ``count`` = the number of distinct neighbour values, ``touching`` = the ring pixels that hold one, ``ring`` =
+    the ring's pixel count, ``main`` = the value on most ring pixels (the smallest among equal counts, 0 without a
+    neighbour).  A label absent from its plane gives four zeros.  All values are exact integers; two runs give
+    identical bytes."""
+    return _companion_table("neighbor_census", _hip.RPX_NEIGHBORS, labels, max_label,
+                            labels if companions is None else companions, out)
+
+
+def nearest_labels(labels: DeviceArray, max_label: int, out=None) -> DeviceArray:
+    """The two nearest labels of every label by centroid distance (``amt_regionprops_ext`` with ``AMT_RPX_NEAREST``).
+
+    Returns (nplanes, max_label, 1, 4) float64 in ``_hip.RPX_DCOLS`` order: ``first`` / ``second`` = the labels of
+    1..max_label present in the plane whose centroids (pixel-coordinate means) are nearest, ordered by (squared
+    distance, label) so that the smallest label wins among equal distances; ``first_distance`` / ``second_distance`` =
+    the Euclidean distances.  Where there is no such label, and for a label absent from its plane, the label is 0 and
+    the distance NaN.  Every pair of labels of a plane is compared; two runs give identical bytes."""
+    ctx = labels.ctx
+    n, H, W = _planes(labels)
+    if labels.dtype != np.int32:
+        raise TypeError("nearest_labels expects int32 labels")
+    o = _out(ctx, out, (n, max_label, 1, 4), np.float64)
+    _no_alias("nearest_labels", {"labels": labels}, {"out": o})
+    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, None, 0, 1, _hip.RPX_NEAREST, None, o.ptr, n, H, W,
+                                          int(max_label)), "amt_regionprops_ext")
     return o
 
 

@@ -689,6 +689,52 @@ class SegmentationMask:
         parent = other.relate(self)["parent"]
         return np.bincount(parent, minlength=self.num_cells + 1)[1:self.num_cells + 1].astype(np.int64)
 
+    def cell_neighbors(self, distance: float = 0, other=None) -> dict[str, ScalarArray]:
+        """Every cell's surroundings, one entry per cell ordered by label like ``cell_properties`` (CellProfiler's
+        MeasureObjectNeighbors), measured on the device:
+
+        number_of_neighbors      how many different cells touch the cell (int64)
+        touching_pixels          the pixels of the cell's ring that belong to another cell (int64)
+        ring_pixels              the pixels of the ring: those outside the cell with one of its pixels among their
+                                 eight neighbours; the image border clips it (int64)
+        percent_touching         100 * touching_pixels / ring_pixels; NaN when the ring is empty, i.e. the cell fills
+                                 the image (float64)
+        main_neighbor            the cell holding most of the ring's pixels, the SMALLEST label among equals; 0 without
+                                 a neighbour (int64)
+        first_closest_label      the cell whose centroid is nearest, the SMALLEST label among equally near ones; 0 when
+                                 the cell is alone (int64)
+        first_closest_distance   the distance between the two centroids in pixels; NaN when the cell is alone (float64)
+        second_closest_label / second_closest_distance   the same for the next nearest cell
+
+        ``distance == 0``: cells are neighbours when they touch, diagonally included.  ``distance > 0``: the first five
+        columns are taken on ``self.expanded(distance)`` -- two cells are neighbours when their GROWN versions touch,
+        CellProfiler's "expand" flavour -- which bridges a gap of about ``2 * distance`` pixels between the cells
+        themselves.  The four closest columns always come from this mask's own centroids.  ``other`` (a
+        ``SegmentationMask`` or a non-negative integer label array of the same shape, as for ``relate``) replaces the
+        label plane whose values are looked up on the rings -- "which cells touch the ring of this nucleus" -- and is
+        used as it is, never grown; the closest columns ignore it.  Works on ``expanded`` / ``ring`` masks and on masks
+        from ``batch_masks``; the label plane does not leave the device, only the two (num_cells x 4) tables come back
+        (``hipops.neighbor_census``, ``hipops.nearest_labels``; keys: ``segment.neighbor_keys``)."""
+        from . import _hip, hipops
+
+        d = float(distance)
+        if not (np.isfinite(d) and d >= 0):
+            raise ValueError(f"distance must be non-negative and finite, got {distance}")
+        plane, k = self._label_plane()
+        comp = None if other is None else self._companion_plane(other)
+        shape = tuple(plane.shape)
+        grown = hipops.expand_labels(plane, d) if d > 0 else plane
+        census = hipops.neighbor_census(grown.reshape((1,) + shape), max(k, 1),
+                                        None if comp is None else comp.reshape((1, 1) + shape)).numpy()[0, :k, 0, :]
+        near = hipops.nearest_labels(plane.reshape((1,) + shape), max(k, 1)).numpy()[0, :k, 0, :]
+        cen = {name: census[:, i].astype(np.int64) for i, name in enumerate(_hip.RPX_NCOLS4)}
+        with np.errstate(invalid="ignore", divide="ignore"):
+            percent = 100.0 * cen["touching"].astype(np.float64) / cen["ring"].astype(np.float64)
+        return {"number_of_neighbors": cen["count"], "touching_pixels": cen["touching"], "ring_pixels": cen["ring"],
+                "percent_touching": percent, "main_neighbor": cen["main"],
+                "first_closest_label": near[:, 0].astype(np.int64), "first_closest_distance": near[:, 1].copy(),
+                "second_closest_label": near[:, 2].astype(np.int64), "second_closest_distance": near[:, 3].copy()}
+
     def convert_properties_to_microns(self, pixel_size_um: float) -> dict[str, ScalarArray]:
         """Scale lengths / areas / volumes to microns with ``_um`` / ``_um2`` / ``_um3`` key suffixes
         (R/masks.py:420-467); dimensionless and intensity columns pass through."""

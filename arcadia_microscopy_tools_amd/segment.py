@@ -455,6 +455,14 @@ def robust_intensity_keys(channel_names) -> list[str]:
     return [f"intensity_{stat}_{name}" for name in names for stat in _hip.RPX_QCOLS]
 
 
+def neighbor_keys() -> list[str]:
+    """The keys of ``SegmentationMask.cell_neighbors``, in order (no device needed): the contact census of
+    ``_hip.RPX_NCOLS4`` with ``percent_touching`` after the two pixel counts it is made of, then the two closest cells
+    of ``_hip.RPX_DCOLS``."""
+    return ["number_of_neighbors", "touching_pixels", "ring_pixels", "percent_touching", "main_neighbor",
+            "first_closest_label", "first_closest_distance", "second_closest_label", "second_closest_distance"]
+
+
 def segment_fovs(fovs, *, ctx: Context | None = None, channel_names=DEFAULT_CHANNELS, **kw) -> SegmentationResult:
     """Convenience: (B, C, H, W) uint16 (numpy or DeviceArray) -> config-3 ``SegmentationResult``."""
     ctx = ctx or get_context()

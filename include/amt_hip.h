@@ -479,6 +479,43 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
  * AMT_RPX_CENTROID_WEIGHTED is set.  A label with zero total intensity gets NaN weighted centroids; labels absent
  * from a plane get 0 in every column.
  *
+ * ---- a label's surroundings: AMT_RPX_NEIGHBORS and AMT_RPX_NEAREST ----
+ * CellProfiler's MeasureObjectNeighbors columns.  Both bits fill wtable_dev = nplanes x max_label x C x 4 doubles; the
+ * integers among them are exact and held in doubles.
+ * AMT_RPX_NEIGHBORS, the contact census: intensity is nplanes x C COMPANION LABEL planes, one (C, Y, X) stack per label
+ * plane, in_code == AMT_I32, C >= 1, exactly as for AMT_RPX_RELATE; a companion may be the very buffer `labels` points
+ * to, which is the usual call.  Companion values <= 0 are background.  For label l with pixel set P the RING R is the set
+ * of in-image pixels q with labels[q] != l that have an 8-neighbour in P (a diagonal contact counts; the plane's border
+ * clips the ring), and the neighbour values N of a companion plane B are the multiset {B[q] : q in R, B[q] > 0,
+ * B[q] != l}: a label is not its own neighbour.  The four columns are
+ *   AMT_RPX_NCOL_COUNT     the number of distinct values in N
+ *   AMT_RPX_NCOL_TOUCHING  |N|, the ring pixels held by another object
+ *   AMT_RPX_NCOL_RING      |R| (0 when the label fills its plane)
+ *   AMT_RPX_NCOL_MAIN      the value with most pixels in N; among equal counts the smallest value wins; 0 when N is
+ *                          empty
+ * A label absent from its plane gives 0, 0, 0, 0.  Label values outside 1..max_label are never measured, but count as
+ * neighbours when positive.  Counts are integer sums: two runs give identical bytes.  Up to AMT_RELATE_LDS_PARTNERS
+ * distinct values of N are counted in LDS in one pass over the label's bounding box grown by one pixel; a label with
+ * more is still exact, at one pass per value, as for AMT_RPX_RELATE.
+ * AMT_RPX_NEAREST, the two nearest labels by centroid: intensity must be NULL, in_code 0 and C == 1.  The centroid of
+ * label m is cy = (double)sum_y / (double)area and cx likewise, from integer sums (exact below 2^53 for every plane
+ * this ABI accepts).  For label l every other label m of 1..max_label that is present in the plane gets
+ * d2 = dy * dy + dx * dx with dy and dx the differences of the centroids, evaluated in that order in float64 without
+ * fused multiply-add; the candidates are ordered by (d2, m), so among equal distances the smallest label wins.
+ *   AMT_RPX_DCOL_FIRST / AMT_RPX_DCOL_FIRST_DISTANCE    the nearest label and sqrt(d2)
+ *   AMT_RPX_DCOL_SECOND / AMT_RPX_DCOL_SECOND_DISTANCE  the next one
+ * A first or second neighbour that does not exist gives label 0 and distance NaN; a label absent from its plane gives
+ * 0, NaN, 0, NaN.  Label values outside 1..max_label are ignored.  The search compares every pair of labels of a plane
+ * (max_label^2 / 2 distances); nothing depends on an order of accumulation: two runs give identical bytes.
+ * One call sets at most one of AMT_RPX_CENTROID_WEIGHTED, AMT_RPX_RELATE, AMT_RPX_ROBUST, AMT_RPX_NEIGHBORS and
+ * AMT_RPX_NEAREST (they share wtable_dev): more is AMT_EINVAL.  The morphology bits may be combined with either new
+ * bit; table_dev is then given and its columns equal those of a call of their own.  AMT_RPX_NEIGHBORS with an in_code
+ * other than AMT_I32 or without planes is AMT_EINVAL, and so is AMT_RPX_NEAREST with planes, an in_code other than 0
+ * or C != 1.  wtable_dev is given exactly when one of the five bits is set, intensity and C >= 1 exactly when one of
+ * the first four is; AMT_I32 planes go with AMT_RPX_RELATE or AMT_RPX_NEIGHBORS.  The accepted mask is
+ * AMT_RPX_ALL | AMT_RPX_RELATE | AMT_RPX_ROBUST | AMT_RPX_NEIGHBORS | AMT_RPX_NEAREST.  nplanes == 0 or max_label == 0
+ * is AMT_OK and writes nothing; every refusal happens before the first launch.
+ *
  * ---- robust intensity statistics per label: AMT_RPX_ROBUST ----
  * With AMT_RPX_ROBUST set, intensity is nplanes x C planes of in_code AMT_U16 or AMT_F64, one (C, Y, X) stack per label
  * plane, C >= 1, and wtable_dev = nplanes x max_label x C x 4 doubles.  For label l with the pixel multiset V of a
@@ -497,12 +534,13 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
  * AMT_F64 selects on order-preserving 64-bit keys, 8 bits per sweep (plain and untuned); images that hold NaN or
  * infinities are not supported, and -0.0 sorts before +0.0.  A label absent from its plane gives four NaNs (numpy on an
  * empty array).  Counts are integer sums: two runs give identical bytes.
- * AMT_RPX_ROBUST together with AMT_RPX_CENTROID_WEIGHTED or AMT_RPX_RELATE is AMT_EINVAL (they share intensity and
- * wtable_dev); the morphology bits may be combined with it, table_dev is then given and its columns equal those of a
- * call of their own.  in_code other than AMT_U16 / AMT_F64 with the bit is AMT_EINVAL.  intensity, C >= 1 and
- * wtable_dev are given exactly when one of AMT_RPX_CENTROID_WEIGHTED, AMT_RPX_RELATE and AMT_RPX_ROBUST is set; the
- * accepted mask is AMT_RPX_ALL | AMT_RPX_RELATE | AMT_RPX_ROBUST.  nplanes == 0 or max_label == 0 is AMT_OK and writes
- * nothing; every refusal happens before the first launch.
+ * AMT_RPX_ROBUST together with AMT_RPX_CENTROID_WEIGHTED, AMT_RPX_RELATE, AMT_RPX_NEIGHBORS or AMT_RPX_NEAREST is
+ * AMT_EINVAL (they share wtable_dev); the morphology bits may be combined with it, table_dev is then given and its
+ * columns equal those of a call of their own.  in_code other than AMT_U16 / AMT_F64 with the bit is AMT_EINVAL.
+ * intensity, C >= 1 and wtable_dev are given exactly when one of AMT_RPX_CENTROID_WEIGHTED, AMT_RPX_RELATE,
+ * AMT_RPX_ROBUST and AMT_RPX_NEIGHBORS is set (AMT_RPX_NEAREST: wtable_dev alone); the accepted mask is
+ * AMT_RPX_ALL | AMT_RPX_RELATE | AMT_RPX_ROBUST | AMT_RPX_NEIGHBORS | AMT_RPX_NEAREST.  nplanes == 0 or max_label == 0
+ * is AMT_OK and writes nothing; every refusal happens before the first launch.
  *
  * ---- relating two label images: AMT_RPX_RELATE ----
  * "Measure label image A with label image B as its intensity image": with AMT_RPX_RELATE set, intensity is
@@ -520,9 +558,9 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
  * with more is still exact, at one pass over its box per partner.
  * AMT_RPX_RELATE and AMT_RPX_CENTROID_WEIGHTED in one call is AMT_EINVAL (they share intensity and wtable_dev); the
  * morphology bits may be combined with either.  in_code != AMT_I32 with the bit set is AMT_EINVAL, and so is
- * in_code == AMT_I32 without it.  intensity, C >= 1 and wtable_dev are given exactly when AMT_RPX_RELATE or
- * AMT_RPX_CENTROID_WEIGHTED is set.  AMT_RPX_ALL stays the scikit-image columns; the accepted mask is
- * AMT_RPX_ALL | AMT_RPX_RELATE.  nplanes == 0 or max_label == 0 is AMT_OK and writes nothing. */
+ * in_code == AMT_I32 without it (or AMT_RPX_NEIGHBORS, which takes the same planes).  AMT_RPX_ALL stays the
+ * scikit-image columns; which of the later bits exclude each other, when intensity, C >= 1 and wtable_dev are given
+ * and the accepted mask stand in the blocks above.  nplanes == 0 or max_label == 0 is AMT_OK and writes nothing. */
 #define AMT_RPX_EULER_NUMBER (1u << 0)
 #define AMT_RPX_PERIMETER_CROFTON (1u << 1)
 #define AMT_RPX_AREA_FILLED (1u << 2)
@@ -544,6 +582,16 @@ int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels, const dou
 #define AMT_RPX_QCOL_Q75 2
 #define AMT_RPX_QCOL_MAD 3
 #define AMT_ROBUST_LDS_BINS 1024
+#define AMT_RPX_NEIGHBORS (1u << 10)
+#define AMT_RPX_NCOL_COUNT 0
+#define AMT_RPX_NCOL_TOUCHING 1
+#define AMT_RPX_NCOL_RING 2
+#define AMT_RPX_NCOL_MAIN 3
+#define AMT_RPX_NEAREST (1u << 11)
+#define AMT_RPX_DCOL_FIRST 0
+#define AMT_RPX_DCOL_FIRST_DISTANCE 1
+#define AMT_RPX_DCOL_SECOND 2
+#define AMT_RPX_DCOL_SECOND_DISTANCE 3
 #define AMT_RPX_COL_EULER_NUMBER 0
 #define AMT_RPX_COL_PERIMETER_CROFTON 1
 #define AMT_RPX_COL_AREA_FILLED 2
