@@ -153,10 +153,25 @@ enum amt_comp_what { AMT_COMP_OBJECTS_BY_AREA, AMT_COMP_HOLES_BY_AREA, AMT_COMP_
 int amt_i_component_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, bool c8,
                            amt_comp_what what, int size);
 
-// AMT_RPX_ROBUST of amt_regionprops_ext (amt_robust.hip), which checks the arguments and makes the bounding boxes:
-// wtable[plane][label][channel] = {q25, median, q75, MAD} of the AMT_U16 / AMT_F64 channel over the label
+// ---- per-label operations: one wave per (label, plane) over the label's bounding box (amt_perlabel.h) ---------------
+// The box pass (amt_props.hip): bbox[plane][label] = {miny, minx, maxy, maxx} of every label 1..max_label, maxy < miny
+// for a label absent from its plane; acc (nullable) = the moment accumulators of amt_props.hip per (plane, label),
+// cleared by the same launch
+int amt_i_label_boxes(amt_ctx* ctx, const int* labels, int* bbox, unsigned long long* acc, int nplanes, int H, int W,
+                      int max_label);
+// The table bits of amt_regionprops_ext, which checks the arguments and makes the bounding boxes; wtable[plane][label]
+// [channel] holds four columns.  AMT_RPX_ROBUST (amt_robust.hip): {q25, median, q75, MAD} of the AMT_U16 / AMT_F64
+// channel over the label
 int amt_i_robust_intensity(amt_ctx* ctx, const int* labels, const int* bbox, const void* intensity, int in_code, int C,
                            double* wtable, int nplanes, int H, int W, int max_label);
+// AMT_RPX_RELATE / AMT_RPX_NEIGHBORS (amt_relate.hip): the census of companion plane `comp[plane][channel]` under the
+// label's pixels / on its ring; AMT_RPX_NEAREST: the two nearest labels by the centroids cen[plane][label] = (cy, cx),
+// NaN for an absent label
+int amt_i_relate_labels(amt_ctx* ctx, const int* labels, const int* bbox, const int* comp, int C, double* wtable,
+                        int nplanes, int H, int W, int max_label);
+int amt_i_neighbor_census(amt_ctx* ctx, const int* labels, const int* bbox, const int* comp, int C, double* wtable,
+                          int nplanes, int H, int W, int max_label);
+int amt_i_nearest_labels(amt_ctx* ctx, const double2* cen, double* wtable, int nplanes, int max_label);
 
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>

@@ -10,6 +10,7 @@
 // A wave covers 64 consecutive pixels of one row; equal-label runs inside it are reduced in closed
 // form (coordinates) or with wave prefix sums (intensities), so each run costs one set of atomics.
 #include "amt_internal.h"
+#include "amt_perlabel.h"
 
 #include <vector>
 
@@ -17,11 +18,12 @@ typedef unsigned long long u64;
 
 // accumulator slots per (plane, label)
 enum { A_N = 0, A_SY, A_SX, A_SYY, A_SXX, A_SXY, A_C1, A_C2, A_C3, A_NACC };
-// bbox ints per (plane, label): miny, minx, maxy, maxx
 
+// empty boxes (amt_box of amt_perlabel.h) and, with `acc`, cleared accumulators
 __global__ void __launch_bounds__(256) rp_init_kernel(u64* __restrict__ acc, int* __restrict__ bbox, size_t nlab) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nlab; i += (size_t)gridDim.x * 256) {
-        for (int k = 0; k < A_NACC; ++k) acc[i * A_NACC + k] = 0;
+        if (acc)
+            for (int k = 0; k < A_NACC; ++k) acc[i * A_NACC + k] = 0;
         bbox[i * 4 + 0] = 0x7fffffff;
         bbox[i * 4 + 1] = 0x7fffffff;
         bbox[i * 4 + 2] = -1;
@@ -83,73 +85,17 @@ __global__ void __launch_bounds__(256) rp_bbox_kernel(const int* __restrict__ la
     }
 }
 
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        unsigned t = __shfl_xor(v, off);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        unsigned t = __shfl_xor(v, off);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
-// Sums of 16 values per lane over the wave for 17 exchanges (one all-reduce each takes 96): every step halves what a lane
-// still carries -- it keeps one half of its values, hands the other half to the lane `4 * HALF` away and adds what that
-// lane hands over; the last two levels are an all-reduce.  On return lane L holds the wave's sum of value (L >> 2) & 15.
-// Integer sums: any order gives the same bits.
-template <int HALF>
-__device__ __forceinline__ void wave_scatter16_step(u64 (&t)[16], int lane) {
-    const bool up = (lane & (4 * HALF)) != 0;
-#pragma unroll
-    for (int i = 0; i < HALF; ++i) {
-        const u64 keep = up ? t[i + HALF] : t[i];
-        const u64 send = up ? t[i] : t[i + HALF];
-        t[i] = keep + __shfl_xor(send, 4 * HALF);
-    }
-}
-__device__ __forceinline__ u64 wave_reduce_scatter16(u64 (&t)[16], int lane) {
-    wave_scatter16_step<8>(t, lane);
-    wave_scatter16_step<4>(t, lane);
-    wave_scatter16_step<2>(t, lane);
-    wave_scatter16_step<1>(t, lane);
-    u64 v = t[0];
-    v += __shfl_xor(v, 2);
-    return v + __shfl_xor(v, 1);
-}
-// The same for the minima of 8 values per lane: on return lane L holds the wave's minimum of value (L >> 3) & 7.
-template <int HALF>
-__device__ __forceinline__ void wave_scatter8_min_step(unsigned (&t)[8], int lane) {
-    const bool up = (lane & (8 * HALF)) != 0;
-#pragma unroll
-    for (int i = 0; i < HALF; ++i) {
-        const unsigned keep = up ? t[i + HALF] : t[i];
-        const unsigned got = __shfl_xor(up ? t[i] : t[i + HALF], 8 * HALF);
-        t[i] = got < keep ? got : keep;
-    }
-}
-__device__ __forceinline__ unsigned wave_min_scatter8(unsigned (&t)[8], int lane) {
-    wave_scatter8_min_step<4>(t, lane);
-    wave_scatter8_min_step<2>(t, lane);
-    wave_scatter8_min_step<1>(t, lane);
-    unsigned v = t[0];
-#pragma unroll
-    for (int off = 4; off >= 1; off >>= 1) {
-        const unsigned o = __shfl_xor(v, off);
-        v = o < v ? o : v;
-    }
-    return v;
+// The box pass of every per-label operation: bbox[plane][label] = the label's box, empty for an absent label; `acc`
+// (nullable) = the A_NACC accumulators per (plane, label), cleared by the same launch.
+int amt_i_label_boxes(amt_ctx* ctx, const int* labels, int* bbox, unsigned long long* acc, int nplanes, int H, int W,
+                      int max_label) {
+    const size_t nlab = (size_t)nplanes * max_label;
+    hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
+    AMT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels, bbox,
+                       H, W, max_label);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
 }
 
 // One wave per label scans the label's bounding box (and nothing else): exact integer moment sums,
@@ -301,9 +247,10 @@ __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ la
     const int l = blockIdx.x;
     const int lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
-    if (y1 < y0) {  // label absent from this plane
-        if (itable && lane < 4 * nc) itable[(li * C + c0) * 4 + lane] = 0.0;
+    const amt_box box = amt_load_box(bbox, li);
+    const int y0 = box.y0, x0 = box.x0, y1 = box.y1, x1 = box.x1;
+    if (box.absent()) {
+        if (itable) amt_fill_row(itable + (li * C + c0) * 4, 4 * nc, 0.0, lane);
         return;
     }
     const size_t n = (size_t)H * W;
@@ -339,10 +286,10 @@ __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ la
         e[RP_MAXC + c] = ~a.mx[c];
     }
     t[14] = t[15] = 0;
-    const u64 red = wave_reduce_scatter16(t, lane);  // value k in the lanes 4 k .. 4 k + 3
+    const u64 red = amt_wave_reduce_scatter<16, amt_op_sum>(t, lane);  // value k in the lanes 4 k .. 4 k + 3
     if (want_morph && (lane & 3) == 0 && lane < 4 * 6) acc[li * A_NACC + (lane >> 2)] = red;
     if (itable) {
-        const unsigned ext = wave_min_scatter8(e, lane);  // value k in the lanes 8 k .. 8 k + 7
+        const unsigned ext = amt_wave_reduce_scatter<8, amt_op_min>(e, lane);  // value k in the lanes 8 k .. 8 k + 7
         // lane c finalises channel c
         const u64 cnt = __shfl(red, 0), S = __shfl(red, 4 * (6 + lane)), Q = __shfl(red, 4 * (6 + RP_MAXC + lane));
         const unsigned lo = __shfl(ext, 8 * lane), hi = ~__shfl(ext, 8 * (RP_MAXC + lane));
@@ -808,17 +755,16 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
     amt_buf<int2> chainL(s, (size_t)nplanes * 3 * cap);
     amt_buf<int2> chainR(s, (size_t)nplanes * 3 * cap);
     AMT_TRY(s.commit());
-    hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
-    AMT_LAUNCH_CHECK();
     if (want_morph) {  // the perimeter pass stages every label tile anyway: it folds the bounding boxes too
+        hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
+        AMT_LAUNCH_CHECK();
         const int nstrips = (W + PR_IN - 1) / PR_IN;
         dim3 gper((nstrips + 3) / 4, (H + PR_ROWS - 1) / PR_ROWS, nplanes);
         hipLaunchKernelGGL(rp_perimeter_rows_kernel, gper, dim3(256), 0, ctx->stream, labels, acc, H, W, max_label, bbox);
+        AMT_LAUNCH_CHECK();
     } else {
-        hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream,
-                           labels, bbox, H, W, max_label);
+        AMT_TRY(amt_i_label_boxes(ctx, labels, bbox, acc, nplanes, H, W, max_label));
     }
-    AMT_LAUNCH_CHECK();
     hipLaunchKernelGGL(rp_heights_kernel, dim3(amt_grid_for(max_label, 256, 256), nplanes), dim3(256), 0, ctx->stream,
                        bbox, hoff, max_label);
     AMT_LAUNCH_CHECK();
@@ -850,16 +796,6 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
     return AMT_OK;
 }
 
-// ---- bounding boxes only (what the outline extractor needs, R/masks.py:99) ---------------------------
-__global__ void __launch_bounds__(256) bbox_init_kernel(int* __restrict__ bbox, size_t nlab) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nlab; i += (size_t)gridDim.x * 256) {
-        bbox[i * 4 + 0] = 0x7fffffff;
-        bbox[i * 4 + 1] = 0x7fffffff;
-        bbox[i * 4 + 2] = -1;
-        bbox[i * 4 + 3] = -1;
-    }
-}
-
 // ---- intensity statistics of float64 images (R/masks.py:319-323 accepts any 2-D ndarray as intensity image) -------
 // One wave per label over its bounding box, two sweeps as np.mean / np.std make them: the mean first, then the mean
 // of the squared deviations (population std).  float64 sums depend on the order of addition: results
@@ -869,19 +805,15 @@ __global__ void __launch_bounds__(64) rp_intensity_f64_kernel(const int* __restr
                                                               double* __restrict__ itable, int H, int W, int max_label) {
     const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    const amt_box box = amt_load_box(bbox, li);
+    const int y0 = box.y0, x0 = box.x0, y1 = box.y1, x1 = box.x1;
     double* out = itable + li * (size_t)C * 4;
-    if (y1 < y0) {
-        for (int i = lane; i < C * 4; i += 64) out[i] = 0.0;
+    if (box.absent()) {
+        amt_fill_row(out, C * 4, 0.0, lane);
         return;
     }
     const size_t n = (size_t)H * W;
     const int* lab = labels + (size_t)plane * n;
-    auto wsum = [&](double v) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        return v;
-    };
     for (int c = 0; c < C; ++c) {
         const double* img = inten + ((size_t)plane * C + c) * n;
         double s = 0.0, cnt = 0.0, mn = __longlong_as_double(0x7ff0000000000000ll), mx = -mn;
@@ -894,14 +826,10 @@ __global__ void __launch_bounds__(64) rp_intensity_f64_kernel(const int* __restr
                     mn = v < mn ? v : mn;
                     mx = v > mx ? v : mx;
                 }
-        s = wsum(s);
-        cnt = wsum(cnt);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double a = __shfl_xor(mn, o), b = __shfl_xor(mx, o);
-            mn = a < mn ? a : mn;
-            mx = b > mx ? b : mx;
-        }
+        s = amt_wave_sum(s);
+        cnt = amt_wave_sum(cnt);
+        mn = amt_wave_min(mn);
+        mx = amt_wave_max(mx);
         const double mean = s / cnt;
         double q = 0.0;
         for (int y = y0; y <= y1; ++y)
@@ -910,7 +838,7 @@ __global__ void __launch_bounds__(64) rp_intensity_f64_kernel(const int* __restr
                     const double d = img[(size_t)y * W + x] - mean;
                     q += d * d;
                 }
-        q = wsum(q);
+        q = amt_wave_sum(q);
         if (lane == 0) {
             out[c * 4 + 0] = mean;
             out[c * 4 + 1] = mx;
@@ -929,21 +857,17 @@ extern "C" int amt_regionprops_intensity_f64(amt_ctx* ctx, const int32_t* labels
     AMT_REQUIRE(labels && intensity && table_dev && nplanes >= 0 && H > 0 && W > 0 && max_label >= 0 && C >= 1,
                 "regionprops_intensity_f64: bad arguments");
     if (nplanes == 0 || max_label == 0) return AMT_OK;
-    const size_t nlab = (size_t)nplanes * max_label;
     amt_scratch s(ctx);
-    amt_buf<int> bbox(s, nlab * 4);
+    amt_buf<int> bbox(s, (size_t)nplanes * max_label * 4);
     AMT_TRY(s.commit());
-    hipLaunchKernelGGL(bbox_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, bbox, nlab);
-    AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels, bbox,
-                       H, W, max_label);
-    AMT_LAUNCH_CHECK();
+    AMT_TRY(amt_i_label_boxes(ctx, labels, bbox, nullptr, nplanes, H, W, max_label));
     hipLaunchKernelGGL(rp_intensity_f64_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox, intensity, C,
                        table_dev, H, W, max_label);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
 
+// ---- bounding boxes only (what the outline extractor needs, R/masks.py:99) ---------------------------
 extern "C" int amt_label_bboxes(amt_ctx* ctx, const int32_t* labels, int32_t* bbox_dev, int nplanes, int H, int W,
                                 int max_label) {
     AMT_CHECK_OPERANDS("amt_label_bboxes", amt_in("labels", labels, amt_span(4, nplanes, H, W)),
@@ -951,13 +875,7 @@ extern "C" int amt_label_bboxes(amt_ctx* ctx, const int32_t* labels, int32_t* bb
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(labels && bbox_dev && nplanes >= 0 && H > 0 && W > 0 && max_label >= 1, "label_bboxes: bad arguments");
     if (nplanes == 0) return AMT_OK;
-    const size_t nlab = (size_t)nplanes * max_label;
-    hipLaunchKernelGGL(bbox_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, bbox_dev, nlab);
-    AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels,
-                       bbox_dev, H, W, max_label);
-    AMT_LAUNCH_CHECK();
-    return AMT_OK;
+    return amt_i_label_boxes(ctx, labels, bbox_dev, nullptr, nplanes, H, W, max_label);
 }
 
 // ---- extended region properties (amt_regionprops_ext) ---------------------------------------------------------------
@@ -979,10 +897,11 @@ __global__ void __launch_bounds__(64) rpx_quad_kernel(const int* __restrict__ la
     const size_t li = (size_t)plane * max_label + l;
     if (lane < 16) hist[lane] = 0;
     __syncthreads();
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    const amt_box box = amt_load_box(bbox, li);
+    const int y0 = box.y0, x0 = box.x0, y1 = box.y1, x1 = box.x1;
     const int* L = labels + (size_t)plane * H * W;
     const int want = l + 1;
-    if (y1 >= y0) {
+    if (!box.absent()) {
         for (int xb = x0; xb <= x1 + 1; xb += 64) {
             const int x = xb + lane;
             const bool col = x <= x1 + 1;
@@ -1013,7 +932,7 @@ __global__ void __launch_bounds__(64) rpx_quad_kernel(const int* __restrict__ la
                                       0, pi / (4 * s2), pi / 4, pi / 2, pi / (4 * s2), pi / (4 * s2), pi / 4, pi / 2, 0, 0};
             double p = 0.0;
             for (int k = 0; k < 16; ++k) p += coefs[k] * (double)h[k];
-            t[AMT_RPX_COL_PERIMETER_CROFTON] = y1 >= y0 ? p : 0.0;
+            t[AMT_RPX_COL_PERIMETER_CROFTON] = box.absent() ? 0.0 : p;
         }
     }
 }
@@ -1035,13 +954,14 @@ __global__ void __launch_bounds__(64) rpx_holes_small_kernel(const int* __restri
                                                              int H, int W, int max_label) {
     const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    const amt_box box = amt_load_box(bbox, li);
+    const int y0 = box.y0, x0 = box.x0;
     double* t = table + li * AMT_RPX_NCOLS;
-    if (y1 < y0) {
+    if (box.absent()) {
         if (lane == 0) t[AMT_RPX_COL_AREA_FILLED] = 0.0;
         return;
     }
-    const int h = y1 - y0 + 1, w = x1 - x0 + 1;
+    const int h = box.h(), w = box.w();
     if (h > HOLE_SMALL || w > HOLE_SMALL) return;  // rpx_holes_large_kernel
     const int* L = labels + (size_t)plane * H * W;
     const u64 wmask = w == 64 ? ~0ull : (1ull << w) - 1ull;
@@ -1065,7 +985,7 @@ __global__ void __launch_bounds__(64) rpx_holes_small_kernel(const int* __restri
         if (!changed) break;
     }
     u64 holes = (u64)__popcll(b & ~r);
-    holes = wave_sum_u64(holes);
+    holes = amt_wave_sum(holes);
     if (lane == 0) t[AMT_RPX_COL_AREA_FILLED] = (double)(acc[li * A_NACC + A_N] + holes);
 }
 
@@ -1150,7 +1070,7 @@ __global__ void __launch_bounds__(256) rpx_holes_large_kernel(const int* __restr
             }
             u64 holes = 0;
             for (int i = tid; i < nw; i += 256) holes += (u64)__popcll(Bw[i] & ~Rw[i]);
-            holes = wave_sum_u64(holes);
+            holes = amt_wave_sum(holes);
             if (lane == 0) red[wv] = holes;
             __syncthreads();
             if (tid == 0)
@@ -1248,11 +1168,7 @@ __global__ void __launch_bounds__(64) rpx_feret_kernel(const int* __restrict__ b
                 best = d > best ? d : best;
             }
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const long long v = __shfl_xor(best, o);
-        best = v > best ? v : best;
-    }
+    best = amt_wave_max(best);
     if (lane == 0) t[AMT_RPX_COL_FERET_DIAMETER_MAX] = sqrt((double)best) * 0.5;  // = sqrt(best / 4), exactly
 }
 
@@ -1310,9 +1226,10 @@ __global__ void __launch_bounds__(64) rpx_weighted_kernel(const int* __restrict_
     const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
     double* out = wtable + li * (size_t)C * 4;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
-    if (y1 < y0) {
-        for (int i = lane; i < C * 4; i += 64) out[i] = 0.0;
+    const amt_box box = amt_load_box(bbox, li);
+    const int y0 = box.y0, x0 = box.x0, y1 = box.y1, x1 = box.x1;
+    if (box.absent()) {
+        amt_fill_row(out, C * 4, 0.0, lane);
         return;
     }
     const size_t n = (size_t)H * W;
@@ -1328,12 +1245,7 @@ __global__ void __launch_bounds__(64) rpx_weighted_kernel(const int* __restrict_
                     sy += v * (S)(y - y0);
                     sx += v * (S)(x - x0);
                 }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            s += __shfl_xor(s, o);
-            sy += __shfl_xor(sy, o);
-            sx += __shfl_xor(sx, o);
-        }
+        s = amt_wave_sum(s), sy = amt_wave_sum(sy), sx = amt_wave_sum(sx);
         if (lane == 0) {
             const double ly = (double)sy / (double)s, lx = (double)sx / (double)s;  // 0 / 0 = NaN, as scikit-image
             out[c * 4 + 0] = ly + (double)y0;
@@ -1344,267 +1256,8 @@ __global__ void __launch_bounds__(64) rpx_weighted_kernel(const int* __restrict_
     }
 }
 
-// ---- relate two label images (AMT_RPX_RELATE) -----------------------------------------------------------------------
-// One wave per (label, plane) over the label's box, one companion label plane after the other: which companion values
-// lie under the label's pixels, and how often.  The (value, count) pairs live in an open-addressed LDS table of
-// RL_SLOTS slots (key 0 = empty: a partner is never 0), home slot = value mod RL_SLOTS, linear probing, claimed with a
-// compare-and-swap and counted with an add.  A probe sequence visits every slot once and then gives up, so the table
-// holds up to RL_SLOTS distinct partners however their values collide, and no lane ever waits for another.  Counts are
-// integer sums: the order in which the lanes arrive changes which slot a value gets, never a count.
-// A lane keeps the run of equal values it is reading down its column in registers and goes to the table when the value
-// changes: a nucleus inside one cell costs a lane one table update, not one per pixel.
-// LDS: 2 x 4 x RL_SLOTS = 1 KiB per workgroup of one wave, so the 32-wave cap of a CU binds (8 waves per SIMD), not
-// the LDS (160 workgroups' worth).
-// More than RL_SLOTS distinct partners (a lane found no slot): the table is dropped and the partners are selected one
-// by one in ascending order, one pass over the box each -- the pass that counts partner v also finds the smallest
-// value above v.  Every pass raises v, so there are (partners + 1) passes and then it ends.
-constexpr int RL_SLOTS = AMT_RELATE_LDS_PARTNERS;
-static_assert((RL_SLOTS & (RL_SLOTS - 1)) == 0 && RL_SLOTS >= 64, "slot index by mask; a lane reduces RL_SLOTS / 64 slots");
-
-// f(v) for the companion value v under every pixel of the label, each pixel once.  The wave covers 2^lc columns x
-// (64 >> lc) rows per row slot (rp_label_scan's layouts, and 8 x 8 for the smallest boxes); two row slots per step with
-// their four loads issued together from coordinates clamped into the box.
-template <typename F>
-__device__ __forceinline__ void rl_for_pixels(const int* __restrict__ L, const int* __restrict__ B, int W, int x0, int y0,
-                                              int x1, int y1, int want, int lc, int lane, F&& f) {
-    const int cols = 1 << lc, rw = 64 >> lc;
-    const int col = lane & (cols - 1), sub = lane >> lc;
-    for (int yb = y0 + sub; yb - sub <= y1; yb += 2 * rw) {
-        const int ya = yb, yc = yb + rw;
-        const size_t ra = (size_t)(ya <= y1 ? ya : y1) * W, rc = (size_t)(yc <= y1 ? yc : y1) * W;
-        for (int xb = x0; xb <= x1; xb += cols) {
-            const int x = xb + col, xc = x <= x1 ? x : x1;
-            const int la = L[ra + xc], lb = L[rc + xc];
-            const int va = B[ra + xc], vb = B[rc + xc];
-            if (x <= x1 && ya <= y1 && la == want) f(va);
-            if (x <= x1 && yc <= y1 && lb == want) f(vb);
-        }
-    }
-}
-
-// add `c` pixels of partner `v` (> 0) to the table; false when all RL_SLOTS slots belong to other values
-__device__ __forceinline__ bool rl_table_add(int* keys, unsigned* cnts, int v, unsigned c) {
-    unsigned s = (unsigned)v & (RL_SLOTS - 1);
-    for (int probe = 0; probe < RL_SLOTS; ++probe) {
-        int k = ((volatile int*)keys)[s];  // a key never changes once set: only an empty slot needs the exchange
-        if (k == 0) k = atomicCAS(&keys[s], 0, v);  // the value found there, 0 when this lane claimed the slot
-        if (k == 0 || k == v) {
-            atomicAdd(&cnts[s], c);
-            return true;
-        }
-        s = (s + 1) & (RL_SLOTS - 1);
-    }
-    return false;
-}
-
-// The census of the values one wave is handed: `each(f)` calls f(v) once for every pixel that counts, every call of
-// `each` in the same order.  Values <= 0 and the value `skip` are seen and not counted.  total = all values seen,
-// counted = those that count, partners = the distinct ones among them, best / bestv = the maximal count of one value and
-// the smallest value that has it (0, 0 without any).  keys / cnts: the wave's table of RL_SLOTS slots.
-struct rl_census_t {
-    unsigned total, counted, partners, best, bestv;
-};
-template <typename Each>
-__device__ __forceinline__ rl_census_t rl_census(int* keys, unsigned* cnts, int lane, int skip, Each&& each) {
-    for (int i = lane; i < RL_SLOTS; i += 64) {
-        keys[i] = 0;
-        cnts[i] = 0;
-    }
-    __syncthreads();
-    rl_census_t r = {0, 0, 0, 0, 0};
-    unsigned runc = 0;
-    int runv = 0;
-    bool full = false;
-    each([&](int v) {
-        r.total += 1u;
-        if (v > 0 && v != skip) r.counted += 1u;
-        if (v == runv) {
-            runc += 1u;
-        } else {
-            if (runv > 0 && runv != skip && !full) full = !rl_table_add(keys, cnts, runv, runc);
-            runv = v;
-            runc = 1u;
-        }
-    });
-    if (runv > 0 && runv != skip && !full) full = !rl_table_add(keys, cnts, runv, runc);
-    __syncthreads();
-    r.total = (unsigned)wave_sum_u64(r.total);  // a plane has fewer than 2^32 pixels
-    r.counted = (unsigned)wave_sum_u64(r.counted);
-    if (!__any(full)) {
-        for (int i = lane; i < RL_SLOTS; i += 64) {
-            const unsigned k = (unsigned)keys[i], cn = cnts[i];
-            if (k != 0) {
-                r.partners += 1u;
-                if (cn > r.best || (cn == r.best && k < r.bestv)) r.best = cn, r.bestv = k;
-            }
-        }
-        r.partners = (unsigned)wave_sum_u64(r.partners);
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const unsigned ob = __shfl_xor(r.best, o), ov = __shfl_xor(r.bestv, o);
-            if (ob > r.best || (ob == r.best && ob != 0 && ov < r.bestv)) r.best = ob, r.bestv = ov;
-        }
-    } else {
-        // smallest value first
-        unsigned cur = 0x7fffffffu;
-        each([&](int v) {
-            if (v > 0 && v != skip && (unsigned)v < cur) cur = (unsigned)v;
-        });
-        cur = wave_min_u32(cur);
-        while (cur != 0x7fffffffu) {
-            unsigned cn = 0, next = 0x7fffffffu;
-            each([&](int v) {
-                if ((unsigned)v == cur) cn += 1u;
-                else if (v > 0 && v != skip && (unsigned)v > cur && (unsigned)v < next) next = (unsigned)v;
-            });
-            cn = (unsigned)wave_sum_u64(cn);
-            next = wave_min_u32(next);
-            r.partners += 1u;
-            if (cn > r.best) r.best = cn, r.bestv = cur;  // ascending values: an equal count keeps the smaller one
-            cur = next;  // > the value just counted, or the end mark
-        }
-    }
-    __syncthreads();  // the table may be cleared for the next census
-    return r;
-}
-
-__global__ void __launch_bounds__(64) rpx_relate_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
-                                                        const int* __restrict__ comp, int C, double* __restrict__ wtable,
-                                                        int H, int W, int max_label) {
-    __shared__ int keys[RL_SLOTS];
-    __shared__ unsigned cnts[RL_SLOTS];
-    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
-    const size_t li = (size_t)plane * max_label + l;
-    double* out = wtable + li * (size_t)C * 4;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
-    if (y1 < y0) {  // label absent from this plane
-        for (int i = lane; i < C * 4; i += 64) out[i] = 0.0;
-        return;
-    }
-    const size_t n = (size_t)H * W;
-    const int* L = labels + (size_t)plane * n;
-    const int w = x1 - x0 + 1;
-    const int lc = w <= 8 ? 3 : (w <= 16 ? 4 : (w <= 32 ? 5 : 6));
-    for (int c = 0; c < C; ++c) {
-        const int* B = comp + ((size_t)plane * C + c) * n;
-        const rl_census_t r = rl_census(keys, cnts, lane, 0, [&](auto&& f) {
-            rl_for_pixels(L, B, W, x0, y0, x1, y1, l + 1, lc, lane, f);
-        });
-        if (lane == 0) {
-            out[c * 4 + AMT_RPX_RCOL_PARENT] = (double)r.bestv;
-            out[c * 4 + AMT_RPX_RCOL_OVERLAP] = (double)r.best;
-            out[c * 4 + AMT_RPX_RCOL_PARTNERS] = (double)r.partners;
-            out[c * 4 + AMT_RPX_RCOL_AREA] = (double)r.total;
-        }
-    }
-}
-
-// ---- a label's neighbours (AMT_RPX_NEIGHBORS) -----------------------------------------------------------------------
-// The same census, taken on the label's RING: the pixels that do not carry the label and have an 8-neighbour that does.
-// One wave per (label, plane) over the label's box grown by one pixel and clamped to the plane (outside it no pixel has
-// such a neighbour).  The wave covers 2^lc columns; its 64 >> lc lane groups share the rows of the grown box in bands of
-// consecutive rows, and a lane walks down its column of its band.  With m = (labels == label) and h = m of the pixel
-// and its two neighbours in the row, a pixel is on the ring when it is not m and h of its row, the row above or the row
-// below is set: a lane carries h of the rows y - 1 and y, gets m of x - 1 / x + 1 in row y + 1 from the lanes beside it
-// and, in the first and last column of the tile, from one halo load -- two loads per lane and row instead of nine.
-// Rows go four at a time, their loads issued together from coordinates clamped into the grown box; the companion is read
-// only where a row of the four has a ring pixel in the wave, and not at all when it is the label plane itself.
-constexpr int NB_ROWS = 4;
-template <typename F>
-__device__ __forceinline__ void nb_for_ring(const int* __restrict__ L, const int* __restrict__ B, int W, int gx0, int gy0,
-                                            int gx1, int gy1, int want, int lc, int lane, F&& f) {
-    const int cols = 1 << lc, rw = 64 >> lc;
-    const int col = lane & (cols - 1), sub = lane >> lc;
-    const int bh = (gy1 - gy0 + rw) / rw;  // rows per band, rounded up
-    const int ya = gy0 + sub * bh;         // this lane's band: rows ya .. yz (none when yz < ya)
-    const int yz = ya + bh - 1 <= gy1 ? ya + bh - 1 : gy1;
-    const bool self = L == B;
-    const bool first = col == 0, last = col == cols - 1;
-    for (int xb = gx0; xb <= gx1; xb += cols) {
-        const int x = xb + col;
-        const bool inx = x <= gx1;
-        const int xc = inx ? x : gx1;
-        const int hx = first ? x - 1 : x + 1;  // the halo column of the tile's first / last lane
-        const bool halo = (first || last) && hx >= gx0 && hx <= gx1;
-        bool hprev = false, hcur = false;  // h of the rows y - 1 and y
-        int lcur = want;                   // labels[y][x]; rows before the band are never emitted
-        // the row in hand is y = ya - 2 + k: two steps fill the window before the band's first row
-        for (int k0 = 0; k0 < bh + 2; k0 += NB_ROWS) {
-            int ln[NB_ROWS], lh[NB_ROWS];
-#pragma unroll
-            for (int j = 0; j < NB_ROWS; ++j) {  // the rows below the rows in hand
-                const int yn = ya - 1 + k0 + j;
-                const size_t row = (size_t)(yn < gy0 ? gy0 : (yn > gy1 ? gy1 : yn)) * W;
-                ln[j] = L[row + xc];
-                lh[j] = halo ? L[row + hx] : 0;
-            }
-            bool ring[NB_ROWS];
-            int lab[NB_ROWS];
-            bool any = false;
-#pragma unroll
-            for (int j = 0; j < NB_ROWS; ++j) {
-                const int y = ya - 2 + k0 + j, yn = y + 1;
-                const bool rown = yn >= gy0 && yn <= gy1;
-                const bool m = rown && inx && ln[j] == want;
-                const bool mh = rown && halo && lh[j] == want;
-                const bool left = __shfl_up((int)m, 1) != 0, right = __shfl_down((int)m, 1) != 0;
-                const bool hnext = m || (first ? mh : left) || (last ? mh : right);
-                ring[j] = y >= ya && y <= yz && inx && lcur != want && (hprev || hcur || hnext);
-                lab[j] = lcur;
-                any = any || ring[j];
-                hprev = hcur;
-                hcur = hnext;
-                lcur = ln[j];
-            }
-            if (!__any(any)) continue;
-            int v[NB_ROWS];
-#pragma unroll
-            for (int j = 0; j < NB_ROWS; ++j) {
-                const int y = ya - 2 + k0 + j;
-                v[j] = self ? lab[j] : B[(size_t)(y < gy0 ? gy0 : (y > gy1 ? gy1 : y)) * W + xc];
-            }
-#pragma unroll
-            for (int j = 0; j < NB_ROWS; ++j)
-                if (ring[j]) f(v[j]);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(64) rpx_neighbors_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
-                                                           const int* __restrict__ comp, int C,
-                                                           double* __restrict__ wtable, int H, int W, int max_label) {
-    __shared__ int keys[RL_SLOTS];
-    __shared__ unsigned cnts[RL_SLOTS];
-    const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
-    const size_t li = (size_t)plane * max_label + l;
-    double* out = wtable + li * (size_t)C * 4;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
-    if (y1 < y0) {  // label absent from this plane
-        for (int i = lane; i < C * 4; i += 64) out[i] = 0.0;
-        return;
-    }
-    const size_t n = (size_t)H * W;
-    const int* L = labels + (size_t)plane * n;
-    const int gy0 = y0 > 0 ? y0 - 1 : 0, gx0 = x0 > 0 ? x0 - 1 : 0;
-    const int gy1 = y1 < H - 1 ? y1 + 1 : H - 1, gx1 = x1 < W - 1 ? x1 + 1 : W - 1;
-    const int w = gx1 - gx0 + 1;
-    const int lc = w <= 8 ? 3 : (w <= 16 ? 4 : (w <= 32 ? 5 : 6));
-    for (int c = 0; c < C; ++c) {
-        const int* B = comp + ((size_t)plane * C + c) * n;
-        const rl_census_t r = rl_census(keys, cnts, lane, l + 1, [&](auto&& f) {
-            nb_for_ring(L, B, W, gx0, gy0, gx1, gy1, l + 1, lc, lane, f);
-        });
-        if (lane == 0) {
-            out[c * 4 + AMT_RPX_NCOL_COUNT] = (double)r.partners;
-            out[c * 4 + AMT_RPX_NCOL_TOUCHING] = (double)r.counted;
-            out[c * 4 + AMT_RPX_NCOL_RING] = (double)r.total;
-            out[c * 4 + AMT_RPX_NCOL_MAIN] = (double)r.bestv;
-        }
-    }
-}
-
-// ---- the two nearest labels by centroid (AMT_RPX_NEAREST) -----------------------------------------------------------
-// centroid table: (cy, cx) of every (plane, label) from the integer sums of rp_label_kernel; cy = NaN marks a label that
+// ---- the centroid table of AMT_RPX_NEAREST (amt_relate.hip searches it) ------------------------------------------------
+// (cy, cx) of every (plane, label) from the integer sums of rp_label_kernel; cy = NaN marks a label that
 // is absent from its plane
 __global__ void __launch_bounds__(256) rpx_centroid_kernel(const u64* __restrict__ acc, double2* __restrict__ cen,
                                                            size_t nlab) {
@@ -1613,48 +1266,6 @@ __global__ void __launch_bounds__(256) rpx_centroid_kernel(const u64* __restrict
         const u64 n = A[A_N];
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
         cen[i] = n != 0 ? make_double2((double)A[A_SY] / (double)n, (double)A[A_SX] / (double)n) : make_double2(nan, nan);
-    }
-}
-
-// One lane per query label; the labels of the plane pass through LDS in chunks of the workgroup's size (every lane reads
-// the same entry: a broadcast).  Candidates arrive in ascending label order, so "strictly nearer" keeps the smallest
-// label among equal distances.  max_label^2 distances per plane: a plane of a thousand cells is a million of them.
-constexpr int NN_CHUNK = 256;
-__global__ void __launch_bounds__(NN_CHUNK) rpx_nearest_kernel(const double2* __restrict__ cen, double* __restrict__ wtable,
-                                                               int max_label) {
-    __shared__ double2 chunk[NN_CHUNK];
-    const int plane = blockIdx.y, tid = threadIdx.x;
-    const int l = blockIdx.x * NN_CHUNK + tid;
-    const double2* P = cen + (size_t)plane * max_label;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    const double2 me = l < max_label ? P[l] : make_double2(nan, nan);
-    const double inf = __longlong_as_double(0x7ff0000000000000ll);
-    double d1 = inf, d2 = inf;  // centroids lie inside the plane: every distance is finite
-    int m1 = 0, m2 = 0;
-    for (int base = 0; base < max_label; base += NN_CHUNK) {
-        __syncthreads();  // the chunk before has been read
-        if (base + tid < max_label) chunk[tid] = P[base + tid];
-        __syncthreads();
-        const int cnt = max_label - base < NN_CHUNK ? max_label - base : NN_CHUNK;
-        for (int i = 0; i < cnt; ++i) {
-            const double2 o = chunk[i];
-            const double dy = o.x - me.x, dx = o.y - me.y;
-            const double d = dy * dy + dx * dx;  // NaN when either label is absent: no comparison below holds
-            if (base + i == l) continue;
-            if (d < d1) {
-                d2 = d1, m2 = m1;
-                d1 = d, m1 = base + i + 1;
-            } else if (d < d2) {
-                d2 = d, m2 = base + i + 1;
-            }
-        }
-    }
-    if (l < max_label) {
-        double* out = wtable + ((size_t)plane * max_label + l) * 4;
-        out[AMT_RPX_DCOL_FIRST] = (double)m1;
-        out[AMT_RPX_DCOL_FIRST_DISTANCE] = m1 ? sqrt(d1) : nan;
-        out[AMT_RPX_DCOL_SECOND] = (double)m2;
-        out[AMT_RPX_DCOL_SECOND_DISTANCE] = m2 ? sqrt(d2) : nan;
     }
 }
 
@@ -1715,11 +1326,7 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
     amt_buf<u64> hscratch(s, (size_t)nplanes * 2 * hwords);
     amt_buf<double2> cen(s, nlab, want_d);
     AMT_TRY(s.commit());
-    hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
-    AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels,
-                       bbox, H, W, max_label);
-    AMT_LAUNCH_CHECK();
+    AMT_TRY(amt_i_label_boxes(ctx, labels, bbox, acc, nplanes, H, W, max_label));
     if (scan) {
         hipLaunchKernelGGL(rp_heights_kernel, dim3(amt_grid_for(max_label, 256, 256), nplanes), dim3(256), 0, ctx->stream,
                            bbox, hoff, max_label);
@@ -1767,23 +1374,15 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
                                labels, bbox, (const double*)intensity, C, wtable_dev, H, W, max_label);
         AMT_LAUNCH_CHECK();
     }
-    if (want_r) {
-        hipLaunchKernelGGL(rpx_relate_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,
-                           (const int*)intensity, C, wtable_dev, H, W, max_label);
-        AMT_LAUNCH_CHECK();
-    }
-    if (want_n) {
-        hipLaunchKernelGGL(rpx_neighbors_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,
-                           (const int*)intensity, C, wtable_dev, H, W, max_label);
-        AMT_LAUNCH_CHECK();
-    }
+    if (want_r)
+        AMT_TRY(amt_i_relate_labels(ctx, labels, bbox, (const int*)intensity, C, wtable_dev, nplanes, H, W, max_label));
+    if (want_n)
+        AMT_TRY(amt_i_neighbor_census(ctx, labels, bbox, (const int*)intensity, C, wtable_dev, nplanes, H, W, max_label));
     if (want_d) {
         hipLaunchKernelGGL(rpx_centroid_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, cen,
                            nlab);
         AMT_LAUNCH_CHECK();
-        hipLaunchKernelGGL(rpx_nearest_kernel, dim3((max_label + NN_CHUNK - 1) / NN_CHUNK, nplanes), dim3(NN_CHUNK), 0,
-                           ctx->stream, cen, wtable_dev, max_label);
-        AMT_LAUNCH_CHECK();
+        AMT_TRY(amt_i_nearest_labels(ctx, cen, wtable_dev, nplanes, max_label));
     }
     if (want_q) AMT_TRY(amt_i_robust_intensity(ctx, labels, bbox, intensity, in_code, C, wtable_dev, nplanes, H, W, max_label));
     return AMT_OK;
@@ -1807,29 +1406,6 @@ struct coloc_launch {
 __host__ __device__ __forceinline__ int coloc_slot_a(int k) { return k < 3 ? 0 : (k < 5 ? 1 : 2); }
 __host__ __device__ __forceinline__ int coloc_slot_b(int k) { return k < 3 ? k + 1 : (k < 5 ? k - 1 : 3); }
 
-// Sums of 32 values per lane over the wave for the price of ~32 exchanges (64 x 6 as one all-reduce each): every step
-// halves what a lane still carries -- it keeps one half of its values, hands the other half to the lane `off` away and
-// adds what that lane hands over.  On return lane L holds the wave's sum of value L >> 1.  Integer sums: any order
-// gives the same bits.
-template <int HALF>
-__device__ __forceinline__ void wave_scatter_step(u64 (&t)[32], int lane) {
-    const bool up = (lane & (2 * HALF)) != 0;
-#pragma unroll
-    for (int i = 0; i < HALF; ++i) {
-        const u64 keep = up ? t[i + HALF] : t[i];
-        const u64 send = up ? t[i] : t[i + HALF];
-        t[i] = keep + __shfl_xor(send, 2 * HALF);
-    }
-}
-__device__ __forceinline__ u64 wave_reduce_scatter32(u64 (&t)[32], int lane) {
-    wave_scatter_step<16>(t, lane);
-    wave_scatter_step<8>(t, lane);
-    wave_scatter_step<4>(t, lane);
-    wave_scatter_step<2>(t, lane);
-    wave_scatter_step<1>(t, lane);
-    return t[0] + __shfl_xor(t[0], 1);
-}
-
 // layout of the 32 reduced words: per channel slot sum v, sum v^2; per slot pair sum a b, sum a[b > tB], sum b[a > tA];
 // then the counts, two to a word (each stays below 2^32): n, positives per slot, both-positive per pair
 enum { CO_S = 0, CO_Q = 4, CO_AB = 8, CO_AIF = 14, CO_BIF = 20, CO_CNT = 26 };
@@ -1838,7 +1414,7 @@ __device__ __forceinline__ u64 coloc_count(const u64* red, int i) {
 }
 
 __device__ __forceinline__ void coloc_write_empty(double* t) {
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = amt_quiet_nan();
     t[0] = nan;
     t[1] = nan;
     t[2] = t[3] = t[4] = t[5] = 0.0;
@@ -1856,9 +1432,10 @@ __global__ void __launch_bounds__(64) coloc_u16_kernel(const int* __restrict__ l
     __shared__ u64 red[32];
     const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    const amt_box box = amt_load_box(bbox, li);
+    const int y0 = box.y0, x0 = box.x0, y1 = box.y1, x1 = box.x1;
     double* rows = table + li * (size_t)npairs * AMT_COLOC_NCOLS;
-    if (y1 < y0) {  // label absent from this plane
+    if (box.absent()) {
         if (lane < COLOC_MAXP && P.out[lane] >= 0) coloc_write_empty(rows + (size_t)P.out[lane] * AMT_COLOC_NCOLS);
         return;
     }
@@ -1938,7 +1515,7 @@ __global__ void __launch_bounds__(64) coloc_u16_kernel(const int* __restrict__ l
     t[CO_CNT + 3] = (u64)both[1] | ((u64)both[2] << 32);
     t[CO_CNT + 4] = (u64)both[3] | ((u64)both[4] << 32);
     t[CO_CNT + 5] = (u64)both[5];
-    const u64 mine = wave_reduce_scatter32(t, lane);
+    const u64 mine = amt_wave_reduce_scatter<32, amt_op_sum>(t, lane);  // value k in the lanes 2 k, 2 k + 1
     if (!(lane & 1)) red[lane >> 1] = mine;
     __syncthreads();
     if (lane < COLOC_MAXP && P.out[lane] >= 0) {
@@ -1978,9 +1555,10 @@ __global__ void __launch_bounds__(64) coloc_f64_kernel(const int* __restrict__ l
                                                        int max_label) {
     const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
+    const amt_box box = amt_load_box(bbox, li);
+    const int y0 = box.y0, x0 = box.x0, y1 = box.y1, x1 = box.x1;
     double* o = table + (li * (size_t)npairs + pair) * AMT_COLOC_NCOLS;
-    if (y1 < y0) {
+    if (box.absent()) {
         if (lane == 0) coloc_write_empty(o);
         return;
     }
@@ -1989,11 +1567,6 @@ __global__ void __launch_bounds__(64) coloc_f64_kernel(const int* __restrict__ l
     const double* A = inten + ((size_t)plane * C + ca) * n;
     const double* B = inten + ((size_t)plane * C + cb) * n;
     const double ta = thr[(size_t)plane * C + ca], tb = thr[(size_t)plane * C + cb];
-    auto wsum = [&](double v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        return v;
-    };
     const double inf = __longlong_as_double(0x7ff0000000000000ll);
     double cnt = 0, sa = 0, sb = 0, qa = 0, qb = 0, pab = 0, aif = 0, bif = 0, na = 0, nb = 0, nab = 0;
     double mna = inf, mxa = -inf, mnb = inf, mxb = -inf;
@@ -2018,17 +1591,10 @@ __global__ void __launch_bounds__(64) coloc_f64_kernel(const int* __restrict__ l
                 mnb = b < mnb ? b : mnb;
                 mxb = b > mxb ? b : mxb;
             }
-    cnt = wsum(cnt), sa = wsum(sa), sb = wsum(sb), qa = wsum(qa), qb = wsum(qb), pab = wsum(pab);
-    aif = wsum(aif), bif = wsum(bif), na = wsum(na), nb = wsum(nb), nab = wsum(nab);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double a0 = __shfl_xor(mna, off), a1 = __shfl_xor(mxa, off);
-        const double b0 = __shfl_xor(mnb, off), b1 = __shfl_xor(mxb, off);
-        mna = a0 < mna ? a0 : mna;
-        mxa = a1 > mxa ? a1 : mxa;
-        mnb = b0 < mnb ? b0 : mnb;
-        mxb = b1 > mxb ? b1 : mxb;
-    }
+    cnt = amt_wave_sum(cnt), sa = amt_wave_sum(sa), sb = amt_wave_sum(sb), qa = amt_wave_sum(qa), qb = amt_wave_sum(qb);
+    pab = amt_wave_sum(pab), aif = amt_wave_sum(aif), bif = amt_wave_sum(bif);
+    na = amt_wave_sum(na), nb = amt_wave_sum(nb), nab = amt_wave_sum(nab);
+    mna = amt_wave_min(mna), mxa = amt_wave_max(mxa), mnb = amt_wave_min(mnb), mxb = amt_wave_max(mxb);
     const double ma = sa / cnt, mb = sb / cnt;
     double cab = 0, caa = 0, cbb = 0;
     for (int y = y0; y <= y1; ++y)
@@ -2039,7 +1605,7 @@ __global__ void __launch_bounds__(64) coloc_f64_kernel(const int* __restrict__ l
                 caa += da * da;
                 cbb += db * db;
             }
-    cab = wsum(cab), caa = wsum(caa), cbb = wsum(cbb);
+    cab = amt_wave_sum(cab), caa = amt_wave_sum(caa), cbb = amt_wave_sum(cbb);
     if (lane == 0) {
         const double nan = __longlong_as_double(0x7ff8000000000000ll);
         const bool constant = !(mna < mxa) || !(mnb < mxb);  // min == max over the label (an empty label too)
@@ -2072,15 +1638,10 @@ extern "C" int amt_colocalization(amt_ctx* ctx, const int32_t* labels, const voi
                        amt_out("table_dev", table_dev, amt_span(8, nplanes, max_label, npairs, AMT_COLOC_NCOLS)));
     AMT_TRY(amt_set_device(ctx));
     if (nplanes == 0 || max_label == 0) return AMT_OK;
-    const size_t nlab = (size_t)nplanes * max_label;
     amt_scratch s(ctx);
-    amt_buf<int> bbox(s, nlab * 4);
+    amt_buf<int> bbox(s, (size_t)nplanes * max_label * 4);
     AMT_TRY(s.commit());
-    hipLaunchKernelGGL(bbox_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, bbox, nlab);
-    AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels, bbox,
-                       H, W, max_label);
-    AMT_LAUNCH_CHECK();
+    AMT_TRY(amt_i_label_boxes(ctx, labels, bbox, nullptr, nplanes, H, W, max_label));
     if (in_code == AMT_F64) {
         for (int p = 0; p < npairs; ++p) {
             hipLaunchKernelGGL(coloc_f64_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox,

@@ -4,58 +4,15 @@
 //
 // One single-wave workgroup per (label, plane) sweeps the label's bounding box, one channel after the other.  A sweep
 // reads the box in the label plane and in the channel: lanes own columns, two row slots per step with their four loads
-// issued together from coordinates clamped into the box (rl_for_pixels' layouts in amt_props.hip); a uint16 box of at
+// issued together from coordinates clamped into the box (amt_box_for_pixels of amt_perlabel.h); a uint16 box of at
 // most 32 row slots is read once per channel and kept in LDS for the later sweeps (rb_kept_pixels).  Nothing is written
 // to global memory but the four results: the selection state lives in LDS and registers, so no scratch grows with a
 // label's area and no global atomic is used.  Counters are 32 bits wide: exact up to the plane's 2^31 - 2 pixels.
 #include "amt_internal.h"
+#include "amt_perlabel.h"
 #include "amt_rank_rule.h"
 
 namespace {
-
-// f(v) for the channel value v under every pixel of the label, each pixel once.  The wave covers 2^lc columns x
-// (64 >> lc) rows per row slot.
-template <typename T, typename F>
-__device__ __forceinline__ void rb_for_pixels(const int* __restrict__ L, const T* __restrict__ I, int W, int x0, int y0,
-                                              int x1, int y1, int want, int lc, int lane, F&& f) {
-    const int cols = 1 << lc, rw = 64 >> lc;
-    const int col = lane & (cols - 1), sub = lane >> lc;
-    for (int yb = y0 + sub; yb - sub <= y1; yb += 2 * rw) {
-        const int ya = yb, yc = yb + rw;
-        const size_t ra = (size_t)(ya <= y1 ? ya : y1) * W, rc = (size_t)(yc <= y1 ? yc : y1) * W;
-        for (int xb = x0; xb <= x1; xb += cols) {
-            const int x = xb + col, xc = x <= x1 ? x : x1;
-            const int la = L[ra + xc], lb = L[rc + xc];
-            const T va = I[ra + xc], vb = I[rc + xc];
-            if (x <= x1 && ya <= y1 && la == want) f(va);
-            if (x <= x1 && yc <= y1 && lb == want) f(vb);
-        }
-    }
-}
-
-__device__ __forceinline__ int rb_lane_layout(int w) { return w <= 8 ? 3 : (w <= 16 ? 4 : (w <= 32 ? 5 : 6)); }
-
-__device__ __forceinline__ unsigned rb_wave_sum(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ unsigned rb_wave_min(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned t = __shfl_xor(v, o);
-        v = t < v ? t : v;
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned rb_wave_max(unsigned v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const unsigned t = __shfl_xor(v, o);
-        v = t > v ? t : v;
-    }
-    return v;
-}
 
 // A table of `count` counters, lane l owning the `per` consecutive ones from l * per (per * 64 >= count).
 // lsum = the lane's total, lexc = the total of the lanes before it.
@@ -117,10 +74,12 @@ static_assert(6 * (65536 / RB_BINS) <= RB_BINS && 2 * (131072 / RB_BINS) <= RB_B
 struct rb_box_pixels {
     const int* __restrict__ L;
     const uint16_t* __restrict__ I;
-    int W, x0, y0, x1, y1, want, lc, lane;
+    int W;
+    amt_box box;
+    int want, lc, lane;
     template <typename F>
     __device__ __forceinline__ void for_each(F&& f) const {
-        rb_for_pixels(L, I, W, x0, y0, x1, y1, want, lc, lane, f);
+        amt_box_for_pixels(L, I, W, box, want, lc, lane, f);
     }
 };
 
@@ -138,7 +97,8 @@ struct rb_kept_pixels {
     int nslots, lane;
     __device__ __forceinline__ static bool fits(int w, int h, int lc) { return w <= 64 && h <= RB_KEEP * (64 >> lc); }
     __device__ __forceinline__ void load(uint16_t* cells, const int* __restrict__ L, const uint16_t* __restrict__ I, int W,
-                                         int x0, int y0, int x1, int y1, int want, int lc, int lane_) {
+                                         const amt_box& box, int want, int lc, int lane_) {
+        const int x0 = box.x0, y0 = box.y0, x1 = box.x1, y1 = box.y1;
         const int cols = 1 << lc, rw = 64 >> lc;  // the box is at most `cols` wide
         const int x = x0 + (lane_ & (cols - 1)), sub = lane_ >> lc;
         const int xc = x <= x1 ? x : x1;
@@ -230,9 +190,9 @@ __device__ __forceinline__ void rb_channel_u16(const P& px, int lane, unsigned* 
         mn = v < mn ? v : mn;
         mx = v > mx ? v : mx;
     });
-    cnt = rb_wave_sum(cnt);
-    mn = rb_wave_min(mn);
-    mx = rb_wave_max(mx);
+    cnt = amt_wave_sum(cnt);
+    mn = amt_wave_min(mn);
+    mx = amt_wave_max(mx);
     double res[4];
     if (mn == mx) {  // a constant label: every quantile is the value, every distance 0
         res[AMT_RPX_QCOL_Q25] = res[AMT_RPX_QCOL_MEDIAN] = res[AMT_RPX_QCOL_Q75] = (double)mn;
@@ -276,23 +236,23 @@ __global__ void __launch_bounds__(64) robust_u16_kernel(const int* __restrict__ 
     const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
     double* out = wtable + li * (size_t)C * 4;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
-    if (y1 < y0) {  // label absent from this plane: numpy on an empty array
-        for (int i = lane; i < C * 4; i += 64) out[i] = __longlong_as_double(0x7ff8000000000000ll);
+    const amt_box box = amt_load_box(bbox, li);
+    if (box.absent()) {  // numpy on an empty array
+        amt_fill_row(out, C * 4, amt_quiet_nan(), lane);
         return;
     }
     const size_t n = (size_t)H * W;
     const int* L = labels + (size_t)plane * n;
-    const int want = l + 1, w = x1 - x0 + 1, h = y1 - y0 + 1, lc = rb_lane_layout(w);
+    const int want = l + 1, w = box.w(), h = box.h(), lc = amt_box_layout(box.x0, box.x1);
     const bool keep = rb_kept_pixels::fits(w, h, lc);
     for (int c = 0; c < C; ++c) {
         const uint16_t* I = inten + ((size_t)plane * C + c) * n;
         if (keep) {
             rb_kept_pixels px;
-            px.load(cells, L, I, W, x0, y0, x1, y1, want, lc, lane);
+            px.load(cells, L, I, W, box, want, lc, lane);
             rb_channel_u16(px, lane, tab, out + c * 4);
         } else {
-            const rb_box_pixels px{L, I, W, x0, y0, x1, y1, want, lc, lane};
+            const rb_box_pixels px{L, I, W, box, want, lc, lane};
             rb_channel_u16(px, lane, tab, out + c * 4);
         }
     }
@@ -304,14 +264,14 @@ __global__ void __launch_bounds__(64) robust_u16_kernel(const int* __restrict__ 
 // on |v - median|, the difference taken in float64.
 template <typename K>
 __device__ __forceinline__ unsigned long long rb_select_f64(const int* __restrict__ L, const double* __restrict__ I,
-                                                            int W, int x0, int y0, int x1, int y1, int want, int lc,
-                                                            int lane, unsigned* hist, unsigned r, K&& key) {
+                                                            int W, const amt_box& box, int want, int lc, int lane,
+                                                            unsigned* hist, unsigned r, K&& key) {
     unsigned long long prefix = 0;
     for (int shift = 56; shift >= 0; shift -= 8) {
         const unsigned long long himask = shift == 56 ? 0ull : ~0ull << (shift + 8);  // the bits already decided
         for (int i = lane; i < 256; i += 64) hist[i] = 0u;
         __syncthreads();
-        rb_for_pixels(L, I, W, x0, y0, x1, y1, want, lc, lane, [&](double v) {
+        amt_box_for_pixels(L, I, W, box, want, lc, lane, [&](double v) {
             const unsigned long long k = key(v);
             if (((k ^ prefix) & himask) == 0) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
         });
@@ -333,19 +293,19 @@ __global__ void __launch_bounds__(64) robust_f64_kernel(const int* __restrict__ 
     const int plane = blockIdx.y, l = blockIdx.x, lane = threadIdx.x;
     const size_t li = (size_t)plane * max_label + l;
     double* out = wtable + li * (size_t)C * 4;
-    const int y0 = bbox[li * 4 + 0], x0 = bbox[li * 4 + 1], y1 = bbox[li * 4 + 2], x1 = bbox[li * 4 + 3];
-    if (y1 < y0) {
-        for (int i = lane; i < C * 4; i += 64) out[i] = __longlong_as_double(0x7ff8000000000000ll);
+    const amt_box box = amt_load_box(bbox, li);
+    if (box.absent()) {
+        amt_fill_row(out, C * 4, amt_quiet_nan(), lane);
         return;
     }
     const size_t n = (size_t)H * W;
     const int* L = labels + (size_t)plane * n;
-    const int want = l + 1, lc = rb_lane_layout(x1 - x0 + 1);
+    const int want = l + 1, lc = amt_box_layout(box.x0, box.x1);
     for (int c = 0; c < C; ++c) {
         const double* I = inten + ((size_t)plane * C + c) * n;
         unsigned cnt = 0;
-        rb_for_pixels(L, I, W, x0, y0, x1, y1, want, lc, lane, [&](double) { cnt += 1u; });
-        cnt = rb_wave_sum(cnt);
+        amt_box_for_pixels(L, I, W, box, want, lc, lane, [&](double) { cnt += 1u; });
+        cnt = amt_wave_sum(cnt);
         unsigned rk[6];
         double t[3], val[6], res[4];
         for (int q = 0; q < 3; ++q) {
@@ -358,16 +318,16 @@ __global__ void __launch_bounds__(64) robust_f64_kernel(const int* __restrict__ 
             int same = -1;
             for (int j = 0; j < i; ++j) same = rk[j] == rk[i] ? j : same;
             val[i] = same >= 0 ? val[same]
-                               : amt_key_f64(rb_select_f64(L, I, W, x0, y0, x1, y1, want, lc, lane, hist, rk[i],
+                               : amt_key_f64(rb_select_f64(L, I, W, box, want, lc, lane, hist, rk[i],
                                                            [](double v) { return amt_f64_key(v); }));
         }
         for (int q = 0; q < 3; ++q) res[q] = amt_np_lerp(val[2 * q], val[2 * q + 1], t[q]);
         const double med = res[AMT_RPX_QCOL_MEDIAN];
         auto dist = [med](double v) { return amt_f64_key(fabs(v - med)); };
-        const double da = amt_key_f64(rb_select_f64(L, I, W, x0, y0, x1, y1, want, lc, lane, hist, rk[2], dist));
+        const double da = amt_key_f64(rb_select_f64(L, I, W, box, want, lc, lane, hist, rk[2], dist));
         const double db = rk[3] == rk[2]
                               ? da
-                              : amt_key_f64(rb_select_f64(L, I, W, x0, y0, x1, y1, want, lc, lane, hist, rk[3], dist));
+                              : amt_key_f64(rb_select_f64(L, I, W, box, want, lc, lane, hist, rk[3], dist));
         res[AMT_RPX_QCOL_MAD] = amt_np_lerp(da, db, t[1]);
         if (lane == 0) {
             for (int k = 0; k < 4; ++k) out[c * 4 + k] = res[k];

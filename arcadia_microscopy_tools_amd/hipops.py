@@ -77,6 +77,18 @@ def _in_code(a: DeviceArray) -> int:
     raise TypeError(f"device filters accept uint16 or float64 images, got {a.dtype}")
 
 
+def _channel_stack(labels: DeviceArray, intensity: DeviceArray, n: int, H: int, W: int):
+    """(C, in_code) of ``intensity`` (..., C, Y, X) uint16 or float64, one (C, Y, X) stack per plane of ``labels``"""
+    if intensity.dtype not in (np.uint16, np.float64):
+        raise TypeError("intensity images must be uint16 or float64 on the device path")
+    if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
+        raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
+    C = int(intensity.shape[-3])
+    if intensity.size != n * C * H * W:
+        raise ValueError("intensity / labels plane count mismatch")
+    return C, _hip.U16 if intensity.dtype == np.uint16 else _hip.F64
+
+
 def _host_f64(arr):
     a = np.ascontiguousarray(arr, dtype=np.float64)
     return a, a.ctypes.data_as(ctypes.c_void_p)
@@ -1141,11 +1153,7 @@ def regionprops_full(labels: DeviceArray, intensity: DeviceArray, max_label: int
     n, H, W = _planes(labels)
     if intensity.dtype != np.uint16:
         raise TypeError("intensity images must be uint16 on the device path")
-    if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
-        raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
-    C = int(intensity.shape[-3])
-    if intensity.size != n * C * H * W:
-        raise ValueError("intensity / labels plane count mismatch")
+    C, _ = _channel_stack(labels, intensity, n, H, W)
     o = _out(ctx, out, (n, max_label, _hip.RP_NCOLS), np.float64)
     io = _out(ctx, iout, (n, max_label, C, 4), np.float64)
     _no_alias("regionprops_full", {"labels": labels, "intensity": intensity}, {"out": o, "iout": io})
@@ -1192,16 +1200,10 @@ def regionprops_intensity(labels: DeviceArray, intensity: DeviceArray, max_label
     uint16 or float64 with one (C, Y, X) stack per label plane."""
     ctx = labels.ctx
     n, H, W = _planes(labels)
-    if intensity.dtype not in (np.uint16, np.float64):
-        raise TypeError("intensity images must be uint16 or float64 on the device path")
-    if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
-        raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
-    C = int(intensity.shape[-3])
-    if intensity.size != n * C * H * W:
-        raise ValueError("intensity / labels plane count mismatch")
+    C, code = _channel_stack(labels, intensity, n, H, W)
     o = _out(ctx, out, (n, max_label, C, 4), np.float64)
     _no_alias("regionprops_intensity", {"labels": labels, "intensity": intensity}, {"out": o})
-    if intensity.dtype == np.uint16:  # exact integer accumulation
+    if code == _hip.U16:  # exact integer accumulation
         _hip.check(_lib().amt_regionprops(ctx.handle, labels.ptr, intensity.ptr, C, None, o.ptr, n, H, W,
                                           int(max_label)), "amt_regionprops")
     else:  # float64 images: two-sweep mean / std as numpy computes them
@@ -1243,14 +1245,7 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
         raise ValueError("weighted centroids need intensity images, and intensity images are only used for them")
     code, C = 0, 0
     if intensity is not None:
-        if intensity.dtype not in (np.uint16, np.float64):
-            raise TypeError("intensity images must be uint16 or float64 on the device path")
-        if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
-            raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
-        C = int(intensity.shape[-3])
-        if intensity.size != n * C * H * W:
-            raise ValueError("intensity / labels plane count mismatch")
-        code = _hip.U16 if intensity.dtype == np.uint16 else _hip.F64
+        C, code = _channel_stack(labels, intensity, n, H, W)
     o = _out(ctx, out, (n, max_label, _hip.RPX_NCOLS), np.float64) if bits & ~_hip.RPX_WEIGHTED else None
     wo = _out(ctx, wout, (n, max_label, C, 4), np.float64) if want_w else None
     _no_alias("regionprops_ext", {"labels": labels, "intensity": intensity}, {"out": o, "wout": wo})
@@ -1270,15 +1265,33 @@ def relate_labels(labels: DeviceArray, max_label: int, companions: DeviceArray, 
     equal counts, 0 when ``B`` is zero on all of ``l``), ``overlap`` = that count, ``partners`` = the number of
     distinct non-zero values of ``B`` on ``l``, ``area`` = the pixel count of ``l``.  A label absent from its plane
     gives four zeros.  All values are exact integers; two runs give identical bytes."""
-    return _companion_table("relate_labels", _hip.RPX_RELATE, labels, max_label, companions, out)
+    return _companion_table("relate_labels", _hip.RPX_RELATE, labels, max_label, *_label_stack("relate_labels", labels, companions), out)
 
 
-def _companion_table(op: str, bit: int, labels: DeviceArray, max_label: int, companions: DeviceArray, out) -> DeviceArray:
-    """``amt_regionprops_ext`` with one of the bits that take int32 companion label planes -> (nplanes, max_label, C, 4)"""
+def _companion_table(op: str, bit: int, labels: DeviceArray, max_label: int, planes, in_code: int, C: int, out):
+    """``amt_regionprops_ext`` with one of the bits that fill the table of four columns per companion: ``planes`` (None
+    for ``AMT_RPX_NEAREST``) are the ``C`` companion planes of element code ``in_code`` per label plane, already checked
+    -> (nplanes, max_label, C, 4) float64"""
     ctx = labels.ctx
     n, H, W = _planes(labels)
+    o = _out(ctx, out, (n, max_label, C, 4), np.float64)
+    name = "companions" if in_code == _hip.I32 else "intensity"
+    _no_alias(op, {"labels": labels, name: planes}, {"out": o})  # a companion may be `labels`
+    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, None if planes is None else planes.ptr, in_code, C, bit,
+                                          None, o.ptr, n, H, W, int(max_label)), "amt_regionprops_ext")
+    return o
+
+
+def _int32_labels(op: str, labels: DeviceArray):
+    """(nplanes, H, W) of the label planes of ``op``, which must be int32"""
     if labels.dtype != np.int32:
         raise TypeError(f"{op} expects int32 labels")
+    return _planes(labels)
+
+
+def _label_stack(op: str, labels: DeviceArray, companions: DeviceArray):
+    """(companions, AMT_I32, C) of int32 companion label planes (..., C, Y, X), or (..., Y, X) of the labels' own shape"""
+    n, H, W = _int32_labels(op, labels)
     if companions.dtype != np.int32:
         raise TypeError("companion label images must be int32 on the device path")
     if companions.ndim < 2 or companions.shape[-2:] != labels.shape[-2:]:
@@ -1291,11 +1304,7 @@ def _companion_table(op: str, bit: int, labels: DeviceArray, max_label: int, com
         C = int(companions.shape[-3])
     if C < 1 or companions.size != n * C * H * W:
         raise ValueError("companions / labels plane count mismatch")
-    o = _out(ctx, out, (n, max_label, C, 4), np.float64)
-    _no_alias(op, {"labels": labels, "companions": companions}, {"out": o})  # a companion may be `labels`
-    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, companions.ptr, _hip.I32, C, bit, None, o.ptr, n, H, W,
-                                          int(max_label)), "amt_regionprops_ext")
-    return o
+    return companions, _hip.I32, C
 
 
 def neighbor_census(labels: DeviceArray, max_label: int, companions: DeviceArray | None = None, out=None) -> DeviceArray:
@@ -1311,7 +1320,7 @@ def neighbor_census(labels: DeviceArray, max_label: int, companions: DeviceArray
     neighbour).  A label absent from its plane gives four zeros.  All values are exact integers; two runs give
     identical bytes."""
     return _companion_table("neighbor_census", _hip.RPX_NEIGHBORS, labels, max_label,
-                            labels if companions is None else companions, out)
+                            *_label_stack("neighbor_census", labels, labels if companions is None else companions), out)
 
 
 def nearest_labels(labels: DeviceArray, max_label: int, out=None) -> DeviceArray:
@@ -1322,15 +1331,8 @@ def nearest_labels(labels: DeviceArray, max_label: int, out=None) -> DeviceArray
     distance, label) so that the smallest label wins among equal distances; ``first_distance`` / ``second_distance`` =
     the Euclidean distances.  Where there is no such label, and for a label absent from its plane, the label is 0 and
     the distance NaN.  Every pair of labels of a plane is compared; two runs give identical bytes."""
-    ctx = labels.ctx
-    n, H, W = _planes(labels)
-    if labels.dtype != np.int32:
-        raise TypeError("nearest_labels expects int32 labels")
-    o = _out(ctx, out, (n, max_label, 1, 4), np.float64)
-    _no_alias("nearest_labels", {"labels": labels}, {"out": o})
-    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, None, 0, 1, _hip.RPX_NEAREST, None, o.ptr, n, H, W,
-                                          int(max_label)), "amt_regionprops_ext")
-    return o
+    _int32_labels("nearest_labels", labels)
+    return _companion_table("nearest_labels", _hip.RPX_NEAREST, labels, max_label, None, 0, 1, out)
 
 
 def robust_intensity(labels: DeviceArray, intensity: DeviceArray, max_label: int, out=None) -> DeviceArray:
@@ -1341,23 +1343,10 @@ def robust_intensity(labels: DeviceArray, intensity: DeviceArray, max_label: int
     ``labels`` is int32 (..., Y, X); ``intensity`` is (..., C, Y, X) uint16 (exact selection on integers) or float64
     (without NaN or infinities) with one (C, Y, X) stack per label plane.  A label absent from its plane gives four
     NaNs; two runs give identical bytes."""
-    ctx = labels.ctx
-    n, H, W = _planes(labels)
-    if labels.dtype != np.int32:
-        raise TypeError("robust_intensity expects int32 labels")
-    if intensity.dtype not in (np.uint16, np.float64):
-        raise TypeError("intensity images must be uint16 or float64 on the device path")
-    if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
-        raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
-    C = int(intensity.shape[-3])
-    if C < 1 or intensity.size != n * C * H * W:
+    C, code = _channel_stack(labels, intensity, *_int32_labels("robust_intensity", labels))
+    if C < 1:
         raise ValueError("intensity / labels plane count mismatch")
-    o = _out(ctx, out, (n, max_label, C, 4), np.float64)
-    _no_alias("robust_intensity", {"labels": labels, "intensity": intensity}, {"out": o})
-    code = _hip.U16 if intensity.dtype == np.uint16 else _hip.F64
-    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, intensity.ptr, code, C, _hip.RPX_ROBUST, None, o.ptr,
-                                          n, H, W, int(max_label)), "amt_regionprops_ext")
-    return o
+    return _companion_table("robust_intensity", _hip.RPX_ROBUST, labels, max_label, intensity, code, C, out)
 
 
 def colocalization_pairs(C: int, pairs=None) -> np.ndarray:
@@ -1395,15 +1384,9 @@ def colocalization(labels: DeviceArray, intensity: DeviceArray, max_label: int, 
     n, H, W = _planes(labels)
     if labels.dtype != np.int32:
         raise TypeError("colocalization expects int32 labels")
-    if intensity.dtype not in (np.uint16, np.float64):
-        raise TypeError("intensity images must be uint16 or float64 on the device path")
-    if intensity.ndim < 3 or intensity.shape[-2:] != labels.shape[-2:]:
-        raise ValueError("intensity must be (..., C, Y, X) matching the label planes")
-    C = int(intensity.shape[-3])
+    C, code = _channel_stack(labels, intensity, n, H, W)
     if C < 2:
         raise ValueError("colocalization needs at least two channels")
-    if intensity.size != n * C * H * W:
-        raise ValueError("intensity / labels plane count mismatch")
     if isinstance(thresholds, DeviceArray):
         if thresholds.dtype != np.float64 or tuple(thresholds.shape) != (n, C):
             raise ValueError(f"device thresholds must be ({n}, {C}) float64, got {thresholds.shape} {thresholds.dtype}")
@@ -1417,9 +1400,9 @@ def colocalization(labels: DeviceArray, intensity: DeviceArray, max_label: int, 
     pr = colocalization_pairs(C, pairs)
     o = _out(ctx, out, (n, max_label, len(pr), _hip.COLOC_NCOLS), np.float64)
     _no_alias("colocalization", {"labels": labels, "intensity": intensity, "thresholds": thr}, {"out": o})
-    _hip.check(_lib().amt_colocalization(ctx.handle, labels.ptr, intensity.ptr, _hip.U16 if intensity.dtype == np.uint16
-                                         else _hip.F64, C, thr.ptr, pr.ctypes.data_as(ctypes.c_void_p), len(pr), o.ptr,
-                                         n, H, W, int(max_label)), "amt_colocalization")
+    _hip.check(_lib().amt_colocalization(ctx.handle, labels.ptr, intensity.ptr, code, C, thr.ptr,
+                                         pr.ctypes.data_as(ctypes.c_void_p), len(pr), o.ptr, n, H, W, int(max_label)),
+               "amt_colocalization")
     return o
 
 

@@ -42,6 +42,20 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.amt_version()
 
 
+def test_per_label_helpers_exist_once():
+    """The box walk, the wave reductions and the box pass of the per-label kernels stand in amt_perlabel.h and
+    amt_i_label_boxes: the copies that earlier per-label features brought along are gone from every source."""
+    csrc = os.path.join(ROOT, "arcadia_microscopy_tools_amd", "csrc")
+    text = {name: open(os.path.join(csrc, name)).read() for name in sorted(os.listdir(csrc))
+            if name.endswith((".hip", ".h"))}
+    for name, src in text.items():
+        for word in ("rb_for_pixels", "rb_wave_sum", "rb_lane_layout", "bbox_init_kernel"):
+            assert word not in src, f"{name} still has {word}"
+        assert not re.search(r"\bauto\s+wsum\s*=", src), f"{name} still defines a wsum lambda"
+    defined = [name for name, src in text.items() for _ in re.finditer(r"\bvoid\s+amt_box_for_pixels\s*\(", src)]
+    assert defined == ["amt_perlabel.h"], defined
+
+
 def test_ctypes_signatures_match_the_header():
     """Every _hip._SIGS row has the return type and the parameter kinds of its prototype in include/amt_hip.h: a row
     that drifts would pass wrong values into a launch.  Needs neither the library nor a GPU."""

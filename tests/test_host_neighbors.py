@@ -150,7 +150,7 @@ def test_binding_constants_equal_the_header():
     assert _hip.RPX_RELATE == 256 and _hip.RPX_ROBUST == 512 and _hip.RPX_NCOLS == 12
     assert "amt_regionprops_ext" in _hip._SIGS
     assert not [name for name in _hip._SIGS if "neighbor" in name or "nearest" in name]
-    with open(os.path.join(ROOT, "arcadia_microscopy_tools_amd", "csrc", "amt_props.hip")) as f:
+    with open(os.path.join(ROOT, "arcadia_microscopy_tools_amd", "csrc", "amt_relate.hip")) as f:
         src = f.read()
     # one table for the relation and the census: the kernels share its helpers
     assert src.count("__shared__ int keys[RL_SLOTS]") == 2 and src.count("bool rl_table_add(") == 1

@@ -78,7 +78,7 @@ def test_binding_constants_equal_the_header():
     for i, n in enumerate(_hip.RPX_RCOLS):
         assert int(_define(h, "AMT_RPX_RCOL_" + n.upper())) == i
     assert _hip.I32 == int(_define(h, "AMT_I32"))
-    src = open(os.path.join(ROOT, "arcadia_microscopy_tools_amd", "csrc", "amt_props.hip")).read()
+    src = open(os.path.join(ROOT, "arcadia_microscopy_tools_amd", "csrc", "amt_relate.hip")).read()
     assert "RL_SLOTS = AMT_RELATE_LDS_PARTNERS" in src  # the kernel's table is sized by the header's constant
 
 
