@@ -60,8 +60,29 @@ RPX_DCOLS = ("first", "first_distance", "second", "second_distance")
 # amt_colocalization: the columns of a (label, channel pair) row (AMT_COLOC_*)
 COLOC_COLS = ("pearson", "overlap", "m1", "m2", "intersection1", "intersection2")
 COLOC_NCOLS = len(COLOC_COLS)
+# amt_regionprops_ext with AMT_RPX_TEXTURE (the call writes the features) or AMT_RPX_TEXTURE_COUNTS (the raw matrices): the
+# bits, where levels (7 bits) and distance (10 bits) ride in `columns` (rpx_texture_columns below, the header's
+# AMT_RPX_TEXTURE_COLUMNS), the columns of a (label, channel, direction) row (AMT_TEX_*), the four directions in table
+# order and the accepted levels / distances
+RPX_TEXTURE = 1 << 12
+RPX_TEXTURE_COUNTS = 1 << 13
+RPX_TEXTURE_LEVELS_SHIFT, RPX_TEXTURE_DISTANCE_SHIFT = 14, 21
+TEX_COLS = (
+    "angular_second_moment", "contrast", "correlation", "variance", "inverse_difference_moment", "sum_average",
+    "sum_variance", "sum_entropy", "entropy", "difference_variance", "difference_entropy", "info_measure_1",
+    "info_measure_2",
+)
+TEX_NCOLS = len(TEX_COLS)
+TEX_ANGLES = ("0", "45", "90", "135")
+TEX_MAX_LEVELS, TEX_MAX_DISTANCE = 64, 255
 # amt_peak_markers: the longest peak list of a plane that is labelled from LDS (AMT_PEAK_MARKERS_LDS_TIER)
 PEAK_MARKERS_LDS_TIER = 4096
+
+
+def rpx_texture_columns(levels: int, distance: int, counts: bool = False) -> int:
+    """``columns`` of an ``AMT_RPX_TEXTURE`` (``counts``: ``AMT_RPX_TEXTURE_COUNTS``) call of ``amt_regionprops_ext``"""
+    return ((RPX_TEXTURE_COUNTS if counts else RPX_TEXTURE) | int(levels) << RPX_TEXTURE_LEVELS_SHIFT
+            | int(distance) << RPX_TEXTURE_DISTANCE_SHIFT)
 
 
 class HipUnavailableError(RuntimeError):

@@ -172,6 +172,11 @@ int amt_i_relate_labels(amt_ctx* ctx, const int* labels, const int* bbox, const 
 int amt_i_neighbor_census(amt_ctx* ctx, const int* labels, const int* bbox, const int* comp, int C, double* wtable,
                           int nplanes, int H, int W, int max_label);
 int amt_i_nearest_labels(amt_ctx* ctx, const double2* cen, double* wtable, int nplanes, int max_label);
+// AMT_RPX_TEXTURE / AMT_RPX_TEXTURE_COUNTS (amt_texture.hip): a call of its own -- it checks its arguments and operands,
+// makes the bounding boxes and fills out = the feature rows [plane][label][channel][direction][AMT_TEX_NCOLS] or, with
+// `counts`, the uint32 matrices [plane][label][channel][direction][levels][levels] instead
+int amt_i_texture(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C, const double* ranges,
+                  int levels, int distance, bool counts, double* out, int nplanes, int H, int W, int max_label);
 
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>

@@ -53,6 +53,17 @@ __device__ __forceinline__ void amt_box_for_pixels(const int* __restrict__ L, co
     }
 }
 
+// f(x, y) for the cell of every lane in every row slot and column tile of the box, in the lane layout above, one row slot
+// per step: for kernels that need a pixel's coordinates (its partners at an offset) rather than its value.  Cells beyond
+// x1 / y1 are handed over too (a lane of the last tile): the callee drops them, or clamps them for loads it issues.
+template <typename F>
+__device__ __forceinline__ void amt_box_for_cells(const amt_box& box, int lc, int lane, F&& f) {
+    const int cols = 1 << lc, rw = 64 >> lc;
+    const int col = lane & (cols - 1), sub = lane >> lc;
+    for (int yb = box.y0; yb <= box.y1; yb += rw)
+        for (int xb = box.x0; xb <= box.x1; xb += cols) f(xb + col, yb + sub);
+}
+
 // ---- wave reductions: the butterfly over the lanes 32, 16, .. 1 away; every lane gets the result -----------------------
 // float64 sums depend on this order: the tables of the float64 kernels keep their bits only while it stands.
 struct amt_op_sum {

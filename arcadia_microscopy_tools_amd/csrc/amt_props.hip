@@ -1273,6 +1273,16 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
                                    int columns, double* table_dev, double* wtable_dev, int nplanes, int H, int W,
                                    int max_label) {
     const unsigned cols = (unsigned)columns;
+    if (cols & (AMT_RPX_TEXTURE | AMT_RPX_TEXTURE_COUNTS)) {
+        // Haralick texture: levels and distance ride in the upper bits, table_dev holds the ranges
+        const unsigned params = 0x7fu << AMT_RPX_TEXTURE_LEVELS_SHIFT | 0x3ffu << AMT_RPX_TEXTURE_DISTANCE_SHIFT;
+        const bool counts = (cols & AMT_RPX_TEXTURE_COUNTS) != 0;
+        AMT_REQUIRE((cols & ~(AMT_RPX_TEXTURE | AMT_RPX_TEXTURE_COUNTS | params)) == 0 && counts != ((cols & AMT_RPX_TEXTURE) != 0),
+                    "regionprops_ext: one of AMT_RPX_TEXTURE and AMT_RPX_TEXTURE_COUNTS, and no other column bit with it");
+        return amt_i_texture(ctx, labels, intensity, in_code, C, table_dev, (int)(cols >> AMT_RPX_TEXTURE_LEVELS_SHIFT & 0x7fu),
+                             (int)(cols >> AMT_RPX_TEXTURE_DISTANCE_SHIFT & 0x3ffu), counts, wtable_dev, nplanes, H, W,
+                             max_label);
+    }
     const bool want_w = (cols & AMT_RPX_CENTROID_WEIGHTED) != 0;
     const bool want_r = (cols & AMT_RPX_RELATE) != 0;
     const bool want_q = (cols & AMT_RPX_ROBUST) != 0;

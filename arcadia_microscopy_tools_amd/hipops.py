@@ -1240,6 +1240,8 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
     if bits & (_hip.RPX_NEIGHBORS | _hip.RPX_NEAREST):
         raise ValueError("bits 10 and 11 (AMT_RPX_NEIGHBORS, AMT_RPX_NEAREST) measure a label's surroundings: call "
                          "hipops.neighbor_census or hipops.nearest_labels")
+    if bits & (_hip.RPX_TEXTURE | _hip.RPX_TEXTURE_COUNTS):
+        raise ValueError("bits 12 and 13 (AMT_RPX_TEXTURE, AMT_RPX_TEXTURE_COUNTS) measure Haralick texture: call hipops.texture")
     want_w = bool(bits & _hip.RPX_WEIGHTED)
     if want_w != (intensity is not None):
         raise ValueError("weighted centroids need intensity images, and intensity images are only used for them")
@@ -1404,6 +1406,87 @@ def colocalization(labels: DeviceArray, intensity: DeviceArray, max_label: int, 
                                          pr.ctypes.data_as(ctypes.c_void_p), len(pr), o.ptr, n, H, W, int(max_label)),
                "amt_colocalization")
     return o
+
+
+def texture_parameters(levels, distance) -> tuple[int, int]:
+    """(levels, distance) of ``texture`` as ints: integers in 2..TEX_MAX_LEVELS and 1..TEX_MAX_DISTANCE (no device needed)"""
+    for name, v in (("levels", levels), ("distance", distance)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an integer, got {v!r}")
+    if not 2 <= int(levels) <= _hip.TEX_MAX_LEVELS:
+        raise ValueError(f"levels must be in 2..{_hip.TEX_MAX_LEVELS}, got {levels}")
+    if not 1 <= int(distance) <= _hip.TEX_MAX_DISTANCE:
+        raise ValueError(f"distance must be in 1..{_hip.TEX_MAX_DISTANCE}, got {distance}")
+    return int(levels), int(distance)
+
+
+def texture(labels: DeviceArray, intensity: DeviceArray, max_label: int, levels: int = 8, distance: int = 1, ranges=None,
+            out=None, glcm=False):
+    """Per-label Haralick texture (``amt_regionprops_ext`` with ``AMT_RPX_TEXTURE``): table (nplanes, max_label, C, 4,
+    TEX_NCOLS) float64 -- for every label 1..max_label, channel and direction of ``_hip.TEX_ANGLES`` (0, 45, 90, 135 degrees at
+    ``distance`` pixels) the thirteen features of ``_hip.TEX_COLS`` of the symmetric grey-level co-occurrence matrix, as
+    ``mahotas.features.haralick`` (CellProfiler's MeasureTexture) defines them.
+
+    ``labels`` is int32 (..., Y, X); ``intensity`` is (..., C, Y, X) uint16 or float64 (without NaN or infinities), one
+    (C, Y, X) stack per label plane.  A value v of an image with the range (lo, hi) falls into level
+    ``min(levels - 1, floor((clip(v, lo, hi) - lo) / (hi - lo) * levels))``; ``hi <= lo`` puts everything into level 0.
+    ``ranges``: None = every (plane, channel) image's own minimum and maximum, found on the device (no
+    synchronisation); a (lo, hi) pair for all images; an array broadcastable to (nplanes, C, 2); or a float64
+    ``DeviceArray`` of that shape, which is used as it is.  ``levels`` 2..64, ``distance`` 1..255.
+    ``glcm=True`` returns ``(table, counts)`` with counts (nplanes, max_label, C, 4, levels, levels) uint32, the raw
+    matrices (exact integers; a uint32 ``DeviceArray`` of that shape is filled and returned); they come from a second
+    call of the entry point, which the table does not depend on.  ``out`` is always the table.  A direction in which a
+    label has no pair gives NaN features and zero counts for that direction, a label absent from its plane for all
+    four.  Two runs give identical bytes."""
+    n, H, W = _int32_labels("texture", labels)
+    C, code = _channel_stack(labels, intensity, n, H, W)
+    if C < 1:
+        raise ValueError("intensity / labels plane count mismatch")
+    L, d = texture_parameters(levels, distance)
+    K = int(max_label)
+    if K < 0:
+        raise ValueError("max_label must not be negative")
+    host = None
+    if isinstance(ranges, DeviceArray):
+        if ranges.dtype != np.float64 or tuple(ranges.shape) != (n, C, 2):
+            raise ValueError(f"device ranges must be ({n}, {C}, 2) float64, got {ranges.shape} {ranges.dtype}")
+    elif ranges is not None:
+        try:
+            host = np.broadcast_to(np.asarray(ranges, dtype=np.float64), (n, C, 2))
+        except (ValueError, TypeError):
+            raise ValueError(f"ranges must be None, a (lo, hi) pair or broadcastable to ({n}, {C}, 2)") from None
+    ctx = labels.ctx
+    want_glcm = glcm is not None and glcm is not False
+    if want_glcm and glcm is not True and not isinstance(glcm, DeviceArray):
+        raise TypeError("glcm must be False, True or a uint32 DeviceArray for the counts")
+    # the caller's own buffers are judged before anything is reserved or launched; what is made here overlaps nothing
+    o = None if out is None else _out(ctx, out, (n, K, C, 4, _hip.TEX_NCOLS), np.float64)
+    g = _out(ctx, glcm, (n, K, C, 4, L, L), np.uint32) if isinstance(glcm, DeviceArray) else None
+    _no_alias("texture", {"labels": labels, "intensity": intensity,
+                          "ranges": ranges if isinstance(ranges, DeviceArray) else None}, {"out": o, "glcm": g})
+    if isinstance(ranges, DeviceArray):
+        rng = ranges
+    elif host is not None:
+        rng = ctx.asarray(np.ascontiguousarray(host))
+    else:  # the extrema of every (plane, channel) image: percentiles 0 and 100 of a uint16 plane are its min and max
+        rng = ctx.empty((n, C, 2), np.float64)
+        if code == _hip.F64:
+            _hip.check(_lib().amt_minmax_f64(ctx.handle, intensity.ptr, rng.ptr, n * C, H * W), "amt_minmax_f64")
+        else:
+            q, qp = _host_f64([0.0, 100.0])
+            _hip.check(_lib().amt_percentile_u16(ctx.handle, intensity.ptr, qp, 2, rng.ptr, n * C, H * W),
+                       "amt_percentile_u16")
+    if o is None:
+        o = ctx.empty((n, K, C, 4, _hip.TEX_NCOLS), np.float64)
+    if want_glcm and g is None:
+        g = ctx.empty((n, K, C, 4, L, L), np.uint32)
+    # one call per output: the features, then (when asked for) the counts from a second sweep of the same boxes
+    for counts, buf in ((False, o), (True, g)):
+        if buf is not None:
+            _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, intensity.ptr, code, C,
+                                                  _hip.rpx_texture_columns(L, d, counts), rng.ptr, buf.ptr, n, H, W, K),
+                       "amt_regionprops_ext")
+    return o if g is None else (o, g)
 
 
 def cellpose_masks(dP: DeviceArray, cellprob: DeviceArray, cellprob_threshold: float = 0.0, niter: int = 200,

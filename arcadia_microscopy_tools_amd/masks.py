@@ -538,6 +538,69 @@ class SegmentationMask:
         cols = table.reshape(k, -1)
         return {key: cols[:, i].copy() for i, key in enumerate(robust_intensity_keys(channels))}
 
+    def cell_texture(self, levels: int = 8, distance: int = 1, ranges=None, angles: str = "each") -> dict[str, Float64Array]:
+        """Haralick texture of every channel inside every cell, measured on the device (CellProfiler's MeasureTexture):
+        the thirteen features of ``_hip.TEX_COLS`` -- angular_second_moment, contrast, correlation, variance,
+        inverse_difference_moment, sum_average, sum_variance, sum_entropy, entropy, difference_variance,
+        difference_entropy, info_measure_1, info_measure_2, as ``mahotas.features.haralick`` defines them
+        (include/amt_hip.h states the formulas) -- of the symmetric grey-level co-occurrence matrix of the cell's pixels
+        at ``distance`` pixels in the directions 0, 45, 90 and 135 degrees, the image quantised to ``levels`` grey levels
+        (2..64).  Keys are ``texture_<feature>_<channel>_<distance>_<angle>`` with the lower-cased channel names of
+        ``intensity_image_dict``, channel by channel, angle by angle, feature by feature (``segment.texture_keys``), e.g.
+        ``texture_contrast_dapi_1_45``; each entry holds one float64 per cell, ordered by label like ``cell_properties``
+        (row j of an ``expanded`` / ``ring`` mask belongs to ``parent_labels[j]``).
+
+        ``ranges`` says which intensities span the grey levels (values outside are clipped): None = each image's own
+        minimum and maximum, found on the device; a (lo, hi) pair for every channel; or a mapping Channel -> (lo, hi),
+        where channels the mapping leaves out keep their own minimum and maximum.  ``angles="mean"`` averages each
+        feature over the directions in which the cell has a pair of pixels (keys
+        ``texture_<feature>_<channel>_<distance>``).  A direction without a pair -- a cell narrower than ``distance`` --
+        gives NaN.  uint8 / uint16 images are read as integers, any other dtype as float64 (NaN and infinities are not
+        supported).  Raises ``ValueError`` without intensity images."""
+        from . import hipops
+        from .segment import texture_keys
+
+        channels = list(self.intensity_image_dict or {})
+        if not channels:
+            raise ValueError("cell_texture needs intensity images")
+        keys = texture_keys(channels, distance, angles)
+        levels, distance = hipops.texture_parameters(levels, distance)
+
+        def pair(r, what):
+            try:
+                lo, hi = (float(v) for v in r)
+            except (TypeError, ValueError):
+                raise TypeError(f"{what} must be a (lo, hi) pair of numbers, got {r!r}") from None
+            return lo, hi
+
+        if isinstance(ranges, Mapping):
+            for channel in ranges:
+                if channel not in self.intensity_image_dict:
+                    raise ValueError(f"ranges names '{getattr(channel, 'name', channel)}', which has no intensity image")
+            rows = []
+            for channel in channels:
+                if channel in ranges:
+                    rows.append(pair(ranges[channel], f"the range of '{channel.name}'"))
+                else:
+                    image = self.intensity_image_dict[channel]
+                    rows.append((float(image.min()), float(image.max())))
+            ranges = np.asarray(rows, dtype=np.float64)[None]
+        elif ranges is not None:
+            ranges = np.asarray(pair(ranges, "ranges"), dtype=np.float64)
+        lab, k = self._labels_device
+        k = int(k)
+        shape = tuple(lab.shape[-2:])
+        stack, _, _ = self._intensity_stack(shape)
+        table = hipops.texture(lab.reshape((1,) + shape), stack.reshape((1,) + stack.shape), max(k, 1), levels=levels,
+                               distance=distance, ranges=ranges).numpy()[0][:k]
+        if angles == "mean":  # over the directions that have pairs; all-NaN stays NaN
+            valid = ~np.isnan(table)
+            count = valid.sum(axis=2)
+            total = np.where(valid, table, 0.0).sum(axis=2)
+            table = np.where(count > 0, total / np.maximum(count, 1), np.nan)
+        cols = table.reshape(k, -1)
+        return {key: cols[:, i].copy() for i, key in enumerate(keys)}
+
     @cached_property
     def centroids_yx(self) -> Float64Array:
         """(num_cells, 2) array of [y, x] centroids (R/masks.py:330-353)."""

@@ -455,6 +455,22 @@ def robust_intensity_keys(channel_names) -> list[str]:
     return [f"intensity_{stat}_{name}" for name in names for stat in _hip.RPX_QCOLS]
 
 
+def texture_keys(channel_names, distance: int = 1, angles: str = "each") -> list[str]:
+    """The keys of ``SegmentationMask.cell_texture`` for these channels, in order (no device needed): channel by
+    channel, angle by angle (``_hip.TEX_ANGLES``), feature by feature (``_hip.TEX_COLS``),
+    ``f"texture_{feature}_{channel}_{distance}_{angle}"`` with the lower-cased channel names, e.g.
+    ``texture_contrast_dapi_1_45``; with ``angles="mean"`` one key per feature and channel,
+    ``f"texture_{feature}_{channel}_{distance}"``."""
+    if angles not in ("each", "mean"):
+        raise ValueError(f"angles must be 'each' or 'mean', got {angles!r}")
+    if isinstance(distance, bool) or not isinstance(distance, (int, np.integer)):
+        raise TypeError(f"distance must be an integer, got {distance!r}")
+    names = [str(getattr(c, "name", c)).lower() for c in channel_names]
+    if angles == "mean":
+        return [f"texture_{f}_{name}_{int(distance)}" for name in names for f in _hip.TEX_COLS]
+    return [f"texture_{f}_{name}_{int(distance)}_{a}" for name in names for a in _hip.TEX_ANGLES for f in _hip.TEX_COLS]
+
+
 def neighbor_keys() -> list[str]:
     """The keys of ``SegmentationMask.cell_neighbors``, in order (no device needed): the contact census of
     ``_hip.RPX_NCOLS4`` with ``percent_touching`` after the two pixel counts it is made of, then the two closest cells

@@ -639,6 +639,80 @@ int amt_max_i32(amt_ctx* ctx, const int32_t* in, int32_t* max_dev, int nplanes, 
 int amt_colocalization(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C,
                        const double* thresholds_dev, const int32_t* pairs_host, int npairs, double* table_dev,
                        int nplanes, int H, int W, int max_label);
+/* ---- per-label Haralick texture (grey-level co-occurrence): the AMT_RPX_TEXTURE bit of the extended region properties ----
+ * The capability rides on the entry point of the extended region properties, like the relation, the robust statistics
+ * and the neighbours: no entry point of its own.  `columns` = AMT_RPX_TEXTURE_COLUMNS(levels, distance, counts), which
+ * sets ONE of AMT_RPX_TEXTURE (bit 12: the call writes the feature table) and AMT_RPX_TEXTURE_COUNTS (bit 13: the call
+ * writes the raw matrices instead; both bits together are AMT_EINVAL), levels = L in bits 14-20 and distance = d in bits
+ * 21-30 (the fields hold 0..127 and 0..1023, so every value outside 2..64 and 1..255 up to there can be stated and is
+ * refused); no other bit goes with them (the morphology bits and the other table bits are AMT_EINVAL).  labels = nplanes
+ * int32 planes; intensity = nplanes x C planes (C >= 1) of element type in_code (AMT_U16 or AMT_F64), one (C, Y, X) stack
+ * per label plane.  With these bits table_dev is an INPUT: the ranges, nplanes x C x 2 doubles {lo, hi} on the device, one
+ * pair per (plane, channel) image; it is only read.  wtable_dev is the one output of the call: the features, or with
+ * AMT_RPX_TEXTURE_COUNTS the counts (layout below); a caller who wants both calls twice with two buffers of its own,
+ * and the features do not depend on whether the counts are taken.
+ * AMT_EINVAL for levels outside 2..64, distance outside 1..255, an in_code other than AMT_U16 / AMT_F64, C < 1, a null
+ * labels, intensity, table_dev (ranges) or wtable_dev, and for a wtable_dev that overlaps another operand; table_dev
+ * counts as an input in this call.
+ * QUANTISATION (both element types; uint16 converts to float64 exactly):  v' = min(max(v, lo), hi),
+ *   q = min(L - 1, floor((v' - lo) / (hi - lo) * L)),  evaluated in float64 in exactly that order -- subtract, divide,
+ * multiply, floor -- without contraction, so numpy reproduces every bin bit for bit.  hi <= lo gives q = 0 everywhere.
+ * NaN and infinite intensities or ranges are not supported.
+ * CO-OCCURRENCE: for label l with pixel set P, direction a in {0, 45, 90, 135} degrees has the offset (dy, dx) =
+ * (0, d), (d, -d), (d, 0), (d, d).  Every unordered pair {p, p + offset} with both ends in P adds 1 to
+ * G_a[q(p)][q(p + offset)] and 1 to the transposed entry, so a pair of equal levels adds 2 to a diagonal entry: the
+ * symmetric matrix of Haralick (1973) and of skimage.feature.graycomatrix(symmetric=True).  "Both in P" means both carry
+ * the value l: connectivity is not considered (two pieces of a label d apart do pair), a pixel of another label or of
+ * the background never pairs, and no pixel outside the label's bounding box is read.
+ * FEATURES: thirteen columns per (label, channel, direction) from p = G / Sum G, with px(i) = Sum_j p(i, j),
+ * p+(k) = Sum_{i + j = k} p (k = 0 .. 2L - 2), p-(k) = Sum_{|i - j| = k} p (k = 0 .. L - 1), mu = Sum i px(i),
+ * s2 = Sum (i - mu)^2 px(i), 0 log 0 = 0, logarithms to base 2:
+ *   AMT_TEX_ANGULAR_SECOND_MOMENT      Sum p^2
+ *   AMT_TEX_CONTRAST                   Sum k^2 p-(k)
+ *   AMT_TEX_CORRELATION                Sum (i - mu)(j - mu) p / s2; 1 when exactly one grey level occurs (decided on
+ *                                      the integer counts)
+ *   AMT_TEX_VARIANCE                   s2
+ *   AMT_TEX_INVERSE_DIFFERENCE_MOMENT  Sum p / (1 + (i - j)^2)
+ *   AMT_TEX_SUM_AVERAGE                Sum k p+(k)
+ *   AMT_TEX_SUM_VARIANCE               Sum (k - sum_average)^2 p+(k)
+ *   AMT_TEX_SUM_ENTROPY                -Sum p+ log2 p+
+ *   AMT_TEX_ENTROPY                    HXY = -Sum p log2 p
+ *   AMT_TEX_DIFFERENCE_VARIANCE        Sum (k - m)^2 p-(k), m = Sum k p-(k)
+ *   AMT_TEX_DIFFERENCE_ENTROPY         -Sum p- log2 p-
+ *   AMT_TEX_INFO_MEASURE_1             (HXY - HXY1) / HX, HX = -Sum px log2 px, HXY1 = -Sum p(i, j) log2(px(i) px(j));
+ *                                      0 when HX = 0
+ *   AMT_TEX_INFO_MEASURE_2             sqrt(max(0, 1 - exp(-2 (HXY2 - HXY)))), HXY2 = -Sum px(i) px(j) log2(px(i) px(j))
+ * These restate mahotas.features.haralick, the routine behind CellProfiler's MeasureTexture (its sum_average inside
+ * sum_variance included); parity with that module is unpinned offline.
+ * A direction in which the label has no pair (a single pixel, a one-pixel-wide row in direction 90, d larger than the
+ * box) gives thirteen quiet NaNs for that direction only and zero counts; a label absent from its plane gives NaN in all
+ * four directions.
+ * wtable_dev = nplanes x max_label x C x 4 x AMT_TEX_NCOLS doubles, directions in the order 0, 45, 90, 135; with
+ * AMT_RPX_TEXTURE_COUNTS instead nplanes x max_label x C x 4 x levels x levels uint32 behind the same pointer: the raw
+ * counts G_a, exact integers.
+ * Planes of up to 2^31 - 1 pixels.  Counting is integer and the float64 sums run in one fixed order: two runs give
+ * identical bytes; no global atomics.  nplanes == 0 or max_label == 0 writes nothing. */
+#define AMT_TEX_ANGULAR_SECOND_MOMENT 0
+#define AMT_TEX_CONTRAST 1
+#define AMT_TEX_CORRELATION 2
+#define AMT_TEX_VARIANCE 3
+#define AMT_TEX_INVERSE_DIFFERENCE_MOMENT 4
+#define AMT_TEX_SUM_AVERAGE 5
+#define AMT_TEX_SUM_VARIANCE 6
+#define AMT_TEX_SUM_ENTROPY 7
+#define AMT_TEX_ENTROPY 8
+#define AMT_TEX_DIFFERENCE_VARIANCE 9
+#define AMT_TEX_DIFFERENCE_ENTROPY 10
+#define AMT_TEX_INFO_MEASURE_1 11
+#define AMT_TEX_INFO_MEASURE_2 12
+#define AMT_TEX_NCOLS 13
+#define AMT_RPX_TEXTURE (1u << 12)
+#define AMT_RPX_TEXTURE_COUNTS (1u << 13)
+#define AMT_RPX_TEXTURE_LEVELS_SHIFT 14
+#define AMT_RPX_TEXTURE_DISTANCE_SHIFT 21
+#define AMT_RPX_TEXTURE_COLUMNS(levels, distance, counts)                                      \
+    ((int)(((counts) ? AMT_RPX_TEXTURE_COUNTS : AMT_RPX_TEXTURE) |                             \
+           ((unsigned)(levels) << AMT_RPX_TEXTURE_LEVELS_SHIFT) | ((unsigned)(distance) << AMT_RPX_TEXTURE_DISTANCE_SHIFT)))
 
 /* ---- per-plate feature rows (the reference's analogue is the list of cell_properties dicts a
  * user collects per image, R/masks.py:247-328, R/pipeline.py:145-149) ------------------------------------------
