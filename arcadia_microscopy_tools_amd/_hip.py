@@ -75,6 +75,15 @@ TEX_COLS = (
 TEX_NCOLS = len(TEX_COLS)
 TEX_ANGLES = ("0", "45", "90", "135")
 TEX_MAX_LEVELS, TEX_MAX_DISTANCE = 64, 255
+# amt_regionprops_ext with AMT_RPX_RADIAL: the bit (the sign bit of `columns`; the bins ride in the field of the texture
+# levels, rpx_radial_columns below, the header's AMT_RPX_RADIAL_COLUMNS), the columns of a (label, channel, ring) row
+# (AMT_RAD_*), the accepted bins and the geometry row (AMT_RAD_GEOM_*): two radii, then RAD_MAX_BINS ring counts
+RPX_RADIAL = 1 << 31
+RAD_COLS = ("frac_at_d", "mean_frac", "radial_cv")
+RAD_NCOLS = len(RAD_COLS)
+RAD_MAX_BINS = 16
+RAD_GEOM_COLS = ("maximum_radius", "mean_radius")
+RAD_GEOM_NCOLS = len(RAD_GEOM_COLS) + RAD_MAX_BINS
 # amt_peak_markers: the longest peak list of a plane that is labelled from LDS (AMT_PEAK_MARKERS_LDS_TIER)
 PEAK_MARKERS_LDS_TIER = 4096
 
@@ -83,6 +92,12 @@ def rpx_texture_columns(levels: int, distance: int, counts: bool = False) -> int
     """``columns`` of an ``AMT_RPX_TEXTURE`` (``counts``: ``AMT_RPX_TEXTURE_COUNTS``) call of ``amt_regionprops_ext``"""
     return ((RPX_TEXTURE_COUNTS if counts else RPX_TEXTURE) | int(levels) << RPX_TEXTURE_LEVELS_SHIFT
             | int(distance) << RPX_TEXTURE_DISTANCE_SHIFT)
+
+
+def rpx_radial_columns(bins: int) -> int:
+    """``columns`` of an ``AMT_RPX_RADIAL`` call of ``amt_regionprops_ext``: bit 31 is the sign bit of the C ``int``, so
+    the value is the negative number that ``int`` holds"""
+    return (RPX_RADIAL | int(bins) << RPX_TEXTURE_LEVELS_SHIFT) - (1 << 32)
 
 
 class HipUnavailableError(RuntimeError):

@@ -177,6 +177,10 @@ int amt_i_nearest_labels(amt_ctx* ctx, const double2* cen, double* wtable, int n
 // `counts`, the uint32 matrices [plane][label][channel][direction][levels][levels] instead
 int amt_i_texture(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C, const double* ranges,
                   int levels, int distance, bool counts, double* out, int nplanes, int H, int W, int max_label);
+// AMT_RPX_RADIAL (amt_radial.hip): a call of its own, like texture -- geom = the rows [plane][label][AMT_RAD_GEOM_NCOLS]
+// (radii and ring counts), out = [plane][label][channel][ring][AMT_RAD_NCOLS], absent (with intensity) when C == 0
+int amt_i_radial(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C, int bins, double* geom,
+                 double* out, int nplanes, int H, int W, int max_label);
 
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>

@@ -64,6 +64,27 @@ __device__ __forceinline__ void amt_box_for_cells(const amt_box& box, int lc, in
         for (int xb = box.x0; xb <= box.x1; xb += cols) f(xb + col, yb + sub);
 }
 
+// The same walk with a value per cell, f(x, y, v) with v = load(yc, xc) from the coordinates clamped into the box: four
+// row slots per step, their four loads issued together before the first f runs (f may wait on LDS, which would
+// otherwise put every load's latency into the loop one after the other).
+template <typename Ld, typename F>
+__device__ __forceinline__ void amt_box_for_loaded_cells(const amt_box& box, int lc, int lane, Ld&& load, F&& f) {
+    const int cols = 1 << lc, rw = 64 >> lc;
+    const int col = lane & (cols - 1), sub = lane >> lc;
+    const int x1 = box.x1, y1 = box.y1;
+    for (int yb = box.y0 + sub; yb - sub <= y1; yb += 4 * rw)
+        for (int xb = box.x0; xb <= x1; xb += cols) {
+            const int x = xb + col, xc = x <= x1 ? x : x1;
+            const int ya = yb, yc = yb + rw, yd = yb + 2 * rw, ye = yb + 3 * rw;
+            const auto va = load(ya <= y1 ? ya : y1, xc), vc = load(yc <= y1 ? yc : y1, xc);
+            const auto vd = load(yd <= y1 ? yd : y1, xc), ve = load(ye <= y1 ? ye : y1, xc);
+            f(x, ya, va);
+            f(x, yc, vc);
+            f(x, yd, vd);
+            f(x, ye, ve);
+        }
+}
+
 // ---- wave reductions: the butterfly over the lanes 32, 16, .. 1 away; every lane gets the result -----------------------
 // float64 sums depend on this order: the tables of the float64 kernels keep their bits only while it stands.
 struct amt_op_sum {

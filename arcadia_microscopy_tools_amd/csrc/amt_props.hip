@@ -1273,6 +1273,13 @@ extern "C" int amt_regionprops_ext(amt_ctx* ctx, const int32_t* labels, const vo
                                    int columns, double* table_dev, double* wtable_dev, int nplanes, int H, int W,
                                    int max_label) {
     const unsigned cols = (unsigned)columns;
+    if (cols & AMT_RPX_RADIAL) {
+        // radial distribution: the bins ride in the field of the texture levels, table_dev takes the geometry rows
+        const unsigned bins = 0x7fu << AMT_RPX_TEXTURE_LEVELS_SHIFT;
+        AMT_REQUIRE((cols & ~(AMT_RPX_RADIAL | bins)) == 0, "regionprops_ext: no other column bit goes with AMT_RPX_RADIAL");
+        return amt_i_radial(ctx, labels, intensity, in_code, C, (int)(cols >> AMT_RPX_TEXTURE_LEVELS_SHIFT & 0x7fu), table_dev,
+                            wtable_dev, nplanes, H, W, max_label);
+    }
     if (cols & (AMT_RPX_TEXTURE | AMT_RPX_TEXTURE_COUNTS)) {
         // Haralick texture: levels and distance ride in the upper bits, table_dev holds the ranges
         const unsigned params = 0x7fu << AMT_RPX_TEXTURE_LEVELS_SHIFT | 0x3ffu << AMT_RPX_TEXTURE_DISTANCE_SHIFT;

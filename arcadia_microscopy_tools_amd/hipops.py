@@ -1242,6 +1242,8 @@ def regionprops_ext(labels: DeviceArray, max_label: int, columns, intensity: Dev
                          "hipops.neighbor_census or hipops.nearest_labels")
     if bits & (_hip.RPX_TEXTURE | _hip.RPX_TEXTURE_COUNTS):
         raise ValueError("bits 12 and 13 (AMT_RPX_TEXTURE, AMT_RPX_TEXTURE_COUNTS) measure Haralick texture: call hipops.texture")
+    if bits & _hip.RPX_RADIAL or bits < 0:
+        raise ValueError("bit 31 (AMT_RPX_RADIAL) measures the radial distribution: call hipops.radial_distribution")
     want_w = bool(bits & _hip.RPX_WEIGHTED)
     if want_w != (intensity is not None):
         raise ValueError("weighted centroids need intensity images, and intensity images are only used for them")
@@ -1487,6 +1489,57 @@ def texture(labels: DeviceArray, intensity: DeviceArray, max_label: int, levels:
                                                   _hip.rpx_texture_columns(L, d, counts), rng.ptr, buf.ptr, n, H, W, K),
                        "amt_regionprops_ext")
     return o if g is None else (o, g)
+
+
+def radial_parameters(bins) -> int:
+    """``bins`` of ``radial_distribution`` as an int: an integer in 1..RAD_MAX_BINS (no device needed)"""
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)):
+        raise TypeError(f"bins must be an integer, got {bins!r}")
+    if not 1 <= int(bins) <= _hip.RAD_MAX_BINS:
+        raise ValueError(f"bins must be in 1..{_hip.RAD_MAX_BINS}, got {bins}")
+    return int(bins)
+
+
+def radial_distribution(labels: DeviceArray, intensity: DeviceArray | None, max_label: int, bins: int = 4, out=None,
+                        geometry_out=None):
+    """Per-label radial intensity distribution and inscribed radii (``amt_regionprops_ext`` with ``AMT_RPX_RADIAL``; after
+    CellProfiler's MeasureObjectIntensityDistribution and the radius columns of MeasureObjectSizeShape).
+
+    ``labels`` is int32 (..., Y, X); ``intensity`` is (..., C, Y, X) uint16 (exact integer sums, every column
+    reproducible bit for bit) or float64 (without NaN or infinities), one (C, Y, X) stack per label plane, or None.
+    Returns ``(geometry, table)``: geometry (nplanes, max_label, RAD_GEOM_NCOLS) float64 -- ``maximum_radius`` (the
+    radius of the largest inscribed circle), ``mean_radius`` (the mean distance of the label's pixels to its edge), then
+    the pixel counts of the rings 0 (innermost) .. bins - 1 and zeros up to sixteen; table (nplanes, max_label, C, bins,
+    RAD_NCOLS) float64 in ``_hip.RAD_COLS`` order, None without ``intensity``.  The distance of a pixel is the exact
+    Euclidean distance to the nearest pixel that does not carry its label (background, a touching neighbour, or the
+    frame outside the image); a pixel at distance d of a label whose largest distance is dmax lies in ring
+    ``floor(bins * (1 - d / dmax))``, decided on integers; include/amt_hip.h states every column.  ``out`` is the table,
+    ``geometry_out`` the geometry.  A label absent from its plane gives NaN radii, zero counts and NaN columns.  Two
+    runs give identical bytes."""
+    n, H, W = _int32_labels("radial_distribution", labels)
+    B = radial_parameters(bins)
+    K = int(max_label)
+    if K < 0:
+        raise ValueError("max_label must not be negative")
+    C, code = 0, 0
+    if intensity is not None:
+        C, code = _channel_stack(labels, intensity, n, H, W)
+        if C < 1:
+            raise ValueError("intensity / labels plane count mismatch")
+    elif out is not None:
+        raise ValueError("out is the table of the intensity images: without them there is none")
+    ctx = labels.ctx
+    g = None if geometry_out is None else _out(ctx, geometry_out, (n, K, _hip.RAD_GEOM_NCOLS), np.float64)
+    o = None if out is None else _out(ctx, out, (n, K, C, B, _hip.RAD_NCOLS), np.float64)
+    _no_alias("radial_distribution", {"labels": labels, "intensity": intensity}, {"geometry_out": g, "out": o})
+    if g is None:
+        g = ctx.empty((n, K, _hip.RAD_GEOM_NCOLS), np.float64)
+    if o is None and C:
+        o = ctx.empty((n, K, C, B, _hip.RAD_NCOLS), np.float64)
+    _hip.check(_lib().amt_regionprops_ext(ctx.handle, labels.ptr, None if intensity is None else intensity.ptr, code, C,
+                                          _hip.rpx_radial_columns(B), g.ptr, None if o is None else o.ptr, n, H, W, K),
+               "amt_regionprops_ext")
+    return g, o
 
 
 def cellpose_masks(dP: DeviceArray, cellprob: DeviceArray, cellprob_threshold: float = 0.0, niter: int = 200,

@@ -601,6 +601,44 @@ class SegmentationMask:
         cols = table.reshape(k, -1)
         return {key: cols[:, i].copy() for i, key in enumerate(keys)}
 
+    def cell_radial_distribution(self, bins: int = 4) -> dict[str, Float64Array]:
+        """How every channel's signal is spread between the centre and the rim of every cell, and the two radii of the
+        cell's shape, measured on the device (after CellProfiler's MeasureObjectIntensityDistribution and the
+        MaximumRadius / MeanRadius of MeasureObjectSizeShape; include/amt_hip.h states the definitions).  Every pixel of
+        a cell has its exact Euclidean distance d to the nearest pixel outside the cell -- background, a touching
+        neighbour, or the frame around the image; ``maximum_radius`` is the largest d (the radius of the largest
+        inscribed circle) and ``mean_radius`` the mean of d.  The cell is cut into ``bins`` rings (1..16) of equal width
+        in ``d / maximum_radius``, ring 1 the innermost; per channel and ring, ``frac_at_d`` is the ring's share of the
+        cell's total intensity, ``mean_frac`` that share divided by the ring's share of the cell's pixels, and
+        ``radial_cv`` the coefficient of variation of the mean intensity over the (up to) eight wedges of the ring
+        around the centroid.
+
+        Keys are ``maximum_radius``, ``mean_radius``, then ``radial_<measure>_<channel>_<i>of<bins>`` with the
+        lower-cased channel names of ``intensity_image_dict``, channel by channel, ring by ring
+        (``segment.radial_keys``), e.g. ``radial_frac_at_d_fitc_1of4``; each entry holds one float64 per cell, ordered
+        by label like ``cell_properties`` (row j of an ``expanded`` / ``ring`` mask belongs to ``parent_labels[j]``).
+        Without intensity images the two radii alone are returned.  uint8 / uint16 images are read as integers, any
+        other dtype as float64 (NaN and infinities are not supported).  A ring without a pixel, or a cell whose channel
+        sums to zero, gives NaN."""
+        from . import _hip, hipops
+        from .segment import radial_keys
+
+        channels = list(self.intensity_image_dict or {})
+        keys = radial_keys(channels, bins)
+        bins = hipops.radial_parameters(bins)
+        lab, k = self._labels_device
+        k = int(k)
+        shape = tuple(lab.shape[-2:])
+        stack = None
+        if channels:
+            stack, _, _ = self._intensity_stack(shape)
+            stack = stack.reshape((1,) + stack.shape)
+        geometry, table = hipops.radial_distribution(lab.reshape((1,) + shape), stack, max(k, 1), bins=bins)
+        cols = geometry.numpy()[0][:k, :len(_hip.RAD_GEOM_COLS)]
+        if table is not None:
+            cols = np.concatenate([cols, table.numpy()[0][:k].reshape(k, -1)], axis=1)
+        return {key: cols[:, i].copy() for i, key in enumerate(keys)}
+
     @cached_property
     def centroids_yx(self) -> Float64Array:
         """(num_cells, 2) array of [y, x] centroids (R/masks.py:330-353)."""

@@ -471,6 +471,17 @@ def texture_keys(channel_names, distance: int = 1, angles: str = "each") -> list
     return [f"texture_{f}_{name}_{int(distance)}_{a}" for name in names for a in _hip.TEX_ANGLES for f in _hip.TEX_COLS]
 
 
+def radial_keys(channel_names, bins: int = 4) -> list[str]:
+    """The keys of ``SegmentationMask.cell_radial_distribution`` for these channels, in order (no device needed):
+    ``maximum_radius`` and ``mean_radius``, then channel by channel, ring by ring (1 = the innermost), measure by
+    measure (``_hip.RAD_COLS``) ``f"radial_{measure}_{channel}_{i}of{bins}"`` with the lower-cased channel names, e.g.
+    ``radial_frac_at_d_fitc_1of4``."""
+    bins = hipops.radial_parameters(bins)
+    names = [str(getattr(c, "name", c)).lower() for c in channel_names]
+    return list(_hip.RAD_GEOM_COLS) + [f"radial_{m}_{name}_{i}of{bins}" for name in names
+                                        for i in range(1, bins + 1) for m in _hip.RAD_COLS]
+
+
 def neighbor_keys() -> list[str]:
     """The keys of ``SegmentationMask.cell_neighbors``, in order (no device needed): the contact census of
     ``_hip.RPX_NCOLS4`` with ``percent_touching`` after the two pixel counts it is made of, then the two closest cells

@@ -713,6 +713,60 @@ int amt_colocalization(amt_ctx* ctx, const int32_t* labels, const void* intensit
 #define AMT_RPX_TEXTURE_COLUMNS(levels, distance, counts)                                      \
     ((int)(((counts) ? AMT_RPX_TEXTURE_COUNTS : AMT_RPX_TEXTURE) |                             \
            ((unsigned)(levels) << AMT_RPX_TEXTURE_LEVELS_SHIFT) | ((unsigned)(distance) << AMT_RPX_TEXTURE_DISTANCE_SHIFT)))
+/* ---- per-label radial intensity distribution and inscribed radii: the AMT_RPX_RADIAL bit of the extended region
+ * properties ----
+ * How a channel's signal is spread between a label's centre and its rim, and the two radii of the label's shape.  Like
+ * texture the capability rides on amt_regionprops_ext.  `columns` = AMT_RPX_RADIAL_COLUMNS(bins): AMT_RPX_RADIAL (bit 31,
+ * so the value is negative as an int) and bins = B in the 7-bit field at AMT_RPX_TEXTURE_LEVELS_SHIFT (bits 14-20; the
+ * field holds 0..127, so 0 and 17 can be stated and are refused).  With bit 31 set every other bit, bits 21-30 included,
+ * must be 0: the morphology bits, the other table bits and both texture bits are AMT_EINVAL.  labels = nplanes int32
+ * planes; intensity = nplanes x C planes of element type in_code (AMT_U16 or AMT_F64; other codes are AMT_EINVAL), one
+ * (C, Y, X) stack per label plane.  C == 0 with intensity == NULL and wtable_dev == NULL is the geometry-only call
+ * (in_code is not looked at); C >= 1 needs both.  table_dev (never NULL) and wtable_dev are both outputs.  AMT_EINVAL
+ * for B outside 1..16 and for an output that overlaps another operand.
+ * These definitions are our own, after CellProfiler's MeasureObjectIntensityDistribution / MeasureObjectSizeShape;
+ * parity with CellProfiler is unpinned offline.  For label l of a plane with pixel set P (n pixels), channel values v_p:
+ * DISTANCE TO THE EDGE: d2(p) = the smallest squared Euclidean distance from p to a pixel that does not carry l --
+ * background, another label, or any position outside the image: the plane counts as framed with zeros.  So d2 >= 1, and
+ * a label cut by the border has its edge there.  Connectivity plays no part: a hole, or a gap between two pieces of l,
+ * is outside.  d2 is an exact integer; dmax2 = max over P of d2.
+ * RING: ring 0 is the innermost, ring B - 1 the outermost.  b(p) = the largest k in 0..B-1 with
+ *   d2(p) * B * B <= dmax2 * (B - k) * (B - k)   in 64-bit integers;
+ * in real numbers floor(B * (1 - d / dmax)) with exact ties going outward.  No square root and no float decides a ring.
+ * WEDGE: with sy = Sum_P y, sx = Sum_P x, ey = n * y - sy and ex = n * x - sx in int64,
+ *   w(p) = (ey > 0) + 2 * (ex > 0) + 4 * (|ey| > |ex|):  eight wedges around the centroid, decided on integers.
+ * GEOMETRY ROW per (plane, label): table_dev = nplanes x max_label x AMT_RAD_GEOM_NCOLS doubles,
+ *   AMT_RAD_GEOM_MAXIMUM_RADIUS      sqrt((double)dmax2), the radius of the largest inscribed circle
+ *   AMT_RAD_GEOM_MEAN_RADIUS         (Sum_P sqrt((double)d2)) / n; the sum is the exact sum of the float64 roots rounded
+ *                                    once (Python's math.fsum), so it depends on no order of summation
+ *   AMT_RAD_GEOM_RING_COUNT0 + b     n_b, the pixel count of ring b, for b < B; the columns from B to 15 are 0
+ * INTENSITY ROWS per (plane, label, channel, ring): wtable_dev = nplanes x max_label x C x B x AMT_RAD_NCOLS doubles.
+ * With S_bw the sum of v over the pixels of ring b in wedge w, n_bw their number, S_b = Sum_w S_bw and S = Sum_b S_b:
+ *   AMT_RAD_FRAC_AT_D   S_b / S; NaN when S == 0
+ *   AMT_RAD_MEAN_FRAC   (S_b / S) / (n_b / n), in that order; NaN when n_b == 0 or S == 0
+ *   AMT_RAD_RADIAL_CV   over the wedges w = 0..7 that hold a pixel of ring b, m_w = S_bw / n_bw; mu = the sum of the m_w
+ *                       in wedge order divided by their number; var = the sum of (m_w - mu)^2 in wedge order divided by
+ *                       their number; the column is sqrt(var) / mu.  NaN when the ring is empty or mu == 0
+ * all in float64 without contraction in exactly this order, so that a scalar numpy loop reproduces the bits.
+ * AMT_U16: S_bw, S_b and S are exact 64-bit integers, each converted once; every column is then a fixed sequence of
+ * correctly rounded operations and does not depend on the order of summation.  AMT_F64: S_bw is summed in the order of
+ * the box walk and the wave reductions, S_b over the wedges and S over the rings in ascending order: fixed, so two runs
+ * give identical bits; NaN and infinite intensities are not supported.
+ * A label absent from its plane gives NaN radii, zero counts and NaN intensity columns.  Every box size gives the exact
+ * result: a label whose bounding box has more cells than LDS holds keeps its distances in scratch planes (16 + 32 bits
+ * per pixel of the call, always reserved); its row search costs time in proportion to its radius.  Planes of up to
+ * 2^31 - 1 pixels.  No global atomics.  nplanes == 0 or max_label == 0 writes nothing. */
+#define AMT_RAD_FRAC_AT_D 0
+#define AMT_RAD_MEAN_FRAC 1
+#define AMT_RAD_RADIAL_CV 2
+#define AMT_RAD_NCOLS 3
+#define AMT_RAD_MAX_BINS 16
+#define AMT_RAD_GEOM_MAXIMUM_RADIUS 0
+#define AMT_RAD_GEOM_MEAN_RADIUS 1
+#define AMT_RAD_GEOM_RING_COUNT0 2
+#define AMT_RAD_GEOM_NCOLS 18
+#define AMT_RPX_RADIAL (1u << 31)
+#define AMT_RPX_RADIAL_COLUMNS(bins) ((int)(AMT_RPX_RADIAL | ((unsigned)(bins) << AMT_RPX_TEXTURE_LEVELS_SHIFT)))
 
 /* ---- per-plate feature rows (the reference's analogue is the list of cell_properties dicts a
  * user collects per image, R/masks.py:247-328, R/pipeline.py:145-149) ------------------------------------------
