@@ -7,8 +7,9 @@
 //
 // All accumulation is integer (counts, coordinate sums, intensity sums) and therefore independent of
 // the order in which pixels arrive; floating point only enters in the final per-label kernel.
-// A wave covers 64 consecutive pixels of one row; equal-label runs inside it are reduced in closed
-// form (coordinates) or with wave prefix sums (intensities), so each run costs one set of atomics.
+// Two passes: rp_boxes_kernel streams the label planes once for the bounding boxes (atomics only from runs that can
+// be an extreme of their label); rp_label_kernel, one wave per label over its box, makes everything else privately
+// per lane -- moment sums, row extents, intensities, and the perimeter from the row words of the scan -- no atomics.
 #include "amt_internal.h"
 #include "amt_perlabel.h"
 
@@ -49,39 +50,108 @@ __device__ __forceinline__ double diff_of_products(u64 a, u64 b, u64 c, u64 d) {
     return neg ? -v : v;
 }
 
-// bounding boxes: a wave covers 64 consecutive pixels of 8 rows (all 8 loads issued up front); every
-// run of equal labels costs one set of min/max atomics.
-__global__ void __launch_bounds__(256) rp_bbox_kernel(const int* __restrict__ labels, int* __restrict__ bbox, int H,
-                                                      int W, int max_label) {
+// bounding boxes, a pure streaming read of the label planes: a wave owns a strip of BX_COLS columns (four per lane, one
+// 16-byte load per row) and slides down BX_ROWS rows (+ 1 halo row above / below) with a three-row window in registers;
+// loads are issued BX_BATCH rows ahead of their use.  Rows that are all background skip everything.  Atomics come only
+// from runs that can be an extreme of their label: a run asks for y0 / y1 only if the pixel above / below its head is
+// not its label, for x0 only from a head with no pixel of the label above-left or below-left, for x1 from a tail
+// likewise -- interior rows of a blob ask for nothing.  The four requests of the lane's four pixels are flat per-lane
+// conditions behind ONE uniform test.  What lies left of a strip's first column and right of its last one is not
+// loaded and counts as another label: a request too many there, never one too few.
+// VEC: the plane pointer is 16-byte aligned and W % 4 == 0 (every row, of every plane, then starts on 16 bytes);
+// otherwise four scalar loads per lane (odd widths, sliced planes).
+constexpr int BX_ROWS = 30, BX_COLS = 256, BX_BATCH = 4, BX_NBATCH = (BX_ROWS + 2) / BX_BATCH;
+static_assert(BX_BATCH * BX_NBATCH == BX_ROWS + 2, "row batches must tile the strip");
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) rp_boxes_kernel(const int* __restrict__ labels, int* __restrict__ bbox, int H,
+                                                       int W, int max_label) {
     const int lane = threadIdx.x & 63;
-    const int x = blockIdx.x * 64 + lane;
-    const int yb = (blockIdx.y * 4 + (threadIdx.x >> 6)) * 8;
-    if (yb >= H) return;
-    const size_t n = (size_t)H * W;
+    const int strip = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (strip > (W - 1) / BX_COLS) return;  // whole wave; the kernel has no barrier
     const int plane = blockIdx.z;
-    int labs[8];
+    const int* L = labels + (size_t)plane * H * W;
+    int* bbp = bbox + (size_t)plane * max_label * 4;
+    const unsigned x = (unsigned)strip * BX_COLS + 4u * lane;  // the first of the lane's four columns
+    const unsigned uw = (unsigned)W, ml = (unsigned)max_label;
+    const int ya = blockIdx.y * BX_ROWS, yend = ya + BX_ROWS < H ? ya + BX_ROWS : H;
+
+    // UNCONDITIONAL loads from clamped coordinates; what lies outside the image or outside 1..max_label is zeroed
+    // where the value is used
+    unsigned xc[4], mlx[4];  // mlx: the largest label of the column, none outside the image
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int y = yb + k;
-        int v = 0;
-        if (x < W && y < H) v = labels[(size_t)plane * n + (size_t)y * W + x];
-        labs[k] = (v < 0 || v > max_label) ? 0 : v;
+    for (int k = 0; k < 4; ++k) {
+        xc[k] = x + k < uw ? x + k : uw - 1u;
+        mlx[k] = x + k < uw ? ml : 0u;
     }
+    const unsigned xv = x < uw ? x : uw - 4u;  // VEC: W >= 4
+    auto load_row = [&](int y) -> int4 {
+        const int yc = y < 0 ? 0 : (y < H ? y : H - 1);
+        const int* row = L + (size_t)yc * W;
+        if constexpr (VEC) return *(const int4*)(row + xv);
+        else return make_int4(row[xc[0]], row[xc[1]], row[xc[2]], row[xc[3]]);
+    };
+    int4 cur[BX_BATCH], nxt[BX_BATCH];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int lab = labs[k];
-        const int left = __shfl_up(lab, 1);
-        const bool head = (lane == 0) || (left != lab);
-        const u64 heads = __ballot(head);
-        if (lab != 0 && head) {
-            const u64 later = heads & ~((2ull << lane) - 1ull);
-            const int end_lane = later ? (__ffsll((long long)later) - 2) : 63;
-            int* B = bbox + ((size_t)plane * max_label + (lab - 1)) * 4;
-            atomicMin(&B[0], yb + k);
-            atomicMin(&B[1], x);
-            atomicMax(&B[2], yb + k);
-            atomicMax(&B[3], x + (end_lane - lane));
+    for (int j = 0; j < BX_BATCH; ++j) cur[j] = load_row(ya - 1 + j);
+    // window: c = row r-1 (the row whose runs ask), u = row r-2; index 0 / 5 = the pixel left / right of the lane's four
+    int c[6] = {}, u[6] = {};
+    for (int b = 0; b < BX_NBATCH; ++b) {
+        if (ya - 1 + b * BX_BATCH > yend) break;  // uniform: row yend is the last one a row of this strip looks at
+        if (b + 1 < BX_NBATCH) {
+#pragma unroll
+            for (int j = 0; j < BX_BATCH; ++j) nxt[j] = load_row(ya - 1 + (b + 1) * BX_BATCH + j);
         }
+#pragma unroll
+        for (int j = 0; j < BX_BATCH; ++j) {
+            const int r = ya - 1 + b * BX_BATCH + j;  // row of d
+            const bool rin = r >= 0 && r < H;
+            const int raw[4] = {cur[j].x, cur[j].y, cur[j].z, cur[j].w};
+            int d[6];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {  // as unsigned a negative value is above every max_label
+                const unsigned top = rin ? mlx[VEC ? 0 : k] : 0u;  // VEC: the lane's four columns lie inside or outside together
+                d[k + 1] = (unsigned)raw[k] <= top ? raw[k] : 0;
+            }
+            d[0] = amt_lane_left(d[4]);
+            d[5] = amt_lane_right(d[1]);
+            const int yc = r - 1;
+            if (yc >= ya && yc < yend && __ballot((c[1] | c[2] | c[3] | c[4]) != 0) != 0ull) {  // uniform
+                // a request is a minimum of differences: nonzero if the label is one and differs from every pixel named
+                // (vector instructions; as compares the same logic is twice as many scalar ones)
+                unsigned q0[4], q1[4], q2[4], q3[4], qk[4], any = 0u;
+#pragma unroll
+                for (int k = 1; k <= 4; ++k) {
+                    const unsigned v = (unsigned)c[k];
+                    const unsigned cl = c[k - 1] ^ v, cr = c[k + 1] ^ v, uu = u[k] ^ v, dd = d[k] ^ v;
+                    const unsigned ul = u[k - 1] ^ v, dl = d[k - 1] ^ v, ur = u[k + 1] ^ v, dr = d[k + 1] ^ v;
+                    q0[k - 1] = min(min(v, cl), uu);               // head of a run, not the label above it
+                    q2[k - 1] = min(min(v, cl), dd);               //                              below it
+                    q1[k - 1] = min(min(min(cl, ul), dl), v);      // head, not the label above-left or below-left
+                    q3[k - 1] = min(min(min(cr, ur), dr), v);      // tail likewise
+                    qk[k - 1] = q0[k - 1] | q1[k - 1] | q2[k - 1] | q3[k - 1];
+                    any |= qk[k - 1];
+                }
+                if (__ballot(any != 0u)) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if (!qk[k]) continue;  // one skipped block per pixel, not four
+                        int* B = bbp + (size_t)(c[k + 1] - 1) * 4;
+                        if (q0[k]) atomicMin(&B[0], yc);
+                        if (q2[k]) atomicMax(&B[2], yc);
+                        if (q1[k]) atomicMin(&B[1], (int)(x + k));
+                        if (q3[k]) atomicMax(&B[3], (int)(x + k));
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                u[k] = c[k];
+                c[k] = d[k];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < BX_BATCH; ++j) cur[j] = nxt[j];
     }
 }
 
@@ -92,8 +162,12 @@ int amt_i_label_boxes(amt_ctx* ctx, const int* labels, int* bbox, unsigned long 
     const size_t nlab = (size_t)nplanes * max_label;
     hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
     AMT_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rp_bbox_kernel, dim3((W + 63) / 64, (H + 31) / 32, nplanes), dim3(256), 0, ctx->stream, labels, bbox,
-                       H, W, max_label);
+    const int nstrips = (W - 1) / BX_COLS + 1;
+    const dim3 grid((nstrips + 3) / 4, (H - 1) / BX_ROWS + 1, nplanes);
+    if ((uintptr_t)labels % 16 == 0 && W % 4 == 0)
+        hipLaunchKernelGGL(rp_boxes_kernel<true>, grid, dim3(256), 0, ctx->stream, labels, bbox, H, W, max_label);
+    else
+        hipLaunchKernelGGL(rp_boxes_kernel<false>, grid, dim3(256), 0, ctx->stream, labels, bbox, H, W, max_label);
     AMT_LAUNCH_CHECK();
     return AMT_OK;
 }
@@ -103,6 +177,13 @@ int amt_i_label_boxes(amt_ctx* ctx, const int* labels, int* bbox, unsigned long 
 // per call, all accumulated privately per lane and reduced once -- no atomics, run-to-run identical.
 constexpr int RP_MAXC = 4;
 constexpr int RPS = 3;  // row slots per step: their label and intensity loads are issued together
+// The perimeter's row words: an LDS ring of RP_PW 32-bit words per wave, 4 KB (the kernel's registers allow 24 single-wave
+// workgroups per CU, which leaves 6.6 KB each).  A box of nw 32-column words per row keeps RP_PW >> lb rows in it, lb =
+// ceil(log2(nw)) (a row's words start at a power of two); it is scanned in bands of rp_band_rows(lb) rows, the four
+// rows less are the rows the next band's count still looks at.  Boxes wider than RP_WIDE columns (lb > RP_LBMAX: fewer
+// than 8 rows would fit) take rp_perimeter_plain.
+constexpr int RP_PW = 1024, RP_LBMAX = 7, RP_WIDE = 32 << RP_LBMAX;
+__host__ __device__ constexpr int rp_band_rows(int lb) { return (RP_PW >> lb) - 4; }
 __device__ __forceinline__ size_t rp_uniform(size_t v) {  // a wave-uniform value, kept in scalar registers
     const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
     const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
@@ -124,10 +205,14 @@ struct RpSums {
 // The kernel is bound by instruction issue, not by the round trips ("What the numbers say"): a second register
 // set that kept the loads of step s + 1 in flight while step s was consumed cost a fifth of the waves per SIMD and ran
 // 20-90 us slower per 48 planes.  What pays is fewer instructions per pixel and per wave.
+// The scan takes the rows ya .. y1 of the box that starts at (y0, x0): the whole box, or one band of it (rp_label_kernel).
+// `pw` (nullable): every row's words of "label == want" go to the LDS ring of rp_perimeter_rows, the columns 32 k ..
+// 32 k + 31 of row y to pw[((y - y0) & (RP_PW - 1 >> lb)) << lb | k].
 template <int LC>
 __device__ __forceinline__ void rp_label_scan(const int* __restrict__ L, const uint16_t* __restrict__ I, size_t n, int W,
-                                              int x0, int y0, int x1, int y1, int want, int nc, bool rows_ok,
-                                              int2* __restrict__ myrows, int lane, RpSums& a) {
+                                              int x0, int y0, int x1, int ya, int y1, int want, int nc, bool rows_ok,
+                                              int2* __restrict__ myrows, unsigned* __restrict__ pw, int lb, int lane,
+                                              RpSums& a, unsigned& tcnt, u64& tsy) {
     constexpr int COLS = 1 << LC, RW = 64 >> LC;
     const int col = lane & (COLS - 1), sub = lane >> LC;
     // addresses: a wave-uniform base per row slot (scalar registers) and one small byte offset per lane, which the label
@@ -154,10 +239,9 @@ __device__ __forceinline__ void rp_label_scan(const int* __restrict__ L, const u
             }
         }
     };
-    int nyb = y0, nxb = x0;
+    int nyb = ya, nxb = x0;
     int rmin[RPS], rmax[RPS];     // LC == 6: a row's extent over the blocks of its row group
-    unsigned tcnt = 0;            // LC < 6: the lane's column is the same in every step,
-    u64 tsy = 0;                  //         so the closed forms are taken once at the end
+    // tcnt, tsy: LC < 6: the lane's column is the same in every step, so the closed forms are taken once at the end
     do {
         const int yb = nyb, xb = nxb;
         load_step(yb, xb);
@@ -198,6 +282,8 @@ __device__ __forceinline__ void rp_label_scan(const int* __restrict__ L, const u
             }
             const u64 bal = __ballot(m);
             if constexpr (LC == 6) {
+                if (pw && lane == 0 && y <= y1)  // lb >= 1: two words, 8-byte aligned
+                    *(u64*)(pw + (((y - y0) & ((RP_PW - 1) >> lb)) << lb) + ((xb - x0) >> 5)) = bal;
                 if (bal) {
                     const int first = xb + __ffsll((long long)bal) - 1;
                     const int last = xb + 63 - __clzll((long long)bal);
@@ -209,6 +295,7 @@ __device__ __forceinline__ void rp_label_scan(const int* __restrict__ L, const u
                 if (rows_ok && col == 0 && y <= y1)
                     steprows[j * RW] = sm ? make_int2(x0 + __ffs((int)sm) - 1, x0 + 31 - __clz((int)sm))
                                           : make_int2(0x7fffffff, -1);
+                if (pw && col == 0 && y <= y1) pw[(y - y0) & (RP_PW - 1)] = sm;
             }
         }
         if constexpr (LC == 6) {
@@ -227,8 +314,114 @@ __device__ __forceinline__ void rp_label_scan(const int* __restrict__ L, const u
             tsy += bsy;
         }
     } while (nyb <= y1);
+}
+
+// perimeter (SK/measure/_regionprops_utils.py:186-249) of the label whose row words m[y] the scan has left in the ring:
+// border pixels B[y] = m[y] & ~(m[y-1] & m[y+1] & west(m[y]) & east(m[y])) (4-neighbourhood, outside = background), and
+// for every border pixel the 3 x 3 code 1 + 2 a + 10 d, a / d = its border neighbours across an edge / a corner, as
+// bit-sliced sums over all 64 columns of a word at once.  skimage weights the codes {5, 7, 15, 17, 25, 27} (C1: a in
+// {2, 3}, d <= 2), {21, 33} (C2: (a, d) = (0, 2), (1, 3)) and {13, 23} (C3: a = 1, d in {1, 2}).
+// One lane per (row, word of 32 columns) counts the rows ya .. yb; rows outside y0 .. ylast and words outside 0 .. nw - 1
+// are zero.  Of the words left and right only the carry bits matter: column 31 / 0 of m and of B, and columns 30 / 1 of
+// m for those.
+__device__ __forceinline__ void rp_sum4(unsigned p, unsigned q, unsigned r, unsigned t, unsigned& s0, unsigned& s1,
+                                        unsigned& s2) {
+    const unsigned x1 = p ^ q, c1 = p & q, x2 = r ^ t, c2 = r & t, k = x1 & x2;
+    s0 = x1 ^ x2;
+    s1 = c1 ^ c2 ^ k;
+    s2 = c1 & c2;
+}
+template <bool MULTI>  // more than one word per row
+__device__ __forceinline__ void rp_perimeter_rows(const unsigned* __restrict__ pw, int lb, int nw, int y0, int ylast,
+                                                  int ya, int yb, int lane, unsigned (&cls)[3]) {
+    const int rmask = (RP_PW - 1) >> lb;
+    for (int i = lane; i < (yb - ya + 1) << lb; i += 64) {
+        const int y = ya + (i >> lb), b = MULTI ? i & ((1 << lb) - 1) : 0;
+        if (MULTI && b >= nw) continue;
+        unsigned m[5];
+        unsigned lf[5], rt[5];  // MULTI: the columns 31 (bit 1), 30 (bit 0) of word b - 1 and 0, 1 of word b + 1
+#pragma unroll
+        for (int r = 0; r < 5; ++r) {
+            const int yy = y - 2 + r;
+            const bool ok = yy >= y0 && yy <= ylast;
+            const int base = (((yy - y0) & rmask) << lb) + b;  // inside the ring whatever yy is
+            const unsigned mc = pw[base];
+            m[r] = ok ? mc : 0u;
+            lf[r] = rt[r] = 0u;
+            if constexpr (MULTI) {
+                const unsigned ml = pw[base - (b > 0 ? 1 : 0)], mr = pw[base + (b + 1 < nw ? 1 : 0)];
+                lf[r] = (ok && b > 0) ? ml >> 30 : 0u;
+                rt[r] = (ok && b + 1 < nw) ? mr & 3u : 0u;
+            }
+        }
+        unsigned B[3], wst[3], est[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const unsigned c = m[r + 1];
+            const unsigned cin_w = lf[r + 1] >> 1, cin_e = (rt[r + 1] & 1u) << 31;
+            B[r] = c & ~(m[r] & m[r + 2] & ((c << 1) | cin_w) & ((c >> 1) | cin_e));
+            // B of column 31 of word b - 1 and of column 0 of word b + 1 (bit 0 of each expression)
+            const unsigned bl = (lf[r + 1] >> 1) & ~((lf[r] >> 1) & (lf[r + 2] >> 1) & lf[r + 1] & c) & 1u;
+            const unsigned br = rt[r + 1] & ~(rt[r] & rt[r + 2] & (c >> 31) & (rt[r + 1] >> 1)) & 1u;
+            wst[r] = (B[r] << 1) | bl;
+            est[r] = (B[r] >> 1) | (br << 31);
+        }
+        unsigned a0, a1, a2, d0, d1, d2;
+        rp_sum4(B[0], B[2], wst[1], est[1], a0, a1, a2);
+        rp_sum4(wst[0], est[0], wst[2], est[2], d0, d1, d2);
+        const unsigned ctr = B[1];
+        const unsigned a_is1 = a0 & ~a1 & ~a2, d_is2 = d1 & ~d0 & ~d2;
+        cls[0] += (unsigned)__popc(ctr & a1 & ~a2 & ~d2 & ~(d1 & d0));
+        cls[1] += (unsigned)__popc(ctr & ((~(a0 | a1 | a2) & d_is2) | (a_is1 & d1 & d0)));
+        cls[2] += (unsigned)__popc(ctr & a_is1 & ((d0 & ~d1 & ~d2) | d_is2));
+    }
+}
+
+// The same counts for a box wider than RP_WIDE columns, pixel by pixel from the label plane: speed does not matter here.
+__device__ __forceinline__ void rp_perimeter_plain(const int* __restrict__ L, int H, int W, int x0, int y0, int x1, int y1,
+                                                   int want, int lane, unsigned (&cls)[3]) {
+    auto on = [&](int y, int x) {
+        return (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W && L[(size_t)y * W + x] == want;
+    };
+    auto border = [&](int y, int x) {
+        return on(y, x) && !(on(y - 1, x) && on(y + 1, x) && on(y, x - 1) && on(y, x + 1));
+    };
+    for (int y = y0; y <= y1; ++y)
+        for (int xb = x0; xb <= x1; xb += 64) {
+            const int x = xb + lane;
+            if (x > x1 || !border(y, x)) continue;
+            const int a = border(y - 1, x) + border(y + 1, x) + border(y, x - 1) + border(y, x + 1);
+            const int d = border(y - 1, x - 1) + border(y - 1, x + 1) + border(y + 1, x - 1) + border(y + 1, x + 1);
+            cls[0] += (a == 2 || a == 3) && d <= 2;
+            cls[1] += (a == 0 && d == 2) || (a == 1 && d == 3);
+            cls[2] += a == 1 && (d == 1 || d == 2);
+        }
+}
+
+// The scan of a box and, with `pw`, its perimeter counts: band by band if the box is taller than the ring.
+template <int LC>
+__device__ __forceinline__ void rp_label_bands(const int* __restrict__ L, const uint16_t* __restrict__ I, size_t n, int W,
+                                               int x0, int y0, int x1, int y1, int want, int nc, bool rows_ok,
+                                               int2* __restrict__ myrows, unsigned* __restrict__ pw, int lb, int nw, int lane,
+                                               RpSums& a, unsigned (&cls)[3]) {
+    const int band = rp_band_rows(lb);
+    unsigned tcnt = 0;
+    u64 tsy = 0;
+    int ya = y0, ycount = y0;
+    do {
+        const int yb = (pw && y1 - ya >= band) ? ya + band - 1 : y1;
+        rp_label_scan<LC>(L, I, n, W, x0, y0, x1, ya, yb, want, nc, rows_ok, myrows, pw, lb, lane, a, tcnt, tsy);
+        if (pw) {
+            __syncthreads();  // one wave: orders the row words before the lanes that read them
+            const int yc = yb == y1 ? y1 : yb - 2;  // row yc + 2 is the last one in the ring
+            rp_perimeter_rows<LC == 6>(pw, lb, nw, y0, yb, ycount, yc, lane, cls);
+            ycount = yc + 1;
+            __syncthreads();
+        }
+        ya = yb + 1;
+    } while (ya <= y1);
     if constexpr (LC < 6) {
-        const unsigned x = (unsigned)(x0 + col);
+        const unsigned x = (unsigned)(x0 + (lane & ((1 << LC) - 1)));
         a.cnt = tcnt;
         a.sy = tsy;
         a.sx = (u64)x * tcnt;
@@ -237,6 +430,8 @@ __device__ __forceinline__ void rp_label_scan(const int* __restrict__ L, const u
     }
 }
 
+// want_morph: bit 0 = the moment sums go to `acc` and the row extents to `rows`, bit 1 = the perimeter's three class
+// counts go to acc[A_C1 .. A_C3] too
 __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ labels, const int* __restrict__ bbox,
                                                       const int* __restrict__ hoff, const int* __restrict__ htot,
                                                       int2* __restrict__ rows, size_t cap, u64* __restrict__ acc,
@@ -269,9 +464,18 @@ __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ la
     }
     // wave-uniform; the 2- and 4-row slots keep their per-lane byte offsets (< 4 * (3 * W + 64)) in 32 bits
     const int w = W < (1 << 28) ? x1 - x0 + 1 : 64;
-    if (w <= 16) rp_label_scan<4>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, lane, a);
-    else if (w <= 32) rp_label_scan<5>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, lane, a);
-    else rp_label_scan<6>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, lane, a);
+    // the perimeter: the scan leaves the row words in the ring, band by band if the box is taller than the ring
+    __shared__ __attribute__((aligned(8))) unsigned s_pw[RP_PW];
+    const bool per = (want_morph & 2) != 0;
+    // 64 x 1: whole 64-column blocks, so an even number (>= 2) of words per row
+    const int nw = w <= 32 ? 1 : (((x1 - x0) >> 6) + 1) * 2, lb = 32 - __clz(nw - 1);
+    const bool ring = per && x1 - x0 < RP_WIDE;  // lb <= RP_LBMAX
+    unsigned cls[3] = {0u, 0u, 0u};
+    unsigned* pw = ring ? s_pw : nullptr;
+    if (w <= 16) rp_label_bands<4>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, pw, 0, 1, lane, a, cls);
+    else if (w <= 32) rp_label_bands<5>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, pw, 0, 1, lane, a, cls);
+    else rp_label_bands<6>(L, I, n, W, x0, y0, x1, y1, l + 1, nc, rows_ok, myrows, pw, lb, nw, lane, a, cls);
+    if (per && !ring) rp_perimeter_plain(L, H, W, x0, y0, x1, y1, l + 1, lane, cls);
     // ONE reduction of everything: the six moment sums in the order of the accumulator slots, then sum and sum of
     // squares per channel; the extrema as minima (max v = ~min ~v)
     static_assert(A_N == 0 && A_SXY == 5, "the moment sums are the first six accumulator slots");
@@ -288,6 +492,12 @@ __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ la
     t[14] = t[15] = 0;
     const u64 red = amt_wave_reduce_scatter<16, amt_op_sum>(t, lane);  // value k in the lanes 4 k .. 4 k + 3
     if (want_morph && (lane & 3) == 0 && lane < 4 * 6) acc[li * A_NACC + (lane >> 2)] = red;
+    if (per) {
+        static_assert(A_C2 == A_C1 + 1 && A_C3 == A_C1 + 2, "the class counts are three consecutive accumulator slots");
+        u64 pc[8] = {cls[0], cls[1], cls[2], 0, 0, 0, 0, 0};
+        const u64 pr = amt_wave_reduce_scatter<8, amt_op_sum>(pc, lane);  // value k in the lanes 8 k .. 8 k + 7
+        if ((lane & 7) == 0 && lane < 8 * 3) acc[li * A_NACC + A_C1 + (lane >> 3)] = pr;
+    }
     if (itable) {
         const unsigned ext = amt_wave_reduce_scatter<8, amt_op_min>(e, lane);  // value k in the lanes 8 k .. 8 k + 7
         // lane c finalises channel c
@@ -307,104 +517,6 @@ __global__ void __launch_bounds__(64) rp_label_kernel(const int* __restrict__ la
                 o[3] = sqrt(var < 0.0 ? 0.0 : var);
             }
         }
-    }
-}
-
-// perimeter: border pixels (4-neighbourhood, outside = background) and their 3x3 weighted codes
-// (SK/measure/_regionprops_utils.py:186-249); with `bbox` the kernel also folds the bounding boxes (per-run
-// atomics, only for runs that can be an extreme of their label), which spares the morphology path a separate
-// pass over the label image.
-// No LDS and no barrier: a wave owns a strip of PR_IN columns (+ 2 halo columns on
-// either side = 64 lanes) and slides down PR_ROWS rows (+ 2 halo rows above / below) with a three-row window in
-// registers.  Horizontal neighbours come from DPP wave shifts, the "is a border pixel" flag rides in bit 31 of the
-// label (w = v | flag), so "neighbour is a border pixel of MY label" is one compare, w(q) == w(p).  Rows whose
-// whole window is background skip everything.  Loads are issued 17 rows ahead of their use.
-constexpr int PR_ROWS = 64, PR_IN = 60, PR_BATCH = 17, PR_NBATCH = (PR_ROWS + 4) / PR_BATCH;
-static_assert(PR_BATCH * PR_NBATCH == PR_ROWS + 4, "row batches must tile the strip");
-
-__global__ void __launch_bounds__(256) rp_perimeter_rows_kernel(const int* __restrict__ labels, u64* __restrict__ acc,
-                                                                int H, int W, int max_label, int* __restrict__ bbox) {
-    const int lane = threadIdx.x & 63;
-    const int strip = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (strip * PR_IN >= W) return;  // whole wave; the kernel has no barrier
-    const int plane = blockIdx.z;
-    const size_t n = (size_t)H * W;
-    const int* L = labels + (size_t)plane * n;
-    const int x = strip * PR_IN - 2 + lane;
-    const int y0 = blockIdx.y * PR_ROWS;
-    const bool xin = x >= 0 && x < W;
-    const bool inner = xin && lane >= 2 && lane < 2 + PR_IN;
-    const unsigned ml = (unsigned)max_label;
-    u64* accp = acc + (size_t)plane * max_label * A_NACC;
-    int* bbp = bbox ? bbox + (size_t)plane * max_label * 4 : nullptr;
-
-    // UNCONDITIONAL loads from clamped coordinates; positions outside the image are zeroed where the value is
-    // used (a select next to the load would be turned back into a branch around it, and the wait that comes with
-    // it serialises the loads)
-    const int xc = x < 0 ? 0 : (x < W ? x : W - 1);
-    auto load_row = [&](int y) -> int {
-        const int yc = y < 0 ? 0 : (y < H ? y : H - 1);
-        return L[(size_t)yc * W + xc];
-    };
-    int cur[PR_BATCH], nxt[PR_BATCH];
-#pragma unroll
-    for (int j = 0; j < PR_BATCH; ++j) cur[j] = load_row(y0 - 2 + j);
-    // window: v1 / v2 = label rows r-1 / r-2 (+ their horizontal neighbours), wA / wB = flagged rows r-2 / r-3
-    int v1 = 0, v1l = 0, v1r = 0, v2 = 0, v2l = 0, v2r = 0;
-    int wA = 0, wAl = 0, wAr = 0, wB = 0, wBl = 0, wBr = 0;
-    for (int b = 0; b < PR_NBATCH; ++b) {
-        if (b + 1 < PR_NBATCH) {
-#pragma unroll
-            for (int j = 0; j < PR_BATCH; ++j) nxt[j] = load_row(y0 - 2 + (b + 1) * PR_BATCH + j);
-        }
-#pragma unroll
-        for (int j = 0; j < PR_BATCH; ++j) {
-            const int r = y0 - 2 + b * PR_BATCH + j;  // row of v0
-            int v0 = cur[j];
-            v0 = (xin && r >= 0 && r < H && (unsigned)(v0 - 1) < ml) ? v0 : 0;
-            if (__ballot((v0 | v1 | v2 | wB) != 0) == 0ull) continue;  // uniform: the window stays all zero
-            const int v0l = amt_lane_left(v0), v0r = amt_lane_right(v0);
-            // flagged row r-1
-            const bool b1 = v1 != 0 && (v2 != v1 || v0 != v1 || v1l != v1 || v1r != v1);
-            const int w1 = b1 ? (v1 | (int)0x80000000) : v1;
-            const int w1l = amt_lane_left(w1), w1r = amt_lane_right(w1);
-            // bounding box: runs of row r-1 (above v2, below v0)
-            const int yb = r - 1;
-            if (bbp && yb >= y0 && yb < y0 + PR_ROWS) {  // uniform
-                // the four requests as flat per-lane conditions behind ONE uniform test: interior rows of a blob ask for
-                // nothing (their runs have the label above, below and further out on either side), and every divergent
-                // block costs scalar issue slots whether a lane enters it or not
-                const bool live = inner && v1 != 0, head = live && v1l != v1;
-                const bool q0 = head && v2 != v1, q2 = head && v0 != v1, q1 = head && v2l != v1 && v0l != v1;
-                const bool q3 = live && v1r != v1 && v2r != v1 && v0r != v1;  // tail of a run
-                if (__ballot(q0 || q1 || q2 || q3)) {
-                    int* B = bbp + (size_t)(v1 - 1) * 4;
-                    if (q0) atomicMin(&B[0], yb);
-                    if (q2) atomicMax(&B[2], yb);
-                    if (q1) atomicMin(&B[1], x);
-                    if (q3) atomicMax(&B[3], x);
-                }
-            }
-            // perimeter code of row r-2 (centre wA, above wB, below w1)
-            const int yo = r - 2;
-            if (inner && wA < 0 && yo >= y0 && yo < y0 + PR_ROWS) {
-                const int key = wA;
-                const int code = 1 + 2 * ((wB == key) + (w1 == key) + (wAl == key) + (wAr == key)) +
-                                 10 * ((wBl == key) + (wBr == key) + (w1l == key) + (w1r == key));
-                // class of the code without a branch per case (the pass is bound by SCALAR issue: every divergent block
-                // costs an exec save, a branch and a restore): codes are <= 49, the three sets are bit masks
-                constexpr unsigned long long M1 = (1ull << 5) | (1ull << 7) | (1ull << 15) | (1ull << 17) | (1ull << 25) | (1ull << 27);
-                constexpr unsigned long long M2 = (1ull << 21) | (1ull << 33), M3 = (1ull << 13) | (1ull << 23);
-                const int cls = ((M1 >> code) & 1ull) ? A_C1 : ((M2 >> code) & 1ull) ? A_C2 : ((M3 >> code) & 1ull) ? A_C3 : -1;
-                if (cls >= 0) atomicAdd(&accp[(size_t)((key & 0x7fffffff) - 1) * A_NACC + cls], 1ull);
-            }
-            wB = wA, wBl = wAl, wBr = wAr;
-            wA = w1, wAl = w1l, wAr = w1r;
-            v2 = v1, v2l = v1l, v2r = v1r;
-            v1 = v0, v1l = v0l, v1r = v0r;
-        }
-#pragma unroll
-        for (int j = 0; j < PR_BATCH; ++j) cur[j] = nxt[j];
     }
 }
 
@@ -755,28 +867,19 @@ extern "C" int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16
     amt_buf<int2> chainL(s, (size_t)nplanes * 3 * cap);
     amt_buf<int2> chainR(s, (size_t)nplanes * 3 * cap);
     AMT_TRY(s.commit());
-    if (want_morph) {  // the perimeter pass stages every label tile anyway: it folds the bounding boxes too
-        hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
-        AMT_LAUNCH_CHECK();
-        const int nstrips = (W + PR_IN - 1) / PR_IN;
-        dim3 gper((nstrips + 3) / 4, (H + PR_ROWS - 1) / PR_ROWS, nplanes);
-        hipLaunchKernelGGL(rp_perimeter_rows_kernel, gper, dim3(256), 0, ctx->stream, labels, acc, H, W, max_label, bbox);
-        AMT_LAUNCH_CHECK();
-    } else {
-        AMT_TRY(amt_i_label_boxes(ctx, labels, bbox, acc, nplanes, H, W, max_label));
-    }
+    AMT_TRY(amt_i_label_boxes(ctx, labels, bbox, acc, nplanes, H, W, max_label));
     hipLaunchKernelGGL(rp_heights_kernel, dim3(amt_grid_for(max_label, 256, 256), nplanes), dim3(256), 0, ctx->stream,
                        bbox, hoff, max_label);
     AMT_LAUNCH_CHECK();
     AMT_TRY(amt_scan_excl(ctx, hoff, max_label, (size_t)max_label, htot, nplanes));
-    // per-label scan: moments + row extents on the first call, intensity channels in groups of RP_MAXC
+    // per-label scan: moments, row extents and perimeter on the first call, intensity channels in groups of RP_MAXC
     const int groups = intensity ? (C + RP_MAXC - 1) / RP_MAXC : 1;
     for (int g = 0; g < groups; ++g) {
         const int c0 = g * RP_MAXC;
         const int nc = intensity ? ((C - c0) < RP_MAXC ? (C - c0) : RP_MAXC) : 0;
         hipLaunchKernelGGL(rp_label_kernel, dim3(max_label, nplanes), dim3(64), 0, ctx->stream, labels, bbox, hoff, htot,
                            rows, cap, acc, intensity, C, c0, nc, intensity ? itable_dev : (double*)nullptr, H, W,
-                           max_label, (want_morph && g == 0) ? 1 : 0);
+                           max_label, (want_morph && g == 0) ? 3 : 0);
         AMT_LAUNCH_CHECK();
     }
     if (want_morph) {
