@@ -20,6 +20,10 @@ U8, U16, I32, F64, I64, F32 = 0, 1, 2, 3, 4, 5
 MODE_NEAREST, MODE_REFLECT, MODE_MIRROR, MODE_CONSTANT, MODE_WRAP = 0, 1, 2, 3, 4
 MODES = {"nearest": 0, "reflect": 1, "mirror": 2, "constant": 3, "wrap": 4}
 THR_OTSU = 0
+# amt_rank_filter: the reconstruction ops (AMT_RANK_*) and their tile interiors (AMT_RECONSTRUCT_TILE_*), (rows, columns)
+RANK_RECONSTRUCT_DILATION, RANK_RECONSTRUCT_EROSION, RANK_HMAX_RECONSTRUCT, RANK_HMIN_RECONSTRUCT = 3, 4, 5, 6
+RECONSTRUCT_TILE_U16 = (64, 128)
+RECONSTRUCT_TILE_F64 = (32, 64)
 WS_TIES = {"exact": 0, "raster": 1, "report": 2, "refuse": 2}
 RP_COLS = (
     "area", "centroid-0", "centroid-1", "bbox-0", "bbox-1", "bbox-2", "bbox-3", "perimeter",

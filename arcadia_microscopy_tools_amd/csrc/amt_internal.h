@@ -182,6 +182,12 @@ int amt_i_texture(amt_ctx* ctx, const int32_t* labels, const void* intensity, in
 int amt_i_radial(amt_ctx* ctx, const int32_t* labels, const void* intensity, int in_code, int C, int bins, double* geom,
                  double* out, int nplanes, int H, int W, int max_label);
 
+// ---- grey reconstruction (amt_reconstruct.hip): ops AMT_RANK_RECONSTRUCT_DILATION .. AMT_RANK_HMIN_RECONSTRUCT of
+// amt_rank_filter, which has checked the operands' aliasing; it checks everything else, refusing what needs no device
+// before it looks at the context, and returns once `out` holds the reconstruction (it waits for the device)
+int amt_i_reconstruct(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
+                      const uint8_t* footprint, int fh, int fw, int op, double cval, const void* minuend);
+
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>
 static inline void amt_with_bool(bool b, F&& f) {

@@ -921,10 +921,17 @@ static bool mm_plan(const uint8_t* footprint, int fh, int fw, mm_params* P) {
 static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
                             const uint8_t* footprint, int fh, int fw, int op, int mode, double cval,
                             const void* minuend, int* fused) {
+    if (op >= AMT_RANK_RECONSTRUCT_DILATION && op <= AMT_RANK_HMIN_RECONSTRUCT) {
+        // reconstructions (amt_reconstruct.hip): `minuend` is the mask of ops 3 / 4 and nothing to subtract; only the
+        // h-maxima reconstruction keeps the meaning out = minuend - result, subtracted in place by the caller
+        *fused = (op == AMT_RANK_HMAX_RECONSTRUCT && minuend) ? 0 : 1;
+        return amt_i_reconstruct(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, cval, minuend);
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && footprint && nplanes >= 0 && H > 0 && W > 0, "rank_filter: bad arguments");
     AMT_REQUIRE(dtype == AMT_U16 || dtype == AMT_F64, "rank_filter: dtype must be AMT_U16 or AMT_F64");
-    AMT_REQUIRE(op >= 0 && op <= 2, "rank_filter: op must be 0 (erosion), 1 (dilation) or 2 (median)");
+    AMT_REQUIRE(op >= 0 && op <= 2,
+                "rank_filter: op must be 0 (erosion), 1 (dilation), 2 (median) or a reconstruction (3 .. 6)");
     AMT_REQUIRE((fh & 1) && (fw & 1) && fh >= 1 && fw >= 1 && fh <= 63 && fw <= 63,
                 "rank_filter: footprint must be odd-sized and at most 63 x 63 (got %d x %d)", fh, fw);
     static thread_local int2 host[RK_MAX_OFFS];

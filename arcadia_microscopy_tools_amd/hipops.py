@@ -792,6 +792,156 @@ def median(a, footprint=None, mode: str = "nearest", cval: float = 0.0, out=None
     return _rank(a, fp, 2, mode, cval, out)
 
 
+# ---- grey reconstruction (amt_rank_filter ops 3 .. 6; include/amt_hip.h states the definitions) --------------------
+def reconstruct_tile(dtype) -> tuple[int, int]:
+    """(rows, columns) of the tile one workgroup of the reconstruction kernel owns (AMT_RECONSTRUCT_TILE_*): planes
+    larger than this cross tile seams and take several rounds."""
+    dt = np.dtype(dtype)
+    if dt == np.uint16:
+        return _hip.RECONSTRUCT_TILE_U16
+    if dt == np.float64:
+        return _hip.RECONSTRUCT_TILE_F64
+    raise TypeError(f"reconstruction runs on uint16 or float64 images, got {dt}")
+
+
+def _recon_footprint(footprint) -> np.ndarray:
+    """None (scikit-image's default, 3 x 3 all-ones), the 3 x 3 cross or 3 x 3 all-ones -> uint8 (3, 3)."""
+    if footprint is None:
+        return np.ones((3, 3), np.uint8)
+    fp = np.ascontiguousarray(np.asarray(footprint) != 0, dtype=np.uint8)
+    if fp.shape != (3, 3) or not (np.array_equal(fp, cross3()) or fp.all()):
+        raise ValueError("reconstruction: footprint must be None, the 3 x 3 cross (4-connected) or 3 x 3 all-ones "
+                         "(8-connected)")
+    return fp
+
+
+def _recon_method(method: str) -> bool:
+    if method not in ("dilation", "erosion"):
+        raise ValueError(f"Reconstruction method can be one of 'erosion' or 'dilation'. Got '{method}'.")
+    return method == "dilation"
+
+
+def _recon_image(op: str, a: DeviceArray, what: str = "image"):
+    if a.dtype not in (np.uint16, np.float64):
+        raise TypeError(f"{op}: the {what} must be uint16 or float64 on the device, got {a.dtype}")
+    if a.ndim not in (2, 3):
+        raise ValueError(f"{op} takes (H, W) or (N, H, W) images, got shape {a.shape}")
+
+
+def _recon_h(op: str, dtype, h) -> float:
+    """``h`` as the C ABI takes it: an integer in 1..65535 for uint16 images, finite and > 0 for float64."""
+    if isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{op}: h must be a number, got {h!r}")
+    hf = float(h)
+    if not np.isfinite(hf) or hf <= 0:
+        raise ValueError(f"{op}: h must be finite and > 0, got {h!r}")
+    if np.dtype(dtype) == np.uint16 and (hf != int(hf) or hf > 65535):
+        raise ValueError(f"{op}: h of an integer image must be an integer in 1..65535, got {h!r}")
+    return hf
+
+
+def _recon_call(op: str, a: DeviceArray, o: DeviceArray, fp: np.ndarray, code: int, h: float, second):
+    n, H, W = _planes(a)
+    if a.size == 0:
+        return o
+    _hip.check(_lib().amt_rank_filter(a.ctx.handle, a.ptr, o.ptr, _in_code(a), n, H, W, fp.ctypes.data_as(ctypes.c_void_p),
+                                      3, 3, code, _hip.MODE_CONSTANT, float(h), None if second is None else second.ptr),
+               "amt_rank_filter")
+    return o
+
+
+def reconstruction(seed: DeviceArray, mask: DeviceArray, method: str = "dilation", footprint=None,
+                   out: DeviceArray | None = None) -> DeviceArray:
+    """``skimage.morphology.reconstruction(seed, mask, method, footprint)`` per plane of (H, W) or (N, H, W) uint16 or
+    float64 images: by dilation the least image R >= seed with R = min(mask, max over the footprint of R), by erosion
+    the dual.  ``footprint``: None (3 x 3 all-ones, scikit-image's default), the cross or all-ones.  ``seed`` above
+    (below) ``mask`` anywhere raises ValueError.  The call waits for the device (amt_rank_filter,
+    AMT_RANK_RECONSTRUCT_DILATION / _EROSION)."""
+    dil = _recon_method(method)
+    fp = _recon_footprint(footprint)
+    _recon_image("reconstruction", seed, "seed")
+    _recon_image("reconstruction", mask, "mask")
+    if seed.dtype != mask.dtype or tuple(seed.shape) != tuple(mask.shape):
+        raise ValueError(f"reconstruction: seed ({seed.shape} {seed.dtype}) and mask ({mask.shape} {mask.dtype}) must have "
+                         "the same shape and dtype")
+    if mask.ctx is not seed.ctx:
+        raise ValueError("reconstruction: seed and mask belong to different contexts")
+    o = _out(seed.ctx, out, seed.shape, seed.dtype)
+    _no_alias("reconstruction", {"seed": seed, "mask": mask}, {"out": o})
+    return _recon_call("reconstruction", seed, o, fp,
+                       _hip.RANK_RECONSTRUCT_DILATION if dil else _hip.RANK_RECONSTRUCT_EROSION, 0.0, mask)
+
+
+def h_reconstruction(a: DeviceArray, h, method: str = "dilation", footprint=None, out: DeviceArray | None = None,
+                     minuend: DeviceArray | None = None) -> DeviceArray:
+    """The reconstruction behind h-maxima / h-minima, with ``a`` as the mask and a seed that is never in memory:
+    ``method="dilation"`` reconstructs ``max(a - h, 0)`` (uint16) / ``a - h`` (float64) under ``a``, ``"erosion"``
+    ``min(a + h, 65535)`` / ``a + h`` over ``a``.  ``minuend`` (dilation only) stores ``minuend - R`` instead:
+    ``minuend=a`` is the h-dome.  ``h``: an integer in 1..65535 for uint16, finite and > 0 for float64."""
+    dil = _recon_method(method)
+    fp = _recon_footprint(footprint)
+    _recon_image("h_reconstruction", a)
+    hf = _recon_h("h_reconstruction", a.dtype, h)
+    if minuend is not None:
+        if not dil:
+            raise ValueError("h_reconstruction: minuend goes with method='dilation' only")
+        if minuend.dtype != a.dtype or tuple(minuend.shape) != tuple(a.shape):
+            raise ValueError("h_reconstruction: minuend must have the image's shape and dtype")
+    o = _out(a.ctx, out, a.shape, a.dtype)
+    _no_alias("h_reconstruction", {"a": a, "minuend": minuend}, {"out": o})
+    return _recon_call("h_reconstruction", a, o, fp, _hip.RANK_HMAX_RECONSTRUCT if dil else _hip.RANK_HMIN_RECONSTRUCT,
+                       hf, minuend)
+
+
+def _h_extrema(op: str, a: DeviceArray, h, footprint, out, maxima: bool) -> DeviceArray:
+    fp = _recon_footprint(footprint)
+    _recon_image(op, a)
+    hf = _recon_h(op, a.dtype, h)
+    ctx = a.ctx
+    n, H, W = _planes(a)
+    o = _out(ctx, out, a.shape, np.uint8)
+    _no_alias(op, {"a": a}, {"out": o})
+    o.is_bool = True
+    if a.size == 0:
+        return o
+    lib = _lib()
+    code = _in_code(a)
+    if a.dtype == np.uint16:
+        # residue >= h  <=>  residue > h - 1 (integers)
+        if maxima:
+            res = h_reconstruction(a, hf, "dilation", fp, minuend=a)  # a - R
+        else:
+            res = h_reconstruction(a, hf, "erosion", fp)
+            _hip.check(lib.amt_subtract(ctx.handle, res.ptr, a.ptr, res.ptr, code, a.size), "amt_subtract")  # R - a
+        thr = ctx.asarray(np.full(n, hf - 1.0))
+    else:
+        # R == seed exactly  <=>  seed - R (maxima: <= 0) resp. R - seed (minima: <= 0) is zero  <=>  it is above the
+        # largest negative double
+        seed = add_scalar(a, -hf if maxima else hf)
+        r = reconstruction(seed, a, "dilation" if maxima else "erosion", fp)
+        first, second = (seed, r) if maxima else (r, seed)
+        _hip.check(lib.amt_subtract(ctx.handle, first.ptr, second.ptr, r.ptr, code, a.size), "amt_subtract")
+        res = r
+        thr = ctx.asarray(np.full(n, -np.nextafter(0.0, 1.0)))
+    _hip.check(lib.amt_threshold_gt(ctx.handle, res.ptr, code, thr.ptr, o.ptr, n, H * W), "amt_threshold_gt")
+    return o
+
+
+def h_maxima(a: DeviceArray, h, footprint=None, out: DeviceArray | None = None) -> DeviceArray:
+    """``skimage.morphology.h_maxima(a, h, footprint)`` per plane -> uint8 0 / 1 (``is_bool``): the maxima whose height
+    over their surroundings is at least ``h``.  uint16: a pixel is marked iff ``a - R >= h`` with R the reconstruction by
+    dilation of ``max(a - h, 0)`` under ``a`` (scikit-image's rule).  float64 (finite values): iff ``R == seed`` exactly,
+    with ``seed = a - h`` as rounded -- the same set in exact arithmetic, and no tolerance is involved.  The early exit
+    of scikit-image for ``h`` above the image's range is the caller's (``operations.h_maxima`` makes it)."""
+    return _h_extrema("h_maxima", a, h, footprint, out, True)
+
+
+def h_minima(a: DeviceArray, h, footprint=None, out: DeviceArray | None = None) -> DeviceArray:
+    """``skimage.morphology.h_minima``: the dual of ``h_maxima`` (reconstruction by erosion of ``min(a + h, 65535)`` /
+    ``a + h`` over ``a``; uint16 marks ``R - a >= h``, float64 ``R == seed``)."""
+    return _h_extrema("h_minima", a, h, footprint, out, False)
+
+
 # --------------------------------------------------------------------------------------------------
 # labelling
 # --------------------------------------------------------------------------------------------------

@@ -306,6 +306,112 @@ def remove_small_holes(mask, area_threshold: int = 64, connectivity: int = 1):
     return _area_filter_2d("remove_small_holes", mask, area_threshold, connectivity, "pass a bool array (mask != 0)")
 
 
+_RECON_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float64))
+
+
+def _recon_operand(op: str, x, what: str):
+    """-> (host array or None, DeviceArray or None, caller's dtype) of a 2-D uint8 / uint16 / float64 image"""
+    if isinstance(x, DeviceArray):
+        if x.ndim != 2:
+            raise ValueError(f"{what} must be a 2D array")
+        if x.dtype not in (np.uint16, np.float64):
+            raise TypeError(f"{op}: device arrays must be uint16 or float64, got {x.dtype}")
+        return None, x, x.dtype
+    a = np.asarray(x)
+    if a.ndim != 2:
+        raise ValueError(f"{what} must be a 2D array")
+    if a.dtype not in _RECON_DTYPES:
+        raise TypeError(f"{op}: {what} must be uint8, uint16 or float64, got {a.dtype}")
+    return a, None, a.dtype
+
+
+def _recon_upload(a: np.ndarray) -> DeviceArray:
+    return get_context().asarray(np.ascontiguousarray(a.astype(np.uint16) if a.dtype == np.uint8 else a))
+
+
+@device_operator
+def reconstruction(seed, mask, method: str = "dilation", footprint=None, offset=None):
+    """``skimage.morphology.reconstruction(seed, mask, method, footprint)`` on 2-D images: by dilation, ``seed`` spreads
+    under ``mask`` until nothing changes (the least R >= seed with R = min(mask, max over the footprint of R)); by
+    erosion the dual.  ``footprint``: None (3 x 3 all-ones, scikit-image's default), the 3 x 3 cross or all-ones;
+    ``offset`` other than None is refused.  uint8 (numpy only), uint16 and float64 images of one dtype; numpy in gives
+    numpy out in that dtype, a ``DeviceArray`` seed stays on the device (``mask`` may be either).  Stacks are refused:
+    map planes with ``Pipeline(parallel=True)`` or call ``hipops.reconstruction``.  NaN is not supported."""
+    dil = hipops._recon_method(method)
+    fp = hipops._recon_footprint(footprint)
+    if offset is not None:
+        raise ValueError("reconstruction: offset is not supported (the footprint is anchored at its centre)")
+    hs, ds, dts = _recon_operand("reconstruction", seed, "seed")
+    hm, dm, dtm = _recon_operand("reconstruction", mask, "mask")
+    if np.dtype(dts) != np.dtype(dtm):
+        raise TypeError(f"reconstruction: seed ({dts}) and mask ({dtm}) must have the same dtype")
+    shape_s = hs.shape if hs is not None else tuple(ds.shape)
+    shape_m = hm.shape if hm is not None else tuple(dm.shape)
+    if tuple(shape_s) != tuple(shape_m):
+        raise ValueError(f"reconstruction: seed {tuple(shape_s)} and mask {tuple(shape_m)} must have the same shape")
+    if hs is not None and hm is not None:
+        if hs.size == 0:
+            return np.zeros(hs.shape, dtype=hs.dtype)
+        if dil and np.any(hs > hm):
+            raise ValueError("Intensity of seed image must be less than that of the mask image for reconstruction by "
+                             "dilation.")
+        if not dil and np.any(hs < hm):
+            raise ValueError("Intensity of seed image must be greater than that of the mask image for reconstruction by "
+                             "erosion.")
+    elif hs is not None and hs.size == 0:
+        return np.zeros(hs.shape, dtype=hs.dtype)
+    if ds is None:
+        ds = _recon_upload(hs)
+    if dm is None:
+        dm = _recon_upload(hm).on(ds.ctx)
+    if ds.dtype != dm.dtype:
+        raise TypeError(f"reconstruction: seed ({ds.dtype}) and mask ({dm.dtype}) must have the same dtype on the device")
+    r = hipops.reconstruction(ds, dm, method, fp)
+    return r.numpy(dtype=hs.dtype) if hs is not None else r
+
+
+def _h_extrema_2d(op: str, image, h, footprint, maxima: bool):
+    fp = hipops._recon_footprint(footprint)
+    ha, da, dt = _recon_operand(op, image, "image")
+    if isinstance(h, (bool, np.bool_)) or not isinstance(h, (int, float, np.integer, np.floating)) or not np.isfinite(h):
+        raise ValueError(f"{op}: h must be a finite number, got {h!r}")
+    if h == 0:
+        raise ValueError("h = 0 is ambiguous, use local_maxima() or local_minima() instead")
+    if h < 0:
+        raise ValueError(f"{op}: h must be positive, got {h!r}")
+    if np.dtype(dt) != np.float64 and float(h) != int(h):
+        raise ValueError(f"{op}: h must be an integer for an integer image, got {h!r}")
+    if ha is not None:
+        if ha.size == 0:
+            return np.zeros(ha.shape, dtype=np.uint8)
+        lo, hi = ha.min(), ha.max()
+    else:
+        if da.size == 0:
+            return da.ctx.zeros(da.shape, np.uint8)
+        lo, hi = _min_max(da)
+    if float(h) > float(hi) - float(lo):  # scikit-image's early exit: no extremum can stand that high
+        return np.zeros(ha.shape, dtype=np.uint8) if ha is not None else da.ctx.zeros(da.shape, np.uint8)
+    d = da if da is not None else _recon_upload(ha)
+    m = (hipops.h_maxima if maxima else hipops.h_minima)(d, h, fp)
+    return m.numpy(dtype=np.uint8) if ha is not None else m
+
+
+@device_operator
+def h_maxima(image, h, footprint=None):
+    """``skimage.morphology.h_maxima(image, h, footprint)`` on a 2-D image: 1 where a maximum stands at least ``h`` above
+    its surroundings, as ``np.uint8`` (a ``DeviceArray`` stays on the device as a uint8 / bool mask).  ``footprint`` and
+    dtypes as for ``reconstruction``.  ``h`` must be positive, and an integer for an integer image (ValueError);
+    ``h`` above the image's range gives all zeros.  Integer images follow scikit-image's rule (residue >= h); float64
+    images mark the pixels where the reconstruction equals the seed ``image - h`` exactly (``hipops.h_maxima``)."""
+    return _h_extrema_2d("h_maxima", image, h, footprint, True)
+
+
+@device_operator
+def h_minima(image, h, footprint=None):
+    """``skimage.morphology.h_minima(image, h, footprint)``: the dual of ``h_maxima``."""
+    return _h_extrema_2d("h_minima", image, h, footprint, False)
+
+
 def _global_threshold(d: DeviceArray, method: str, kwargs: dict) -> float:
     """Threshold VALUE for the histogram-based methods: histogram on the device, selection on <= 65,536 counts."""
     nbins = int(kwargs.pop("nbins", 256))

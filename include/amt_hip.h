@@ -295,7 +295,47 @@ int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const d
  * op: 0 = erosion (min), 1 = dilation (max, footprint already mirrored by the caller), 2 = median
  * minuend (nullable, != out): out = minuend - rank_filter(in), the last step of ndi.white_tophat (R/ callers reach it
  * through skimage.morphology.white_tophat, SK/morphology/grey.py:425) without a separate subtraction pass; uint16 run
- * footprints subtract inside the filter kernel, everything else filters into `out` and subtracts in place. */
+ * footprints subtract inside the filter kernel, everything else filters into `out` and subtracts in place.
+ *
+ * op 3 .. 6: GREY RECONSTRUCTION (skimage.morphology.reconstruction, and the reconstructions behind
+ * skimage.morphology.h_maxima / h_minima), on the operands the filter already has.  Common to the four: dtype AMT_U16 or
+ * AMT_F64; the footprint is the 3 x 3 cross (4-connected) or 3 x 3 all-ones (8-connected), anything else is AMT_EINVAL;
+ * `mode` is ignored -- nothing propagates from outside the image (scikit-image pads with the neutral value);
+ * nplanes == 0 is AMT_OK and writes nothing; H * W < 2^31; `out` aliases neither input (AMT_EINVAL), `in` and `minuend`
+ * may be the same buffer; NaN is not supported; -0.0 and +0.0 compare equal, and which of the two is stored where they
+ * meet is unspecified.  The refusals that need no device (footprint, NULL mask, h, a minuend with op 6, dtype) come
+ * before the context is looked at.
+ * THESE OPS WAIT FOR THE DEVICE: the number of passes depends on the data, and the call returns once `out` is complete
+ * (every other operator of this header stays asynchronous).
+ *   AMT_RANK_RECONSTRUCT_DILATION  `in` = the seed, `minuend` = the MASK (required: NULL is AMT_EINVAL), cval ignored.
+ *                     out = R, the least image with R >= seed and R = min(mask, max over the footprint of R); equivalently
+ *                     R(p) = max over q of min(seed(q), w(p, q)) with w(p, q) the largest, over footprint-connected paths
+ *                     from p to q, of the smallest mask value on the path (ends included).  The fixed point is unique:
+ *                     the bytes of `out` depend on no schedule, two runs are identical.  Requires seed <= mask
+ *                     everywhere: the first pass counts the violations per plane, and a non-zero count is AMT_EINVAL
+ *                     with a message naming the first such plane (as scikit-image raises); `out` is then unspecified.
+ *   AMT_RANK_RECONSTRUCT_EROSION   the dual (min <-> max); requires seed >= mask.
+ *   AMT_RANK_HMAX_RECONSTRUCT      the mask is `in` itself and the seed is never in memory: AMT_U16 seed(p) =
+ *                     max(in(p) - h, 0) with h = cval an integer in 1..65535, AMT_F64 seed(p) = in(p) - h (one rounding)
+ *                     with h finite and > 0, else AMT_EINVAL before any launch.  out = R by dilation.  `minuend` keeps its
+ *                     meaning out = minuend - R: with minuend == in that is the h-dome.
+ *   AMT_RANK_HMIN_RECONSTRUCT      seed = min(in + h, 65535) (AMT_U16) or in + h (AMT_F64); out = R by erosion; a non-NULL
+ *                     minuend is AMT_EINVAL.
+ * The h-maxima / h-minima MASKS built on ops 5 / 6 (the Python layer's h_maxima / h_minima): uint16 -- a pixel is marked
+ * iff residue >= h, with residue = in - R for maxima and R - in for minima (scikit-image's rule; with h an integer it
+ * is residue > h - 1, which amt_threshold_gt evaluates); float64 -- a pixel is marked iff R(p) == seed(p) exactly, with
+ * seed = fl(in -+ h): the same set in exact arithmetic, and it needs no tolerance (scikit-image subtracts a resolution
+ * term that differs between versions).
+ * A workgroup owns one tile of AMT_RECONSTRUCT_TILE_H_* x AMT_RECONSTRUCT_TILE_W_* pixels per round (csrc/
+ * amt_reconstruct.hip); planes that cross tile seams need several rounds. */
+#define AMT_RANK_RECONSTRUCT_DILATION 3
+#define AMT_RANK_RECONSTRUCT_EROSION  4
+#define AMT_RANK_HMAX_RECONSTRUCT     5
+#define AMT_RANK_HMIN_RECONSTRUCT     6
+#define AMT_RECONSTRUCT_TILE_H_U16 64
+#define AMT_RECONSTRUCT_TILE_W_U16 128
+#define AMT_RECONSTRUCT_TILE_H_F64 32
+#define AMT_RECONSTRUCT_TILE_W_F64 64
 int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
                     const uint8_t* footprint, int fh, int fw, int op, int mode, double cval, const void* minuend);
 /* out = a - b (same dtype; white_tophat = image - opening); out may be a, b or both (in place) */
