@@ -24,7 +24,11 @@ THR_OTSU = 0
 RANK_RECONSTRUCT_DILATION, RANK_RECONSTRUCT_EROSION, RANK_HMAX_RECONSTRUCT, RANK_HMIN_RECONSTRUCT = 3, 4, 5, 6
 RECONSTRUCT_TILE_U16 = (64, 128)
 RECONSTRUCT_TILE_F64 = (32, 64)
-WS_TIES = {"exact": 0, "raster": 1, "report": 2, "refuse": 2}
+# amt_binary_morph: the skeleton ops (AMT_MORPH_*) and the thinning kernel's geometry (AMT_SKELETON_*): tile rows, tile
+# words of 64 pixels, sub-iterations per launch
+MORPH_SKELETONIZE, MORPH_NEIGHBOR_CLASSES = 7, 8
+SKELETON_TILE_ROWS, SKELETON_TILE_WORDS, SKELETON_BLOCK_SUBITERS = 64, 8, 32
+WS_TIES ={"exact": 0, "raster": 1, "report": 2, "refuse": 2}
 RP_COLS = (
     "area", "centroid-0", "centroid-1", "bbox-0", "bbox-1", "bbox-2", "bbox-3", "perimeter",
     "axis_major_length", "axis_minor_length", "eccentricity", "orientation", "area_convex", "solidity",

@@ -1,4 +1,5 @@
-// Binary morphology on uint8 0/1 masks: erode, dilate, and fused open / close.
+// Binary morphology on uint8 0/1 masks: erode, dilate, and fused open / close; thinning to centre lines (skeletonize) and
+// the neighbour classes of a skeleton's pixels further down.
 //
 // Semantics = skimage.morphology.binary_* (SK/morphology/binary.py:42,77,82-147), which call
 // scipy.ndimage.binary_erosion(structure, border_value=True) and binary_dilation(structure):
@@ -12,6 +13,9 @@
 // per 64 pixels -- and the result is unpacked to bytes.  The packed plane (H * ceil(W / 64) words; 512 KB
 // at 2048^2) lives in L2, so an opening or closing costs one HBM read and one HBM write of the byte mask.
 #include "amt_internal.h"
+
+#include <cstdlib>
+#include <vector>
 
 typedef unsigned long long u64;
 constexpr int MAX_OFFS = 1024;
@@ -226,17 +230,327 @@ static int build_offsets(const uint8_t* fp, int fh, int fw, int2* host, int* n) 
     return AMT_OK;
 }
 
+// ---- skeletonize (AMT_MORPH_SKELETONIZE) and neighbour classes (AMT_MORPH_NEIGHBOR_CLASSES) ----------------------------
+// Zhang and Suen's thinning, as include/amt_hip.h states it, on the packed plane.  A sub-iteration is a pure 3 x 3 boolean
+// function of the plane before it: the eight neighbour words of a word come from the rows above and below and from funnel
+// shifts with the adjacent words, B (set neighbours) from a bit-sliced adder, A (0 -> 1 transitions round the ring) from
+// "at least one" / "at least two" of the eight transitions, the two products from ANDs -- a few dozen word operations per
+// 64 pixels, no per-pixel branch.
+//
+// sk_block_kernel: a 256-thread workgroup owns a tile of SK_ROWS rows x SK_WORDS words.  It loads the tile with a halo of
+// SK_T rows above and below and one word left and right into LDS and runs up to SK_T sub-iterations LDS -> LDS (two
+// buffers).  After t sub-iterations only positions at least t pixels from the loaded edge are right, so sub-iteration t
+// computes rows [t + 1, rows - t - 1) only and the tile itself is exact after SK_T.  Positions outside the image and the
+// bits beyond W are loaded as 0, and a sub-iteration only clears bits, so they stay 0 without a fix-up per step; the
+// physical padding of the LDS tile (one row / word on every side) is zeroed once and never written.
+// Two packed planes in scratch are read and written in turns (a launch reads the halos its neighbours own, so it cannot
+// update in place); every tile therefore stores its interior, changed or not.  What a launch changed is recorded per
+// plane as a 64-bit mask: bit t is set when sub-iteration t cleared a pixel of some tile's interior.  The host finds the
+// first iteration (bit pair) that cleared nothing in it -- the plane's iteration count -- and a plane whose mask came out
+// 0 has both packed planes equal, so its tiles return at once in every later launch.
+constexpr int SK_ROWS = AMT_SKELETON_TILE_ROWS, SK_WORDS = AMT_SKELETON_TILE_WORDS, SK_T = AMT_SKELETON_BLOCK_SUBITERS;
+constexpr int SK_TR = SK_ROWS + 2 * SK_T;          // loaded rows
+constexpr int SK_PW = SK_WORDS + 4;                // physical words per LDS row: tile, two halo words, two padding words
+constexpr int SK_PHYS = (SK_TR + 2) * SK_PW;       // one LDS buffer
+constexpr int SK_BATCH = 3;                        // most launches between two looks at the masks
+static_assert(SK_T >= 2 && SK_T <= 64 && SK_T % 2 == 0, "the halo word holds 64 pixels, an iteration is two sub-iterations");
+static_assert(SK_TR * (SK_WORDS + 2) < 2048 && SK_WORDS + 2 <= 34, "the row / column split by multiplication");
+
+#define SK_L(c, p) (((c) << 1) | ((p) >> 63)) /* pixel x - 1 */
+#define SK_R(c, n) (((c) >> 1) | ((n) << 63)) /* pixel x + 1 */
+
+// the pixels of word c that sub-iteration `second` clears; u / d = the rows above / below, p / n = the words left / right
+__device__ __forceinline__ u64 sk_cleared(u64 up, u64 uc, u64 un, u64 cp, u64 c, u64 cn, u64 dp, u64 dc, u64 dn, bool second) {
+    const u64 p2 = uc, p3 = SK_R(uc, un), p4 = SK_R(c, cn), p5 = SK_R(dc, dn);
+    const u64 p6 = dc, p7 = SK_L(dc, dp), p8 = SK_L(c, cp), p9 = SK_L(uc, up);
+    // B = p2 + .. + p9 as four bit planes b0..b3
+    const u64 x1 = p2 ^ p3, s1 = x1 ^ p4, c1 = (p2 & p3) | (p4 & x1);
+    const u64 x2 = p5 ^ p6, s2 = x2 ^ p7, c2 = (p5 & p6) | (p7 & x2);
+    const u64 s3 = p8 ^ p9, c3 = p8 & p9;
+    const u64 x4 = s1 ^ s2, b0 = x4 ^ s3, c4 = (s1 & s2) | (s3 & x4);
+    const u64 x5 = c1 ^ c2, t = x5 ^ c3, d1 = (c1 & c2) | (c3 & x5);
+    const u64 b1 = t ^ c4, d2 = t & c4;
+    const u64 b2 = d1 ^ d2, b3 = d1 & d2;
+    const u64 b_ok = (b1 | b2) & ~b3 & ~(b0 & b1 & b2);  // 2 <= B <= 6
+    // A == 1: exactly one of the eight transitions ~P_i & P_{i+1}
+    u64 one = ~p2 & p3, two = 0ull, tr;
+    tr = ~p3 & p4, two |= one & tr, one |= tr;
+    tr = ~p4 & p5, two |= one & tr, one |= tr;
+    tr = ~p5 & p6, two |= one & tr, one |= tr;
+    tr = ~p6 & p7, two |= one & tr, one |= tr;
+    tr = ~p7 & p8, two |= one & tr, one |= tr;
+    tr = ~p8 & p9, two |= one & tr, one |= tr;
+    tr = ~p9 & p2, two |= one & tr, one |= tr;
+    const u64 prod = second ? ((p2 & p4 & p8) | (p2 & p6 & p8)) : ((p2 & p4 & p6) | (p4 & p6 & p8));
+    return c & b_ok & one & ~two & ~prod;
+}
+
+// prev / cur: this launch's and the one before's change masks, one word per plane
+__global__ void __launch_bounds__(256) sk_block_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int H, int W,
+                                                       int WW, int nsub, const u64* __restrict__ prev, u64* cur) {
+    __shared__ u64 lds[2 * SK_PHYS];
+    __shared__ u64 s_chg;
+    const int plane = blockIdx.z;
+    if (prev[plane] == 0ull) return;  // the launch before this one changed nothing in the plane: dst already equals src
+    const int tid = threadIdx.x;
+    const int wx0 = (int)blockIdx.x * SK_WORDS, y0 = (int)blockIdx.y * SK_ROWS;  // the tile's first word / row
+    const int tww = (WW - wx0) < SK_WORDS ? (WW - wx0) : SK_WORDS;
+    const int TW = tww + 2;
+    const int y_top = y0 - SK_T, wx_left = wx0 - 1;
+    const unsigned inv = ((1u << 20) + (unsigned)TW - 1u) / (unsigned)TW;  // idx / TW as a multiply
+    for (int i = tid; i < 2 * SK_PHYS; i += 256) lds[i] = 0ull;
+    if (tid == 0) s_chg = 0ull;
+    __syncthreads();
+    u64* a = lds + SK_PW + 1;  // logical (row 0, word 0)
+    u64* b = a + SK_PHYS;
+    const u64* rows = src + (size_t)plane * H * WW;
+    const u64 last_valid = (W & 63) ? (1ull << (W & 63)) - 1ull : ~0ull;
+    int any = 0;
+    for (int idx = tid; idx < SK_TR * TW; idx += 256) {
+        const int r = (int)(((unsigned)idx * inv) >> 20), wc = idx - r * TW;
+        const int y = y_top + r, wx = wx_left + wc;
+        u64 v = 0ull;
+        if (y >= 0 && y < H && wx >= 0 && wx < WW) {
+            v = rows[(size_t)y * WW + wx];
+            if (wx == WW - 1) v &= last_valid;
+        }
+        a[r * SK_PW + wc] = v;
+        any |= v != 0ull;
+    }
+    u64 chg = 0ull;
+    if (__syncthreads_or(any)) {
+        int clean = 0;
+        for (int t = 0; t < nsub; ++t) {
+            const int r_lo = t + 1, count = (SK_TR - 2 * (t + 1)) * TW;
+            int step = 0;
+            for (int idx = tid; idx < count; idx += 256) {
+                const int rr = (int)(((unsigned)idx * inv) >> 20);
+                const int r = r_lo + rr, wc = idx - rr * TW;
+                const u64* s = a + r * SK_PW + wc;
+                const u64 c = s[0];
+                u64 v = c;
+                if (c) {
+                    v = c & ~sk_cleared(s[-SK_PW - 1], s[-SK_PW], s[-SK_PW + 1], s[-1], c, s[1], s[SK_PW - 1], s[SK_PW],
+                                        s[SK_PW + 1], t & 1);
+                    if (v != c) {
+                        step = 1;
+                        if (r >= SK_T && r < SK_T + SK_ROWS && wc >= 1 && wc <= tww) chg |= 1ull << t;
+                    }
+                }
+                b[r * SK_PW + wc] = v;
+            }
+            u64* sw = a;
+            a = b;
+            b = sw;
+            // two sub-iterations in a row that cleared nothing: the next reads what the one before last read
+            clean = __syncthreads_or(step) ? 0 : clean + 1;
+            if (clean == 2) break;
+        }
+        if (chg) atomicOr(&s_chg, chg);
+        __syncthreads();
+    }
+    u64* o = dst + (size_t)plane * H * WW;
+    for (int idx = tid; idx < SK_ROWS * tww; idx += 256) {
+        const int r = idx / tww, wc = idx - r * tww;
+        const int y = y0 + r;
+        if (y < H) o[(size_t)y * WW + wx0 + wc] = a[(SK_T + r) * SK_PW + 1 + wc];
+    }
+    if (tid == 0 && s_chg) atomicOr(cur + plane, s_chg);
+}
+
+static int sk_run(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, int max_iter) {
+    const int WW = (W + 63) / 64;
+    const size_t words = (size_t)nplanes * H * WW;
+    const int ntx = (WW + SK_WORDS - 1) / SK_WORDS, nty = (H + SK_ROWS - 1) / SK_ROWS;
+    AMT_REQUIRE(nplanes <= 65535, "skeletonize: at most 65535 planes per call (got %d)", nplanes);
+    amt_scratch s(ctx);
+    amt_buf<u64> pa(s, words);
+    amt_buf<u64> pb(s, words);
+    amt_buf<u64> masks(s, (size_t)(SK_BATCH + 1) * nplanes);  // row 0: the launch before the batch; then one row per launch
+    AMT_TRY(s.commit());
+    const size_t nwords = (size_t)H * WW;
+    const unsigned gpack = (unsigned)((nwords + 4 * PACK_WORDS_PER_WAVE - 1) / (4 * PACK_WORDS_PER_WAVE));
+    hipLaunchKernelGGL(pack_kernel, dim3(gpack, nplanes), dim3(256), 0, ctx->stream, in, pa, H, W, WW);
+    AMT_LAUNCH_CHECK();
+    u64* const m = masks;
+    const size_t row = sizeof(u64) * (size_t)nplanes;
+    AMT_HIP_CHECK(hipMemsetAsync(m, 0xFF, row, ctx->stream));
+    u64 *src = pa, *dst = pb;
+    std::vector<u64> host((size_t)SK_BATCH * nplanes);
+    std::vector<long long> iters((size_t)nplanes, -1);
+    // a launch that is not clean clears at least one pixel
+    const unsigned long long limit = (unsigned long long)H * W + 2;
+    const long long budget = max_iter > 0 ? 2ll * max_iter : -1;  // sub-iterations; -1: to the fixed point
+    long long done_sub = 0;
+    unsigned long long launches = 0, syncs = 0;
+    int open = nplanes;
+    while (open > 0 && (budget < 0 || done_sub < budget)) {
+        AMT_HIP_CHECK(hipMemsetAsync(m + nplanes, 0, row * SK_BATCH, ctx->stream));
+        int n = 0, nsub[SK_BATCH];
+        long long sub = done_sub;
+        // 1, 2, then SK_BATCH launches between looks: most masks are done after one launch, deep ones after many
+        const int batch = syncs + 1 < (unsigned long long)SK_BATCH ? (int)syncs + 1 : SK_BATCH;
+        while (n < batch && (budget < 0 || sub < budget)) {
+            nsub[n] = budget < 0 || budget - sub >= SK_T ? SK_T : (int)(budget - sub);
+            hipLaunchKernelGGL(sk_block_kernel, dim3(ntx, nty, nplanes), dim3(256), 0, ctx->stream, src, dst, H, W, WW,
+                               nsub[n], m + (size_t)n * nplanes, m + (size_t)(n + 1) * nplanes);
+            AMT_LAUNCH_CHECK();
+            u64* sw = src;
+            src = dst;
+            dst = sw;
+            sub += nsub[n++];
+        }
+        AMT_HIP_CHECK(hipMemcpyAsync(host.data(), m + nplanes, row * n, hipMemcpyDeviceToHost, ctx->stream));
+        AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        ++syncs;
+        launches += n;
+        for (int k = 0; k < n; ++k) {
+            for (int p = 0; p < nplanes; ++p) {
+                if (iters[p] >= 0) continue;
+                const u64 bits = host[(size_t)k * nplanes + p];
+                for (int i = 0; i < nsub[k] / 2; ++i)
+                    if (((bits >> (2 * i)) & 3ull) == 0ull) {
+                        iters[p] = done_sub / 2 + i + 1;
+                        --open;
+                        break;
+                    }
+            }
+            done_sub += nsub[k];
+        }
+        if (launches > limit) {
+            amt_set_error("binary morphology: skeletonize did not converge in %llu launches", launches);
+            return AMT_EHIP;
+        }
+        if (open > 0 && (budget < 0 || done_sub < budget))
+            AMT_HIP_CHECK(hipMemcpyAsync(m, m + (size_t)n * nplanes, row, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    const size_t nq = (size_t)H * ((W + 15) / 16);
+    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((nq + 255) / 256), nplanes), dim3(256), 0, ctx->stream, src, out, H, W,
+                       WW);
+    AMT_LAUNCH_CHECK();
+    AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    ++syncs;
+    // AMT_DEBUG_SKELETONIZE=1 (tools/time_skeletonize.py): how long the data made the call -- the iterations of the plane
+    // that needed most (the one that cleared nothing included; max_iter where that came first), launches and host waits
+    const char* report = getenv("AMT_DEBUG_SKELETONIZE");  // read per call: the op waits for the device anyway
+    if (report && report[0] == '1') {
+        long long most = 0;
+        for (int p = 0; p < nplanes; ++p) {
+            const long long it = iters[p] >= 0 ? iters[p] : (long long)max_iter;
+            most = it > most ? it : most;
+        }
+        fprintf(stderr, "amt skeletonize: iterations=%lld launches=%llu syncs=%llu\n", most, launches, syncs);
+    }
+    return AMT_OK;
+}
+
+// out = 0 where the pixel is clear, else 1 + its set neighbours (eight with `full`, the four edge neighbours otherwise).
+// One thread per 16 pixels of a row, as unpack_kernel: the three rows' bits x - 1 .. x + 16 as 18-bit windows, the count
+// as bit planes over the 16 pixels, spread to bytes.
+__device__ __forceinline__ unsigned nc_window(const u64* __restrict__ rows, int y, int wx, int xs, int H, int WW, int W) {
+    const u64 c = row_word(rows, y, wx, H, WW, W, 0ull);
+    u64 v = xs ? c >> (xs - 1) : (c << 1) | (row_word(rows, y, wx - 1, H, WW, W, 0ull) >> 63);
+    if (xs == 48) v = (v & 0x1FFFFull) | ((row_word(rows, y, wx + 1, H, WW, W, 0ull) & 1ull) << 17);
+    return (unsigned)v & 0x3FFFFu;
+}
+
+__global__ void __launch_bounds__(256) neighbor_classes_kernel(const u64* __restrict__ packed, uint8_t* __restrict__ out,
+                                                               int H, int W, int WW, int full) {
+    const size_t plane = blockIdx.y;
+    const int per_row = (W + 15) / 16;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (size_t)H * per_row) return;
+    const int y = (int)(q / per_row);
+    const int x = (int)(q - (size_t)y * per_row) * 16;
+    const u64* rows = packed + plane * (size_t)H * WW;
+    const unsigned wu = nc_window(rows, y - 1, x >> 6, x & 63, H, WW, W);
+    const unsigned wc = nc_window(rows, y, x >> 6, x & 63, H, WW, W);
+    const unsigned wd = nc_window(rows, y + 1, x >> 6, x & 63, H, WW, W);
+    const unsigned corner = full ? 0xFFFFu : 0u;
+    const unsigned p2 = (wu >> 1) & 0xFFFFu, p3 = (wu >> 2) & corner, p4 = (wc >> 2) & 0xFFFFu, p5 = (wd >> 2) & corner;
+    const unsigned p6 = (wd >> 1) & 0xFFFFu, p7 = wd & corner, p8 = wc & 0xFFFFu, p9 = wu & corner;
+    const unsigned centre = (wc >> 1) & 0xFFFFu;
+    const unsigned x1 = p2 ^ p3, s1 = x1 ^ p4, c1 = (p2 & p3) | (p4 & x1);
+    const unsigned x2 = p5 ^ p6, s2 = x2 ^ p7, c2 = (p5 & p6) | (p7 & x2);
+    const unsigned s3 = p8 ^ p9, c3 = p8 & p9;
+    const unsigned x4 = s1 ^ s2, b0 = x4 ^ s3, c4 = (s1 & s2) | (s3 & x4);
+    const unsigned x5 = c1 ^ c2, t = x5 ^ c3, d1 = (c1 & c2) | (c3 & x5);
+    const unsigned b1 = t ^ c4, d2 = t & c4;
+    const unsigned b2 = d1 ^ d2, b3 = d1 & d2;
+    unsigned r[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int sh = 4 * k;
+        const unsigned on = spread4((centre >> sh) & 0xFu);  // 0 / 1 per byte
+        const unsigned n = spread4((b0 >> sh) & 0xFu) | (spread4((b1 >> sh) & 0xFu) << 1) |
+                           (spread4((b2 >> sh) & 0xFu) << 2) | (spread4((b3 >> sh) & 0xFu) << 3);
+        r[k] = (n + on) & (on * 0xFFu);  // bytes of at most 9: no carry between them
+    }
+    uint8_t* o = out + (plane * H + y) * W + x;
+    if ((W & 15) == 0) {
+        *reinterpret_cast<uint4*>(o) = make_uint4(r[0], r[1], r[2], r[3]);
+    } else {
+        for (int k = 0; k < 16 && x + k < W; ++k) o[k] = (uint8_t)((r[k >> 2] >> (8 * (k & 3))) & 0xFFu);
+    }
+}
+
+// pack, count: asynchronous
+static int nc_run(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, int full) {
+    AMT_REQUIRE(nplanes <= 65535, "neighbor_classes: at most 65535 planes per call (got %d)", nplanes);
+    const int WW = (W + 63) / 64;
+    amt_scratch s(ctx);
+    amt_buf<u64> pa(s, (size_t)nplanes * H * WW);
+    AMT_TRY(s.commit());
+    const size_t nwords = (size_t)H * WW;
+    const unsigned gpack = (unsigned)((nwords + 4 * PACK_WORDS_PER_WAVE - 1) / (4 * PACK_WORDS_PER_WAVE));
+    hipLaunchKernelGGL(pack_kernel, dim3(gpack, nplanes), dim3(256), 0, ctx->stream, in, pa, H, W, WW);
+    AMT_LAUNCH_CHECK();
+    const size_t nq = (size_t)H * ((W + 15) / 16);
+    hipLaunchKernelGGL(neighbor_classes_kernel, dim3((unsigned)((nq + 255) / 256), nplanes), dim3(256), 0, ctx->stream,
+                       (const u64*)pa, out, H, W, WW, full);
+    AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+// 0: neither, 1: the 3 x 3 cross, 2: 3 x 3 all-ones
+static int structure3(const uint8_t* footprint, int fh, int fw) {
+    if (!footprint || fh != 3 || fw != 3) return 0;
+    bool cross = true, ones = true;
+    for (int i = 0; i < 9; ++i) {
+        const bool on = footprint[i] != 0, arm = (i & 1) || i == 4;
+        if (on != arm) cross = false;
+        if (!on) ones = false;
+    }
+    return ones ? 2 : cross ? 1 : 0;
+}
+
 // op: AMT_MORPH_ERODE, AMT_MORPH_DILATE, AMT_MORPH_OPEN (erode then dilate), AMT_MORPH_CLOSE (dilate then erode),
 // AMT_MORPH_FILL_HOLES, AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES (amt_label.hip: amt_i_component_filter, the area
-// filters' size in border_value)
+// filters' size in border_value), AMT_MORPH_SKELETONIZE (max_iter in border_value), AMT_MORPH_NEIGHBOR_CLASSES
 extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
                                 const uint8_t* footprint, int fh, int fw, int op, int border_value) {
     // every op: a component filter's write-out of one plane would land in input still to be read, and erosion / dilation /
     // opening / closing are right in place only because the packed words happen to sit in scratch in between
     AMT_CHECK_OPERANDS("amt_binary_morph", amt_in("in", in, amt_span(1, nplanes, H, W)), amt_out("out", out, amt_span(1, nplanes, H, W)));
+    // the refusals that need no device
+    AMT_REQUIRE(op >= AMT_MORPH_ERODE && op <= AMT_MORPH_NEIGHBOR_CLASSES, "binary morphology: op must be 0..8, got %d", op);
+    if (op == AMT_MORPH_SKELETONIZE) {
+        AMT_REQUIRE(structure3(footprint, fh, fw) == 2,
+                    "skeletonize: the footprint must be 3 x 3 all-ones, the eight-neighbourhood the rule reads");
+        AMT_REQUIRE(border_value >= 0, "skeletonize: max_iter (border_value) must be 0 (no limit) or positive, got %d",
+                    border_value);
+    }
+    if (op == AMT_MORPH_NEIGHBOR_CLASSES)
+        AMT_REQUIRE(structure3(footprint, fh, fw) != 0,
+                    "neighbor_classes: the footprint must be the 3 x 3 cross (four neighbours) or 3 x 3 all-ones (eight)");
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "binary morphology: bad arguments");
-    AMT_REQUIRE(op >= AMT_MORPH_ERODE && op <= AMT_MORPH_REMOVE_SMALL_HOLES, "binary morphology: op must be 0..6, got %d", op);
+    if (op >= AMT_MORPH_SKELETONIZE) {
+        AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "%s: plane too large", op == AMT_MORPH_SKELETONIZE ? "skeletonize" : "neighbor_classes");
+        if (nplanes == 0) return AMT_OK;
+        if (op == AMT_MORPH_SKELETONIZE) return sk_run(ctx, in, out, nplanes, H, W, border_value);
+        return nc_run(ctx, in, out, nplanes, H, W, structure3(footprint, fh, fw) == 2 ? 1 : 0);
+    }
     if (op >= AMT_MORPH_FILL_HOLES) {
         const bool fill = op == AMT_MORPH_FILL_HOLES;
         const char* name = fill ? "fill_holes" : op == AMT_MORPH_REMOVE_SMALL_OBJECTS ? "remove_small_objects" : "remove_small_holes";

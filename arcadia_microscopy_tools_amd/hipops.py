@@ -568,7 +568,8 @@ def _fp(footprint, even: str = "scipy"):
 
 
 _MORPH_OPS = {"erode": 0, "dilate": 1, "open": 2, "close": 3, "fill_holes": 4, "remove_small_objects": 5,
-              "remove_small_holes": 6}  # AMT_MORPH_*
+              "remove_small_holes": 6, "skeletonize": _hip.MORPH_SKELETONIZE,
+              "neighbor_classes": _hip.MORPH_NEIGHBOR_CLASSES}  # AMT_MORPH_*
 
 
 def _binary(which: str, a: DeviceArray, footprint, out, border_value=None):
@@ -689,6 +690,61 @@ def remove_small_holes(a: DeviceArray, area_threshold: int = 64, connectivity: i
     filled when its background component has fewer than ``area_threshold`` pixels, whether or not the component touches
     the frame (amt_binary_morph, AMT_MORPH_REMOVE_SMALL_HOLES)."""
     return _area_filter("remove_small_holes", a, area_threshold, connectivity, out)
+
+
+def skeleton_block() -> tuple[int, int, int]:
+    """(tile rows, tile words of 64 pixels, sub-iterations per launch) of the thinning kernel (AMT_SKELETON_*): planes
+    larger than a tile cross tile seams, and shapes thicker than twice the depth take several launches."""
+    return _hip.SKELETON_TILE_ROWS, _hip.SKELETON_TILE_WORDS, _hip.SKELETON_BLOCK_SUBITERS
+
+
+def _skeleton_op(which: str, a: DeviceArray, st: np.ndarray, value: int, out) -> DeviceArray:
+    """Ops 7 / 8 of amt_binary_morph once the scalar arguments are checked: every other refusal, then the call."""
+    if a.dtype != np.uint8:
+        raise TypeError(f"{which} expects a uint8 / bool mask on the device")
+    if a.ndim not in (2, 3):
+        raise ValueError(f"{which} takes (H, W) or (N, H, W) masks, got shape {a.shape}")
+    ctx = a.ctx
+    n, H, W = _planes(a)
+    if out is a:
+        raise ValueError(f"{which}: out must not alias the input")
+    o = _out(ctx, out, a.shape, np.uint8)  # allocates only when no `out` was given, and then nothing is left to refuse
+    _no_alias(which, {"a": a}, {"out": o})
+    o.is_bool = which == "skeletonize"
+    if a.size == 0:
+        return o
+    _hip.check(_lib().amt_binary_morph(ctx.handle, a.ptr, o.ptr, n, H, W, st.ctypes.data_as(ctypes.c_void_p), 3, 3,
+                                       _MORPH_OPS[which], value), "amt_binary_morph")
+    return o
+
+
+def skeletonize(a: DeviceArray, max_iter: int = 0, out: DeviceArray | None = None) -> DeviceArray:
+    """Thinning of every plane of a (H, W) or (N, H, W) uint8 / bool mask to its centre lines by Zhang and Suen's 1984
+    rule, the one ``skimage.morphology.skeletonize`` cites for 2-D input (amt_binary_morph, AMT_MORPH_SKELETONIZE;
+    include/amt_hip.h states the rule in full).  Foreground is ``a != 0``, outside the image is background, the result
+    holds 0 / 1.  ``max_iter``: at most that many iterations (two sub-iterations each) per plane, 0 = until an iteration
+    clears nothing.  The fixed point is unique, so two runs give identical bytes.  scikit-image applies the rule through
+    a 256-entry table; parity with that table is unpinned offline.  The call waits for the device."""
+    if isinstance(max_iter, (bool, np.bool_)):
+        raise TypeError("skeletonize: max_iter must be an integer, got a bool")
+    try:
+        k = int(operator.index(max_iter))
+    except TypeError:
+        raise TypeError(f"skeletonize: max_iter must be an integer, got {type(max_iter).__name__}") from None
+    if k < 0 or k > 2**31 - 1:
+        raise ValueError(f"skeletonize: max_iter must be 0 (no limit) or a positive int32, got {k}")
+    return _skeleton_op("skeletonize", a, np.ones((3, 3), np.uint8), k, out)
+
+
+def neighbor_classes(a: DeviceArray, connectivity: int = 2, out: DeviceArray | None = None) -> DeviceArray:
+    """Per pixel of a (H, W) or (N, H, W) uint8 / bool mask: 0 where ``a == 0``, else 1 + the number of set neighbours
+    (``connectivity`` 2: the eight neighbours, values 1..9; 1: the four edge neighbours, values 1..5); outside the image
+    is background (amt_binary_morph, AMT_MORPH_NEIGHBOR_CLASSES).  On a skeleton with connectivity 2: 1 an isolated
+    pixel, 2 an end, 3 a path pixel, 4 and more a junction."""
+    if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (1, 2):
+        raise ValueError(f"neighbor_classes: connectivity must be 1 (four neighbours) or 2 (eight), got {connectivity!r}")
+    st = cross3() if connectivity == 1 else np.ones((3, 3), np.uint8)
+    return _skeleton_op("neighbor_classes", a, st, 0, out)
 
 
 def threshold_otsu_bins(a: DeviceArray, minmax: DeviceArray, thr: DeviceArray, thr_code: DeviceArray,

@@ -306,6 +306,61 @@ def remove_small_holes(mask, area_threshold: int = 64, connectivity: int = 1):
     return _area_filter_2d("remove_small_holes", mask, area_threshold, connectivity, "pass a bool array (mask != 0)")
 
 
+def _skeleton_2d(which: str, mask, call, result_dtype):
+    """The 2-D front of ``skeletonize`` / ``skeleton_nodes``, with ``_area_filter_2d``'s rules for its input: a numpy bool
+    array in, a numpy array of ``result_dtype`` out; a ``DeviceArray`` stays on the device."""
+    if isinstance(mask, DeviceArray):
+        if mask.ndim != 2:
+            raise ValueError("mask must be a 2D array")
+        if mask.dtype != np.uint8:
+            raise TypeError(f"{which}: device masks must be uint8 / bool, got {mask.dtype}")
+        return call(mask)
+    a = np.asarray(mask)
+    if a.ndim != 2:
+        raise ValueError("mask must be a 2D array")
+    if a.dtype != np.bool_:
+        if np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"{which}: an integer array may be a label image, whose cells this operator would thin as one "
+                            "mask; pass a bool array (mask != 0)")
+        raise TypeError(f"{which}: mask must have a bool dtype, got {a.dtype}")
+    if a.size == 0:
+        return np.zeros(a.shape, dtype=result_dtype)
+    return call(get_context().asarray(np.ascontiguousarray(a))).numpy(dtype=result_dtype)
+
+
+@device_operator
+def skeletonize(mask, max_iter: int | None = None):
+    """Thinning of a 2-D bool mask to its centre lines by Zhang and Suen's rule, the one
+    ``skimage.morphology.skeletonize`` cites for 2-D input (parity with scikit-image's 256-entry table is unpinned
+    offline; ``hipops.skeletonize`` and include/amt_hip.h state the rule).  ``max_iter``: None runs to the fixed point, a
+    positive integer stops after that many iterations.  A numpy bool array gives a numpy bool array; a ``DeviceArray``
+    (a uint8 / bool mask, e.g. ``apply_threshold``'s result in a ``Pipeline``) stays on the device.  Integer numpy arrays
+    and stacks are refused: map planes with ``Pipeline(parallel=True)`` or call ``hipops.skeletonize``."""
+    if max_iter is None:
+        k = 0
+    else:
+        if isinstance(max_iter, (bool, np.bool_)):
+            raise TypeError("skeletonize: max_iter must be None or a positive integer, got a bool")
+        try:
+            k = int(max_iter.__index__())
+        except AttributeError:
+            raise TypeError(f"skeletonize: max_iter must be None or a positive integer, got {type(max_iter).__name__}") from None
+        if k < 1:
+            raise ValueError(f"skeletonize: max_iter must be None or a positive integer, got {k}")
+    return _skeleton_2d("skeletonize", mask, lambda d: hipops.skeletonize(d, k), bool)
+
+
+@device_operator
+def skeleton_nodes(mask, connectivity: int = 2):
+    """The neighbour class of every pixel of a 2-D bool mask, usually a skeleton: 0 off the mask, else 1 + the number of
+    set neighbours (``connectivity`` 2: eight neighbours -- 1 an isolated pixel, 2 an end, 3 a path pixel, 4 and more a
+    junction; 1: the four edge neighbours).  A numpy bool array gives a numpy uint8 array; a ``DeviceArray`` stays on the
+    device.  Input rules as for ``skeletonize``."""
+    if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (1, 2):
+        raise ValueError(f"skeleton_nodes: connectivity must be 1 (four neighbours) or 2 (eight), got {connectivity!r}")
+    return _skeleton_2d("skeleton_nodes", mask, lambda d: hipops.neighbor_classes(d, connectivity), np.uint8)
+
+
 _RECON_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float64))
 
 

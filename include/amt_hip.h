@@ -269,7 +269,40 @@ int amt_threshold_gt_image(amt_ctx* ctx, const void* in, int in_dtype, const dou
  *                     (connectivity=2); any other footprint is AMT_EINVAL.  out must not alias in, nor overlap it in
  *                     part (AMT_EINVAL); nplanes == 0 is AMT_OK; H * W < 2^31 - 1.  Sizes are exact pixel counts
  *                     (integer sums), so two runs give identical bytes.
- * Any other op (below 0, above 6) is AMT_EINVAL. */
+ *   AMT_MORPH_SKELETONIZE  thinning to centre lines per plane, by Zhang and Suen's 1984 rule (the one
+ *                     skimage.morphology.skeletonize cites for 2-D input).  `in` is a truth value per pixel (byte != 0),
+ *                     positions outside the image are 0, `out` holds 0 / 1 bytes.  The neighbours of p = (y, x):
+ *                       P2 = (y-1, x)    P3 = (y-1, x+1)  P4 = (y, x+1)    P5 = (y+1, x+1)
+ *                       P6 = (y+1, x)    P7 = (y+1, x-1)  P8 = (y, x-1)    P9 = (y-1, x-1)
+ *                     B(p) is the number of set neighbours; A(p) is the number of i for which P_i = 0 and P_{i+1} = 1 in
+ *                     the cyclic order P2, P3, ..., P9, P2.
+ *                     First sub-iteration: every set p with 2 <= B <= 6, A = 1, P2 * P4 * P6 = 0 and P4 * P6 * P8 = 0 is
+ *                     cleared; all such p are cleared together, judged on the plane as it was before the sub-iteration.
+ *                     Second sub-iteration: the same with P2 * P4 * P8 = 0 and P2 * P6 * P8 = 0.
+ *                     One iteration is the first sub-iteration followed by the second.  The result is the plane after
+ *                     the first iteration that clears nothing, or after max_iter iterations if that comes first;
+ *                     max_iter travels in border_value, 0 means no limit, a negative value is AMT_EINVAL.  Each plane of
+ *                     a batch has its own count, and a plane that has reached its fixed point stays as it is whatever
+ *                     the others need.  The fixed point of the rule is unique for a given input, so the bytes depend on
+ *                     no schedule and two runs are identical.  scikit-image applies the rule through a literal 256-entry
+ *                     table; parity with that table is unpinned offline (no scikit-image was at hand to compare with):
+ *                     the tests pin the rule as stated here, nothing more.
+ *                     The footprint names the eight-neighbourhood the rule reads: it must be 3 x 3 all-ones, every
+ *                     other footprint (the 3 x 3 cross included) is AMT_EINVAL.  out must not alias in, nor overlap it
+ *                     in part (AMT_EINVAL); nplanes == 0 is AMT_OK; H * W < 2^31 - 1.
+ *                     THIS OP WAITS FOR THE DEVICE (it waits for the device as the reconstruction ops of amt_rank_filter
+ *                     do): the number of launches depends on the data, and the call returns once `out` is complete.
+ *                     A workgroup owns a tile of AMT_SKELETON_TILE_ROWS rows x AMT_SKELETON_TILE_WORDS 64-pixel words
+ *                     and runs up to AMT_SKELETON_BLOCK_SUBITERS sub-iterations per launch (csrc/amt_morph.hip).
+ *                     AMT_DEBUG_SKELETONIZE=1 in the environment prints iterations, launches and syncs to stderr.
+ *   AMT_MORPH_NEIGHBOR_CLASSES  one pass: out[p] = 0 where in[p] == 0, else 1 + the number of set neighbours under the
+ *                     footprint's non-centre cells.  3 x 3 all-ones gives 1..9 (on a skeleton: 1 isolated, 2 an end,
+ *                     3 a path pixel, >= 4 a junction), the 3 x 3 cross gives 1..5; any other footprint is AMT_EINVAL.
+ *                     Positions outside the image are 0; border_value is ignored; asynchronous like ops 0..3; out must
+ *                     not alias in; nplanes == 0 is AMT_OK; H * W < 2^31 - 1.
+ * For ops 7 and 8 the refusals that need no device (footprint, max_iter) come before the context is looked at, as the op
+ * range does for every op.
+ * Any other op (below 0, above 8) is AMT_EINVAL. */
 #define AMT_MORPH_ERODE 0
 #define AMT_MORPH_DILATE 1
 #define AMT_MORPH_OPEN 2
@@ -277,6 +310,11 @@ int amt_threshold_gt_image(amt_ctx* ctx, const void* in, int in_dtype, const dou
 #define AMT_MORPH_FILL_HOLES 4
 #define AMT_MORPH_REMOVE_SMALL_OBJECTS 5
 #define AMT_MORPH_REMOVE_SMALL_HOLES 6
+#define AMT_MORPH_SKELETONIZE 7
+#define AMT_MORPH_NEIGHBOR_CLASSES 8
+#define AMT_SKELETON_TILE_ROWS 64
+#define AMT_SKELETON_TILE_WORDS 8
+#define AMT_SKELETON_BLOCK_SUBITERS 32
 int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W,
                      const uint8_t* footprint, int fh, int fw, int op, int border_value);
 /* Otsu threshold of a float64 image (as amt_threshold_value) that also leaves the byte plane of its 256-bin indices
