@@ -28,6 +28,12 @@ RECONSTRUCT_TILE_F64 = (32, 64)
 # words of 64 pixels, sub-iterations per launch
 MORPH_SKELETONIZE, MORPH_NEIGHBOR_CLASSES = 7, 8
 SKELETON_TILE_ROWS, SKELETON_TILE_WORDS, SKELETON_BLOCK_SUBITERS = 64, 8, 32
+# amt_rank_filter: the per-cell skeleton ops (AMT_RANK_LABEL_*), the label thinning's geometry (AMT_LABEL_SKELETON_*, as
+# above) and the columns of a census row (AMT_LCEN_*)
+RANK_LABEL_SKELETON, RANK_LABEL_CENSUS = 8, 9
+LABEL_SKELETON_TILE_ROWS, LABEL_SKELETON_TILE_WORDS, LABEL_SKELETON_BLOCK_SUBITERS = 64, 8, 32
+LCEN_COLS = ("pixels", "isolated", "ends", "path", "junctions", "orth_links", "diag_links")
+LCEN_NCOLS = len(LCEN_COLS)
 WS_TIES ={"exact": 0, "raster": 1, "report": 2, "refuse": 2}
 RP_COLS = (
     "area", "centroid-0", "centroid-1", "bbox-0", "bbox-1", "bbox-2", "bbox-3", "perimeter",

@@ -188,6 +188,17 @@ int amt_i_radial(amt_ctx* ctx, const int32_t* labels, const void* intensity, int
 int amt_i_reconstruct(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
                       const uint8_t* footprint, int fh, int fw, int op, double cval, const void* minuend);
 
+// ---- per-cell skeletons: ops AMT_RANK_LABEL_SKELETON (amt_morph.hip, beside the binary thinning it shares its kernel
+// with) and AMT_RANK_LABEL_CENSUS (amt_skelcensus.hip) of amt_rank_filter, which has checked the operands' aliasing; they
+// check everything else, the refusals that need no device (amt_i_label_op_refusals: dtype, footprint, a negative `mode`,
+// a minuend, the plane size) before they look at the context.  The skeleton waits for the device, the census does not.
+int amt_i_label_op_refusals(const char* what, const char* mode_name, const void* in, void* out, int dtype, int nplanes,
+                            int H, int W, const uint8_t* footprint, int fh, int fw, int mode, const void* minuend);
+int amt_i_label_skeleton(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
+                         const uint8_t* footprint, int fh, int fw, int max_iter, const void* minuend);
+int amt_i_label_census(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
+                       const uint8_t* footprint, int fh, int fw, int max_label, const void* minuend);
+
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>
 static inline void amt_with_bool(bool b, F&& f) {

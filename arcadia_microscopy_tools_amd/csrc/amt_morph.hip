@@ -255,14 +255,51 @@ constexpr int SK_PHYS = (SK_TR + 2) * SK_PW;       // one LDS buffer
 constexpr int SK_BATCH = 3;                        // most launches between two looks at the masks
 static_assert(SK_T >= 2 && SK_T <= 64 && SK_T % 2 == 0, "the halo word holds 64 pixels, an iteration is two sub-iterations");
 static_assert(SK_TR * (SK_WORDS + 2) < 2048 && SK_WORDS + 2 <= 34, "the row / column split by multiplication");
+// The label variant (AMT_RANK_LABEL_SKELETON of amt_rank_filter) runs the same kernel on the mask labels != 0 with four
+// constant LINK planes beside it, one bit per pixel: E / S / SE / SW(p) = "p carries a label and the pixel at (0, 1) /
+// (1, 0) / (1, 1) / (1, -1) from p carries the same one".  A neighbour counts as set when its mask bit is set AND the link
+// between the two pixels is: towards E, S, SE, SW that is the centre's own link word, towards W, N, NW, NE the
+// neighbour's, shifted as the neighbour's mask word is.  Its LDS holds the two mask buffers and the four link tiles.
+static_assert(AMT_LABEL_SKELETON_TILE_ROWS == SK_ROWS && AMT_LABEL_SKELETON_TILE_WORDS == SK_WORDS &&
+              AMT_LABEL_SKELETON_BLOCK_SUBITERS == SK_T, "one kernel, one geometry: the label variant shares the binary one's");
+constexpr int SK_NLINKS = 4;  // E, S, SE, SW, in this order in scratch and in LDS
+static_assert((2 + SK_NLINKS) * SK_PHYS * 8 + 64 <= 160 * 1024 / 2, "two workgroups of the label variant per CU");
 
 #define SK_L(c, p) (((c) << 1) | ((p) >> 63)) /* pixel x - 1 */
 #define SK_R(c, n) (((c) >> 1) | ((n) << 63)) /* pixel x + 1 */
 
-// the pixels of word c that sub-iteration `second` clears; u / d = the rows above / below, p / n = the words left / right
-__device__ __forceinline__ u64 sk_cleared(u64 up, u64 uc, u64 un, u64 cp, u64 c, u64 cn, u64 dp, u64 dc, u64 dn, bool second) {
-    const u64 p2 = uc, p3 = SK_R(uc, un), p4 = SK_R(c, cn), p5 = SK_R(dc, dn);
-    const u64 p6 = dc, p7 = SK_L(dc, dp), p8 = SK_L(c, cp), p9 = SK_L(uc, up);
+// the eight neighbour words P2 .. P9 of a word, in the header's order
+struct sk_ring {
+    u64 p2, p3, p4, p5, p6, p7, p8, p9;
+};
+
+// s = the word in an LDS mask buffer; the rows above / below are SK_PW words away
+__device__ __forceinline__ sk_ring sk_ring_plain(const u64* s) {
+    const u64 up = s[-SK_PW - 1], uc = s[-SK_PW], un = s[-SK_PW + 1], cp = s[-1], c = s[0], cn = s[1];
+    const u64 dp = s[SK_PW - 1], dc = s[SK_PW], dn = s[SK_PW + 1];
+    return {uc, SK_R(uc, un), SK_R(c, cn), SK_R(dc, dn), dc, SK_L(dc, dp), SK_L(c, cp), SK_L(uc, up)};
+}
+
+// the same with the links: k = the word's link tile E; S, SE, SW follow SK_PHYS words apart, laid out as the mask
+__device__ __forceinline__ sk_ring sk_ring_linked(const u64* s, const u64* k) {
+    const u64 *S = k + SK_PHYS, *SE = S + SK_PHYS, *SW = SE + SK_PHYS;
+    const u64 c = s[0], cn = s[1], dp = s[SK_PW - 1], dc = s[SK_PW], dn = s[SK_PW + 1];
+    const u64 uc = s[-SK_PW];
+    sk_ring r;
+    r.p4 = SK_R(c, cn) & k[0];
+    r.p6 = dc & S[0];
+    r.p5 = SK_R(dc, dn) & SE[0];
+    r.p7 = SK_L(dc, dp) & SW[0];
+    r.p8 = SK_L(c & k[0], s[-1] & k[-1]);
+    r.p2 = uc & S[-SK_PW];
+    r.p3 = SK_R(uc & SW[-SK_PW], s[-SK_PW + 1] & SW[-SK_PW + 1]);
+    r.p9 = SK_L(uc & SE[-SK_PW], s[-SK_PW - 1] & SE[-SK_PW - 1]);
+    return r;
+}
+
+// the pixels of word c that sub-iteration `second` clears, given its neighbour words
+__device__ __forceinline__ u64 sk_cleared(const sk_ring& r, u64 c, bool second) {
+    const u64 p2 = r.p2, p3 = r.p3, p4 = r.p4, p5 = r.p5, p6 = r.p6, p7 = r.p7, p8 = r.p8, p9 = r.p9;
     // B = p2 + .. + p9 as four bit planes b0..b3
     const u64 x1 = p2 ^ p3, s1 = x1 ^ p4, c1 = (p2 & p3) | (p4 & x1);
     const u64 x2 = p5 ^ p6, s2 = x2 ^ p7, c2 = (p5 & p6) | (p7 & x2);
@@ -285,10 +322,14 @@ __device__ __forceinline__ u64 sk_cleared(u64 up, u64 uc, u64 un, u64 cp, u64 c,
     return c & b_ok & one & ~two & ~prod;
 }
 
-// prev / cur: this launch's and the one before's change masks, one word per plane
-__global__ void __launch_bounds__(256) sk_block_kernel(const u64* __restrict__ src, u64* __restrict__ dst, int H, int W,
+// prev / cur: this launch's and the one before's change masks, one word per plane.  LINKED: links = the four link planes
+// of the whole batch, link_stride words apart (nullptr otherwise)
+template <bool LINKED>
+__global__ void __launch_bounds__(256) sk_block_kernel(const u64* __restrict__ src, u64* __restrict__ dst,
+                                                       const u64* __restrict__ links, size_t link_stride, int H, int W,
                                                        int WW, int nsub, const u64* __restrict__ prev, u64* cur) {
-    __shared__ u64 lds[2 * SK_PHYS];
+    constexpr int NBUF = LINKED ? 2 + SK_NLINKS : 2;
+    __shared__ u64 lds[NBUF * SK_PHYS];
     __shared__ u64 s_chg;
     const int plane = blockIdx.z;
     if (prev[plane] == 0ull) return;  // the launch before this one changed nothing in the plane: dst already equals src
@@ -298,7 +339,7 @@ __global__ void __launch_bounds__(256) sk_block_kernel(const u64* __restrict__ s
     const int TW = tww + 2;
     const int y_top = y0 - SK_T, wx_left = wx0 - 1;
     const unsigned inv = ((1u << 20) + (unsigned)TW - 1u) / (unsigned)TW;  // idx / TW as a multiply
-    for (int i = tid; i < 2 * SK_PHYS; i += 256) lds[i] = 0ull;
+    for (int i = tid; i < NBUF * SK_PHYS; i += 256) lds[i] = 0ull;
     if (tid == 0) s_chg = 0ull;
     __syncthreads();
     u64* a = lds + SK_PW + 1;  // logical (row 0, word 0)
@@ -319,6 +360,21 @@ __global__ void __launch_bounds__(256) sk_block_kernel(const u64* __restrict__ s
     }
     u64 chg = 0ull;
     if (__syncthreads_or(any)) {
+        if constexpr (LINKED) {
+            // the links of the loaded region: constant through the launch; outside the image 0, and a link word is only
+            // read ANDed with mask bits of its own plane position, which are 0 there too
+            const u64* lrows = links + (size_t)plane * H * WW;
+            for (int idx = tid; idx < SK_TR * TW; idx += 256) {
+                const int r = (int)(((unsigned)idx * inv) >> 20), wc = idx - r * TW;
+                const int y = y_top + r, wx = wx_left + wc;
+                if (y >= 0 && y < H && wx >= 0 && wx < WW) {
+                    const size_t at = (size_t)y * WW + wx;
+#pragma unroll
+                    for (int k = 0; k < SK_NLINKS; ++k) a[(2 + k) * SK_PHYS + r * SK_PW + wc] = lrows[k * link_stride + at];
+                }
+            }
+            __syncthreads();
+        }
         int clean = 0;
         for (int t = 0; t < nsub; ++t) {
             const int r_lo = t + 1, count = (SK_TR - 2 * (t + 1)) * TW;
@@ -330,8 +386,13 @@ __global__ void __launch_bounds__(256) sk_block_kernel(const u64* __restrict__ s
                 const u64 c = s[0];
                 u64 v = c;
                 if (c) {
-                    v = c & ~sk_cleared(s[-SK_PW - 1], s[-SK_PW], s[-SK_PW + 1], s[-1], c, s[1], s[SK_PW - 1], s[SK_PW],
-                                        s[SK_PW + 1], t & 1);
+                    if constexpr (LINKED) {
+                        // a and b take turns: the link tiles lie 2 or 1 buffers behind the word
+                        const u64* k = s + (a < b ? 2 * SK_PHYS : SK_PHYS);
+                        v = c & ~sk_cleared(sk_ring_linked(s, k), c, t & 1);
+                    } else {
+                        v = c & ~sk_cleared(sk_ring_plain(s), c, t & 1);
+                    }
                     if (v != c) {
                         step = 1;
                         if (r >= SK_T && r < SK_T + SK_ROWS && wc >= 1 && wc <= tww) chg |= 1ull << t;
@@ -358,19 +419,115 @@ __global__ void __launch_bounds__(256) sk_block_kernel(const u64* __restrict__ s
     if (tid == 0 && s_chg) atomicOr(cur + plane, s_chg);
 }
 
-static int sk_run(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, int H, int W, int max_iter) {
+// The label variant's way in: the mask labels != 0 and the four link planes (E, S, SE, SW, link_stride words apart) of an
+// int32 label plane in one pass.  A wave makes LK_WORDS_PER_WAVE consecutive words of the packed plane, lane i the bit of
+// pixel word * 64 + i: the pixel and its four partners are loaded UNCONDITIONALLY from clamped coordinates, all loads of
+// the wave's words issued before the first ballot, and a partner outside the image is dropped where the bit is made.  Bits
+// beyond W are 0 in all five planes.
+constexpr int LK_WORDS_PER_WAVE = 4;
+__global__ void __launch_bounds__(256) sk_pack_links_kernel(const int* __restrict__ labels, u64* __restrict__ mask,
+                                                            u64* __restrict__ links, size_t link_stride, int H, int W,
+                                                            int WW) {
+    const size_t plane = blockIdx.y;
+    const int* L = labels + plane * (size_t)H * W;
+    u64* m = mask + plane * (size_t)H * WW;
+    u64* k = links + plane * (size_t)H * WW;
+    const int lane = threadIdx.x & 63;
+    const unsigned nwords = (unsigned)H * (unsigned)WW;
+    const unsigned w0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 4u + (threadIdx.x >> 6)) * LK_WORDS_PER_WAVE);
+    if (w0 >= nwords) return;
+    const int y0 = (int)(w0 / (unsigned)WW), wx0 = (int)(w0 - (unsigned)y0 * (unsigned)WW);
+    int v[LK_WORDS_PER_WAVE], e[LK_WORDS_PER_WAVE], s[LK_WORDS_PER_WAVE], se[LK_WORDS_PER_WAVE], sw[LK_WORDS_PER_WAVE];
+    {
+        int y = y0, wx = wx0;
+#pragma unroll
+        for (int j = 0; j < LK_WORDS_PER_WAVE; ++j) {
+            const int yc = y < H ? y : H - 1, yd = yc + 1 < H ? yc + 1 : H - 1;
+            const int x = wx * 64 + lane;
+            const int xc = x < W ? x : W - 1, xr = xc + 1 < W ? xc + 1 : W - 1, xl = xc > 0 ? xc - 1 : 0;
+            const int *rc = L + (size_t)yc * W, *rd = L + (size_t)yd * W;
+            v[j] = rc[xc];
+            e[j] = rc[xr];
+            s[j] = rd[xc];
+            se[j] = rd[xr];
+            sw[j] = rd[xl];
+            if (++wx == WW) {
+                wx = 0;
+                ++y;
+            }
+        }
+    }
+    int y = y0, wx = wx0;
+#pragma unroll
+    for (int j = 0; j < LK_WORDS_PER_WAVE; ++j) {
+        const int x = wx * 64 + lane;
+        const bool on = y < H && x < W && v[j] != 0;
+        const bool below = y + 1 < H, right = x + 1 < W, left = x >= 1;
+        const u64 bm = __ballot(on);
+        const u64 be = __ballot(on && right && e[j] == v[j]);
+        const u64 bs = __ballot(on && below && s[j] == v[j]);
+        const u64 bse = __ballot(on && below && right && se[j] == v[j]);
+        const u64 bsw = __ballot(on && below && left && sw[j] == v[j]);
+        if (lane == 0 && y < H) {
+            m[w0 + j] = bm;
+            k[w0 + j] = be;
+            k[link_stride + w0 + j] = bs;
+            k[2 * link_stride + w0 + j] = bse;
+            k[3 * link_stride + w0 + j] = bsw;
+        }
+        if (++wx == WW) {
+            wx = 0;
+            ++y;
+        }
+    }
+}
+
+// ... and its way out: out = labels where the bit is set, 0 elsewhere; one thread per four pixels of a row, a 16-byte
+// load and store per lane where VEC (both planes 16-byte aligned and W % 4 == 0)
+template <bool VEC>
+__global__ void __launch_bounds__(256) sk_unpack_labels_kernel(const u64* __restrict__ packed, const int* __restrict__ labels,
+                                                               int* __restrict__ out, int H, int W, int WW) {
+    const size_t plane = blockIdx.y;
+    const int per_row = (W + 3) / 4;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= (size_t)H * per_row) return;
+    const int y = (int)(q / per_row);
+    const int x = (int)(q - (size_t)y * per_row) * 4;
+    const u64 w = packed[(plane * H + y) * WW + (x >> 6)];
+    const unsigned bits = (unsigned)(w >> (x & 63)) & 0xFu;  // x % 4 == 0: the four bits lie in one word
+    const size_t at = (plane * H + y) * W + x;
+    if constexpr (VEC) {
+        const int4 l = *reinterpret_cast<const int4*>(labels + at);
+        *reinterpret_cast<int4*>(out + at) = make_int4(l.x & -(int)(bits & 1u), l.y & -(int)((bits >> 1) & 1u),
+                                                       l.z & -(int)((bits >> 2) & 1u), l.w & -(int)((bits >> 3) & 1u));
+    } else {
+        for (int j = 0; j < 4 && x + j < W; ++j) out[at + j] = labels[at + j] & -(int)((bits >> j) & 1u);
+    }
+}
+
+// The driver of both variants.  LINKED: in / out are int32 label planes (amt_i_label_skeleton), otherwise uint8 masks.
+template <bool LINKED>
+static int sk_run(amt_ctx* ctx, const void* in, void* out, int nplanes, int H, int W, int max_iter) {
+    const char* const name = LINKED ? "label_skeleton" : "skeletonize";
     const int WW = (W + 63) / 64;
     const size_t words = (size_t)nplanes * H * WW;
     const int ntx = (WW + SK_WORDS - 1) / SK_WORDS, nty = (H + SK_ROWS - 1) / SK_ROWS;
-    AMT_REQUIRE(nplanes <= 65535, "skeletonize: at most 65535 planes per call (got %d)", nplanes);
+    AMT_REQUIRE(nplanes <= 65535, "%s: at most 65535 planes per call (got %d)", name, nplanes);
     amt_scratch s(ctx);
     amt_buf<u64> pa(s, words);
     amt_buf<u64> pb(s, words);
     amt_buf<u64> masks(s, (size_t)(SK_BATCH + 1) * nplanes);  // row 0: the launch before the batch; then one row per launch
+    amt_buf<u64> links(s, SK_NLINKS * words, LINKED);
     AMT_TRY(s.commit());
     const size_t nwords = (size_t)H * WW;
-    const unsigned gpack = (unsigned)((nwords + 4 * PACK_WORDS_PER_WAVE - 1) / (4 * PACK_WORDS_PER_WAVE));
-    hipLaunchKernelGGL(pack_kernel, dim3(gpack, nplanes), dim3(256), 0, ctx->stream, in, pa, H, W, WW);
+    if constexpr (LINKED) {
+        const unsigned gpack = (unsigned)((nwords + 4 * LK_WORDS_PER_WAVE - 1) / (4 * LK_WORDS_PER_WAVE));
+        hipLaunchKernelGGL(sk_pack_links_kernel, dim3(gpack, nplanes), dim3(256), 0, ctx->stream, (const int*)in, (u64*)pa,
+                           (u64*)links, words, H, W, WW);
+    } else {
+        const unsigned gpack = (unsigned)((nwords + 4 * PACK_WORDS_PER_WAVE - 1) / (4 * PACK_WORDS_PER_WAVE));
+        hipLaunchKernelGGL(pack_kernel, dim3(gpack, nplanes), dim3(256), 0, ctx->stream, (const uint8_t*)in, pa, H, W, WW);
+    }
     AMT_LAUNCH_CHECK();
     u64* const m = masks;
     const size_t row = sizeof(u64) * (size_t)nplanes;
@@ -392,8 +549,9 @@ static int sk_run(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, in
         const int batch = syncs + 1 < (unsigned long long)SK_BATCH ? (int)syncs + 1 : SK_BATCH;
         while (n < batch && (budget < 0 || sub < budget)) {
             nsub[n] = budget < 0 || budget - sub >= SK_T ? SK_T : (int)(budget - sub);
-            hipLaunchKernelGGL(sk_block_kernel, dim3(ntx, nty, nplanes), dim3(256), 0, ctx->stream, src, dst, H, W, WW,
-                               nsub[n], m + (size_t)n * nplanes, m + (size_t)(n + 1) * nplanes);
+            hipLaunchKernelGGL(sk_block_kernel<LINKED>, dim3(ntx, nty, nplanes), dim3(256), 0, ctx->stream, src, dst,
+                               (const u64*)links, words, H, W, WW, nsub[n], m + (size_t)n * nplanes,
+                               m + (size_t)(n + 1) * nplanes);
             AMT_LAUNCH_CHECK();
             u64* sw = src;
             src = dst;
@@ -418,15 +576,26 @@ static int sk_run(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, in
             done_sub += nsub[k];
         }
         if (launches > limit) {
-            amt_set_error("binary morphology: skeletonize did not converge in %llu launches", launches);
+            amt_set_error("%s did not converge in %llu launches", name, launches);
             return AMT_EHIP;
         }
         if (open > 0 && (budget < 0 || done_sub < budget))
             AMT_HIP_CHECK(hipMemcpyAsync(m, m + (size_t)n * nplanes, row, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    const size_t nq = (size_t)H * ((W + 15) / 16);
-    hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((nq + 255) / 256), nplanes), dim3(256), 0, ctx->stream, src, out, H, W,
-                       WW);
+    if constexpr (LINKED) {
+        const size_t nq = (size_t)H * ((W + 3) / 4);
+        const dim3 grid((unsigned)((nq + 255) / 256), nplanes);
+        if (W % 4 == 0 && (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0)
+            hipLaunchKernelGGL(sk_unpack_labels_kernel<true>, grid, dim3(256), 0, ctx->stream, src, (const int*)in, (int*)out,
+                               H, W, WW);
+        else
+            hipLaunchKernelGGL(sk_unpack_labels_kernel<false>, grid, dim3(256), 0, ctx->stream, src, (const int*)in,
+                               (int*)out, H, W, WW);
+    } else {
+        const size_t nq = (size_t)H * ((W + 15) / 16);
+        hipLaunchKernelGGL(unpack_kernel, dim3((unsigned)((nq + 255) / 256), nplanes), dim3(256), 0, ctx->stream, src,
+                           (uint8_t*)out, H, W, WW);
+    }
     AMT_LAUNCH_CHECK();
     AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     ++syncs;
@@ -439,7 +608,7 @@ static int sk_run(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int nplanes, in
             const long long it = iters[p] >= 0 ? iters[p] : (long long)max_iter;
             most = it > most ? it : most;
         }
-        fprintf(stderr, "amt skeletonize: iterations=%lld launches=%llu syncs=%llu\n", most, launches, syncs);
+        fprintf(stderr, "amt %s: iterations=%lld launches=%llu syncs=%llu\n", name, most, launches, syncs);
     }
     return AMT_OK;
 }
@@ -524,6 +693,31 @@ static int structure3(const uint8_t* footprint, int fh, int fw) {
     return ones ? 2 : cross ? 1 : 0;
 }
 
+// The refusals ops AMT_RANK_LABEL_SKELETON / AMT_RANK_LABEL_CENSUS of amt_rank_filter share, none of which needs a device:
+// `what` = the op's name, `mode` = max_iter / max_label
+int amt_i_label_op_refusals(const char* what, const char* mode_name, const void* in, void* out, int dtype, int nplanes,
+                            int H, int W, const uint8_t* footprint, int fh, int fw, int mode, const void* minuend) {
+    AMT_REQUIRE(in && out && nplanes >= 0 && H > 0 && W > 0, "rank_filter: %s: bad arguments", what);
+    AMT_REQUIRE(dtype == AMT_I32, "rank_filter: %s: dtype must be AMT_I32 (a label plane), got %d", what, dtype);
+    AMT_REQUIRE(structure3(footprint, fh, fw) == 2,
+                "rank_filter: %s: the footprint must be 3 x 3 all-ones, the eight-neighbourhood the rule reads", what);
+    AMT_REQUIRE(mode >= 0, "rank_filter: %s: %s (mode) must not be negative, got %d", what, mode_name, mode);
+    AMT_REQUIRE(minuend == nullptr, "rank_filter: %s takes no minuend", what);
+    AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "rank_filter: %s: plane too large (H * W must be below 2^31 - 1)", what);
+    AMT_REQUIRE(nplanes <= 65535, "rank_filter: %s: at most 65535 planes per call (got %d)", what, nplanes);
+    return AMT_OK;
+}
+
+// AMT_RANK_LABEL_SKELETON: amt_rank_filter has checked the operands' aliasing; everything else is checked here
+int amt_i_label_skeleton(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
+                         const uint8_t* footprint, int fh, int fw, int max_iter, const void* minuend) {
+    AMT_TRY(amt_i_label_op_refusals("label_skeleton", "max_iter", in, out, dtype, nplanes, H, W, footprint, fh, fw, max_iter,
+                                    minuend));
+    AMT_TRY(amt_set_device(ctx));
+    if (nplanes == 0) return AMT_OK;
+    return sk_run<true>(ctx, in, out, nplanes, H, W, max_iter);
+}
+
 // op: AMT_MORPH_ERODE, AMT_MORPH_DILATE, AMT_MORPH_OPEN (erode then dilate), AMT_MORPH_CLOSE (dilate then erode),
 // AMT_MORPH_FILL_HOLES, AMT_MORPH_REMOVE_SMALL_OBJECTS / _HOLES (amt_label.hip: amt_i_component_filter, the area
 // filters' size in border_value), AMT_MORPH_SKELETONIZE (max_iter in border_value), AMT_MORPH_NEIGHBOR_CLASSES
@@ -548,7 +742,7 @@ extern "C" int amt_binary_morph(amt_ctx* ctx, const uint8_t* in, uint8_t* out, i
     if (op >= AMT_MORPH_SKELETONIZE) {
         AMT_REQUIRE((size_t)H * W < 0x7fffffffull, "%s: plane too large", op == AMT_MORPH_SKELETONIZE ? "skeletonize" : "neighbor_classes");
         if (nplanes == 0) return AMT_OK;
-        if (op == AMT_MORPH_SKELETONIZE) return sk_run(ctx, in, out, nplanes, H, W, border_value);
+        if (op == AMT_MORPH_SKELETONIZE) return sk_run<false>(ctx, in, out, nplanes, H, W, border_value);
         return nc_run(ctx, in, out, nplanes, H, W, structure3(footprint, fh, fw) == 2 ? 1 : 0);
     }
     if (op >= AMT_MORPH_FILL_HOLES) {

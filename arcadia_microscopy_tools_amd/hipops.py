@@ -747,6 +747,81 @@ def neighbor_classes(a: DeviceArray, connectivity: int = 2, out: DeviceArray | N
     return _skeleton_op("neighbor_classes", a, st, 0, out)
 
 
+def label_skeleton_block() -> tuple[int, int, int]:
+    """(tile rows, tile words of 64 pixels, sub-iterations per launch) of the label thinning (AMT_LABEL_SKELETON_*), as
+    ``skeleton_block`` gives them for the binary one."""
+    return _hip.LABEL_SKELETON_TILE_ROWS, _hip.LABEL_SKELETON_TILE_WORDS, _hip.LABEL_SKELETON_BLOCK_SUBITERS
+
+
+def _label_planes(which: str, labels: DeviceArray):
+    """(nplanes, H, W) of the int32 (H, W) or (N, H, W) label planes of a per-cell skeleton op"""
+    if labels.dtype != np.int32:
+        raise TypeError(f"{which} expects int32 label planes on the device, got {labels.dtype}")
+    if labels.ndim not in (2, 3):
+        raise ValueError(f"{which} takes (H, W) or (N, H, W) label planes, got shape {labels.shape}")
+    return _planes(labels)
+
+
+def _label_skeleton_op(which: str, labels: DeviceArray, o: DeviceArray, n: int, H: int, W: int, code: int, mode: int):
+    """Ops 8 / 9 of amt_rank_filter once everything is checked"""
+    st = np.ones((3, 3), np.uint8)
+    _hip.check(_lib().amt_rank_filter(labels.ctx.handle, labels.ptr, o.ptr, _hip.I32, n, H, W,
+                                      st.ctypes.data_as(ctypes.c_void_p), 3, 3, code, mode, 0.0, None), "amt_rank_filter")
+    return o
+
+
+def label_skeleton(labels: DeviceArray, max_iter: int = 0, out: DeviceArray | None = None) -> DeviceArray:
+    """The skeleton of every label of (H, W) or (N, H, W) int32 label planes, touching cells included (amt_rank_filter,
+    AMT_RANK_LABEL_SKELETON; include/amt_hip.h states the rule): Zhang and Suen's thinning as in ``skeletonize``, but a
+    neighbour counts as set only when it carries the same label as the centre pixel, which gives exactly the union of the
+    skeletons each label would get alone in its plane.  Every non-zero value is a label (negative ones too: only
+    equality is looked at).  The result holds ``labels[p]`` on the skeleton of p's label and 0 elsewhere.  ``max_iter``:
+    at most that many iterations per plane, 0 = until an iteration clears nothing.  Two runs give identical bytes.
+    Parity with scikit-image's ``skeletonize`` per label is unpinned offline.  The call waits for the device."""
+    if isinstance(max_iter, (bool, np.bool_)):
+        raise TypeError("label_skeleton: max_iter must be an integer, got a bool")
+    try:
+        k = int(operator.index(max_iter))
+    except TypeError:
+        raise TypeError(f"label_skeleton: max_iter must be an integer, got {type(max_iter).__name__}") from None
+    if k < 0 or k > 2**31 - 1:
+        raise ValueError(f"label_skeleton: max_iter must be 0 (no limit) or a positive int32, got {k}")
+    n, H, W = _label_planes("label_skeleton", labels)
+    if out is labels:
+        raise ValueError("label_skeleton: out must not alias the input")
+    o = _out(labels.ctx, out, labels.shape, np.int32)
+    _no_alias("label_skeleton", {"labels": labels}, {"out": o})
+    if labels.size == 0:
+        return o
+    return _label_skeleton_op("label_skeleton", labels, o, n, H, W, _hip.RANK_LABEL_SKELETON, k)
+
+
+def label_census(labels: DeviceArray, max_label: int, out: DeviceArray | None = None) -> DeviceArray:
+    """The census of the same-label pixel graph of (H, W) or (N, H, W) int32 label planes, usually the result of
+    ``label_skeleton`` (amt_rank_filter, AMT_RANK_LABEL_CENSUS) -> (N, max_label, 7) int32 in ``_hip.LCEN_COLS`` order,
+    row ``l - 1`` for label ``l``.  With deg(p) the number of the eight neighbours carrying p's label: ``pixels``,
+    ``isolated`` (deg 0), ``ends`` (deg 1), ``path`` (deg 2), ``junctions`` (deg >= 3; a property of pixels, not of graph
+    nodes), ``orth_links`` (horizontally or vertically adjacent pairs) and ``diag_links`` (diagonal pairs that no
+    orthogonal pair bridges), so that ``orth_links + sqrt(2) * diag_links`` is the skeleton's length.  Values outside
+    1..max_label own no row; a label absent from its plane gives zeros.  Exact integers; two runs give identical bytes."""
+    if isinstance(max_label, (bool, np.bool_)):
+        raise TypeError("label_census: max_label must be an integer, got a bool")
+    try:
+        k = int(operator.index(max_label))
+    except TypeError:
+        raise TypeError(f"label_census: max_label must be an integer, got {type(max_label).__name__}") from None
+    if k < 0 or k > 2**31 - 1:
+        raise ValueError(f"label_census: max_label must be a non-negative int32, got {k}")
+    n, H, W = _label_planes("label_census", labels)
+    o = _out(labels.ctx, out, (n, k, _hip.LCEN_NCOLS), np.int32)
+    _no_alias("label_census", {"labels": labels}, {"out": o})
+    if labels.size == 0 or k == 0:
+        if o.nbytes:  # planes without pixels: every label is absent
+            _hip.check(_lib().amt_memset(labels.ctx.handle, o.ptr, 0, o.nbytes), "amt_memset")
+        return o
+    return _label_skeleton_op("label_census", labels, o, n, H, W, _hip.RANK_LABEL_CENSUS, k)
+
+
 def threshold_otsu_bins(a: DeviceArray, minmax: DeviceArray, thr: DeviceArray, thr_code: DeviceArray,
                         bins: DeviceArray) -> DeviceArray:
     """``threshold_otsu`` of float64 planes whose [min, max] is known, leaving every sample's 256-bin index in the uint8

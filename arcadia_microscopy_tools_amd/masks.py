@@ -836,6 +836,49 @@ class SegmentationMask:
                 "first_closest_label": near[:, 0].astype(np.int64), "first_closest_distance": near[:, 1].copy(),
                 "second_closest_label": near[:, 2].astype(np.int64), "second_closest_distance": near[:, 3].copy()}
 
+    def _skeleton_plane(self):
+        """(int32 (Y, X) device plane: the label on the skeleton of its cell, 0 elsewhere; num_cells)"""
+        from . import hipops
+
+        plane, k = self._label_plane()
+        return hipops.label_skeleton(plane), k
+
+    def skeleton_image(self):
+        """The skeletons of all cells as one image of ``label_image``'s dtype: a pixel on the skeleton of cell ``i``
+        holds ``i``, every other pixel 0.  Each cell is thinned as if it were alone in the image (Zhang and Suen's rule,
+        ``hipops.label_skeleton``), so touching cells keep a skeleton each."""
+        return self._skeleton_plane()[0].numpy_int64()
+
+    def cell_skeleton(self) -> dict[str, ScalarArray]:
+        """Every cell's skeleton, one entry per cell ordered by label like ``cell_properties`` (the per-object part of
+        CellProfiler's MeasureObjectSkeleton that needs no traversal), thinned and counted on the device.  With the
+        degree of a skeleton pixel = how many of its eight neighbours are skeleton pixels of the same cell:
+
+        skeleton_pixels           the pixels of the cell's skeleton (int64)
+        skeleton_isolated         of these, the ones of degree 0: a round cell thins to a single pixel (int64)
+        skeleton_ends             degree 1 (int64)
+        skeleton_path_pixels      degree 2 (int64)
+        skeleton_junction_pixels  degree 3 and more -- a property of pixels, not of branch points: one crossing may
+                                  hold several (int64)
+        skeleton_length           orth + sqrt(2) * diag in pixels, with orth the horizontally or vertically adjacent
+                                  pairs of skeleton pixels and diag the diagonal pairs that no such pair bridges
+                                  (float64)
+
+        The skeleton of a cell is the one it would get alone in the image, however its neighbours touch it
+        (``skeleton_image`` shows it).  Works on ``expanded`` / ``ring`` masks and on masks from ``batch_masks``; the label
+        plane and the skeleton do not leave the device, only the (num_cells x 7) table comes back
+        (``hipops.label_skeleton``, ``hipops.label_census``; keys: ``segment.skeleton_keys``).  Parity with scikit-image or
+        CellProfiler is unpinned offline."""
+        from . import _hip, hipops
+
+        skel, k = self._skeleton_plane()
+        table = hipops.label_census(skel, max(k, 1)).numpy()[0, :k, :]
+        col = {name: table[:, i].astype(np.int64) for i, name in enumerate(_hip.LCEN_COLS)}
+        orth, diag = col["orth_links"].astype(np.float64), col["diag_links"].astype(np.float64)
+        return {"skeleton_pixels": col["pixels"], "skeleton_isolated": col["isolated"], "skeleton_ends": col["ends"],
+                "skeleton_path_pixels": col["path"], "skeleton_junction_pixels": col["junctions"],
+                "skeleton_length": orth + np.sqrt(2.0) * diag}
+
     def convert_properties_to_microns(self, pixel_size_um: float) -> dict[str, ScalarArray]:
         """Scale lengths / areas / volumes to microns with ``_um`` / ``_um2`` / ``_um3`` key suffixes
         (R/masks.py:420-467); dimensionless and intensity columns pass through."""

@@ -361,6 +361,56 @@ def skeleton_nodes(mask, connectivity: int = 2):
     return _skeleton_2d("skeleton_nodes", mask, lambda d: hipops.neighbor_classes(d, connectivity), np.uint8)
 
 
+@device_operator
+def skeletonize_labels(label_image, max_iter: int | None = None):
+    """The skeleton of every cell of a 2-D label image, touching cells included: ``skeletonize``'s rule, but a neighbour
+    counts only when it carries the same label as the pixel, which gives exactly the skeletons the cells would get one
+    by one (``hipops.label_skeleton`` and include/amt_hip.h state the rule; parity with scikit-image per label is
+    unpinned offline).  The result holds the label on the skeleton of its cell and 0 elsewhere.  Every non-zero value is
+    a label.  A numpy integer label image gives an array of the same dtype (its values must fit int32); a
+    ``DeviceArray`` (int32, or the uint16 / uint8 a ``Pipeline`` uploads) stays on the device.  bool arrays are masks:
+    use ``skeletonize``.  ``max_iter`` as for ``skeletonize``.  Stacks are refused: map planes with
+    ``Pipeline(parallel=True)`` or call ``hipops.label_skeleton``."""
+    if max_iter is None:
+        k = 0
+    else:
+        if isinstance(max_iter, (bool, np.bool_)):
+            raise TypeError("skeletonize_labels: max_iter must be None or a positive integer, got a bool")
+        try:
+            k = int(max_iter.__index__())
+        except AttributeError:
+            raise TypeError("skeletonize_labels: max_iter must be None or a positive integer, got "
+                            f"{type(max_iter).__name__}") from None
+        if k < 1:
+            raise ValueError(f"skeletonize_labels: max_iter must be None or a positive integer, got {k}")
+    if isinstance(label_image, DeviceArray):
+        d = label_image
+        if d.ndim != 2:
+            raise ValueError("label_image must be a 2D array")
+        if d.is_bool:
+            raise TypeError("skeletonize_labels: a bool array is a mask, not a label image; use skeletonize")
+        if d.dtype == np.int32:
+            return hipops.label_skeleton(d, k)
+        if d.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f"skeletonize_labels: device label images must be int32, uint16 or uint8, got {d.dtype}")
+        if d.size == 0:
+            return d
+        return hipops.cast_labels(hipops.label_skeleton(hipops.cast_labels(d, np.int32), k), d.dtype)
+    a = np.asarray(label_image)
+    if a.ndim != 2:
+        raise ValueError("label_image must be a 2D array")
+    if a.dtype == np.bool_:
+        raise TypeError("skeletonize_labels: a bool array is a mask, not a label image; use skeletonize")
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"skeletonize_labels: label_image must have an integer dtype, got {a.dtype}")
+    if a.size == 0:
+        return np.zeros_like(a)
+    if int(a.min()) < -2**31 or int(a.max()) > 2**31 - 1:
+        raise ValueError("skeletonize_labels: label values must fit int32 on the device path")
+    d = get_context().asarray(a, dtype=np.int32)
+    return hipops.label_skeleton(d, k).numpy(dtype=a.dtype)
+
+
 _RECON_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float64))
 
 

@@ -490,6 +490,13 @@ def neighbor_keys() -> list[str]:
             "first_closest_label", "first_closest_distance", "second_closest_label", "second_closest_distance"]
 
 
+def skeleton_keys() -> list[str]:
+    """The keys of ``SegmentationMask.cell_skeleton``, in order (no device needed): the five pixel counts of
+    ``_hip.LCEN_COLS`` (int64), then ``skeleton_length`` (float64), made of the two link counts."""
+    return ["skeleton_pixels", "skeleton_isolated", "skeleton_ends", "skeleton_path_pixels", "skeleton_junction_pixels",
+            "skeleton_length"]
+
+
 def segment_fovs(fovs, *, ctx: Context | None = None, channel_names=DEFAULT_CHANNELS, **kw) -> SegmentationResult:
     """Convenience: (B, C, H, W) uint16 (numpy or DeviceArray) -> config-3 ``SegmentationResult``."""
     ctx = ctx or get_context()

@@ -365,11 +365,70 @@ int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const d
  * seed = fl(in -+ h): the same set in exact arithmetic, and it needs no tolerance (scikit-image subtracts a resolution
  * term that differs between versions).
  * A workgroup owns one tile of AMT_RECONSTRUCT_TILE_H_* x AMT_RECONSTRUCT_TILE_W_* pixels per round (csrc/
- * amt_reconstruct.hip); planes that cross tile seams need several rounds. */
+ * amt_reconstruct.hip); planes that cross tile seams need several rounds.
+ *
+ * op 8 and 9: PER-CELL SKELETONS of int32 label planes (op 7 is not an op of this call).  Common to the two: dtype must be
+ * AMT_I32; `in` is nplanes x H x W labels, where every non-zero int32 value is a label, negative ones included -- only
+ * equality is looked at; the footprint must be 3 x 3 all-ones (it names the eight-neighbourhood, as for
+ * AMT_MORPH_SKELETONIZE of amt_binary_morph; every other footprint, the 3 x 3 cross included, is AMT_EINVAL); `minuend`
+ * must be NULL and cval is ignored; H * W < 2^31 - 1 and nplanes <= 65535; nplanes == 0 is AMT_OK and writes nothing.
+ * The refusals that need no device (dtype, footprint, a negative `mode`, a non-NULL minuend, the plane size) come before
+ * the context is looked at.  `out` must not alias `in`, nor overlap it in part (AMT_EINVAL).
+ *   AMT_RANK_LABEL_SKELETON  thinning of every label to its centre lines.  The rule is the one of AMT_MORPH_SKELETONIZE
+ *                     with one change: for a pixel p with labels[p] = l != 0, P_i = 1 iff the neighbour lies inside the
+ *                     image and carries the same label l; a pixel with labels[p] == 0 is never set.  B, A, the two
+ *                     sub-iterations, "judged on the plane as it was before the sub-iteration", the iteration count and
+ *                     max_iter are word for word those of AMT_MORPH_SKELETONIZE.  By induction over the sub-iterations
+ *                     the result is exactly the union of the skeletons each label would get alone in its plane -- a
+ *                     pixel of another label looks like background, which is what it would be there -- so touching
+ *                     cells get a skeleton each, and there is no limit on a label's size.
+ *                     out[p] = labels[p] where p is on the skeleton of its label, 0 elsewhere (an int32 plane like
+ *                     `in`).  `mode` carries max_iter: 0 means to the fixed point, a negative value is AMT_EINVAL.
+ *                     Each plane of a batch has its own iteration count.  THIS OP WAITS FOR THE DEVICE (it
+ *                     waits for the device as the reconstruction ops and AMT_MORPH_SKELETONIZE do); AMT_DEBUG_SKELETONIZE=1
+ *                     in the environment prints iterations, launches and syncs to stderr ("amt label_skeleton: ...").
+ *                     The kernel is the bit-sliced tile kernel of AMT_MORPH_SKELETONIZE on the mask labels != 0, with four
+ *                     constant link bit planes beside it (same label towards E, S, SE, SW): a tile of
+ *                     AMT_LABEL_SKELETON_TILE_ROWS rows x AMT_LABEL_SKELETON_TILE_WORDS 64-pixel words and up to
+ *                     AMT_LABEL_SKELETON_BLOCK_SUBITERS sub-iterations per launch (csrc/amt_morph.hip).  Parity with
+ *                     scikit-image's skeletonize per label, or with CellProfiler's MeasureObjectSkeleton, is
+ *                     unpinned offline, as for AMT_MORPH_SKELETONIZE: the tests pin the rule as stated here.
+ *   AMT_RANK_LABEL_CENSUS    the census of the same-label pixel graph of a label plane -- any label plane; the Python
+ *                     layer feeds it the result of AMT_RANK_LABEL_SKELETON.  `mode` carries max_label (>= 0; 0 writes
+ *                     nothing, negative is AMT_EINVAL); `out` is nplanes x max_label x AMT_LCEN_NCOLS INT32, row l - 1 for
+ *                     label l.  Values outside 1..max_label own no row; they still differ from every neighbour.  With
+ *                     deg(p) the number of the eight neighbours that carry labels[p], the columns of label l:
+ *                       AMT_LCEN_PIXELS      pixels carrying l
+ *                       AMT_LCEN_ISOLATED    of these, deg == 0
+ *                       AMT_LCEN_ENDS        deg == 1
+ *                       AMT_LCEN_PATH        deg == 2
+ *                       AMT_LCEN_JUNCTIONS   deg >= 3 (the classes of AMT_MORPH_NEIGHBOR_CLASSES minus one, and like them a
+ *                                            property of pixels, not of graph nodes)
+ *                       AMT_LCEN_ORTH_LINKS  unordered pairs {p, p+(0,1)} and {p, p+(1,0)} with both ends l
+ *                       AMT_LCEN_DIAG_LINKS  pairs {p, p+(1,1)} with both ends l and neither p+(0,1) nor p+(1,0) carrying
+ *                                            l, and pairs {p, p+(1,-1)} with neither p+(0,-1) nor p+(1,0) carrying l: a
+ *                                            diagonal link that an orthogonal pair already bridges is not counted, so a
+ *                                            staircase is not measured twice (length = ORTH_LINKS + sqrt(2) * DIAG_LINKS)
+ *                     A label absent from its plane gives seven zeros.  The counts are exact integers made without global
+ *                     atomics, so two runs give identical bytes.  Asynchronous.  The table must not overlap `in`.
+ */
 #define AMT_RANK_RECONSTRUCT_DILATION 3
 #define AMT_RANK_RECONSTRUCT_EROSION  4
 #define AMT_RANK_HMAX_RECONSTRUCT     5
 #define AMT_RANK_HMIN_RECONSTRUCT     6
+#define AMT_RANK_LABEL_SKELETON 8
+#define AMT_RANK_LABEL_CENSUS 9
+#define AMT_LABEL_SKELETON_TILE_ROWS 64
+#define AMT_LABEL_SKELETON_TILE_WORDS 8
+#define AMT_LABEL_SKELETON_BLOCK_SUBITERS 32
+#define AMT_LCEN_PIXELS 0
+#define AMT_LCEN_ISOLATED 1
+#define AMT_LCEN_ENDS 2
+#define AMT_LCEN_PATH 3
+#define AMT_LCEN_JUNCTIONS 4
+#define AMT_LCEN_ORTH_LINKS 5
+#define AMT_LCEN_DIAG_LINKS 6
+#define AMT_LCEN_NCOLS 7
 #define AMT_RECONSTRUCT_TILE_H_U16 64
 #define AMT_RECONSTRUCT_TILE_W_U16 128
 #define AMT_RECONSTRUCT_TILE_H_F64 32
