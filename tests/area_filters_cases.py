@@ -11,7 +11,6 @@ component areas are computed once; the sizes only change a comparison.
 from __future__ import annotations
 
 import hashlib
-import json
 import os
 import sys
 import time
@@ -24,6 +23,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
         sys.path.insert(0, _p)
 
 import area_filters_reference as ref  # noqa: E402
+import poison_child  # noqa: E402
 
 
 def _sha(a: np.ndarray) -> str:
@@ -126,11 +126,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    poison = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
-    res = run(get_context(), scratch_check=poison)
-    res["poison"] = poison
-    with open(args.json, "w") as f:
-        json.dump(res, f)
+    res = run(get_context(), scratch_check=poison_child.poisoned())
+    poison_child.write(args.json, res)
     for k in res["mismatches"][:20]:
         print("MISMATCH", k, flush=True)
     for d in res["dirty"][:20]:

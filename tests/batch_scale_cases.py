@@ -46,6 +46,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 import operator_sweep as sw  # noqa: E402
 import parameter_limits as pl  # noqa: E402
+import poison_child  # noqa: E402
 import reconstruction_reference as rr  # noqa: E402
 import skeleton_reference as skref  # noqa: E402
 from oracle import skops  # noqa: E402
@@ -832,12 +833,10 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    poison = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
+    poison = poison_child.poisoned()
     ctx = get_context()
     res = run(ctx, args.group, scratch_check=poison)
-    res["poison"] = poison
-    with open(args.json, "w") as f:
-        json.dump(res, f)
+    poison_child.write(args.json, res)
     bad = [r for r in res["records"] if r["status"] != "pass"]
     if args.profile:
         groups = GROUPS if args.group is None else args.group

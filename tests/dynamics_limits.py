@@ -39,6 +39,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
         sys.path.insert(0, _p)
 
 import operator_sweep as sw  # noqa: E402
+import poison_child  # noqa: E402
 from oracle import cellpose_dynamics as cd  # noqa: E402
 
 _I32, _F32, _F64 = np.int32, np.float32, np.float64
@@ -796,11 +797,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    poison = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
+    poison = poison_child.poisoned()
     res = run(get_context(), args.group, scratch_check=poison)
-    res["poison"] = poison
-    with open(args.json, "w") as f:
-        json.dump(res, f)
+    poison_child.write(args.json, res)
     bad = [r for r in res["records"] if r["status"] != "pass"]
     if args.profile:
         head = {"device": get_context().device_name(), "poison": poison, "seconds": round(res["seconds"], 2),

@@ -39,6 +39,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 import colocalization_reference as coloc_ref  # noqa: E402
 import expand_labels_reference as expand_ref  # noqa: E402
+import poison_child  # noqa: E402
 from oracle import blending as oblend  # noqa: E402
 from oracle import cellpose_dynamics as cd  # noqa: E402
 from oracle import contours as ocontours  # noqa: E402
@@ -1362,11 +1363,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    poison = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
+    poison = poison_child.poisoned()
     res = run(get_context(), args.family, scratch_check=poison)
-    res["poison"] = poison
-    with open(args.json, "w") as f:
-        json.dump(res, f)
+    poison_child.write(args.json, res)
     if args.profile:
         per = {f: sum(r["family"] == f for r in res["records"]) for f in FAMILIES}
         with open(args.profile, "w") as f:

@@ -38,6 +38,7 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 import colocalization_reference as coloc_ref  # noqa: E402
 import expand_labels_reference as expand_ref  # noqa: E402
 import operator_sweep as sw  # noqa: E402
+import poison_child  # noqa: E402
 from oracle import blending as oblend  # noqa: E402
 from oracle import regionprops as orp  # noqa: E402
 from oracle import skops  # noqa: E402
@@ -1348,11 +1349,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    poison = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
+    poison = poison_child.poisoned()
     res = run(get_context(), args.group, scratch_check=poison)
-    res["poison"] = poison
-    with open(args.json, "w") as f:
-        json.dump(res, f)
+    poison_child.write(args.json, res)
     bad = [r for r in res["records"] if r["status"] != "pass"]
     if args.profile:
         per = {g: round(sum(r["ms"] for r in res["records"] if r["group"] == g) / 1e3, 2) for g in GROUPS}

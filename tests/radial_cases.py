@@ -16,6 +16,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import poison_child  # noqa: E402
 import radial_reference as rr  # noqa: E402
 
 KINDS = ("u16", "f64")
@@ -213,17 +214,13 @@ def main(argv=None):
     """``python -m tests.radial_cases --json FILE``: the whole table in a process of its own (the GPU test starts it
     with AMT_DEBUG_POISON=1), a scratch check after every call"""
     import argparse
-    import json
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", required=True)
     a = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    res = run(get_context(), check_scratch=True)
-    res["poison"] = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
-    with open(a.json, "w") as f:
-        json.dump(res, f)
+    poison_child.write(a.json, run(get_context(), check_scratch=True))
     return 0
 
 

@@ -19,6 +19,7 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import poison_child  # noqa: E402
 import reconstruction_reference as rr  # noqa: E402
 
 KINDS = {"u16": np.uint16, "f64": np.float64}
@@ -193,17 +194,13 @@ def run(ctx, check_scratch=False):
 
 def main(argv=None):
     import argparse
-    import json
 
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", required=True)
     a = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    res = run(get_context(), check_scratch=True)
-    res["poison"] = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
-    with open(a.json, "w") as f:
-        json.dump(res, f)
+    poison_child.write(a.json, run(get_context(), check_scratch=True))
     return 0
 
 

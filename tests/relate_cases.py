@@ -8,7 +8,6 @@ AMT_DEBUG_POISON=1), calls ``Context.scratch_check()`` after every call and writ
 from __future__ import annotations
 
 import hashlib
-import json
 import os
 import sys
 
@@ -19,6 +18,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import poison_child  # noqa: E402
 import relate_reference as rr  # noqa: E402
 
 SHAPES = [(1, 1), (1, 17), (19, 1), (7, 5), (16, 16), (33, 40), (64, 64), (65, 128), (70, 131)]
@@ -180,10 +180,7 @@ def main(argv):
     from arcadia_microscopy_tools_amd.device import get_context
 
     out = argv[argv.index("--json") + 1]
-    res = run(get_context(), check=True)
-    res["poison"] = os.environ.get("AMT_DEBUG_POISON") == "1"
-    with open(out, "w") as f:
-        json.dump(res, f)
+    poison_child.write(out, run(get_context(), check=True))
     return 0
 
 

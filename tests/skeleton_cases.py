@@ -11,8 +11,6 @@ reference, and -- with AMT_DEBUG_POISON=1 -- what ``Context.scratch_check()`` fo
 pytest (no test_ prefix)."""
 from __future__ import annotations
 
-import hashlib
-import json
 import os
 import sys
 
@@ -23,8 +21,10 @@ for _p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import poison_child  # noqa: E402
 import skeleton_reference as ref  # noqa: E402
 from arcadia_microscopy_tools_amd import _hip  # noqa: E402
+from poison_child import digest  # noqa: E402
 
 ROWS, WORDS, T = _hip.SKELETON_TILE_ROWS, _hip.SKELETON_TILE_WORDS, _hip.SKELETON_BLOCK_SUBITERS
 TILE_W = 64 * WORDS
@@ -190,11 +190,6 @@ def class_reference(case):
     return _memo(("classes", name), lambda: np.stack([ref.neighbor_classes(p, conn) for p in stack]))
 
 
-def digest(a):
-    a = np.ascontiguousarray(a)
-    return hashlib.sha256(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes()).hexdigest()
-
-
 def run_skeleton(ctx, case):
     from arcadia_microscopy_tools_amd import hipops
 
@@ -228,10 +223,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     from arcadia_microscopy_tools_amd.device import get_context
 
-    poison = os.environ.get("AMT_DEBUG_POISON", "")[:1] == "1"
-    res = {"poison": poison, "cases": run(get_context(), scratch_check=poison)}
-    with open(args.json, "w") as f:
-        json.dump(res, f)
+    poison_child.write(args.json, {"cases": run(get_context(), scratch_check=poison_child.poisoned())})
     return 0
 
 

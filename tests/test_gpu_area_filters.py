@@ -5,10 +5,6 @@ from random planes, on the run-table and on the general path; connectivity; trut
 the unchanged codes 0..4; ``operations.*`` and a ``Pipeline``; the classical chain with ``min_size``; and all sweep cases
 once more in a child process with the scratch arena poisoned."""
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -16,6 +12,7 @@ from scipy import ndimage as ndi
 
 import area_filters_cases as cases
 import area_filters_reference as ref
+import poison_child
 from arcadia_microscopy_tools_amd import _hip, hipops, operations
 from arcadia_microscopy_tools_amd.device import DeviceArray, get_context
 from arcadia_microscopy_tools_amd.model import SegmentationModel
@@ -24,7 +21,6 @@ from arcadia_microscopy_tools_amd.segment import FovSegmenter
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # meant to be ten times the in-process run of all sweep cases on the MI355X.  That run is not measured yet: until it is,
 # the limit of the fill-holes child (tests/test_gpu_fill_holes.py), whose sweep has the same shapes and fewer calls
 CHILD_TIMEOUT_S = 120
@@ -365,26 +361,10 @@ def test_run_c3_and_batch_masks_with_min_size(ctx, field):
 
 def test_all_cases_under_poison(ctx, tmp_path):
     out = tmp_path / "area_filters.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.area_filters_cases", "--json", str(out)], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned area filter cases did not end within {CHILD_TIMEOUT_S} s; their last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned area filter cases ended with status {child.returncode}; their last output:\n{tail}",
-                    returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.area_filters_cases", out, CHILD_TIMEOUT_S, "the poisoned area filter cases")
     assert not res["mismatches"], f"{len(res['mismatches'])} outputs differ under poison: {res['mismatches'][:10]}"
     assert not res["dirty"], f"{len(res['dirty'])} scratch checks came back dirty; the first: {res['dirty'][:5]}"
     here = {}
     for shape in ref.SHAPES:
         here.update(_shape_result(ctx, shape)["digests"])
-    assert set(here) == set(res["digests"])
-    moved = [k for k in here if here[k] != res["digests"][k]]
-    assert not moved, f"{len(moved)} results depend on what the scratch held; the first: {moved[:10]}"
+    poison_child.assert_unmoved(here, res["digests"])

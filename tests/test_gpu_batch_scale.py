@@ -2,19 +2,13 @@
 every batch compared, the variant the model says each call took in the report, and the whole table once more in a child
 process under AMT_DEBUG_POISON=1 -- no mismatch, no stray write behind a scratch buffer, every output digest equal to the
 in-process run's."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import batch_scale_cases as bs
+import poison_child
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the child's time limit: ten times the in-process run of the table on an MI355X, rounded up to a whole minute
 # (profiles/batch_scale.json: 14.6 s measured, references included)
@@ -85,20 +79,7 @@ def test_d2_does_not_depend_on_the_tile_variant(ctx):
 
 def test_table_under_poison(ctx, tmp_path):
     out = tmp_path / "batch_scale.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.batch_scale_cases", "--json", str(out)], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned table did not end within {CHILD_TIMEOUT_S} s; its last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned table ended with status {child.returncode}; its last output:\n{tail}", returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.batch_scale_cases", out, CHILD_TIMEOUT_S, "the poisoned table")
     bad = _mismatches(res["records"])
     assert not bad, f"{len(bad)} calls differ from their reference under poison; the first: {bad[:10]}"
     assert not res["dirty"], f"{len(res['dirty'])} scratch checks came back dirty; the first: {res['dirty'][:5]}"
@@ -106,6 +87,4 @@ def test_table_under_poison(ctx, tmp_path):
     for group in bs.GROUPS:
         here.update({_key(r): r["sha256"] for r in _group(ctx, group)["records"]})
     there = {_key(r): r["sha256"] for r in res["records"]}
-    assert set(here) == set(there)
-    moved = [k for k in here if here[k] != there[k]]
-    assert not moved, f"{len(moved)} results depend on what the scratch held; the first: {moved[:10]}"
+    poison_child.assert_unmoved(here, there)

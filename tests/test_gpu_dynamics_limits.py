@@ -10,18 +10,12 @@ Findings these cases pin (reverting the fix fails the named case):
   "ceiling 19 20 21 of 2000 x 0.01" (both paths): the size ceiling was int(n * float32(fraction)) = 19, the oracle's 20;
   "labels 1 3 6, nlabels 6, max_label 9": amt_cellpose_flow_error handed out the error slots above nlabels unwritten;
   "a value above max_label" (fill 1): a flagged plane kept such a value and indexed the keep flags with it."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
 import dynamics_limits as dl
+import poison_child
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the child's time limit: ten times the in-process run on an MI355X, rounded up to a whole minute
 # (profiles/dynamics_limits.json: 3.3 s measured, references included; 33 s -> 60 s)
@@ -73,20 +67,7 @@ def _key(r):
 
 def test_everything_under_poison(ctx, tmp_path):
     out = tmp_path / "dynamics.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.dynamics_limits", "--json", str(out)], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned run did not end within {CHILD_TIMEOUT_S} s; its last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned run ended with status {child.returncode}; its last output:\n{tail}", returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.dynamics_limits", out, CHILD_TIMEOUT_S, "the poisoned run")
     bad = _mismatches(res["records"])
     assert not bad, f"{len(bad)} cases differ from their reference under poison; the first: {bad[:10]}"
     assert not res["dirty"], f"{len(res['dirty'])} scratch checks came back dirty; the first: {res['dirty'][:5]}"
@@ -94,6 +75,4 @@ def test_everything_under_poison(ctx, tmp_path):
     for g in dl.GROUPS:
         here.update({_key(r): r["sha256"] for r in _group(ctx, g)["records"]})
     there = {_key(r): r["sha256"] for r in res["records"]}
-    assert set(here) == set(there)
-    moved = [k for k in here if here[k] != there[k]]
-    assert not moved, f"{len(moved)} results depend on what the scratch held; the first: {moved[:10]}"
+    poison_child.assert_unmoved(here, there)

@@ -4,24 +4,21 @@ iteration count, the raw entry point, the operator in a Pipeline, SegmentationMa
 table once more in a child process under AMT_DEBUG_POISON=1 (the thinning keeps six tiles in LDS and five packed planes
 in scratch: a result that depends on what their padding held is its most likely defect)."""
 import ctypes
-import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import label_skeleton_cases as cases
 import label_skeleton_reference as ref
+import poison_child
 from arcadia_microscopy_tools_amd import _hip, hipops, operations, segment
 from arcadia_microscopy_tools_amd.device import DeviceArray
 from arcadia_microscopy_tools_amd.pipeline import ImageOperation, Pipeline
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the child imports the package, creates a context and runs the table (a few seconds in process, references included)
 CHILD_TIMEOUT_S = 120
 
@@ -232,25 +229,10 @@ def test_table_under_poison(ctx, tmp_path):
         if case[0] not in here:
             here[case[0]] = cases.digest(cases.run_census(ctx, case))
     out = tmp_path / "label_skeleton.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.label_skeleton_cases", "--json", str(out)], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned table did not end within {CHILD_TIMEOUT_S} s; its last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned table ended with status {child.returncode}; its last output:\n{tail}", returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.label_skeleton_cases", out, CHILD_TIMEOUT_S, "the poisoned table")
     there = res["cases"]
-    assert set(there) == set(here)
     wrong = [k for k, v in there.items() if not v["equal"]]
     assert not wrong, f"{len(wrong)} cases differ from the rule under poison; the first: {wrong[:10]}"
     dirty = [(k, v["dirty"]) for k, v in there.items() if v["dirty"] is not None]
     assert not dirty, f"{len(dirty)} scratch checks came back dirty; the first: {dirty[:5]}"
-    moved = [k for k in here if here[k] != there[k]["sha256"]]
-    assert not moved, f"{len(moved)} results depend on what the scratch held; the first: {moved[:10]}"
+    poison_child.assert_unmoved(here, {k: v["sha256"] for k, v in there.items()})

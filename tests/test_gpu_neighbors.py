@@ -4,19 +4,16 @@ equality (NaN compared as NaN): the census columns and the labels are exact inte
 the same float64 ``d2`` on both sides, and ``percent_touching`` is the same float64 expression over the integer columns.
 The case list (tests/neighbors_cases.py) runs once more in a child process with the scratch arena poisoned."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import neighbors_cases as nc
 import neighbors_reference as nr
+import poison_child
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 60
 
 _RESULTS: dict = {}
@@ -271,21 +268,7 @@ def test_mask_cell_neighbors(ctx):
 
 def test_cases_under_poison(ctx, tmp_path):
     out = tmp_path / "neighbors.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.neighbors_cases", "--json", str(out)], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned neighbour cases did not end within {CHILD_TIMEOUT_S} s; their last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned neighbour cases ended with status {child.returncode}; their last output:\n{tail}",
-                    returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.neighbors_cases", out, CHILD_TIMEOUT_S, "the poisoned neighbour cases")
     bad = [r["key"] for r in res["records"] if not r["ok"]]
     assert not bad, f"{len(bad)} results differ from the reference under poison; the first: {bad[:10]}"
     assert not res["dirty"], f"{len(res['dirty'])} scratch checks came back dirty; the first: {res['dirty'][:5]}"
@@ -293,6 +276,4 @@ def test_cases_under_poison(ctx, tmp_path):
     for shape in nc.SHAPES:
         here.update({json.dumps(r["key"]): r["sha256"] for r in _shape_run(ctx, shape)["records"]})
     there = {json.dumps(r["key"]): r["sha256"] for r in res["records"]}
-    assert set(here) == set(there)
-    moved = [k for k in here if here[k] != there[k]]
-    assert not moved, f"{len(moved)} results depend on what the scratch held; the first: {moved[:10]}"
+    poison_child.assert_unmoved(here, there)

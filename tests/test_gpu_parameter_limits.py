@@ -3,18 +3,12 @@ parameter ranges and at each switch inside them against the reference of its own
 amt_nn_affine_act_bf16 against its definition; then everything once more in a child process under AMT_DEBUG_POISON=1 -- no
 mismatch, no dirty scratch padding, every output digest equal to the in-process run's.
 tests/test_host_parameter_limits.py shows that each case sits on the end or switch it names."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
 import parameter_limits as pl
+import poison_child
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the child's time limit: ten times the in-process run on an MI355X, rounded up to a whole minute
 # (profiles/parameter_limits.json: 13.5 s measured, references included)
@@ -66,20 +60,7 @@ def _key(r):
 
 def test_everything_under_poison(ctx, tmp_path):
     out = tmp_path / "limits.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.parameter_limits", "--json", str(out)], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned run did not end within {CHILD_TIMEOUT_S} s; its last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned run ended with status {child.returncode}; its last output:\n{tail}", returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.parameter_limits", out, CHILD_TIMEOUT_S, "the poisoned run")
     bad = _mismatches(res["records"])
     assert not bad, f"{len(bad)} cases differ from their reference under poison; the first: {bad[:10]}"
     assert not res["dirty"], f"{len(res['dirty'])} scratch checks came back dirty; the first: {res['dirty'][:5]}"
@@ -87,6 +68,4 @@ def test_everything_under_poison(ctx, tmp_path):
     for g in pl.GROUPS:
         here.update({_key(r): r["sha256"] for r in _group(ctx, g)["records"]})
     there = {_key(r): r["sha256"] for r in res["records"]}
-    assert set(here) == set(there)
-    moved = [k for k in here if here[k] != there[k]]
-    assert not moved, f"{len(moved)} results depend on what the scratch held; the first: {moved[:10]}"
+    poison_child.assert_unmoved(here, there)

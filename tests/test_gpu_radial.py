@@ -3,9 +3,12 @@
 tests/radial_cases.py.  The geometry rows -- both radii and the ring counts -- are compared bit for bit, and so are the
 three intensity columns of uint16 channels (NaNs in the same places); float64 channels within rtol 1e-9 / atol 1e-12,
 the project's bound for float64 per-label sums."""
+import json
+
 import numpy as np
 import pytest
 
+import poison_child
 import radial_cases as rc
 import radial_reference as rr
 
@@ -215,32 +218,11 @@ CHILD_TIMEOUT_S = 120
 def test_cases_under_poison(ctx, tmp_path):
     """The whole table once more in a process whose scratch arena and allocations are filled with 0xCD: the results keep
     their bits, so nothing is read that the call did not write first, and no padding of the scratch planes is written."""
-    import json
-    import os
-    import subprocess
-    import sys
-
-    out = tmp_path / "radial.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.radial_cases", "--json", str(out)], cwd=rc.ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned radial cases did not end within {CHILD_TIMEOUT_S} s; their last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned radial cases ended with status {child.returncode}; their last output:\n{tail}",
-                    returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.radial_cases", tmp_path / "radial.json", CHILD_TIMEOUT_S, "the poisoned radial cases")
     bad = [r["key"] for r in res["records"] if not r["ok"]]
     assert not bad, f"{len(bad)} results differ from the reference under poison; the first: {bad[:10]}"
     assert not res["dirty"], f"{len(res['dirty'])} scratch checks came back dirty; the first: {res['dirty'][:5]}"
     here = {json.dumps(r["key"]): r["sha256"] for r in rc.run(ctx)["records"]}
     there = {json.dumps(r["key"]): r["sha256"] for r in res["records"]}
-    assert set(here) == set(there) == {json.dumps([n, k]) for n, k in _RUNS}
-    moved = [k for k in here if here[k] != there[k]]
-    assert not moved, f"{len(moved)} results changed their bits under poison; the first: {moved[:10]}"
+    assert set(here) == {json.dumps([n, k]) for n, k in _RUNS}
+    poison_child.assert_unmoved(here, there)

@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import poison_child
 import reconstruction_cases as rc
 import reconstruction_reference as rr
 
@@ -236,28 +237,13 @@ CHILD_TIMEOUT_S = 120
 def test_cases_under_poison(ctx, tmp_path):
     """The whole table once more in a process whose scratch arena and allocations are filled with 0xCD: the results keep
     their bits (nothing is read that the call did not write first), and no padding of the scratch buffers is written."""
-    import json
-    import os
-    import subprocess
-    import sys
-
-    out = tmp_path / "reconstruction.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.reconstruction_cases", "--json", str(out)], cwd=rc.ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned reconstruction cases did not end within {CHILD_TIMEOUT_S} s; their last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned reconstruction cases ended with status {child.returncode}; their last output:\n{tail}",
-                    returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] and res["dirty"] == [], res["dirty"]
+    res = poison_child.run_module("tests.reconstruction_cases", tmp_path / "reconstruction.json", CHILD_TIMEOUT_S,
+                                  "the poisoned reconstruction cases")
+    assert res["dirty"] == [], res["dirty"]
     here = rc.run(ctx)
     assert [r["key"] for r in res["records"]] == [r["key"] for r in here["records"]] and len(here["records"]) > 80
-    differ = [a["key"] for a, b in zip(res["records"], here["records"]) if a["sha256"] != b["sha256"]]
-    assert differ == [], differ
+
+    def by_position(run):  # the records are compared pairwise, in order
+        return {f"{i} {r['key']}": r["sha256"] for i, r in enumerate(run["records"])}
+
+    poison_child.assert_unmoved(by_position(here), by_position(res))

@@ -3,19 +3,16 @@ tests/texture_reference.py.  The co-occurrence counts are compared byte for byte
 rtol 1e-9 / atol 1e-12 with NaNs in the same places, info_measure_2 on its square (tests/texture_cases.py ``compare``).  The
 case list runs once more in a child process with the scratch arena poisoned."""
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import poison_child
 import texture_cases as tc
 import texture_reference as tr
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT_S = 120
 
 _RESULTS: dict = {}
@@ -337,21 +334,7 @@ def test_mean_of_a_cell_without_any_pair_is_nan_without_a_warning(ctx):
 
 def test_cases_under_poison(ctx, tmp_path):
     out = tmp_path / "texture.json"
-    env = dict(os.environ, AMT_DEBUG_POISON="1")
-    try:
-        child = subprocess.run([sys.executable, "-m", "tests.texture_cases", "--json", str(out)], cwd=ROOT, env=env,
-                               capture_output=True, text=True, timeout=CHILD_TIMEOUT_S)
-    except subprocess.TimeoutExpired as e:
-        pytest.exit(f"the poisoned texture cases did not end within {CHILD_TIMEOUT_S} s; their last output:\n"
-                    f"{(e.stdout or b'')[-2000:]!r}\n{(e.stderr or b'')[-2000:]!r}", returncode=1)
-    tail = (child.stdout[-3000:] + "\n" + child.stderr[-3000:]).strip()
-    if child.returncode in (134, -6, 139, -11, 124, 137):
-        # an abort, a segmentation fault or a time limit: the card may have faulted, nothing more is started on it
-        pytest.exit(f"the poisoned texture cases ended with status {child.returncode}; their last output:\n{tail}",
-                    returncode=1)
-    assert child.returncode == 0, tail
-    res = json.loads(out.read_text())
-    assert res["poison"] is True
+    res = poison_child.run_module("tests.texture_cases", out, CHILD_TIMEOUT_S, "the poisoned texture cases")
     bad = [r["key"] for r in res["records"] if not r["ok"]]
     assert not bad, f"{len(bad)} results differ from the reference under poison; the first: {bad[:10]}"
     assert not res["dirty"], f"{len(res['dirty'])} scratch checks came back dirty; the first: {res['dirty'][:5]}"
@@ -360,6 +343,4 @@ def test_cases_under_poison(ctx, tmp_path):
         for kind in tc.KINDS:
             here.update({json.dumps(r["key"]): r["sha256"] for r in _shape_run(ctx, shape, kind)["records"]})
     there = {json.dumps(r["key"]): r["sha256"] for r in res["records"]}
-    assert set(here) == set(there)
-    moved = [k for k in here if here[k] != there[k]]
-    assert not moved, f"{len(moved)} results depend on what the scratch held; the first: {moved[:10]}"
+    poison_child.assert_unmoved(here, there)
