@@ -36,7 +36,34 @@ struct amt_ctx {
     size_t plan_total;
     bool plan_valid;
     unsigned long long* dbg_first;  // device word of amt_debug_scratch_check (allocated on its first use)
+    // ---- label boxes handed from amt_watershed_edt_cleared to the per-label call that directly follows it ----
+    // op_serial counts the image operations of this context: every entry point that checks operands
+    // (amt_check_operands counts), every copy, fill, allocation, release and synchronisation, and every call that makes
+    // the context's work visible to another stream or to the host (amt_stream_wait on either side, event record / wait /
+    // sync, amt_timer_elapsed_ms) advances it.  The note names the label planes whose boxes box_buf holds (grow-only,
+    // outside the arena, which the next op reuses) and the serial of the call that enqueued them; amt_box_note_take
+    // (below) is the one look at it.
+    unsigned long long op_serial;
+    int* box_buf;
+    size_t box_cap;  // ints
+    struct {
+        bool valid;
+        const void* labels;
+        int nplanes, H, W, max_label, device;
+        unsigned long long serial;
+    } box_note;
 };
+static inline void amt_note_op(amt_ctx* ctx) {
+    if (ctx) ++ctx->op_serial;
+}
+// amt_ctx.hip.  amt_box_buffer: box_buf with room for `ints` ints (drops the note; may synchronise to grow).
+// amt_box_note_leave: the producer has ENQUEUED the boxes {ymin, xmin, ymax, xmax} of labels 1..max_label of these planes.
+// amt_box_note_take: the consumer's one look -- the boxes if the note was left by the image operation directly before
+// the current one on this context and names exactly these planes, else nullptr; the note is gone either way.
+int amt_box_buffer(amt_ctx* ctx, size_t ints, int** buf);
+void amt_box_note_leave(amt_ctx* ctx, const void* labels, int nplanes, int H, int W, int max_label);
+const int* amt_box_note_take(amt_ctx* ctx, const void* labels, int nplanes, int H, int W, int max_label);
+bool amt_poison_enabled();  // AMT_DEBUG_POISON=1
 
 // fork: aux streams wait for everything enqueued so far on the main stream; join: main waits for them
 int amt_fork(amt_ctx* ctx);
@@ -78,11 +105,12 @@ void amt_set_error(const char* fmt, ...);
 
 // ---- operand aliasing (include/amt_hip.h, Conventions) ---------------------------------------------------------
 // Every entry point that writes device memory hands its device operands to amt_check_operands FIRST: before the context
-// is touched and before anything is reserved or launched (a refusal needs no device; a few pointer comparisons on the
-// host, no launch, no synchronisation).  Inputs may overlap inputs.  An output -- caller-owned scratch and in/out planes
-// included -- must not overlap any other operand, except that it may COINCIDE with the inputs named in `inplace` (a mask
-// over the indices of the operand list): same start, same byte length, same element size.  A null pointer or a length of
-// zero is an absent operand.
+// is touched -- but for its count of image operations, which amt_check_operands advances (amt_note_op) -- and before
+// anything is reserved or launched (a refusal needs no device; a few pointer comparisons on the host, no launch, no
+// synchronisation).  Inputs may overlap inputs.  An output -- caller-owned scratch and in/out planes included -- must
+// not overlap any other operand, except that it may COINCIDE with the inputs named in `inplace` (a mask over the
+// indices of the operand list): same start, same byte length, same element size.  A null pointer or a length of zero is
+// an absent operand.
 struct amt_operand {
     const char* name;
     const void* ptr;
@@ -117,11 +145,13 @@ static inline size_t amt_esize(int dtype) {
         default: return 0;  // an unknown code: the operand counts as absent, the entry point refuses the code
     }
 }
-int amt_check_operands(const char* op, const amt_operand* ops, int n);
+// counts an image operation of `ctx` (nullable), refused or not, then checks
+int amt_check_operands(amt_ctx* ctx, const char* op, const amt_operand* ops, int n);
+// needs the entry point's context in scope under the name `ctx`
 #define AMT_CHECK_OPERANDS(op, ...)                                                              \
     do {                                                                                         \
         const amt_operand _ops[] = {__VA_ARGS__};                                                \
-        AMT_TRY(amt_check_operands(op, _ops, (int)(sizeof(_ops) / sizeof(_ops[0]))));            \
+        AMT_TRY(amt_check_operands(ctx, op, _ops, (int)(sizeof(_ops) / sizeof(_ops[0]))));       \
     } while (0)
 
 // ---- scratch ----------------------------------------------------------------------------------

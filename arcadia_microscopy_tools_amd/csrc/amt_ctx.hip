@@ -12,7 +12,8 @@ void amt_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-int amt_check_operands(const char* op, const amt_operand* ops, int n) {
+int amt_check_operands(amt_ctx* ctx, const char* op, const amt_operand* ops, int n) {
+    amt_note_op(ctx);
     for (int i = 0; i < n; ++i) {
         const amt_operand& a = ops[i];
         if (!a.ptr || !a.bytes) continue;
@@ -110,6 +111,7 @@ extern "C" int amt_ctx_destroy(amt_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->dbg_first) (void)hipFree(ctx->dbg_first);
+    if (ctx->box_buf) (void)hipFree(ctx->box_buf);
     if (ctx->mailbox) (void)hipHostFree(ctx->mailbox);
     if (ctx->aux_ready) {
         for (int i = 0; i < 3; ++i) (void)hipStreamDestroy(ctx->aux_own[i]);
@@ -138,6 +140,43 @@ static bool poison_enabled() {
         v = (e && e[0] == '1') ? 1 : 0;
     }
     return v == 1;
+}
+bool amt_poison_enabled() { return poison_enabled(); }
+
+// ---- the hand-off of label boxes (amt_common.h: amt_ctx::box_note) ----
+int amt_box_buffer(amt_ctx* ctx, size_t ints, int** buf) {
+    ctx->box_note.valid = false;  // whatever the buffer held is about to be replaced
+    if (ints > ctx->box_cap) {
+        // an earlier hand-off's copy may still be reading the buffer: drain the stream before freeing
+        AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (ctx->box_buf) AMT_HIP_CHECK(hipFree(ctx->box_buf));
+        ctx->box_buf = nullptr;
+        ctx->box_cap = 0;
+        const size_t cap = ints + ints / 4;
+        hipError_t e = hipMalloc((void**)&ctx->box_buf, cap * sizeof(int));
+        if (e != hipSuccess) {
+            amt_set_error("label box buffer allocation of %zu bytes failed: %s", cap * sizeof(int), hipGetErrorString(e));
+            return AMT_ENOMEM;
+        }
+        ctx->box_cap = cap;
+    }
+    *buf = ctx->box_buf;
+    return AMT_OK;
+}
+
+void amt_box_note_leave(amt_ctx* ctx, const void* labels, int nplanes, int H, int W, int max_label) {
+    // a borrowed stream (amt_ctx_create_on_stream) carries its owner's work between two calls of the library, ordered
+    // and unseen: no note there
+    if (!ctx->own_stream) return;
+    ctx->box_note = {true, labels, nplanes, H, W, max_label, ctx->device, ctx->op_serial};
+}
+
+const int* amt_box_note_take(amt_ctx* ctx, const void* labels, int nplanes, int H, int W, int max_label) {
+    const auto n = ctx->box_note;
+    ctx->box_note.valid = false;  // one look, used or not
+    const bool hit = n.valid && n.serial + 1 == ctx->op_serial && n.labels == labels && n.nplanes == nplanes && n.H == H &&
+                     n.W == W && n.max_label == max_label && n.device == ctx->device && ctx->box_buf;
+    return hit ? ctx->box_buf : nullptr;
 }
 
 int amt_scratch::commit() {
@@ -301,6 +340,7 @@ int amt_param_upload(amt_ctx* ctx, void* dev_dst, const void* host_src, size_t b
 }
 
 extern "C" int amt_malloc(amt_ctx* ctx, size_t bytes, void** dptr) {
+    amt_note_op(ctx);
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(dptr != nullptr, "amt_malloc: dptr is null");
     if (bytes == 0) bytes = 256;
@@ -317,32 +357,38 @@ extern "C" int amt_malloc(amt_ctx* ctx, size_t bytes, void** dptr) {
 }
 
 extern "C" int amt_free(amt_ctx* ctx, void* dptr) {
+    amt_note_op(ctx);
     AMT_TRY(amt_set_device(ctx));
     if (dptr) AMT_HIP_CHECK(hipFree(dptr));
     return AMT_OK;
 }
 
 extern "C" int amt_memcpy_h2d(amt_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    amt_note_op(ctx);
     AMT_TRY(amt_set_device(ctx));
     if (bytes) AMT_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return AMT_OK;
 }
 extern "C" int amt_memcpy_d2h(amt_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    amt_note_op(ctx);
     AMT_TRY(amt_set_device(ctx));
     if (bytes) AMT_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     return AMT_OK;
 }
 extern "C" int amt_memcpy_d2d(amt_ctx* ctx, void* dst, const void* src, size_t bytes) {
+    amt_note_op(ctx);
     AMT_TRY(amt_set_device(ctx));
     if (bytes) AMT_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return AMT_OK;
 }
 extern "C" int amt_memset(amt_ctx* ctx, void* dst, int value, size_t bytes) {
+    amt_note_op(ctx);
     AMT_TRY(amt_set_device(ctx));
     if (bytes) AMT_HIP_CHECK(hipMemsetAsync(dst, value, bytes, ctx->stream));
     return AMT_OK;
 }
 extern "C" int amt_sync(amt_ctx* ctx) {
+    amt_note_op(ctx);
     AMT_TRY(amt_set_device(ctx));
     AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return AMT_OK;
@@ -355,9 +401,11 @@ extern "C" int amt_ctx_stream(amt_ctx* ctx, void** hip_stream) {
 }
 
 extern "C" int amt_stream_wait(amt_ctx* ctx, amt_ctx* other) {
+    amt_note_op(ctx);
     // everything enqueued so far on `other`'s stream happens-before what is enqueued next on `ctx`'s stream
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(other != nullptr, "amt_stream_wait: other is null");
+    amt_note_op(other);  // its work so far is published: `ctx` may change what it wrote
     AMT_REQUIRE(other->device == ctx->device, "amt_stream_wait: contexts on different devices");
     hipEvent_t ev;
     AMT_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -377,12 +425,14 @@ extern "C" int amt_event_create(amt_ctx* ctx, void** event) {
     return AMT_OK;
 }
 extern "C" int amt_event_record(amt_ctx* ctx, void* event) {
+    amt_note_op(ctx);  // publishes the context's work so far to whoever waits for the event
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(event != nullptr, "amt_event_record: event is null");
     AMT_HIP_CHECK(hipEventRecord((hipEvent_t)event, ctx->stream));
     return AMT_OK;
 }
 extern "C" int amt_event_wait(amt_ctx* ctx, void* event) {
+    amt_note_op(ctx);
     // what is enqueued next on ctx's stream happens after the event's last record (no-op if never recorded)
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(event != nullptr, "amt_event_wait: event is null");
@@ -390,6 +440,7 @@ extern "C" int amt_event_wait(amt_ctx* ctx, void* event) {
     return AMT_OK;
 }
 extern "C" int amt_event_sync(amt_ctx* ctx, void* event) {
+    amt_note_op(ctx);  // the host has seen the context's work: it may start anything
     // the HOST waits for the event's last record: a chunked download hands finished chunks to host threads
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(event != nullptr, "amt_event_sync: event is null");
@@ -543,6 +594,7 @@ extern "C" int amt_timer_stop(amt_ctx* ctx, void* timer) {
     return AMT_OK;
 }
 extern "C" int amt_timer_elapsed_ms(amt_ctx* ctx, void* timer, float* ms) {
+    amt_note_op(ctx);  // a host synchronisation on the stop event
     AMT_TRY(amt_set_device(ctx));
     amt_timer* t = (amt_timer*)timer;
     AMT_HIP_CHECK(hipEventSynchronize(t->stop));

@@ -159,6 +159,10 @@ int amt_i_component_filter(amt_ctx* ctx, const uint8_t* in, uint8_t* out, int np
 // cleared by the same launch
 int amt_i_label_boxes(amt_ctx* ctx, const int* labels, int* bbox, unsigned long long* acc, int nplanes, int H, int W,
                       int max_label);
+// the plane pass alone, over the planes whose flag in only_planes[] (device) is non-zero: their labels' extremes are
+// folded into bbox by atomics, so bbox must hold empty boxes or parts of the true ones (amt_watershed.hip's fused tail)
+int amt_i_label_boxes_flagged(amt_ctx* ctx, const int* labels, int* bbox, const int* only_planes, int nplanes, int H, int W,
+                              int max_label);
 // The table bits of amt_regionprops_ext, which checks the arguments and makes the bounding boxes; wtable[plane][label]
 // [channel] holds four columns.  AMT_RPX_ROBUST (amt_robust.hip): {q25, median, q75, MAD} of the AMT_U16 / AMT_F64
 // channel over the label

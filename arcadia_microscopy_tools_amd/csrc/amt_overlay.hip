@@ -73,7 +73,7 @@ extern "C" int amt_overlay(amt_ctx* ctx, const double* background, const double*
         ops[k++] = amt_out("out_rgb", out_rgb, amt_span(8, H, W, 3));
         for (int l = 0; layers_host && l < nlayers && l < OV_MAX_LAYERS; ++l)
             ops[k++] = amt_in(lname[l], layers_host[l], amt_span(8, H, W));
-        AMT_TRY(amt_check_operands("amt_overlay", ops, k));
+        AMT_TRY(amt_check_operands(ctx, "amt_overlay", ops, k));
     }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(background && out_rgb && H > 0 && W > 0, "overlay: bad arguments");

@@ -20,16 +20,26 @@ typedef unsigned long long u64;
 // accumulator slots per (plane, label)
 enum { A_N = 0, A_SY, A_SX, A_SYY, A_SXX, A_SXY, A_C1, A_C2, A_C3, A_NACC };
 
-// empty boxes (amt_box of amt_perlabel.h) and, with `acc`, cleared accumulators
-__global__ void __launch_bounds__(256) rp_init_kernel(u64* __restrict__ acc, int* __restrict__ bbox, size_t nlab) {
+// empty boxes (amt_box of amt_perlabel.h) -- or, with `src`, the boxes the watershed's tail left with the context -- and,
+// with `acc`, cleared accumulators
+__global__ void __launch_bounds__(256) rp_init_kernel(u64* __restrict__ acc, int* __restrict__ bbox, size_t nlab,
+                                                      const int* __restrict__ src) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nlab; i += (size_t)gridDim.x * 256) {
         if (acc)
             for (int k = 0; k < A_NACC; ++k) acc[i * A_NACC + k] = 0;
-        bbox[i * 4 + 0] = 0x7fffffff;
-        bbox[i * 4 + 1] = 0x7fffffff;
-        bbox[i * 4 + 2] = -1;
-        bbox[i * 4 + 3] = -1;
+        bbox[i * 4 + 0] = src ? src[i * 4 + 0] : 0x7fffffff;
+        bbox[i * 4 + 1] = src ? src[i * 4 + 1] : 0x7fffffff;
+        bbox[i * 4 + 2] = src ? src[i * 4 + 2] : -1;
+        bbox[i * 4 + 3] = src ? src[i * 4 + 3] : -1;
     }
+}
+
+// AMT_DEBUG_POISON=1: the boxes that were handed over against those of the plane pass; *first = the smallest index of an
+// int that differs
+__global__ void __launch_bounds__(256) rp_boxes_differ_kernel(const int* __restrict__ a, const int* __restrict__ b, size_t n,
+                                                              u64* __restrict__ first) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+        if (a[i] != b[i]) atomicMin(first, (u64)i);
 }
 
 // exact a*b - c*d for 64-bit operands, as a double (the difference itself must fit in 127 bits)
@@ -60,16 +70,19 @@ __device__ __forceinline__ double diff_of_products(u64 a, u64 b, u64 c, u64 d) {
 // loaded and counts as another label: a request too many there, never one too few.
 // VEC: the plane pointer is 16-byte aligned and W % 4 == 0 (every row, of every plane, then starts on 16 bytes);
 // otherwise four scalar loads per lane (odd widths, sliced planes).
+// only_planes (nullable): planes whose flag is 0 are skipped (the watershed's tail, which has the boxes of all but the
+// planes it flags: amt_i_label_boxes_flagged).
 constexpr int BX_ROWS = 30, BX_COLS = 256, BX_BATCH = 4, BX_NBATCH = (BX_ROWS + 2) / BX_BATCH;
 static_assert(BX_BATCH * BX_NBATCH == BX_ROWS + 2, "row batches must tile the strip");
 
 template <bool VEC>
 __global__ void __launch_bounds__(256) rp_boxes_kernel(const int* __restrict__ labels, int* __restrict__ bbox, int H,
-                                                       int W, int max_label) {
+                                                       int W, int max_label, const int* __restrict__ only_planes) {
     const int lane = threadIdx.x & 63;
     const int strip = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (strip > (W - 1) / BX_COLS) return;  // whole wave; the kernel has no barrier
     const int plane = blockIdx.z;
+    if (only_planes && !only_planes[plane]) return;
     const int* L = labels + (size_t)plane * H * W;
     int* bbp = bbox + (size_t)plane * max_label * 4;
     const unsigned x = (unsigned)strip * BX_COLS + 4u * lane;  // the first of the lane's four columns
@@ -155,20 +168,56 @@ __global__ void __launch_bounds__(256) rp_boxes_kernel(const int* __restrict__ l
     }
 }
 
-// The box pass of every per-label operation: bbox[plane][label] = the label's box, empty for an absent label; `acc`
-// (nullable) = the A_NACC accumulators per (plane, label), cleared by the same launch.
-int amt_i_label_boxes(amt_ctx* ctx, const int* labels, int* bbox, unsigned long long* acc, int nplanes, int H, int W,
-                      int max_label) {
-    const size_t nlab = (size_t)nplanes * max_label;
-    hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab);
-    AMT_LAUNCH_CHECK();
+// the plane pass: boxes folded into `bbox` (whose entries are empty boxes or parts of the true ones) by atomics
+static int rp_boxes_pass(amt_ctx* ctx, const int* labels, int* bbox, int nplanes, int H, int W, int max_label,
+                         const int* only_planes) {
     const int nstrips = (W - 1) / BX_COLS + 1;
     const dim3 grid((nstrips + 3) / 4, (H - 1) / BX_ROWS + 1, nplanes);
     if ((uintptr_t)labels % 16 == 0 && W % 4 == 0)
-        hipLaunchKernelGGL(rp_boxes_kernel<true>, grid, dim3(256), 0, ctx->stream, labels, bbox, H, W, max_label);
+        hipLaunchKernelGGL(rp_boxes_kernel<true>, grid, dim3(256), 0, ctx->stream, labels, bbox, H, W, max_label, only_planes);
     else
-        hipLaunchKernelGGL(rp_boxes_kernel<false>, grid, dim3(256), 0, ctx->stream, labels, bbox, H, W, max_label);
+        hipLaunchKernelGGL(rp_boxes_kernel<false>, grid, dim3(256), 0, ctx->stream, labels, bbox, H, W, max_label, only_planes);
     AMT_LAUNCH_CHECK();
+    return AMT_OK;
+}
+
+int amt_i_label_boxes_flagged(amt_ctx* ctx, const int* labels, int* bbox, const int* only_planes, int nplanes, int H, int W,
+                              int max_label) {
+    return rp_boxes_pass(ctx, labels, bbox, nplanes, H, W, max_label, only_planes);
+}
+
+// The box pass of every per-label operation: bbox[plane][label] = the label's box, empty for an absent label; `acc`
+// (nullable) = the A_NACC accumulators per (plane, label), cleared by the same launch.
+// The hand-off ("Label boxes from the watershed's tail"): when the image operation directly before this one on
+// the context was the amt_watershed_edt_cleared that wrote exactly these planes, the boxes it left with the context are
+// copied by the clearing launch and the label planes are not read.  With AMT_DEBUG_POISON=1 the plane pass runs all the
+// same and the call fails unless the two tables agree.
+int amt_i_label_boxes(amt_ctx* ctx, const int* labels, int* bbox, unsigned long long* acc, int nplanes, int H, int W,
+                      int max_label) {
+    const size_t nlab = (size_t)nplanes * max_label;
+    const int* handed = amt_box_note_take(ctx, labels, nplanes, H, W, max_label);
+    const bool check = handed && amt_poison_enabled();
+    hipLaunchKernelGGL(rp_init_kernel, dim3(amt_grid_for(nlab, 256, 1024)), dim3(256), 0, ctx->stream, acc, bbox, nlab,
+                       check ? (const int*)nullptr : handed);
+    AMT_LAUNCH_CHECK();
+    if (handed && !check) return AMT_OK;
+    AMT_TRY(rp_boxes_pass(ctx, labels, bbox, nplanes, H, W, max_label, nullptr));
+    if (check) {
+        if (!ctx->dbg_first) AMT_HIP_CHECK(hipMalloc((void**)&ctx->dbg_first, sizeof(unsigned long long)));
+        AMT_HIP_CHECK(hipMemsetAsync(ctx->dbg_first, 0xFF, sizeof(unsigned long long), ctx->stream));
+        hipLaunchKernelGGL(rp_boxes_differ_kernel, dim3(amt_grid_for(nlab * 4, 256, 1024)), dim3(256), 0, ctx->stream, handed,
+                           (const int*)bbox, nlab * 4, ctx->dbg_first);
+        AMT_LAUNCH_CHECK();
+        unsigned long long first = 0;
+        AMT_HIP_CHECK(hipMemcpyAsync(&first, ctx->dbg_first, sizeof(first), hipMemcpyDeviceToHost, ctx->stream));
+        AMT_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (first != ~0ull) {
+            amt_set_error("label boxes: the boxes handed over by amt_watershed_edt_cleared differ from the plane pass at "
+                          "plane %llu, label %llu, field %llu",
+                          first / 4 / (unsigned long long)max_label, first / 4 % (unsigned long long)max_label + 1, first % 4);
+            return AMT_EHIP;
+        }
+    }
     return AMT_OK;
 }
 

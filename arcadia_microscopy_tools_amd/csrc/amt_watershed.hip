@@ -64,6 +64,8 @@ constexpr int M_PX = 4096, M_NB = 512;
 constexpr int M2_PX = 8192, M2_NB = 1024;
 constexpr int L_PX = 24576, L_NB = 2048;
 constexpr int X_PX = 32512, X_NB = 2048;  // pixel indices must fit the 15-bit link field
+// ws_flood_boxes_kernel: workgroups of four waves per plane, a piece of WS_BOX_ROWS rows x 64 columns per wave and turn
+constexpr int WS_BOX_BLOCKS = 64, WS_BOX_ROWS = 32;
 
 struct comp_row {
     int cmax;            // max d2 (bucket mode) or pixel count (heap mode)
@@ -1857,12 +1859,35 @@ __global__ void __launch_bounds__(256) ws_final_kernel(const int* __restrict__ L
 // presence_fill + the marking of the frame-touching labels + drop_flagged + presence_scan (amt_label.hip) for one plane
 // per workgroup:
 // P[l] = new label of l (0 = absent or touching the frame), count[plane] = number of survivors
+// With `bx.bbox` (the run-table path) the workgroup then starts the plane's table of FINAL label boxes, {ymin, xmin, ymax,
+// xmax} as amt_i_label_boxes makes them: every entry empty, then the box of every single-label component -- which
+// ws_stats_runs_kernel put into its comp_row from ALL its runs before any class was known -- folded into the entry of its
+// final label.  Atomics, not stores: markers are the caller's, and one label may seed components that do not touch.
+// Flooded components, whose labels exist per pixel only, are listed for ws_flood_boxes_kernel, cut into pieces of
+// WS_BOX_ROWS rows x 64 columns so that no wave has more than WS_BOX_ROWS / 4 round trips to memory in front of it: a
+// 130 x 144 plane that is one component cost 0.14 ms more than before with one wave per component, 0.05-0.07 ms with
+// pieces.  On 48 planes of 2048 x 2048 the pieces changed little (105 -> 100 us), so the depth of the walk is not what
+// bounds it there; what does is not measured (profiles/label_box_handoff.json: supposedly the requests).  A component whose box is above the walk's limit -- the box
+// alone decides, not the class: a small class-G component (16-bit labels, a distance above the bucket limit) is walked --
+// or whose pieces no longer fit the list raises the plane's flag instead (ws_fused_tail); a flagged plane is not walked
+// at all.
+struct ws_box_args {
+    int* bbox;              // [nplanes][max_label][4]; nullptr = no boxes
+    const comp_row* rows;
+    const int* ncomp;
+    size_t row_stride;
+    int2* flist;            // [nplanes][row_stride / 2]: {component row, band | chunk << 16} of every piece to walk
+    int* fcount;            // [nplanes]: pieces listed (0 for a flagged plane)
+    int* fbig;              // [nplanes]: the plane holds a flooded component that is not walked
+};
+
 __global__ void __launch_bounds__(1024) ws_label_map_kernel(const int* __restrict__ L, const int* __restrict__ F,
                                                             const int* __restrict__ ws, int* __restrict__ present,
                                                             const int* __restrict__ nlabels, int* __restrict__ count_dev,
-                                                            int H, int W, int max_label, amt_runtabs rt) {
+                                                            int H, int W, int max_label, amt_runtabs rt, ws_box_args bx) {
     __shared__ int s[1024];
     __shared__ int carry;
+    __shared__ int nwalk, big;
     const int plane = blockIdx.x;
     const size_t n = (size_t)H * W;
     const size_t base = (size_t)plane * n;
@@ -1918,6 +1943,102 @@ __global__ void __launch_bounds__(1024) ws_label_map_kernel(const int* __restric
         __syncthreads();
     }
     if (threadIdx.x == 0) count_dev[plane] = carry;
+    if (!bx.bbox) return;  // whole workgroup
+    int* B = bx.bbox + (size_t)plane * max_label * 4;
+    for (int i = threadIdx.x; i < max_label * 4; i += 1024) B[i] = (i & 2) ? -1 : 0x7fffffff;
+    if (threadIdx.x == 0) nwalk = 0, big = 0;
+    __syncthreads();  // also: P is final (the scan's last barrier, or the one before it when max_label == 0)
+    const comp_row* rows = bx.rows + (size_t)plane * bx.row_stride;
+    const int fcap = (int)(bx.row_stride / 2);
+    int2* fl = bx.flist + (size_t)plane * fcap;
+    const int nc = bx.ncomp[plane];
+    for (int i = threadIdx.x; i < nc; i += 1024) {
+        const comp_row c = rows[i];
+        if (c.cls == CLS_UNIFORM) {
+            const int m = (unsigned)(c.labmin - 1) < (unsigned)max_label ? P[c.labmin] : 0;
+            if (m > 0) {
+                int* b = B + (size_t)(m - 1) * 4;
+                atomicMin(&b[0], c.y0);
+                atomicMin(&b[1], c.x0);
+                atomicMax(&b[2], c.y1);
+                atomicMax(&b[3], c.x1);
+            }
+        } else if (c.cls >= CLS_S) {
+            // the walk's limit is the largest LDS flood class's, measured like it (with the ring around the box)
+            const long long area = (long long)(c.x1 - c.x0 + 3) * (c.y1 - c.y0 + 3);
+            const int nb = (c.y1 - c.y0) / WS_BOX_ROWS + 1, nch = (c.x1 - c.x0) / 64 + 1;
+            // a list too short for the pieces (reservations only grow: every later one fails as well)
+            const int at = area > X_PX ? fcap : atomicAdd(&nwalk, nb * nch);
+            if (area > X_PX || at > fcap - nb * nch) {
+                big = 1;  // several threads may store the same 1: no atomic needed
+            } else {
+                for (int k = 0; k < nb * nch; ++k) fl[at + k] = make_int2(i, (k % nb) | ((k / nb) << 16));
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) bx.fcount[plane] = big ? 0 : nwalk, bx.fbig[plane] = big;
+}
+
+// The boxes of the labels of flooded components: a wave per listed piece (WS_BOX_ROWS rows x 64 columns of a component's
+// box) walks it in the FINAL label plane, a three-row window in registers, loads four rows ahead; the rows above and
+// below a piece are read like its own.  A pixel asks for an extreme of its label by the filters of rp_boxes_kernel: for
+// ymin / ymax only as the head of a run with another label above / below it, for xmin only as a head with no pixel of
+// the label above-left or below-left, for xmax as a tail likewise.  What lies left of a piece's first lane and right of
+// its last one is not looked at and counts as another label: a request too many, never one too few.  Pixels of
+// neighbouring components inside the box ask with true coordinates of their own labels, which their own components ask
+// for as well.
+__global__ void __launch_bounds__(256) ws_flood_boxes_kernel(const int* __restrict__ labels, ws_box_args bx, int H, int W,
+                                                             int max_label) {
+    const int lane = threadIdx.x & 63;
+    const int plane = blockIdx.y;
+    const int cnt = bx.fcount[plane];
+    const int* Lp = labels + (size_t)plane * H * W;
+    int* B = bx.bbox + (size_t)plane * max_label * 4;
+    const comp_row* rows = bx.rows + (size_t)plane * bx.row_stride;
+    const int2* fl = bx.flist + (size_t)plane * (bx.row_stride / 2);
+    const unsigned ml = (unsigned)max_label;
+    constexpr int FQ = 4;  // rows whose loads are in flight together
+    for (int j = blockIdx.x * 4 + (threadIdx.x >> 6); j < cnt; j += gridDim.x * 4) {  // wave-uniform
+        const int2 it = fl[j];
+        const comp_row c = rows[it.x];
+        const int ya = c.y0 + (it.y & 0xffff) * WS_BOX_ROWS;
+        const int yb = ya + WS_BOX_ROWS - 1 < c.y1 ? ya + WS_BOX_ROWS - 1 : c.y1;
+        const int x = c.x0 + (it.y >> 16) * 64 + lane;
+        const bool in = x <= c.x1;  // c.x1 < W
+        const int xl = in ? x : c.x1;
+        // rows outside the image and lanes outside the box hold 0: another label
+        auto load = [&](int y) -> int {
+            int v = 0;
+            if (in && y >= 0 && y < H && y <= yb + 1) v = Lp[(size_t)y * W + xl];
+            return (unsigned)(v - 1) < ml ? v : 0;
+        };
+        int up = load(ya - 1), cur = load(ya);
+        for (int y = ya; y <= yb; y += FQ) {
+            int nx[FQ];
+#pragma unroll
+            for (int q = 0; q < FQ; ++q) nx[q] = load(y + 1 + q);
+#pragma unroll
+            for (int q = 0; q < FQ; ++q) {
+                const int yy = y + q;
+                if (yy > yb) break;  // uniform
+                const int dn = nx[q];
+                const int l = amt_lane_left(cur), r = amt_lane_right(cur);
+                const int ul = amt_lane_left(up), ur = amt_lane_right(up);
+                const int dl = amt_lane_left(dn), dr = amt_lane_right(dn);
+                if (cur) {
+                    int* b = B + (size_t)(cur - 1) * 4;
+                    const bool head = l != cur, tail = r != cur;
+                    if (head && up != cur) atomicMin(&b[0], yy);
+                    if (head && dn != cur) atomicMax(&b[2], yy);
+                    if (head && ul != cur && dl != cur) atomicMin(&b[1], x);
+                    if (tail && ur != cur && dr != cur) atomicMax(&b[3], x);
+                }
+                up = cur;
+                cur = dn;
+            }
+        }
+    }
 }
 
 // ws_final_kernel from the run tables: a wave per tile turns (row words, run table, the final label of every tile root,
@@ -2065,6 +2186,7 @@ struct ws_bufs {
     int *L, *T, *moff, *boff, *cursor, *mlist, *next, *F, *rootlist, *nroots;
     comp_row* rows;
     int *btot, *mtot, *counters, *wl, *pf_idx, *pf_ctl, *ccl_scratch, *ties, *P;
+    int* fctl;  // ws_box_args: per plane the number of listed pieces, then the plane's flag
     unsigned long long* tbits;
     unsigned short* rtab;
     int* nruns;
@@ -2236,8 +2358,17 @@ static int ws_fused_tail(const ws_args& a, const ws_bufs& b) {
     amt_ctx* ctx = a.ctx;
     const ccl_geom& g = a.g;
     const ws_fused& fu = a.fu;
+    // the run-table path leaves the boxes of the final labels with the context, for the per-label call that follows
+    ws_box_args bx = {};
+    if (a.runs && fu.max_label > 0 && ctx->own_stream) {  // a borrowed stream takes no note (amt_box_note_leave)
+        AMT_TRY(amt_box_buffer(ctx, (size_t)a.nplanes * fu.max_label * 4, &bx.bbox));
+        bx.rows = b.rows, bx.ncomp = b.ncomp, bx.row_stride = a.row_stride;
+        // the list lives in `cursor`: the HBM flood's preparation was its last user, and row_stride ints hold
+        // row_stride / 2 pieces
+        bx.flist = reinterpret_cast<int2*>(b.cursor), bx.fcount = b.fctl, bx.fbig = b.fctl + a.nplanes;
+    }
     hipLaunchKernelGGL(ws_label_map_kernel, dim3(a.nplanes), dim3(1024), 0, ctx->stream, b.L, b.F, a.out, b.P, fu.nlabels_dev,
-                       fu.count, a.H, a.W, fu.max_label, b.rt);
+                       fu.count, a.H, a.W, fu.max_label, b.rt, bx);
     AMT_LAUNCH_CHECK();
     if (a.runs) {
         hipLaunchKernelGGL(ws_final_map_kernel, g.glists, dim3(256), 0, ctx->stream, b.F, b.P, b.rootlist, b.nroots, g.cap, a.n,
@@ -2245,6 +2376,16 @@ static int ws_fused_tail(const ws_args& a, const ws_bufs& b) {
         AMT_LAUNCH_CHECK();
         hipLaunchKernelGGL(ws_final_runs_kernel, dim3((unsigned)((g.ntiles + 3) / 4)), dim3(256), 0, ctx->stream, b.tbits, b.rtab,
                            b.nruns, b.F, a.out, b.P, fu.labels, a.H, a.W, g.segs, g.trows, (int)g.ntiles, fu.max_label);
+        if (bx.bbox) {
+            AMT_LAUNCH_CHECK();
+            hipLaunchKernelGGL(ws_flood_boxes_kernel, dim3(WS_BOX_BLOCKS, a.nplanes), dim3(256), 0, ctx->stream,
+                               (const int*)fu.labels, bx, a.H, a.W, fu.max_label);
+            AMT_LAUNCH_CHECK();
+            // planes with a flooded component too large to walk: the plane pass, whose blocks leave at once elsewhere
+            // (no host synchronisation: the flags stay on the device)
+            AMT_TRY(amt_i_label_boxes_flagged(ctx, fu.labels, bx.bbox, bx.fbig, a.nplanes, a.H, a.W, fu.max_label));
+            amt_box_note_leave(ctx, fu.labels, a.nplanes, a.H, a.W, fu.max_label);
+        }
     } else {
         hipLaunchKernelGGL(ws_final_kernel, dim3(amt_grid_for(a.n, 1024, 4096), a.nplanes), dim3(256), 0, ctx->stream, b.L, b.F,
                            a.out, b.P, fu.labels, a.n, fu.max_label);
@@ -2303,6 +2444,7 @@ static int watershed_components(amt_ctx* ctx, const void* relief, bool use_d2, c
     amt_buf<int> nruns(s, g.ntiles, runs);
     amt_buf<unsigned short> roff(s, g.ntiles * 64, runs);
     amt_buf<int> rcomp(s, g.ntiles * RT_CAP, runs);  // only the runs that exist are touched
+    amt_buf<int> fctl(s, (size_t)2 * nplanes, runs);
     // the sequential emulation's heap (every pixel is pushed at most once): the float64 path reuses its per-component
     // heap space (bstride == n: those heaps are dead when the emulation starts), the bucket path needs it extra -- and
     // only when ties are to be resolved exactly
@@ -2316,6 +2458,7 @@ static int watershed_components(amt_ctx* ctx, const void* relief, bool use_d2, c
     b.rootlist = rootlist, b.nroots = nroots, b.rows = rows, b.btot = btot, b.mtot = mtot, b.counters = counters, b.wl = wl;
     b.pf_idx = pf_idx, b.pf_ctl = pf_ctl, b.ccl_scratch = ccl_scratch, b.P = P;
     b.tbits = tbits, b.rtab = rtab, b.nruns = nruns, b.roff = roff, b.rcomp = rcomp, b.head = head, b.tail = tail;
+    b.fctl = fctl;
     b.ties = ties_dev ? ties_dev : ties_own.p;
     b.heap = heap, b.gheap = use_d2 ? gheap_own.p : heap.p;
     b.ncomp = b.counters + WS_CTR_NCOMP * (size_t)nplanes;

@@ -560,7 +560,22 @@ int amt_watershed_f64(amt_ctx* ctx, const double* relief, const int32_t* markers
  * marker_list[plane * list_capacity ...][0 .. marker_count[plane]) = flat indices of every non-zero pixel of the marker
  * plane): the per-component marker statistics come from the list and the dense statistics pass does not read the
  * marker plane (4 of its 12 bytes per pixel).  A plane whose list is incomplete (count above the capacity) gives
- * undefined labels -- amt_label_sparse reports that plane with count -1. */
+ * undefined labels -- amt_label_sparse reports that plane with count -1.
+ * Label boxes.  With a marker list, W % 16 == 0 and 16-byte aligned planes (the path that works from the mask's run
+ * tables) the call also leaves the bounding boxes of its final labels with the context.  The per-label entry point --
+ * amt_regionprops, amt_regionprops_ext, amt_regionprops_intensity_f64, amt_colocalization, amt_label_bboxes -- that is
+ * the DIRECTLY FOLLOWING image operation on the same context and names the same labels_out, nplanes, H, W and max_label
+ * takes these boxes and does not read the label planes for them.  Any other operation in between voids them: every
+ * entry point that takes device operands, every amt_memcpy_*, amt_memset, amt_malloc, amt_free and amt_sync, and every
+ * call through which the context's work becomes visible to another stream or to the host -- amt_stream_wait (on the
+ * waiting context AND on the one waited for), amt_event_record, amt_event_wait, amt_event_sync, amt_timer_elapsed_ms.
+ * amt_timer_start / amt_timer_stop, amt_last_error, amt_version and amt_device_name do not.  The boxes serve one call,
+ * and results are the same either way.  A context on a borrowed stream (amt_ctx_create_on_stream) leaves no boxes: its
+ * owner's work runs on that stream between two calls of the library, ordered and unseen.  What remains: between two
+ * consecutive calls on a context with its own stream, labels_out can only change through work that races with this
+ * call's kernels, or through a caller that takes the raw stream (amt_ctx_stream) and orders or synchronises on it
+ * outside the library; such a caller issues any image operation or amt_sync on the context before the per-label call.
+ * Every other configuration of the watershed entry points leaves no boxes. */
 int amt_watershed_edt_cleared(amt_ctx* ctx, const int32_t* d2, const int32_t* markers, const uint8_t* mask,
                               int32_t* ws_scratch, int32_t* labels_out, int32_t* count_dev, int nplanes, int H, int W,
                               int max_label, const int32_t* nlabels_dev, const int32_t* marker_list,
@@ -588,7 +603,11 @@ int amt_watershed_edt_cleared(amt_ctx* ctx, const int32_t* d2, const int32_t* ma
  * A.9), nplanes x max_label x C x 4 doubles, from intensity = nplanes x C planes of uint16 (one (C,Y,X) FOV per label
  * plane).  intensity and C >= 1 are given exactly when itable_dev is; at least one table is.  Both tables in one
  * call share the bounding-box pass and the per-label scan: what SegmentationMask.cell_properties needs for a (C,Y,X)
- * field of view (R/masks.py:286-326). */
+ * field of view (R/masks.py:286-326).
+ * This and the other per-label entry points (amt_regionprops_ext, amt_regionprops_intensity_f64, amt_colocalization,
+ * amt_label_bboxes) take their bounding boxes from the amt_watershed_edt_cleared call that directly precedes them on
+ * the context when it wrote exactly these label planes -- see there for the rule and for what a caller who works on the
+ * raw stream owes it; in every other case they read the label planes once for the boxes. */
 int amt_regionprops(amt_ctx* ctx, const int32_t* labels, const uint16_t* intensity, int C, double* table_dev,
                     double* itable_dev, int nplanes, int H, int W, int max_label);
 /* The same {mean, max, min, std} for float64 intensity images (R/masks.py:178-190, :319-323 accept any 2-D ndarray):
