@@ -34,6 +34,14 @@ RANK_LABEL_SKELETON, RANK_LABEL_CENSUS = 8, 9
 LABEL_SKELETON_TILE_ROWS, LABEL_SKELETON_TILE_WORDS, LABEL_SKELETON_BLOCK_SUBITERS = 64, 8, 32
 LCEN_COLS = ("pixels", "isolated", "ends", "path", "junctions", "orth_links", "diag_links")
 LCEN_NCOLS = len(LCEN_COLS)
+# amt_rank_filter: the Z-stack ops (AMT_RANK_Z_*), the columns of a focus-sums row (AMT_ZF_*), the output tile (rows,
+# columns) a workgroup of the focus kernel owns (AMT_ZSTACK_TILE_*) and the largest window radius
+RANK_Z_PROJECT, RANK_Z_FOCUS_SUMS, RANK_Z_FOCUS_INDEX, RANK_Z_FOCUS_STACK, RANK_Z_TAKE = 10, 11, 12, 13, 14
+Z_PROJECT_METHODS = {"max": 0, "min": 1, "mean": 2}
+ZF_COLS = ("sum", "sumsq", "lap_sumsq", "brenner")
+ZF_NCOLS = len(ZF_COLS)
+ZSTACK_TILE = (64, 64)
+ZSTACK_MAX_RADIUS = 15
 WS_TIES ={"exact": 0, "raster": 1, "report": 2, "refuse": 2}
 RP_COLS = (
     "area", "centroid-0", "centroid-1", "bbox-0", "bbox-1", "bbox-2", "bbox-3", "perimeter",

@@ -203,6 +203,15 @@ int amt_i_label_skeleton(amt_ctx* ctx, const void* in, void* out, int dtype, int
 int amt_i_label_census(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W,
                        const uint8_t* footprint, int fh, int fw, int max_label, const void* minuend);
 
+// ---- Z-stacks (amt_zstack.hip): ops AMT_RANK_Z_PROJECT .. AMT_RANK_Z_TAKE of amt_rank_filter, whose `mode` carries Z.
+// amt_i_zstack_spans gives the byte lengths of the three operands for the aliasing check amt_rank_filter makes;
+// amt_i_zstack checks everything else, the refusals that need no device (dtype, Z, footprint, minuend, sizes) before it
+// looks at the context.  Asynchronous, no scratch.
+void amt_i_zstack_spans(int op, int dtype, int nplanes, int H, int W, int Z, double cval, size_t* in_bytes, size_t* out_bytes,
+                        size_t* minuend_bytes);
+int amt_i_zstack(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W, const uint8_t* footprint,
+                 int fh, int fw, int op, int Z, double cval, const void* minuend);
+
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>
 static inline void amt_with_bool(bool b, F&& f) {

@@ -934,12 +934,17 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
                    ? amt_i_label_skeleton(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, mode, minuend)
                    : amt_i_label_census(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, mode, minuend);
     }
+    if (op >= AMT_RANK_Z_PROJECT && op <= AMT_RANK_Z_TAKE) {
+        // Z-stacks (amt_zstack.hip): `mode` carries Z; the `minuend` of AMT_RANK_Z_TAKE is its index map, nothing to subtract
+        *fused = 1;
+        return amt_i_zstack(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, minuend);
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && footprint && nplanes >= 0 && H > 0 && W > 0, "rank_filter: bad arguments");
     AMT_REQUIRE(dtype == AMT_U16 || dtype == AMT_F64, "rank_filter: dtype must be AMT_U16 or AMT_F64");
     AMT_REQUIRE(op >= 0 && op <= 2,
-                "rank_filter: op must be 0 (erosion), 1 (dilation), 2 (median), a reconstruction (3 .. 6) or a label "
-                "skeleton op (8, 9)");
+                "rank_filter: op must be 0 (erosion), 1 (dilation), 2 (median), a reconstruction (3 .. 6), a label "
+                "skeleton op (8, 9) or a Z-stack op (10 .. 14)");
     AMT_REQUIRE((fh & 1) && (fw & 1) && fh >= 1 && fw >= 1 && fh <= 63 && fw <= 63,
                 "rank_filter: footprint must be odd-sized and at most 63 x 63 (got %d x %d)", fh, fw);
     static thread_local int2 host[RK_MAX_OFFS];
@@ -1146,9 +1151,13 @@ extern "C" int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtyp
     AMT_REQUIRE(!minuend || minuend != out, "amt_rank_filter: minuend must differ from out (out must not alias minuend)");
     {
         const size_t bytes = amt_span(amt_esize(dtype), nplanes, H, W);
+        size_t ibytes = bytes, mbytes = bytes;
         // the census writes its int32 table, nplanes x max_label (`mode`) rows, not a plane
-        const size_t obytes = op == AMT_RANK_LABEL_CENSUS ? amt_span(4, nplanes, mode, AMT_LCEN_NCOLS) : bytes;
-        AMT_CHECK_OPERANDS("amt_rank_filter", amt_in("in", in, bytes), amt_out("out", out, obytes), amt_in("minuend", minuend, bytes));
+        size_t obytes = op == AMT_RANK_LABEL_CENSUS ? amt_span(4, nplanes, mode, AMT_LCEN_NCOLS) : bytes;
+        // the Z-stack ops read nplanes x Z (`mode`) planes, and each has its own output and minuend
+        if (op >= AMT_RANK_Z_PROJECT && op <= AMT_RANK_Z_TAKE)
+            amt_i_zstack_spans(op, dtype, nplanes, H, W, mode, cval, &ibytes, &obytes, &mbytes);
+        AMT_CHECK_OPERANDS("amt_rank_filter", amt_in("in", in, ibytes), amt_out("out", out, obytes), amt_in("minuend", minuend, mbytes));
     }
     int fused = 0;
     AMT_TRY(rank_filter_impl(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, minuend, &fused));

@@ -923,6 +923,118 @@ def median(a, footprint=None, mode: str = "nearest", cval: float = 0.0, out=None
     return _rank(a, fp, 2, mode, cval, out)
 
 
+# ---- Z-stacks (amt_rank_filter ops 10 .. 14; include/amt_hip.h states the definitions) ------------------------------
+def zstack_tile() -> tuple[int, int]:
+    """(rows, columns) of the output tile one workgroup of the focus kernel owns (AMT_ZSTACK_TILE_*): planes larger than
+    this cross tile seams."""
+    return _hip.ZSTACK_TILE
+
+
+_Z_CODES = {np.dtype(np.uint8): _hip.U8, np.dtype(np.uint16): _hip.U16, np.dtype(np.float64): _hip.F64}
+
+
+def _zstack(op: str, stack, integer_only: bool = False):
+    """(code, N, Z, H, W) of an (N, Z, H, W) stack batch, refused before any device access"""
+    if not isinstance(stack, DeviceArray):
+        raise ValueError(f"{op}: stack must be a DeviceArray, got {type(stack).__name__}")
+    if stack.ndim != 4:
+        raise ValueError(f"{op} takes (N, Z, H, W) stacks, got shape {stack.shape}")
+    if stack.dtype not in _Z_CODES or (integer_only and stack.dtype == np.float64):
+        want = "uint8 or uint16 (focus is judged on raw data)" if integer_only else "uint8, uint16 or float64"
+        raise ValueError(f"{op}: stacks must be {want}, got {stack.dtype}")
+    N, Z, H, W = stack.shape
+    if not 1 <= Z <= 65535:
+        raise ValueError(f"{op}: Z must be in 1..65535, got {Z}")
+    if H < 1 or W < 1 or H * W >= 2**31:
+        raise ValueError(f"{op}: planes must have 1 <= H * W < 2^31 pixels, got {H} x {W}")
+    return _Z_CODES[stack.dtype], int(N), int(Z), int(H), int(W)
+
+
+def _zstack_radius(op: str, radius) -> int:
+    if isinstance(radius, (bool, np.bool_)):
+        raise ValueError(f"{op}: radius must be an integer in 0..{_hip.ZSTACK_MAX_RADIUS}, got a bool")
+    try:
+        r = int(operator.index(radius))
+    except TypeError:
+        raise ValueError(f"{op}: radius must be an integer in 0..{_hip.ZSTACK_MAX_RADIUS}, got {radius!r}") from None
+    if not 0 <= r <= _hip.ZSTACK_MAX_RADIUS:
+        raise ValueError(f"{op}: radius must be in 0..{_hip.ZSTACK_MAX_RADIUS}, got {r}")
+    return r
+
+
+def _zstack_call(stack, o, code, N, Z, H, W, fp, op, cval=0.0, minuend=None):
+    if N == 0:
+        return o
+    fh = int(fp.shape[0])
+    _hip.check(_lib().amt_rank_filter(stack.ctx.handle, stack.ptr, o.ptr, code, N, H, W, fp.ctypes.data_as(ctypes.c_void_p),
+                                      fh, fh, op, Z, float(cval), None if minuend is None else minuend.ptr), "amt_rank_filter")
+    return o
+
+
+def z_project(stack: DeviceArray, method: str = "max", out: DeviceArray | None = None) -> DeviceArray:
+    """The projection of every (Z, H, W) stack of an (N, Z, H, W) uint8 / uint16 / float64 batch along z -> (N, H, W)
+    (amt_rank_filter, AMT_RANK_Z_PROJECT).  ``method``: "max" and "min" keep the dtype; "mean" gives float64, the sum over
+    z = 0, 1, ... divided once by Z.  All three equal numpy's ``max`` / ``min`` / ``mean(axis=0)`` bit for bit (NaN is
+    unsupported)."""
+    if method not in _hip.Z_PROJECT_METHODS:
+        raise ValueError(f"z_project: method must be 'max', 'min' or 'mean', got {method!r}")
+    code, N, Z, H, W = _zstack("z_project", stack)
+    o = _out(stack.ctx, out, (N, H, W), np.float64 if method == "mean" else stack.dtype)
+    _no_alias("z_project", {"stack": stack}, {"out": o})
+    return _zstack_call(stack, o, code, N, Z, H, W, np.ones((1, 1), np.uint8), _hip.RANK_Z_PROJECT,
+                        _hip.Z_PROJECT_METHODS[method])
+
+
+def focus_sums(stack: DeviceArray, out: DeviceArray | None = None) -> DeviceArray:
+    """Four exact integer sums per plane of an (N, Z, H, W) uint8 / uint16 batch -> (N, Z, 4) int64 in ``_hip.ZF_COLS``
+    order (amt_rank_filter, AMT_RANK_Z_FOCUS_SUMS): the sum of the plane, of its squares, of the squared Laplacian (four
+    neighbours, edge replication) and Brenner's sum of (P(y, x + 2) - P(y, x))^2.  H * W <= 2^27."""
+    code, N, Z, H, W = _zstack("focus_sums", stack, integer_only=True)
+    if H * W > 2**27:
+        raise ValueError(f"focus_sums: H * W must not exceed 2^27, got {H} x {W}")
+    o = _out(stack.ctx, out, (N, Z, _hip.ZF_NCOLS), np.int64)
+    _no_alias("focus_sums", {"stack": stack}, {"out": o})
+    return _zstack_call(stack, o, code, N, Z, H, W, np.ones((1, 1), np.uint8), _hip.RANK_Z_FOCUS_SUMS)
+
+
+def focus_index(stack: DeviceArray, radius: int = 4, out: DeviceArray | None = None) -> DeviceArray:
+    """Per pixel of every stack of an (N, Z, H, W) uint8 / uint16 batch, the plane in best focus -> (N, H, W) uint16
+    (amt_rank_filter, AMT_RANK_Z_FOCUS_INDEX): the smallest z at which the sum of the squared Laplacian over the
+    (2 radius + 1)^2 window, clipped to the image, is largest.  Exact 64-bit integers: two runs give identical bytes.
+    ``radius`` in 0..15.  The rule is this package's own (include/amt_hip.h states it)."""
+    r = _zstack_radius("focus_index", radius)
+    code, N, Z, H, W = _zstack("focus_index", stack, integer_only=True)
+    o = _out(stack.ctx, out, (N, H, W), np.uint16)
+    _no_alias("focus_index", {"stack": stack}, {"out": o})
+    return _zstack_call(stack, o, code, N, Z, H, W, np.ones((2 * r + 1, 2 * r + 1), np.uint8), _hip.RANK_Z_FOCUS_INDEX)
+
+
+def focus_stack(stack: DeviceArray, radius: int = 4, out: DeviceArray | None = None) -> DeviceArray:
+    """The all-in-focus composite of every stack of an (N, Z, H, W) uint8 / uint16 batch -> (N, H, W) of the same dtype
+    (amt_rank_filter, AMT_RANK_Z_FOCUS_STACK): ``stack[focus_index(stack, radius)[y, x], y, x]`` in one pass, without
+    the index map in memory."""
+    r = _zstack_radius("focus_stack", radius)
+    code, N, Z, H, W = _zstack("focus_stack", stack, integer_only=True)
+    o = _out(stack.ctx, out, (N, H, W), stack.dtype)
+    _no_alias("focus_stack", {"stack": stack}, {"out": o})
+    return _zstack_call(stack, o, code, N, Z, H, W, np.ones((2 * r + 1, 2 * r + 1), np.uint8), _hip.RANK_Z_FOCUS_STACK)
+
+
+def z_take(stack: DeviceArray, index: DeviceArray, out: DeviceArray | None = None) -> DeviceArray:
+    """``stack[n, min(index[n, y, x], Z - 1), y, x]`` of an (N, Z, H, W) uint8 / uint16 / float64 batch and an (N, H, W)
+    uint16 index map -> (N, H, W) of the stack's dtype (amt_rank_filter, AMT_RANK_Z_TAKE).  An index past the stack is
+    clamped."""
+    code, N, Z, H, W = _zstack("z_take", stack)
+    if not isinstance(index, DeviceArray) or tuple(index.shape) != (N, H, W) or index.dtype != np.uint16:
+        raise ValueError(f"z_take: index must be a uint16 DeviceArray of shape {(N, H, W)}, got "
+                         f"{getattr(index, 'shape', None)} {getattr(index, 'dtype', type(index).__name__)}")
+    if index.ctx is not stack.ctx:
+        raise ValueError("z_take: stack and index belong to different contexts")
+    o = _out(stack.ctx, out, (N, H, W), stack.dtype)
+    _no_alias("z_take", {"stack": stack, "index": index}, {"out": o})
+    return _zstack_call(stack, o, code, N, Z, H, W, np.ones((1, 1), np.uint8), _hip.RANK_Z_TAKE, minuend=index)
+
+
 # ---- grey reconstruction (amt_rank_filter ops 3 .. 6; include/amt_hip.h states the definitions) --------------------
 def reconstruct_tile(dtype) -> tuple[int, int]:
     """(rows, columns) of the tile one workgroup of the reconstruction kernel owns (AMT_RECONSTRUCT_TILE_*): planes

@@ -517,6 +517,126 @@ def h_minima(image, h, footprint=None):
     return _h_extrema_2d("h_minima", image, h, footprint, False)
 
 
+# ---- Z-stacks: (Z, Y, X) in, one (Y, X) plane out (hipops.z_project .. z_take; include/amt_hip.h states the rules) -----
+_Z_DTYPES = (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.float64))
+FOCUS_METHODS = ("laplacian_variance", "normalized_variance", "brenner")
+_EDF_SMOOTH = (0, 3, 5, 7, 9, 11, 13, 15)
+
+
+def _z_batch(op: str, stack, integer_only: bool = False):
+    """-> ((1, Z, Y, X) DeviceArray, was_numpy) of a (Z, Y, X) stack, refused before any device access"""
+    if isinstance(stack, DeviceArray):
+        d, was_numpy = stack, False
+    else:
+        d, was_numpy = np.asarray(stack), True
+    if d.ndim != 3:
+        raise ValueError(f"{op}: stack must be a (Z, Y, X) array, got shape {tuple(d.shape)}")
+    if d.dtype not in _Z_DTYPES or (integer_only and d.dtype == np.float64):
+        want = "uint8 or uint16 (focus is judged on raw data)" if integer_only else "uint8, uint16 or float64"
+        raise TypeError(f"{op}: stack must be {want}, got {d.dtype}")
+    if min(d.shape) < 1:
+        raise ValueError(f"{op}: stack must not be empty, got shape {tuple(d.shape)}")
+    if was_numpy:
+        d = get_context().asarray(np.ascontiguousarray(d))
+    return d.reshape((1,) + tuple(d.shape)), was_numpy
+
+
+def _z_plane(d: DeviceArray, was_numpy: bool):
+    """The (1, Y, X) result of a batch of one as a (Y, X) plane"""
+    d = d.reshape(d.shape[1:])
+    return d.numpy() if was_numpy else d
+
+
+def _focus_method(op: str, method) -> str:
+    if method not in FOCUS_METHODS:
+        raise ValueError(f"{op}: method must be one of {FOCUS_METHODS}, got {method!r}")
+    return method
+
+
+def _scores_from_sums(sums, n: int, method: str) -> np.ndarray:
+    """float64 scores of the planes whose integer sums are the rows of ``sums`` (hipops.focus_sums), n pixels a plane:
+    exact rationals, rounded once"""
+    from fractions import Fraction
+
+    out = np.empty(len(sums), dtype=np.float64)
+    for z, row in enumerate(sums):
+        s, ss, lap, br = (int(v) for v in row)
+        if method == "laplacian_variance":
+            # the Laplacian sums to 0 under edge replication (the differences telescope): its mean square IS its variance
+            out[z] = float(Fraction(lap, n))
+        elif method == "normalized_variance":
+            out[z] = float(Fraction(n * ss - s * s, n * s)) if s else 0.0
+        else:
+            out[z] = float(br)
+    return out
+
+
+@device_operator
+def z_project(stack, method: str = "max"):
+    """The maximum, minimum or mean projection of a (Z, Y, X) uint8 / uint16 / float64 stack along z: numpy's
+    ``stack.max(axis=0)`` / ``min`` / ``mean`` bit for bit (the mean is float64).  numpy in gives numpy out; a
+    ``DeviceArray`` stays on the device."""
+    if method not in ("max", "min", "mean"):
+        raise ValueError(f"z_project: method must be 'max', 'min' or 'mean', got {method!r}")
+    d, was_numpy = _z_batch("z_project", stack)
+    return _z_plane(hipops.z_project(d, method), was_numpy)
+
+
+def focus_scores(stack, method: str = "laplacian_variance") -> Float64Array:
+    """One focus score per plane of a (Z, Y, X) uint8 / uint16 stack -> float64 (Z,), larger = sharper.  The device makes
+    four exact integer sums per plane (``hipops.focus_sums``); the score is formed from them on the host in exact
+    rationals and rounded once.  With n = Y * X: ``"laplacian_variance"`` = sum(L^2) / n, the variance of the
+    four-neighbour Laplacian L under edge replication (whose sum is identically 0); ``"normalized_variance"`` =
+    (n sum(P^2) - sum(P)^2) / (n sum(P)), 0.0 for an all-zero plane; ``"brenner"`` = sum of (P(y, x+2) - P(y, x))^2."""
+    _focus_method("focus_scores", method)
+    d, _ = _z_batch("focus_scores", stack, integer_only=True)
+    return _scores_from_sums(hipops.focus_sums(d).numpy()[0], d.shape[2] * d.shape[3], method)
+
+
+@device_operator
+def best_focus(stack, method: str = "laplacian_variance", return_index: bool = False):
+    """The plane of a (Z, Y, X) uint8 / uint16 stack with the largest ``focus_scores``, the smallest z among equals; with
+    ``return_index`` the pair (plane, z).  On the device the plane is a view of the stack, not a copy."""
+    _focus_method("best_focus", method)
+    d, was_numpy = _z_batch("best_focus", stack, integer_only=True)
+    z = int(np.argmax(_scores_from_sums(hipops.focus_sums(d).numpy()[0], d.shape[2] * d.shape[3], method)))
+    plane = np.asarray(stack)[z] if was_numpy else stack[z]
+    return (plane, z) if return_index else plane
+
+
+def _edf_args(radius, smooth):
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= 15:
+        raise ValueError(f"extended_depth_of_field: radius must be an integer in 0..15, got {radius!r}")
+    if isinstance(smooth, (bool, np.bool_)) or not isinstance(smooth, (int, np.integer)) or int(smooth) not in _EDF_SMOOTH:
+        raise ValueError(f"extended_depth_of_field: smooth must be 0 or an odd integer in 3..15, got {smooth!r}")
+    return int(radius), int(smooth)
+
+
+def _edf_batch(d: DeviceArray, radius: int, smooth: int, need_index: bool):
+    """-> (composite, index map or None) of an (N, Z, Y, X) batch"""
+    if smooth == 0 and not need_index:
+        return hipops.focus_stack(d, radius), None
+    index = hipops.focus_index(d, radius)
+    if smooth:
+        index = hipops.median(index, np.ones((smooth, smooth), np.uint8), mode="nearest")
+    return hipops.z_take(d, index), index
+
+
+@device_operator
+def extended_depth_of_field(stack, radius: int = 4, smooth: int = 0, return_index: bool = False):
+    """The all-in-focus composite of a (Z, Y, X) uint8 / uint16 stack: every pixel comes from the plane where the squared
+    Laplacian, summed over the (2 radius + 1)^2 window around it, is largest (the smallest z among equals;
+    ``hipops.focus_index`` states the rule, which is this package's own).  ``smooth``: 0, or the odd side (3..15) of a
+    median filter of the index map (``mode="nearest"``) before the pixels are taken.  With ``return_index`` the pair
+    (composite, uint16 index map).  numpy in gives numpy out; a ``DeviceArray`` stays on the device."""
+    radius, smooth = _edf_args(radius, smooth)
+    d, was_numpy = _z_batch("extended_depth_of_field", stack, integer_only=True)
+    plane, index = _edf_batch(d, radius, smooth, bool(return_index))
+    if return_index:
+        return _z_plane(plane, was_numpy), _z_plane(index, was_numpy)
+    return _z_plane(plane, was_numpy)
+
+
 def _global_threshold(d: DeviceArray, method: str, kwargs: dict) -> float:
     """Threshold VALUE for the histogram-based methods: histogram on the device, selection on <= 65,536 counts."""
     nbins = int(kwargs.pop("nbins", 256))

@@ -411,6 +411,47 @@ int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const d
  *                                            staircase is not measured twice (length = ORTH_LINKS + sqrt(2) * DIAG_LINKS)
  *                     A label absent from its plane gives seven zeros.  The counts are exact integers made without global
  *                     atomics, so two runs give identical bytes.  Asynchronous.  The table must not overlap `in`.
+ *
+ * op 10 .. 14: Z-STACKS (csrc/amt_zstack.hip).  Common to the five: `in` is nplanes x Z x H x W, stacks back to back and
+ * the planes of one stack back to back; `mode` carries Z, 1..65535, anything else is AMT_EINVAL; `dtype` is the dtype of
+ * `in`; nplanes == 0 is AMT_OK and writes nothing; `out` must not overlap `in` or `minuend`, not even in part
+ * (AMT_EINVAL); H * W < 2^31, and every offset is 64-bit, so Z * H * W of one stack may pass 2^31 elements.  The refusals
+ * that need no device (dtype, Z, the footprint, a minuend where none is allowed or a missing one, cval of op 10, the
+ * sizes) come before the context is looked at.  The five ops are asynchronous and reserve no scratch.
+ *   AMT_RANK_Z_PROJECT      dtype AMT_U8, AMT_U16 or AMT_F64.  cval selects the projection: 0 = max, 1 = min, 2 = mean,
+ *                     anything else is AMT_EINVAL.  `out` is nplanes x H x W: max / min in the dtype of `in`, mean in
+ *                     FLOAT64.  The integer mean is the exact integer sum over z divided once by Z; the float64 mean is
+ *                     the sum taken in the order z = 0, 1, ..., Z - 1 divided once by Z: both equal numpy's
+ *                     mean(stack, axis=0) bit for bit (numpy reduces a leading axis plane by plane).  NaN in float64
+ *                     input is unsupported.  The footprint is ignored; `minuend` must be NULL.
+ *   AMT_RANK_Z_FOCUS_SUMS   dtype AMT_U8 or AMT_U16 (AMT_F64 is AMT_EINVAL: focus is judged on raw data).  `out` is
+ *                     nplanes x Z x AMT_ZF_NCOLS 64-bit integers, one row per plane P:
+ *                       AMT_ZF_SUM        sum of P
+ *                       AMT_ZF_SUMSQ      sum of P^2
+ *                       AMT_ZF_LAP_SUMSQ  sum of L^2, L as defined under AMT_RANK_Z_FOCUS_INDEX
+ *                       AMT_ZF_BRENNER    sum over x + 2 < W of (P(y, x + 2) - P(y, x))^2
+ *                     H * W <= 2^27, else AMT_EINVAL: with uint16 L^2 <= 262140^2 < 2^36, and 2^27 of them still fit 64
+ *                     bits.  The sums are integers (workgroup totals added with 64-bit integer atomics), so their bytes
+ *                     depend on no order.  The footprint is ignored; `minuend` must be NULL.
+ *   AMT_RANK_Z_FOCUS_INDEX  dtype AMT_U8 or AMT_U16.  The footprint must be (2r+1) x (2r+1) with every cell non-zero, r in
+ *                     0..AMT_ZSTACK_MAX_RADIUS; anything else is AMT_EINVAL.  `out` is nplanes x H x W UINT16.  With P_z
+ *                     plane z of a stack:
+ *                       L_z(y, x) = 4 P(y, x) - P(y-1, x) - P(y+1, x) - P(y, x-1) - P(y, x+1), coordinates clamped to the
+ *                                   image (edge replication);
+ *                       E_z(y, x) = sum of L_z(y+dy, x+dx)^2 over |dy|, |dx| <= r with (y+dy, x+dx) inside the image
+ *                                   (outside counts 0);
+ *                       out(y, x) = the smallest z at which E_z(y, x) is largest.
+ *                     E < 961 * 2^36 < 2^46: the arithmetic is exact 64-bit integers, no float appears, and two runs
+ *                     give identical bytes.  `minuend` must be NULL.  This focus rule is this library's own: parity
+ *                     with CellProfiler's or ImageJ's stack focusers is unpinned offline.
+ *   AMT_RANK_Z_FOCUS_STACK  the operands and the rule of AMT_RANK_Z_FOCUS_INDEX; `out` is nplanes x H x W of the dtype of
+ *                     `in` and holds in[index(y, x), y, x].  The index map never reaches memory.
+ *   AMT_RANK_Z_TAKE         dtype AMT_U8, AMT_U16 or AMT_F64.  `minuend` is an nplanes x H x W UINT16 index map and is
+ *                     required (NULL is AMT_EINVAL).  out(y, x) = in[min(index(y, x), Z - 1), y, x] in the dtype of
+ *                     `in`: an index past the stack is clamped, since refusing it would need a wait for the device.
+ *                     The footprint is ignored.
+ * Ops 12 / 13: a workgroup owns one tile of AMT_ZSTACK_TILE_H x AMT_ZSTACK_TILE_W output pixels and loops over z; each
+ * stack is read once plus a halo of r + 1 pixels, and nothing but `out` is written.
  */
 #define AMT_RANK_RECONSTRUCT_DILATION 3
 #define AMT_RANK_RECONSTRUCT_EROSION  4
@@ -418,6 +459,19 @@ int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const d
 #define AMT_RANK_HMIN_RECONSTRUCT     6
 #define AMT_RANK_LABEL_SKELETON 8
 #define AMT_RANK_LABEL_CENSUS 9
+#define AMT_RANK_Z_PROJECT 10
+#define AMT_RANK_Z_FOCUS_SUMS 11
+#define AMT_RANK_Z_FOCUS_INDEX 12
+#define AMT_RANK_Z_FOCUS_STACK 13
+#define AMT_RANK_Z_TAKE 14
+#define AMT_ZF_SUM 0
+#define AMT_ZF_SUMSQ 1
+#define AMT_ZF_LAP_SUMSQ 2
+#define AMT_ZF_BRENNER 3
+#define AMT_ZF_NCOLS 4
+#define AMT_ZSTACK_TILE_H 64
+#define AMT_ZSTACK_TILE_W 64
+#define AMT_ZSTACK_MAX_RADIUS 15
 #define AMT_LABEL_SKELETON_TILE_ROWS 64
 #define AMT_LABEL_SKELETON_TILE_WORDS 8
 #define AMT_LABEL_SKELETON_BLOCK_SUBITERS 32
