@@ -42,6 +42,13 @@ ZF_COLS = ("sum", "sumsq", "lap_sumsq", "brenner")
 ZF_NCOLS = len(ZF_COLS)
 ZSTACK_TILE = (64, 64)
 ZSTACK_MAX_RADIUS = 15
+# amt_rank_filter: the spot ops (AMT_RANK_LOCAL_MAXIMA .. AMT_RANK_TAKE_AT), the columns of a spot-measure row
+# (AMT_SPOT_*), the output tile a workgroup of the local-maximum kernel owns and the largest radius
+RANK_LOCAL_MAXIMA, RANK_MASK_LIST, RANK_SPOT_MEASURE, RANK_TAKE_AT = 15, 16, 17, 18
+SPOT_COLS = ("value", "dy", "dx", "sum", "n", "ring_sum", "ring_n")
+SPOT_NCOLS = len(SPOT_COLS)
+SPOT_TILE = (64, 64)
+SPOT_MAX_RADIUS = 15
 WS_TIES ={"exact": 0, "raster": 1, "report": 2, "refuse": 2}
 RP_COLS = (
     "area", "centroid-0", "centroid-1", "bbox-0", "bbox-1", "bbox-2", "bbox-3", "perimeter",

@@ -212,6 +212,16 @@ void amt_i_zstack_spans(int op, int dtype, int nplanes, int H, int W, int Z, dou
 int amt_i_zstack(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W, const uint8_t* footprint,
                  int fh, int fw, int op, int Z, double cval, const void* minuend);
 
+// ---- spot detection (amt_spots.hip): ops AMT_RANK_LOCAL_MAXIMA .. AMT_RANK_TAKE_AT of amt_rank_filter, whose `mode`
+// carries the border width (op 15) or the capacity of a list of spots (ops 16 .. 18).  amt_i_spots_spans gives the byte
+// lengths of the three operands for the aliasing check amt_rank_filter makes; amt_i_spots checks everything else, the
+// refusals that need no device (dtype, footprint, mode, minuend, sizes) before it looks at the context.  Asynchronous;
+// only the mask list reserves scratch (its per-row counts).
+void amt_i_spots_spans(int op, int dtype, int nplanes, int H, int W, int mode, size_t* in_bytes, size_t* out_bytes,
+                       size_t* minuend_bytes);
+int amt_i_spots(amt_ctx* ctx, const void* in, void* out, int dtype, int nplanes, int H, int W, const uint8_t* footprint,
+                int fh, int fw, int op, int mode, double cval, const void* minuend);
+
 // runtime bool -> template argument: f(std::true_type) or f(std::false_type), for launches of <bool> kernel templates
 template <typename F>
 static inline void amt_with_bool(bool b, F&& f) {

@@ -939,12 +939,18 @@ static int rank_filter_impl(amt_ctx* ctx, const void* in, void* out, int dtype, 
         *fused = 1;
         return amt_i_zstack(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, minuend);
     }
+    if (op >= AMT_RANK_LOCAL_MAXIMA && op <= AMT_RANK_TAKE_AT) {
+        // spot detection (amt_spots.hip): `mode` carries the border width or a list's capacity; the `minuend` of op 15 is
+        // its per-plane thresholds, that of ops 17 / 18 their list of spots, nothing to subtract
+        *fused = 1;
+        return amt_i_spots(ctx, in, out, dtype, nplanes, H, W, footprint, fh, fw, op, mode, cval, minuend);
+    }
     AMT_TRY(amt_set_device(ctx));
     AMT_REQUIRE(in && out && footprint && nplanes >= 0 && H > 0 && W > 0, "rank_filter: bad arguments");
     AMT_REQUIRE(dtype == AMT_U16 || dtype == AMT_F64, "rank_filter: dtype must be AMT_U16 or AMT_F64");
     AMT_REQUIRE(op >= 0 && op <= 2,
                 "rank_filter: op must be 0 (erosion), 1 (dilation), 2 (median), a reconstruction (3 .. 6), a label "
-                "skeleton op (8, 9) or a Z-stack op (10 .. 14)");
+                "skeleton op (8, 9), a Z-stack op (10 .. 14) or a spot op (15 .. 18)");
     AMT_REQUIRE((fh & 1) && (fw & 1) && fh >= 1 && fw >= 1 && fh <= 63 && fw <= 63,
                 "rank_filter: footprint must be odd-sized and at most 63 x 63 (got %d x %d)", fh, fw);
     static thread_local int2 host[RK_MAX_OFFS];
@@ -1157,6 +1163,9 @@ extern "C" int amt_rank_filter(amt_ctx* ctx, const void* in, void* out, int dtyp
         // the Z-stack ops read nplanes x Z (`mode`) planes, and each has its own output and minuend
         if (op >= AMT_RANK_Z_PROJECT && op <= AMT_RANK_Z_TAKE)
             amt_i_zstack_spans(op, dtype, nplanes, H, W, mode, cval, &ibytes, &obytes, &mbytes);
+        // the spot ops write a mask, a list or a table, and their minuend is a row of thresholds or a list
+        if (op >= AMT_RANK_LOCAL_MAXIMA && op <= AMT_RANK_TAKE_AT)
+            amt_i_spots_spans(op, dtype, nplanes, H, W, mode, &ibytes, &obytes, &mbytes);
         AMT_CHECK_OPERANDS("amt_rank_filter", amt_in("in", in, ibytes), amt_out("out", out, obytes), amt_in("minuend", minuend, mbytes));
     }
     int fused = 0;

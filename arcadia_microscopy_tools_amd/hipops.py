@@ -1035,6 +1035,142 @@ def z_take(stack: DeviceArray, index: DeviceArray, out: DeviceArray | None = Non
     return _zstack_call(stack, o, code, N, Z, H, W, np.ones((1, 1), np.uint8), _hip.RANK_Z_TAKE, minuend=index)
 
 
+# ---- spot detection (amt_rank_filter ops 15 .. 18; include/amt_hip.h states the rules) ------------------------------
+def spot_tile() -> tuple[int, int]:
+    """(rows, columns) of the output tile one workgroup of the local-maximum kernel owns (AMT_SPOT_TILE_*)."""
+    return _hip.SPOT_TILE
+
+
+def _spot_int(op: str, name: str, value, lo: int, hi: int | None) -> int:
+    rng = f"{lo}..{hi}" if hi is not None else f"at least {lo}"
+    if isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{op}: {name} must be an integer ({rng}), got a bool")
+    try:
+        v = int(operator.index(value))
+    except TypeError:
+        raise ValueError(f"{op}: {name} must be an integer ({rng}), got {value!r}") from None
+    if v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{op}: {name} must be {rng}, got {v}")
+    return v
+
+
+def spot_capacity(H: int, W: int, min_distance: int = 1) -> int:
+    """The most marks ``local_maxima`` can leave in an H x W plane: marks are more than ``min_distance`` apart
+    (Chebyshev), so ceil(H / (min_distance + 1)) * ceil(W / (min_distance + 1))."""
+    r = _spot_int("spot_capacity", "min_distance", min_distance, 1, _hip.SPOT_MAX_RADIUS)
+    H, W = _spot_int("spot_capacity", "H", H, 1, None), _spot_int("spot_capacity", "W", W, 1, None)
+    return -(-H // (r + 1)) * -(-W // (r + 1))
+
+
+def _spot_planes(op: str, a, dtypes, name: str = "a"):
+    """(N, H, W) of an (N, H, W) batch, refused before any device access"""
+    if not isinstance(a, DeviceArray):
+        raise ValueError(f"{op}: {name} must be a DeviceArray, got {type(a).__name__}")
+    if a.ndim != 3:
+        raise ValueError(f"{op} takes (N, H, W) batches, got shape {a.shape} for {name}")
+    if a.dtype not in [np.dtype(d) for d in dtypes]:
+        raise ValueError(f"{op}: {name} must be {' or '.join(np.dtype(d).name for d in dtypes)}, got {a.dtype}")
+    N, H, W = (int(v) for v in a.shape)
+    if H < 1 or W < 1 or H * W >= 2**31:
+        raise ValueError(f"{op}: planes must have 1 <= H * W < 2^31 pixels, got {H} x {W}")
+    return N, H, W
+
+
+def _spot_list(op: str, spots, N: int, ctx) -> int:
+    """the capacity of an (N, capacity + 1) int32 list of spots as ``mask_list`` writes it"""
+    if not isinstance(spots, DeviceArray) or spots.ndim != 2 or spots.dtype != np.int32 or spots.shape[0] != N \
+            or spots.shape[1] < 2:
+        raise ValueError(f"{op}: spots must be an int32 DeviceArray of shape ({N}, capacity + 1) as mask_list writes it, got "
+                         f"{getattr(spots, 'shape', None)} {getattr(spots, 'dtype', type(spots).__name__)}")
+    if spots.ctx is not ctx:
+        raise ValueError(f"{op}: the image and spots belong to different contexts")
+    return int(spots.shape[1]) - 1
+
+
+_SPOT_CODES = {np.dtype(np.uint8): _hip.U8, np.dtype(np.uint16): _hip.U16, np.dtype(np.int32): _hip.I32,
+               np.dtype(np.float64): _hip.F64}
+_ONE = np.ones((1, 1), np.uint8)
+
+
+def _spot_call(a, o, N, H, W, fp, op, mode, cval=0.0, minuend=None):
+    if N == 0:
+        return o
+    fh = int(fp.shape[0])
+    _hip.check(_lib().amt_rank_filter(a.ctx.handle, a.ptr, o.ptr, _SPOT_CODES[a.dtype], N, H, W,
+                                      fp.ctypes.data_as(ctypes.c_void_p), fh, fh, op, int(mode), float(cval),
+                                      None if minuend is None else minuend.ptr), "amt_rank_filter")
+    return o
+
+
+def local_maxima(a: DeviceArray, min_distance: int = 1, threshold=0.0, exclude_border: int = 0,
+                 out: DeviceArray | None = None) -> DeviceArray:
+    """The local maxima of every plane of an (N, H, W) uint16 / float64 batch -> (N, H, W) uint8 0 / 1 with ``is_bool``
+    set (amt_rank_filter, AMT_RANK_LOCAL_MAXIMA).  A pixel is marked iff it exceeds ``threshold`` (a number, or an (N,)
+    float64 DeviceArray with one threshold per plane), is >= every pixel within ``min_distance`` (Chebyshev) and > those
+    of them that precede it in raster order, and lies at least ``exclude_border`` pixels from every edge.  Marks are more
+    than ``min_distance`` apart; a plateau yields one mark, at its first pixel.  The rule is this package's own
+    (include/amt_hip.h states it); NaN is unsupported."""
+    r = _spot_int("local_maxima", "min_distance", min_distance, 1, _hip.SPOT_MAX_RADIUS)
+    b = _spot_int("local_maxima", "exclude_border", exclude_border, 0, 2**31 - 1)
+    per_plane = isinstance(threshold, DeviceArray)
+    if not per_plane:
+        try:
+            t = float(threshold)
+        except (TypeError, ValueError):
+            raise ValueError(f"local_maxima: threshold must be a number or an (N,) float64 DeviceArray, got {threshold!r}") from None
+        if np.isnan(t):
+            raise ValueError("local_maxima: threshold must not be NaN")
+    N, H, W = _spot_planes("local_maxima", a, (np.uint16, np.float64))
+    if per_plane:
+        if tuple(threshold.shape) != (N,) or threshold.dtype != np.float64:
+            raise ValueError(f"local_maxima: per-plane thresholds must be float64 of shape ({N},), got {threshold.shape} "
+                             f"{threshold.dtype}")
+        if threshold.ctx is not a.ctx:
+            raise ValueError("local_maxima: the image and threshold belong to different contexts")
+    o = _out(a.ctx, out, (N, H, W), np.uint8)
+    _no_alias("local_maxima", {"a": a, "threshold": threshold if per_plane else None}, {"out": o})
+    o.is_bool = True
+    return _spot_call(a, o, N, H, W, np.ones((2 * r + 1, 2 * r + 1), np.uint8), _hip.RANK_LOCAL_MAXIMA, b,
+                      0.0 if per_plane else t, threshold if per_plane else None)
+
+
+def mask_list(mask: DeviceArray, capacity: int | None = None, out: DeviceArray | None = None) -> DeviceArray:
+    """``np.flatnonzero`` of every plane of an (N, H, W) uint8 mask batch, truncated -> (N, capacity + 1) int32
+    (amt_rank_filter, AMT_RANK_MASK_LIST): column 0 the true number of set pixels (also when it exceeds ``capacity``),
+    then their raster indices y * W + x ascending, then -1.  ``capacity`` defaults to H * W."""
+    if capacity is not None:
+        capacity = _spot_int("mask_list", "capacity", capacity, 1, 2**31 - 2)
+    N, H, W = _spot_planes("mask_list", mask, (np.uint8,), "mask")
+    cap = H * W if capacity is None else capacity
+    o = _out(mask.ctx, out, (N, cap + 1), np.int32)
+    _no_alias("mask_list", {"mask": mask}, {"out": o})
+    return _spot_call(mask, o, N, H, W, _ONE, _hip.RANK_MASK_LIST, cap)
+
+
+def spot_measure(a: DeviceArray, spots: DeviceArray, radius: int = 2, out: DeviceArray | None = None) -> DeviceArray:
+    """One row per entry of a list of spots (as ``mask_list`` writes it) on an (N, H, W) uint16 / float64 batch ->
+    (N, capacity, 7) float64 in ``_hip.SPOT_COLS`` order (amt_rank_filter, AMT_RANK_SPOT_MEASURE): the value, the
+    sub-pixel offsets (dy, dx) of the parabola through three samples per axis (0 on the image's edge and where the
+    samples are not concave, clamped to +-0.5), sum and count over the (2 radius + 1)^2 window and over the frame at
+    distance radius + 1 .. radius + 2, both clipped to the image.  Rows past the count are NaN."""
+    k = _spot_int("spot_measure", "radius", radius, 0, _hip.SPOT_MAX_RADIUS)
+    N, H, W = _spot_planes("spot_measure", a, (np.uint16, np.float64))
+    cap = _spot_list("spot_measure", spots, N, a.ctx)
+    o = _out(a.ctx, out, (N, cap, _hip.SPOT_NCOLS), np.float64)
+    _no_alias("spot_measure", {"a": a, "spots": spots}, {"out": o})
+    return _spot_call(a, o, N, H, W, np.ones((2 * k + 1, 2 * k + 1), np.uint8), _hip.RANK_SPOT_MEASURE, cap, minuend=spots)
+
+
+def take_at(a: DeviceArray, spots: DeviceArray, out: DeviceArray | None = None) -> DeviceArray:
+    """The values of an (N, H, W) uint8 / uint16 / int32 / float64 batch at the entries of a list of spots ->
+    (N, capacity) of the same dtype, 0 past the count (amt_rank_filter, AMT_RANK_TAKE_AT)."""
+    N, H, W = _spot_planes("take_at", a, (np.uint8, np.uint16, np.int32, np.float64))
+    cap = _spot_list("take_at", spots, N, a.ctx)
+    o = _out(a.ctx, out, (N, cap), a.dtype)
+    _no_alias("take_at", {"a": a, "spots": spots}, {"out": o})
+    return _spot_call(a, o, N, H, W, _ONE, _hip.RANK_TAKE_AT, cap, minuend=spots)
+
+
 # ---- grey reconstruction (amt_rank_filter ops 3 .. 6; include/amt_hip.h states the definitions) --------------------
 def reconstruct_tile(dtype) -> tuple[int, int]:
     """(rows, columns) of the tile one workgroup of the reconstruction kernel owns (AMT_RECONSTRUCT_TILE_*): planes

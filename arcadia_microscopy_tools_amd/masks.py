@@ -879,6 +879,43 @@ class SegmentationMask:
                 "skeleton_path_pixels": col["path"], "skeleton_junction_pixels": col["junctions"],
                 "skeleton_length": orth + np.sqrt(2.0) * diag}
 
+    def _spot_channel(self, what: str, channel):
+        if not self.intensity_image_dict:
+            raise ValueError(f"{what} needs intensity images")
+        if channel not in self.intensity_image_dict:
+            raise ValueError(f"{what}: '{getattr(channel, 'name', channel)}' has no intensity image")
+        return self.intensity_image_dict[channel]
+
+    def spots(self, channel, **detect_kwargs) -> dict[str, ScalarArray]:
+        """The puncta of ``channel``'s intensity image as ``operations.detect_spots`` finds them (its keyword arguments
+        pass through, ``labels=`` excepted), with ``label`` = the cell under each spot, 0 on background: a dict of
+        equal-length arrays in raster order.  Works on ``expanded`` / ``ring`` masks (``label`` then numbers their rows)
+        and on masks from ``batch_masks``; the label plane does not leave the device, the labels under the spots are
+        gathered there (``hipops.take_at``)."""
+        from .operations import detect_spots
+
+        if "labels" in detect_kwargs:
+            raise TypeError("spots: labels= is this mask; it cannot be passed")
+        return detect_spots(self._spot_channel("spots", channel), labels=self, **detect_kwargs)
+
+    def cell_spots(self, channel, **detect_kwargs) -> dict[str, ScalarArray]:
+        """Per-cell spot columns of ``channel``, one entry per cell ordered by label like ``cell_properties``
+        (CellProfiler's per-object child count for puncta; keys: ``segment.spot_keys``): ``spot_count_<ch>`` (int64; spots
+        on background are not counted), ``spot_intensity_sum_<ch>`` (the sum of the spots' ``intensity_net``) and
+        ``spot_intensity_mean_<ch>`` (NaN at count 0), with the lower-cased channel name.  The spots are those of
+        ``spots(channel, **detect_kwargs)``; the columns are a ``bincount`` over that short list."""
+        from .segment import spot_keys
+
+        table = self.spots(channel, **detect_kwargs)
+        k = self.num_cells
+        label = table["label"]
+        inside = (label >= 1) & (label <= k)
+        count = np.bincount(label[inside], minlength=k + 1)[1:k + 1].astype(np.int64)
+        total = np.bincount(label[inside], weights=table["intensity_net"][inside], minlength=k + 1)[1:k + 1].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = np.where(count > 0, total / np.maximum(count, 1), np.nan)
+        return dict(zip(spot_keys(channel), (count, total, mean)))
+
     def convert_properties_to_microns(self, pixel_size_um: float) -> dict[str, ScalarArray]:
         """Scale lengths / areas / volumes to microns with ``_um`` / ``_um2`` / ``_um3`` key suffixes
         (R/masks.py:420-467); dimensionless and intensity columns pass through."""

@@ -846,3 +846,189 @@ def apply_threshold(
         mask = mask.reshape(shape)
         mask.is_bool = is_bool
     return _result(mask, was_numpy)
+
+
+# ---- spot detection (hipops.local_maxima / mask_list / spot_measure / take_at) ----------------------------------------
+def _spot_arg(what: str, name: str, value, lo: int, hi: int) -> int:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+        raise ValueError(f"{what}: {name} must be an integer in {lo}..{hi}, got {value!r}")
+    return int(value)
+
+
+def _spot_number(what: str, name: str, value, finite: bool = False) -> float:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, float, np.integer, np.floating)) \
+            or np.isnan(float(value)) or (finite and not np.isfinite(float(value))):
+        raise ValueError(f"{what}: {name} must be a {'finite ' if finite else ''}number, got {value!r}")
+    return float(value)
+
+
+def _spot_plane(what: str, image, name: str = "image"):
+    """-> ((1, Y, X) uint16 / float64 DeviceArray, was_numpy) of one 2-D image; a numpy image with NaN is refused"""
+    if not isinstance(image, DeviceArray):
+        a = np.asarray(image)
+        if a.ndim != 2:
+            raise ValueError(f"{what}: {name} must be 2-D, got shape {a.shape}")
+        if a.size == 0:
+            raise ValueError(f"{what}: {name} is empty")
+        if a.dtype.kind == "f" and np.isnan(a).any():
+            raise ValueError(f"{what}: {name} contains NaN, which the local-maximum rule does not order")
+        if a.dtype.kind not in "buif":
+            raise TypeError(f"{what}: {name} has dtype {a.dtype}, which is not supported")
+    elif image.ndim != 2:
+        raise ValueError(f"{what}: {name} must be 2-D, got shape {image.shape}")
+    d, was_numpy = _to_device(image, what)
+    return d.reshape((1,) + tuple(d.shape)), was_numpy
+
+
+def _spot_list_of(mask: DeviceArray, capacity: int):
+    """-> ((1, K + 1) list of the K set pixels of a (1, Y, X) mask, K): one 4-byte look at the count, then a view"""
+    spots = hipops.mask_list(mask, capacity)
+    flat = spots.reshape(spots.size)
+    count = int(flat[0:1].numpy()[0])
+    if count > capacity:
+        raise AssertionError(f"{count} marks in a plane that can hold {capacity}")
+    keep = max(count, 1)  # a list has at least capacity 1; its one entry is -1 then
+    return flat[0:keep + 1].reshape((1, keep + 1)), count
+
+
+@device_operator
+def peak_local_max(image, min_distance: int = 1, threshold_abs=None, threshold_rel=None, exclude_border=True,
+                   num_peaks=np.inf, labels=None, footprint=None, p_norm=None, num_peaks_per_label=None):
+    """The coordinates of the local maxima of a 2-D image -> (K, 2) int64 ``(row, col)``, sorted by descending value with
+    raster order among equals (``skimage.feature.peak_local_max``'s signature and threshold rule).  A pixel is a peak iff
+    it exceeds the threshold, is >= every pixel within ``min_distance`` (Chebyshev) and > those that precede it in raster
+    order (``hipops.local_maxima`` states the rule, which is this package's own: a plateau yields ONE peak, at its first
+    pixel, and peaks are more than ``min_distance`` apart; parity with scikit-image on plateaus is unpinned offline).
+    The threshold is ``threshold_abs``, or the image minimum when it is None; with ``threshold_rel`` the larger of that
+    and ``threshold_rel * image.max()``.  ``exclude_border``: True = ``min_distance``, False = 0, an int = that width.
+    ``num_peaks`` keeps the first so many.  The maxima are found on the device; the short list is sorted on the host.
+    ``labels=``, ``footprint=``, ``p_norm=`` and ``num_peaks_per_label=`` are not implemented: see ``detect_spots`` and
+    ``SegmentationMask.cell_spots`` for spots per label."""
+    for name, value in (("labels", labels), ("footprint", footprint), ("p_norm", p_norm),
+                        ("num_peaks_per_label", num_peaks_per_label)):
+        if value is not None:
+            raise NotImplementedError(f"peak_local_max: {name}= is not implemented; use detect_spots(labels=) or "
+                                      "SegmentationMask.cell_spots for spots per label")
+    r = _spot_arg("peak_local_max", "min_distance", min_distance, 1, 15)
+    if isinstance(exclude_border, (bool, np.bool_)):
+        b = r if exclude_border else 0
+    else:
+        b = _spot_arg("peak_local_max", "exclude_border", exclude_border, 0, 2**31 - 1)
+    if num_peaks != np.inf:
+        num_peaks = _spot_arg("peak_local_max", "num_peaks", num_peaks, 0, 2**62)
+    for name, value in (("threshold_abs", threshold_abs), ("threshold_rel", threshold_rel)):
+        if value is not None:
+            _spot_number("peak_local_max", name, value)
+    d, _ = _spot_plane("peak_local_max", image)
+    t = None if threshold_abs is None else float(threshold_abs)
+    if t is None or threshold_rel is not None:
+        mm = hipops.minmax(d if d.dtype == np.float64 else hipops.to_float64(d)).numpy()[0]
+        if t is None:
+            t = float(mm[0])
+        if threshold_rel is not None:
+            t = max(t, float(threshold_rel) * float(mm[1]))
+    H, W = d.shape[1:]
+    spots, count = _spot_list_of(hipops.local_maxima(d, r, t, b), hipops.spot_capacity(H, W, r))
+    index = spots.numpy()[0, 1:1 + count].astype(np.int64)
+    value = hipops.take_at(d, spots).numpy()[0, :count]
+    order = np.argsort(-value.astype(np.float64), kind="stable")  # stable: raster order among equals
+    index = index[order]
+    if num_peaks != np.inf:
+        index = index[:num_peaks]
+    return np.stack([index // W, index % W], axis=1).reshape(-1, 2)
+
+
+SPOT_KEYS = ("row", "col", "y", "x", "response", "intensity_sum", "background_mean", "intensity_net")
+
+
+def _spot_table(response: DeviceArray, intensity: DeviceArray, r: int, t: float, b: int, k: int, labels: DeviceArray | None):
+    """The table of ``detect_spots`` from (1, Y, X) planes on the device"""
+    from . import _hip
+
+    H, W = response.shape[1:]
+    spots, count = _spot_list_of(hipops.local_maxima(response, r, t, b), hipops.spot_capacity(H, W, r))
+    index = spots.numpy()[0, 1:1 + count].astype(np.int64)
+    col = {name: i for i, name in enumerate(_hip.SPOT_COLS)}
+    on_response = hipops.spot_measure(response, spots, k).numpy()[0, :count]
+    on_intensity = on_response if intensity is response else hipops.spot_measure(intensity, spots, k).numpy()[0, :count]
+    row, column = index // W, index % W
+    with np.errstate(invalid="ignore", divide="ignore"):
+        background = on_intensity[:, col["ring_sum"]] / on_intensity[:, col["ring_n"]]
+    total = on_intensity[:, col["sum"]].copy()
+    out = {"row": row, "col": column, "y": row + on_response[:, col["dy"]], "x": column + on_response[:, col["dx"]],
+           "response": on_response[:, col["value"]].copy(), "intensity_sum": total, "background_mean": background,
+           "intensity_net": total - on_intensity[:, col["n"]] * background}
+    if labels is not None:
+        out["label"] = hipops.take_at(labels, spots).numpy()[0, :count].astype(np.int64)
+    return out
+
+
+def _spot_labels(what: str, labels, shape, ctx):
+    """``labels=`` of ``detect_spots`` as a (1, Y, X) int32 device plane: an integer label array, a DeviceArray or a
+    ``SegmentationMask`` (whose device plane is used where it is)"""
+    if labels is None:
+        return None
+    if hasattr(labels, "_label_plane"):
+        plane = labels._label_plane()[0]
+    elif isinstance(labels, DeviceArray):
+        plane = labels
+    else:
+        a = np.asarray(labels)
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise TypeError(f"{what}: labels must be an integer label array or a SegmentationMask, got dtype {a.dtype}")
+        if a.size and (int(a.min()) < -2**31 or int(a.max()) >= 2**31):
+            raise ValueError(f"{what}: labels must fit int32")
+        plane = None if tuple(a.shape) != tuple(shape) else ctx.asarray(np.ascontiguousarray(a, dtype=np.int32))
+    if plane is None or tuple(plane.shape[-2:]) != tuple(shape) or plane.size != shape[0] * shape[1]:
+        raise ValueError(f"{what}: labels must have the image's shape {tuple(shape)}")
+    if plane.dtype != np.int32:
+        raise TypeError(f"{what}: device labels must be int32, got {plane.dtype}")
+    return plane.reshape((1,) + tuple(shape))
+
+
+@device_operator
+def detect_spots(image, sigma=1.5, min_distance: int = 2, threshold=None, snr: float = 5.0, radius: int = 2,
+                 exclude_border=None, labels=None, intensity=None):
+    """Puncta (smFISH dots, foci, vesicles) of a 2-D image as a table: a dict of equal-length arrays in raster order --
+    ``row``, ``col`` (int64), ``y``, ``x`` (float64: the pixel plus its sub-pixel offset), ``response``,
+    ``intensity_sum``, ``background_mean``, ``intensity_net`` (float64) and, with ``labels=`` (an integer label array or
+    a ``SegmentationMask``), ``label`` (int64, 0 on background).
+
+    The response is ``difference_of_gaussians(image, sigma, 1.6 * sigma)``, with ``sigma=None`` the image itself.  Spots
+    are the local maxima of the response within ``min_distance`` (``hipops.local_maxima``: this package's own rule, one
+    mark per plateau) above ``threshold`` -- a number on the response, or with None
+    ``p50 + snr * (p75 - p25) / 1.349`` of the response: a robust background level plus ``snr`` robust standard
+    deviations, from three device percentiles and host float64 arithmetic -- and at least ``exclude_border`` pixels (None =
+    ``min_distance``) from the edges.  The offsets are the vertex of the parabola through three samples of the response
+    per axis (``hipops.spot_measure``).  ``intensity_sum`` is the sum of ``intensity`` (default: ``image``) over the
+    (2 radius + 1)^2 window, ``background_mean`` its mean over the frame at distance radius + 1 .. radius + 2, and
+    ``intensity_net`` the sum minus window pixels x background.  Everything pixel-sized runs on the device; what comes
+    back is the short list."""
+    what = "detect_spots"
+    r = _spot_arg(what, "min_distance", min_distance, 1, 15)
+    k = _spot_arg(what, "radius", radius, 0, 15)
+    b = r if exclude_border is None else _spot_arg(what, "exclude_border", exclude_border, 0, 2**31 - 1)
+    if sigma is not None and not _spot_number(what, "sigma", sigma, finite=True) > 0:
+        raise ValueError(f"{what}: sigma must be a positive number or None, got {sigma!r}")
+    if threshold is not None:
+        _spot_number(what, "threshold", threshold)
+    else:
+        _spot_number(what, "snr", snr, finite=True)
+    scaled, scale = (image, None) if sigma is None else _img_as_float_plan(image)
+    d, _ = _spot_plane(what, scaled)
+    shape = tuple(d.shape[1:])
+    if intensity is None:
+        # the plane that was uploaded holds the image's own values unless img_as_float rescaled it on the host
+        source = d if scaled is image else _spot_plane(what, image)[0]
+    else:
+        source = _spot_plane(what, intensity, "intensity")[0]
+        if tuple(source.shape[1:]) != shape:
+            raise ValueError(f"{what}: intensity must have the image's shape {shape}, got {tuple(source.shape[1:])}")
+    lab = _spot_labels(what, labels, shape, d.ctx)
+    response = d if sigma is None else hipops.difference_of_gaussians(d, float(sigma), 1.6 * float(sigma), scale=scale)
+    if threshold is None:
+        p25, p50, p75 = (float(v) for v in hipops.percentile(response, [25, 50, 75]).numpy()[0])
+        t = p50 + float(snr) * (p75 - p25) / 1.349
+    else:
+        t = float(threshold)
+    return _spot_table(response, source, r, t, b, k, lab)

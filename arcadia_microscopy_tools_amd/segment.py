@@ -497,6 +497,14 @@ def skeleton_keys() -> list[str]:
             "skeleton_length"]
 
 
+def spot_keys(channel) -> list[str]:
+    """The keys of ``SegmentationMask.cell_spots`` for this channel, in order (no device needed):
+    ``spot_count_<ch>`` (int64), ``spot_intensity_sum_<ch>`` and ``spot_intensity_mean_<ch>`` (float64) with the
+    lower-cased channel name, e.g. ``spot_count_fitc``."""
+    name = str(getattr(channel, "name", channel)).lower()
+    return [f"spot_count_{name}", f"spot_intensity_sum_{name}", f"spot_intensity_mean_{name}"]
+
+
 def segment_fovs(fovs, *, ctx: Context | None = None, channel_names=DEFAULT_CHANNELS, **kw) -> SegmentationResult:
     """Convenience: (B, C, H, W) uint16 (numpy or DeviceArray) -> config-3 ``SegmentationResult``."""
     ctx = ctx or get_context()

@@ -452,6 +452,57 @@ int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const d
  *                     The footprint is ignored.
  * Ops 12 / 13: a workgroup owns one tile of AMT_ZSTACK_TILE_H x AMT_ZSTACK_TILE_W output pixels and loops over z; each
  * stack is read once plus a halo of r + 1 pixels, and nothing but `out` is written.
+ *
+ * op 15 .. 18: SPOT DETECTION (csrc/amt_spots.hip).  Common to the four: `in` is nplanes x H x W of `dtype`; nplanes == 0
+ * is AMT_OK and writes nothing; H * W < 2^31; `out` must not overlap `in` or `minuend`, not even in part (AMT_EINVAL;
+ * buffers that only touch are accepted).  The refusals that need no device (dtype, the footprint, `mode`, a minuend where
+ * none is allowed or a missing one, the sizes) come before the context is looked at.  The four ops are asynchronous and
+ * use no global float atomics: two runs give identical bytes.  A LIST OF SPOTS of capacity c is nplanes x (c + 1) INT32,
+ * per plane: entry 0 the true number of spots, also when it exceeds c; entries 1 .. min(count, c) their raster indices
+ * y * W + x, ascending; every later entry -1.
+ *   AMT_RANK_LOCAL_MAXIMA   dtype AMT_U16 or AMT_F64.  `out` is nplanes x H x W UINT8, 0 or 1.  The footprint must be
+ *                     (2r+1) x (2r+1) with every cell non-zero, r in 1..AMT_SPOT_MAX_RADIUS; `mode` is the border width
+ *                     b >= 0; anything else is AMT_EINVAL.  cval is the threshold t; `minuend` is nullable and, when
+ *                     given, holds nplanes FLOAT64 thresholds, one per plane, used instead of cval.  The rule is this
+ *                     library's own.  Pixel p is marked iff all of these hold:
+ *                       in(p) > t;
+ *                       in(p) >= in(q) for every q inside the image with Chebyshev distance <= r from p;
+ *                       in(p) > in(q), strictly, for those q that precede p in raster order: rows above, and the same
+ *                                   row to the left;
+ *                       p lies at least b pixels from every image edge.
+ *                     The border test is applied last: a plateau whose first pixel lies in the border yields nothing
+ *                     there.  Consequences: any two marked pixels are more than r apart (Chebyshev) -- if p and q are
+ *                     both marked and within r then in(p) = in(q), and the later one fails the strict test; so a plane
+ *                     holds at most ceil(H / (r+1)) * ceil(W / (r+1)) marks; a constant ridge or plateau yields one mark,
+ *                     at its first pixel in raster order.  NaN is unsupported; -0.0 equals +0.0.  Parity with
+ *                     skimage.feature.peak_local_max on plateaus is unpinned offline (scikit-image thins plateau
+ *                     candidates in a second pass); the spacing guarantee is the same.  A workgroup owns one tile of
+ *                     AMT_SPOT_TILE_H x AMT_SPOT_TILE_W output pixels with a halo of r in LDS and takes the window
+ *                     maximum separably (rows, then columns): a plane is read once plus halo.
+ *   AMT_RANK_MASK_LIST      dtype AMT_U8: `in` is any mask, non-zero meaning set.  `mode` is the capacity c >= 1.  The
+ *                     footprint is ignored; `minuend` must be NULL.  `out` is the list of the set pixels, capacity c:
+ *                     np.flatnonzero per plane, truncated.  The order is the raster order, so the bytes depend on no
+ *                     schedule (per-row counts, one exclusive scan per plane, a wave per row placing its entries).
+ *   AMT_RANK_SPOT_MEASURE   dtype AMT_U16 or AMT_F64.  `minuend` is a list of spots and is required (NULL is
+ *                     AMT_EINVAL); `mode` is its capacity c.  The footprint must be (2k+1) x (2k+1) with every cell
+ *                     non-zero, k in 0..AMT_SPOT_MAX_RADIUS.  `out` is nplanes x c x AMT_SPOT_NCOLS FLOAT64.  The row for
+ *                     list entry j at (y, x), with a = `in` as float64:
+ *                       AMT_SPOT_VALUE     a(y, x)
+ *                       AMT_SPOT_DY / _DX  the vertex of the parabola through the three samples along the axis: 0 on the
+ *                                          first or last row (column) of the image; otherwise with
+ *                                          den = (a- - a0) + (a+ - a0): 0 when den >= 0, else (0.5 * (a- - a+)) / den
+ *                                          clamped to [-0.5, 0.5].  The operations run in exactly this order, each rounded
+ *                                          once; no multiply feeds an add, so contraction cannot change a bit.
+ *                       AMT_SPOT_SUM / _N  sum and count of `in` over |dy|, |dx| <= k, clipped to the image
+ *                       AMT_SPOT_RING_SUM / _RING_N  the same over Chebyshev distance k+1 .. k+2, clipped: the local
+ *                                          background frame
+ *                     uint16 sums are exact integers converted once.  float64 sums run in one fixed order: the window
+ *                     (2k+5)^2 is numbered row by row, lane l of a wave adds its elements l, l + 64, ... in that order,
+ *                     and the 64 partial sums are combined by a butterfly (distance 32, 16, ... 1).  Rows past
+ *                     min(count, c), and rows of -1 entries (or of an index outside the plane), are NaN throughout.
+ *   AMT_RANK_TAKE_AT        dtype AMT_U8, AMT_U16, AMT_I32 or AMT_F64.  `minuend` is a list of spots and is required;
+ *                     `mode` is its capacity c.  The footprint is ignored.  `out` is nplanes x c of the dtype of `in`:
+ *                     out[i][j] = in[i] at list entry j, 0 past the count (labels under spots are taken this way).
  */
 #define AMT_RANK_RECONSTRUCT_DILATION 3
 #define AMT_RANK_RECONSTRUCT_EROSION  4
@@ -464,6 +515,21 @@ int amt_threshold_open_close(amt_ctx* ctx, const void* in, int in_dtype, const d
 #define AMT_RANK_Z_FOCUS_INDEX 12
 #define AMT_RANK_Z_FOCUS_STACK 13
 #define AMT_RANK_Z_TAKE 14
+#define AMT_RANK_LOCAL_MAXIMA 15
+#define AMT_RANK_MASK_LIST 16
+#define AMT_RANK_SPOT_MEASURE 17
+#define AMT_RANK_TAKE_AT 18
+#define AMT_SPOT_VALUE 0
+#define AMT_SPOT_DY 1
+#define AMT_SPOT_DX 2
+#define AMT_SPOT_SUM 3
+#define AMT_SPOT_N 4
+#define AMT_SPOT_RING_SUM 5
+#define AMT_SPOT_RING_N 6
+#define AMT_SPOT_NCOLS 7
+#define AMT_SPOT_TILE_H 64
+#define AMT_SPOT_TILE_W 64
+#define AMT_SPOT_MAX_RADIUS 15
 #define AMT_ZF_SUM 0
 #define AMT_ZF_SUMSQ 1
 #define AMT_ZF_LAP_SUMSQ 2
